@@ -11,7 +11,11 @@ SMC-PHD weight update, births + resampling, occupancy/semantic sweep), inputs re
           Z-slab shards, one process per GPU, exchanges over RCCL inside the library (member counts, slab-crossing
           copies, chunk-owner reduction of the partial ck images); per-collective GPU times in `collectives_us`.
 
-Prints ONE JSON line on rank 0 (contract in the task description), with two extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps frames, writes --dump-outputs if asked and
+prints the headline (`value`, `ms_per_step`, the workload in `config`).  Frames come from a pool of at most FRAME_POOL
+rendered ones (frame_schedule), so setting up costs the same whatever --steps says.
+With --full the line carries everything else as well: per-stage times (`stage_ms`), the strong-scaling, one-rank sharded,
+busy-scene, driven and end-to-end legs (each with its --no-* switch), and two extra objects:
   roofline     — occupancy/semantic sweep kernel: algorithmic bytes (80 B/voxel at 8 slots)
                  / HIP-event time on the stream it runs on, against the 8 TB/s HBM peak; beside it what this
                  layout really moves per launch (`layout`), the PMC traffic, the non-incremental launch
@@ -35,6 +39,67 @@ if ROOT not in sys.path:
 
 HBM_PEAK_BPS = 8.0e12  # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
 PREFILL_FACTOR = 1.16   # prefilled / live particles after the first sweeps' culls (see main)
+FRAME_POOL = 64         # distinct frames a run renders and holds in HBM, whatever --steps says (frame_schedule)
+DUMP_SAMPLE = 1 << 20   # rows per array of --dump-outputs (dump_outputs)
+
+
+def frame_schedule(n):
+    """Frame numbers of the scene for n frames issued one after the other: 0, 1, ..., n - 1 while n <= FRAME_POOL.  A longer
+    run drives the first FRAME_POOL frames' stretch of street back and forth (..., P - 1, P - 2, ..., 0, 1, ...), so that
+    the frames rendered and held in HBM stay bounded and every step stays one frame's motion of camera and objects."""
+    period = 2 * (FRAME_POOL - 1)
+    return [k if k < FRAME_POOL else (k % period if k % period < FRAME_POOL else period - k % period) for k in range(n)]
+
+
+def render_workers():
+    """Processes that render the frames (SDM_RENDER_WORKERS, else the CPUs this process may use, at most 16)."""
+    return int(os.environ.get("SDM_RENDER_WORKERS", "0")) or min(16, len(os.sched_getaffinity(0)))
+
+
+def scheduled_frames(synth, scene, scene_kw, cfg, params, n):
+    """(depth, cloud, pos, q, moves) for each of n consecutive frames (frame_schedule), rendered by worker processes (frames
+    are bit-identical wherever they are rendered).  A step back along the street moves the objects back: the inverse of
+    the frame's translations."""
+    ts = frame_schedule(n)
+    uniq = sorted(set(ts))
+    rendered = dict(zip(uniq, synth.render_frames(cfg, params, scene_kw, uniq, workers=render_workers())))
+    back = scene.moves(1)
+    back["T"][:, [3, 7, 11]] = 0 - back["T"][:, [3, 7, 11]]
+    frames = []
+    for k, t in enumerate(ts):
+        moves = back if k > 0 and t < ts[k - 1] else scene.moves(t)
+        frames.append(rendered[t] + (moves,))
+    return frames
+
+
+def upload_frames(m, frames):
+    """(depth, cloud, pos, q, moves, device depth, device cloud) per frame: each distinct image uploaded to HBM once."""
+    dev = {}
+    out = []
+    for depth, cloud, pos, q, moves in frames:
+        if id(depth) not in dev:
+            dev[id(depth)] = (m.device_put(depth), m.device_put(cloud))
+        out.append((depth, cloud, pos, q, moves) + dev[id(depth)])
+    return out
+
+
+def dump_outputs(m, out_dir, prefix=""):
+    """--dump-outputs: what the map hands its caller after the last timed frame, each array as float32 <out_dir>/<name>.npy
+    (about 40 MB at most).  voxel_{wsum,occ,label,track}: sdm_get_voxels' result at DUMP_SAMPLE voxels drawn once with a
+    fixed seed; occupied_{xyz,track,label,occ}: sdm_get_occupied's cloud (every occupied voxel in storage order, a sample
+    of DUMP_SAMPLE rows drawn with a fixed seed where there are more)."""
+    os.makedirs(out_dir, exist_ok=True)
+    vox = m.voxels()
+    pick = np.sort(np.random.default_rng(20250217).choice(len(vox), min(DUMP_SAMPLE, len(vox)), replace=False))
+    s = vox[pick]
+    arrays = {"voxel_wsum": s["wsum"], "voxel_occ": s["occ"], "voxel_label": s["label"], "voxel_track": s["track"]}
+    pts, _ = m.occupied()
+    if len(pts) > DUMP_SAMPLE:
+        pts = pts[np.sort(np.random.default_rng(20250218).choice(len(pts), DUMP_SAMPLE, replace=False))]
+    arrays.update(occupied_xyz=np.stack([pts["x"], pts["y"], pts["z"]], -1), occupied_track=pts["track"],
+                  occupied_label=pts["label"], occupied_occ=pts["occ"])
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def timed_run(synth, sharded, dist, rank, world, local_rank, cfg, params, particles_per_shard, steps, warmup, scene_kw,
@@ -42,16 +107,14 @@ def timed_run(synth, sharded, dist, rank, world, local_rank, cfg, params, partic
     """One more map of its own: frames rendered and uploaded, map prefilled, `warmup` + `steps` frames issued back to back,
     barrier + synchronize on both sides of the timed ones, max over ranks.  Returns the numbers and the engine (open).
     force_comm: the frames go through sdm_update_sharded on an RCCL communicator whatever the world size."""
+    scene = synth.Scene(cfg, **scene_kw)
+    frames = scheduled_frames(synth, scene, scene_kw, cfg, params, warmup + steps)
     eng = sharded.NativeShardedMap(cfg, params, rank, world, local_rank, dist=dist,
                                    force_comm=(dist is not None) if force_comm is None else force_comm,
                                    exchange=exchange or os.environ.get("SDM_EXCHANGE", "rccl"))
     m = eng.map
     m.generate_noise_table(seed=20250217)
-    scene = synth.Scene(cfg, **scene_kw)
-    frames = []
-    for t in range(warmup + steps):
-        depth, cloud, pos, q = scene.render(t, params)
-        frames.append((depth, cloud, pos, q, scene.moves(t), m.device_put(depth), m.device_put(cloud)))
+    frames = upload_frames(m, frames)
     st, ring, _ = synth.prefill_state(cfg, scene, int(particles_per_shard * PREFILL_FACTOR), shard_rank=rank, shard_count=world, **(prefill_kw or {}))
     m.load_state(st)
     m.set_ring_state(ring)
@@ -357,10 +420,14 @@ def spawn_ranks(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=20, help="timed frames")
+    ap.add_argument("--warmup", type=int, default=5, help="untimed frames before them")
     ap.add_argument("--config", default="C3")
     ap.add_argument("--particles", type=int, default=2000000, help="live particles per GPU after prefill")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed frames, write what the map hands its caller as "
+                                                          "DIR/<name>.npy (float32; see dump_outputs; rank r > 0 of N: rank<r>_<name>.npy)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: per-stage times, roofline, CPU baseline, "
+                                                        "dense case, strong scaling and the side legs below (the --no-* options pick among them)")
     ap.add_argument("--cpu-frames", type=int, default=10, help="frames of the CPU baseline sample (0 = skip)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-dense", action="store_true", help="skip the dense-case sweep timing after the run")
@@ -422,21 +489,22 @@ def main():
     S = 1 << cfg["p_n"]
     n_frames = args.warmup + args.steps
 
+    # ---- synthetic frames (same on every rank), rendered before HIP comes up in this process, uploaded to HBM before the
+    # timed region
+    scene_kw = dict(n_static=48, n_dynamic=6, seed=7)
+    scene = synth.Scene(cfg, **scene_kw)
+    t0 = time.time()
+    frames = scheduled_frames(synth, scene, scene_kw, cfg, params, n_frames)
+    t_render = time.time() - t0
+    t_after = frame_schedule(n_frames)[-1] + 1  # the frame one step on from the last one issued
+
     # (SDM_EXCHANGE=ipc: the exchanges of a sharded frame through peer-mapped arenas instead of RCCL)
     eng = sharded.NativeShardedMap(cfg, params, rank, world, local_rank, dist=dist, force_comm=multi, exchange=os.environ.get("SDM_EXCHANGE", "rccl"))
     m = eng.map
     # noise table: rocRAND on the device, read back so that the CPU baseline uses the same floats
     m.generate_noise_table(seed=20250217)
     noise = m.download_noise_table()
-
-    # ---- synthetic frames (same on every rank), uploaded to HBM before the timed region
-    scene = synth.Scene(cfg, n_static=48, n_dynamic=6, seed=7)
-    t0 = time.time()
-    frames = []
-    for t in range(n_frames):
-        depth, cloud, pos, q = scene.render(t, params)
-        frames.append((depth, cloud, pos, q, scene.moves(t), m.device_put(depth), m.device_put(cloud)))
-    t_render = time.time() - t0
+    frames = upload_frames(m, frames)
 
     # The first sweeps cull about one prefilled particle in eight (weights below the initial weight, operations.h:410-424):
     # the map is prefilled with that many more, so that what is LIVE during the timed frames is the 2 M BASELINE.json
@@ -486,6 +554,35 @@ def main():
         lt = torch.tensor([live, n_vis], dtype=torch.int64)
         dist.all_reduce(lt)
         live, n_vis = int(lt[0].item()), int(lt[1].item())
+    if args.dump_outputs:
+        dump_outputs(m, args.dump_outputs, "" if rank == 0 else "rank%d_" % rank)
+
+    line = {
+        "metric": "Mvoxels updated/sec (256^3 grid, 2M particles, VKITTI2 camera; whole hot-path frame)",
+        "value": round(V / (dt / args.steps) / 1e6, 1), "unit": "Mvoxels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt * 1e3 / args.steps, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic", "issue_mode": issue_mode,
+        "config": {"workload": "%s: %dx%dx%d voxels, %d slots/voxel, %dx%d image, window %d, %s params, "
+                               "6 dynamic objects, %d live particles - what the first sweeps left of %d PREFILLED ones, FILLER the camera "
+                               "cannot see (below the ground plane, behind the walls: the map carries BASELINE's 2 M, the frame works on "
+                               "what is visible) -, %d visible/frame; the workload the filter populated itself is `driven`"
+                               % (args.config if world == 1 else "%s weak-scaled x%d" % (args.config, world),
+                                  1 << cfg["x_n"], 1 << cfg["y_n"], 1 << cfg["z_n"], S, cfg["width"], cfg["height"],
+                                  cfg["window_half"], synth.CONFIG_PARAMS[args.config], live, n_pre * world, n_vis),
+                   "voxels": V, "live_particles": live, "prefilled_particles": n_pre * world, "visible_particles": n_vis,
+                   "parallelism": "zslab%d" % world, "inputs": "depth + LabeledPoint image resident in HBM",
+                   "frames": "%d distinct (frames 0..%d of the drive%s)" % (min(n_frames, FRAME_POOL), min(n_frames, FRAME_POOL) - 1,
+                                                                         ", driven back and forth" if n_frames > FRAME_POOL else ""),
+                   "render_s": round(t_render, 1),
+                   "host_enqueue_ms_per_step": round(t_enqueue * 1e3 / args.steps, 4), "launch_mode": launch_mode,
+                   "host_numa": host_numa},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # ---- per-stage GPU times and the roofline of the dominant streaming kernel (occupancy / semantic sweep), taken on
     # a few more frames after the timed region: HIP events on the stream the kernels run on bracket every stage
@@ -516,11 +613,11 @@ def main():
         n = t_hi - t_lo
         return acc / n, float(np.mean(live_l)), float(np.mean(tiles_l)), slabs / n
 
-    stage_ms, sweep_live_avg, sweep_tiles_avg, slabs_avg = profiled(n_frames, n_frames + n_extra)
+    stage_ms, sweep_live_avg, sweep_tiles_avg, slabs_avg = profiled(t_after, t_after + n_extra)
     # the same with the camera also moving one voxel per frame sideways: an x slab of the ring is recycled every frame (a
     # turning vehicle) - one voxel of every x row of the map changes its result
-    scene.lateral_extra = (n_frames + n_extra - 1, cfg["voxel_size"])
-    xs_stage, xs_live, xs_tiles, xs_slabs = profiled(n_frames + n_extra, n_frames + 2 * n_extra)
+    scene.lateral_extra = (t_after + n_extra - 1, cfg["voxel_size"])
+    xs_stage, xs_live, xs_tiles, xs_slabs = profiled(t_after + n_extra, t_after + 2 * n_extra)
     m.set_profiling(False)
     collectives = None
     if multi:
@@ -549,7 +646,6 @@ def main():
         collectives["us_on_critical_path"] = round(sum(v for k, v in collectives["us"].items() if k != "counts_allgather"), 1)
     sweep_ms = float(stage_ms[7])
     ms_per_step = dt * 1e3 / args.steps
-    value = V / (dt / args.steps) / 1e6  # Mvoxels / s, whole map (all shards)
     # Roofline of the occupancy / semantic sweep.  `frac` = bytes the launch has to move in this layout / launch time /
     # peak: one byte per 2048-voxel tile; for the tiles something was written or stamped in since the previous sweep,
     # the 2-byte observation stamp and 1-byte flag of every voxel; the record (10 (S - 1) bytes: round 6 took the time
@@ -685,7 +781,7 @@ def main():
                 m1.comm_timing(True)
                 comm1 = {}
                 sc1 = synth.Scene(cfg, n_static=48, n_dynamic=6, seed=7)
-                for t in range(n_frames, n_frames + 6):
+                for t in range(t_after, t_after + 6):
                     depth, cloud, pos, q = sc1.render(t, params)
                     eng1.update(m1.device_put(depth), m1.device_put(cloud), pos, q, sc1.moves(t))
                     m1.synchronize()
@@ -724,26 +820,7 @@ def main():
         adapter = adapter_e2e(synth, cfg, params, scene, frames)
 
     if rank == 0:
-        out = {
-            "metric": "Mvoxels updated/sec (256^3 grid, 2M particles, VKITTI2 camera; whole hot-path frame)",
-            "value": round(value, 1), "unit": "Mvoxels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic", "issue_mode": issue_mode,
-            "config": {"workload": "%s: %dx%dx%d voxels, %d slots/voxel, %dx%d image, window %d, %s params, "
-                                   "6 dynamic objects, %d live particles - what the first sweeps left of %d PREFILLED ones, FILLER the camera "
-                                   "cannot see (below the ground plane, behind the walls: the map carries BASELINE's 2 M, the frame works on "
-                                   "what is visible) -, %d visible/frame; the workload the filter populated itself is `driven`"
-                                   % (args.config if world == 1 else "%s weak-scaled x%d" % (args.config, world),
-                                      1 << cfg["x_n"], 1 << cfg["y_n"], 1 << cfg["z_n"], S, cfg["width"], cfg["height"],
-                                      cfg["window_half"], synth.CONFIG_PARAMS[args.config], live, n_pre * world, n_vis),
-                       "voxels": V, "live_particles": live, "prefilled_particles": n_pre * world, "visible_particles": n_vis,
-                       "parallelism": "zslab%d" % world, "inputs": "depth + LabeledPoint image resident in HBM",
-                       "render_s": round(t_render, 1),
-                       "host_enqueue_ms_per_step": round(t_enqueue * 1e3 / args.steps, 4), "launch_mode": launch_mode,
-                       "host_numa": host_numa},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-        }
+        out = dict(line, roofline=roofline, cpu_baseline=cpu)
         if collectives is not None:
             out["collectives_us"] = collectives
         if strong is not None:

@@ -98,7 +98,7 @@ def test_sharded_bench_line_rehearsal():
     import subprocess
     import sys
     env = dict(os.environ, SDM_BENCH_SHARDED="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29547", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "3"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "3", "--full"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [x for x in r.stdout.strip().splitlines() if x.strip()]
@@ -111,3 +111,39 @@ def test_sharded_bench_line_rehearsal():
     assert set(c["us"]) == {"counts_allgather", "halo_alltoall", "ck_alltoall", "ck_allgather"}
     assert c["us"]["ck_alltoall"] > 0 and c["us"]["ck_allgather"] > 0 and c["us_on_critical_path"] > 0
     assert d["issue_mode"].startswith("sharded") and d["cpu_baseline"] is None and d["n_gpus"] == 1
+
+
+def test_bench_has_full_and_dump_outputs_options():
+    r = _run_bench(["--help"], {})
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout, r.stdout + r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run prints the headline alone, times exactly --steps frames, and --dump-outputs writes the map's results after
+    the last of them as float32 arrays, the same from run to run."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(d)], {}, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [x for x in r.stdout.strip().splitlines() if x.strip()]
+        assert len(lines) == 1, lines
+        line = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+            assert key in line, key
+        assert line["steps"] == 3 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+        assert abs(line["value"] - line["config"]["voxels"] / (line["ms_per_step"] * 1e-3) / 1e6) / line["value"] < 1e-2
+        for key in ("roofline", "cpu_baseline", "stage_ms", "strong_scaling", "stress", "driven", "adapter_e2e"):
+            assert key not in line, key
+        files = sorted(d.glob("*.npy"))
+        assert {f.stem for f in files} == {"voxel_wsum", "voxel_occ", "voxel_label", "voxel_track",
+                                           "occupied_xyz", "occupied_track", "occupied_label", "occupied_occ"}
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        arrays = {f.stem: np.load(f) for f in files}
+        assert all(a.dtype == np.float32 for a in arrays.values())
+        assert len(arrays["occupied_xyz"]) > 0 and (arrays["occupied_occ"] > 0).all()
+        dumps.append(arrays)
+    for name, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][name]), name

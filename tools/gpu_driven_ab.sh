@@ -11,7 +11,7 @@ export SDM_DRIVEN_CACHE=/tmp/sdm_driven_frames_$$
       timeout 600 python bench.py --only-driven 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])['driven']; print('$lib driven', d['ms_per_step'], d['stage_ms'])"
-      timeout 300 python bench.py --no-cpu --no-dense --no-strong 2>/dev/null | python -c "
+      timeout 300 python bench.py --full --no-cpu --no-dense --no-strong 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$lib c3', d['ms_per_step'], d['stage_ms'])"
     done

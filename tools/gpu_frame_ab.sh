@@ -9,7 +9,7 @@ timeout 1200 python -m pytest $tests -x -q -m gpu 2>&1 | grep -E "passed|failed|
 for i in 1 2; do
   for lib in default $tag; do
     if [ $lib = default ]; then unset SDM_LIB_PATH; else export SDM_LIB_PATH=build/ab/libsdm_$lib.so; fi
-    timeout 300 python bench.py --no-cpu --no-dense --no-strong --no-stress --no-driven --no-adapter 2>/dev/null | python -c "
+    timeout 300 python bench.py --full --no-cpu --no-dense --no-strong --no-stress --no-driven --no-adapter 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$lib', d['ms_per_step'], d['stage_ms'])"
   done

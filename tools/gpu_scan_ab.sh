@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 one() {
   timeout 300 python tools/probes/full_only.py
-  timeout 600 python bench.py --no-cpu --no-stress --no-driven --no-adapter --no-strong --steps 20 --warmup 5 2>/dev/null | grep '"metric"' | python -c "
+  timeout 600 python bench.py --full --no-cpu --no-stress --no-driven --no-adapter --no-strong --steps 20 --warmup 5 2>/dev/null | grep '"metric"' | python -c "
 import sys, json
 for l in sys.stdin:
     j = json.loads(l); r = j['roofline']

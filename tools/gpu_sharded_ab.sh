@@ -8,7 +8,7 @@ mkdir -p gpurun_out
   for i in 1 2; do
     for lib in default "$@"; do
       if [ $lib = default ]; then unset SDM_LIB_PATH; else export SDM_LIB_PATH=build/ab/libsdm_$lib.so; fi
-      timeout 400 python bench.py --no-cpu --no-dense --no-strong --sharded-leg 2>/dev/null | python -c "
+      timeout 400 python bench.py --full --no-cpu --no-dense --no-strong --sharded-leg 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); s = d['sharded_one_rank']
 print('$lib plain', d['ms_per_step'], 'rccl', s['ms_per_step'], s['exchanges_us'], 'ipc', s['ipc_exchange']['ms_per_step'], s['ipc_exchange']['exchanges_us'])"

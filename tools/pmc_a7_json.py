@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""gpurun_out/<tag>_a7_sq.json from the counter passes of tools/pmc_a7.sh: per kernel and workload the SQ counters
+"""$SDM_PROFILE_OUT/<tag>_a7_sq.json from the counter passes of tools/pmc_a7.sh: per kernel and workload the SQ counters
 (averages per launch), instruction mix per wave, VALU and LDS issue utilisation.
 
 Utilisation = quad-cycles the SIMDs spent issuing that instruction class (SQ_ACTIVE_INST_*: one count = 4 shader cycles of
@@ -9,7 +9,10 @@ kernel trace of the same run.  (GRBM_GUI_ACTIVE, which an earlier version of thi
 import csv
 import glob
 import json
+import os
 import sys
+
+OUT = os.environ.get("SDM_PROFILE_OUT", "profile_out")  # tools/pmc_a7.sh writes there
 from collections import defaultdict
 
 tag = sys.argv[1]
@@ -29,13 +32,13 @@ for wl in ("c3", "stress"):
     acc = defaultdict(lambda: defaultdict(list))
     dur = defaultdict(list)
     for p in ("valu", "lds"):
-        for fn in glob.glob("gpurun_out/pmca7_%s_%s_%s/**/*counter_collection.csv" % (tag, wl, p), recursive=True):
+        for fn in glob.glob(OUT + "/pmca7_%s_%s_%s/**/*counter_collection.csv" % (tag, wl, p), recursive=True):
             for r in csv.DictReader(open(fn)):
                 k = short(r["Kernel_Name"])
                 if not k.startswith(KERNELS):
                     continue
                 acc[k][r["Counter_Name"]].append(float(r["Counter_Value"]))
-        for fn in glob.glob("gpurun_out/pmca7_%s_%s_%s/**/*kernel_trace.csv" % (tag, wl, p), recursive=True):
+        for fn in glob.glob(OUT + "/pmca7_%s_%s_%s/**/*kernel_trace.csv" % (tag, wl, p), recursive=True):
             for r in csv.DictReader(open(fn)):
                 k = short(r["Kernel_Name"])
                 if k.startswith(KERNELS):
@@ -59,7 +62,7 @@ for wl in ("c3", "stress"):
                                       (("issuing", "SQ_ACTIVE_INST_ANY"), ("waiting_memory_or_barrier", "SQ_WAIT_ANY"),
                                        ("issue_stalled", "SQ_WAIT_INST_ANY"))} if c.get("SQ_WAVE_CYCLES") else None}
     out["workloads"][wl] = res
-json.dump(out, open("gpurun_out/%s_a7_sq.json" % tag, "w"), indent=1)
+json.dump(out, open(OUT + "/%s_a7_sq.json" % tag, "w"), indent=1)
 for wl, res in out["workloads"].items():
     for k, v in res.items():
         print(wl, k, v["avg_us_under_pmc"], "us  VALU util", v["valu_issue_utilisation"], " LDS util", v["lds_issue_utilisation"], v["per_wave"])

@@ -11,11 +11,12 @@ wide coalesced streaming reads, so for the in-frame launch with its scattered re
 upper estimate)."""
 import csv
 import json
+import os
 import shutil
 import sys
 
 tag = sys.argv[1]
-g = "gpurun_out/"
+g = os.environ.get("SDM_PROFILE_OUT", "profile_out") + "/"  # tools/pmc_sweep.sh writes there
 b = json.loads(open(g + "%s_sweep_bench.json" % tag).read())
 rf = b["roofline"]
 res = {}
@@ -54,8 +55,8 @@ for c in ["FETCH_SIZE", "WRITE_SIZE"]:
 out = {"kernel": rf["kernel"], "non_incremental_kernels": "k_occupancy_scan + k_occupancy_dense (two launches, added; the first sweep of a map: k_occupancy_scan_lists + k_occupancy_listed + k_occupancy_dense; the dense cases after their second sweep: k_occupancy_dense alone)", "voxels": rf["voxels"], "voxels_evaluated_in_full": rf["voxels_evaluated_in_full"], "tiles": rf["tiles"],
        "tiles_looked_into": rf["tiles_looked_into"],
        "fetch_correction": "x2 (MI355X_MICROARCH.md, HBM section)", "cases": {},
-       "commands": ["SDM_GRAPH=0 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -- python bench.py --no-cpu --no-strong --no-stress --steps 20 --warmup 5",
-                    "SDM_GRAPH=0 rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -- python bench.py --no-cpu --no-strong --no-stress --steps 20 --warmup 5"]}
+       "commands": ["SDM_GRAPH=0 rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -- python bench.py --full --no-cpu --no-strong --no-stress --steps 20 --warmup 5",
+                    "SDM_GRAPH=0 rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -- python bench.py --full --no-cpu --no-strong --no-stress --steps 20 --warmup 5"]}
 layout = {"in_frame": rf["bytes_per_launch"], "full_evaluation": rf.get("full_evaluation", {}).get("bytes_per_launch"),
           "dense_case": rf.get("dense_case", {}).get("bytes_per_launch"),
           "dense_case_surface": rf.get("dense_case_surface", {}).get("bytes_per_launch"), "x_shift_frames": None}
