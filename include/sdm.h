@@ -429,6 +429,66 @@ sdm_status sdm_get_freespace_rgb(sdm_map *m, sdm_point_xyzrgb *out, size_t cap, 
 /* device pointer to the per-voxel result array (valid until the next update) */
 sdm_status sdm_voxels_device_ptr(sdm_map *m, const sdm_voxel_result **out);
 
+/* ---- batched map queries (new; the reference has none: its map only fed the RViz cloud) ----
+ * What a planner asks of the map - is this point, this path segment, this footprint free? - answered on the GPU from
+ * the array sdm_get_voxels returns, read in stream order on the map's stream: the results of the last frame enqueued
+ * before the call.  The caller never sees the storage layout (ring buffer, row-major storage index) and never holds a
+ * pointer that goes stale.  Queries never modify map state, and use no scratch a frame uses.  Positions are in the
+ * global frame.
+ *
+ * Flags: SDM_QUERY_ON_DEVICE - every input and output pointer is a device pointer; the call enqueues the kernel on the
+ * map's stream (sdm_stream) and returns without waiting: the results are there after sdm_synchronize, or in stream
+ * order.  The caller must have finished writing the inputs before the map's stream reaches the query (e.g. by writing
+ * them on that stream, or synchronising its own stream first).  Without it, inputs and outputs are host memory: the
+ * call copies the inputs up (in chunks, through a staging area the map grows on demand), runs the kernel, copies the
+ * outputs down and waits.  SDM_QUERY_UNKNOWN_BLOCKS is for segments only.
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map / input / output, n < 0, unknown flag bits, or a Z-slab shard
+ * (shard_count > 1: routing queries to the slab owners is not implemented).  n == 0 is OK and launches nothing.
+ *
+ * Map-index coordinates of a position p: u = ((p - map_center) - map_p_min) / voxel_size, per axis, as the float32
+ * expression the map itself uses ((p - center) - pmin) * (1 / voxel_size).  Cell (i, j, k) of the map is the box
+ * [i, i+1) x [j, j+1) x [k, k+1) of u, inside the map for 0 <= i < NX etc. */
+#define SDM_QUERY_ON_DEVICE 0x1u      /* inputs and outputs are device pointers; enqueued on the map's stream, no host wait */
+#define SDM_QUERY_UNKNOWN_BLOCKS 0x2u /* segments: unknown voxels (occ == -1) and space outside the map block */
+
+/* Points: out[i] = sdm_get_voxels()[voxel], bit for bit, where voxel is exactly the storage index the map would give a
+ * particle at xyz[3i..3i+2] (operations.h:849-883 with the last frame's map center and ring offsets, including the
+ * PINNED cast that accepts u in (-1, 0) as cell 0).  A point outside the map, or with a non-finite coordinate, gets
+ * {wsum -1, track 0, label 0, occ -1} and voxel 0xffffffff.  voxel_out (n entries) may be NULL. */
+sdm_status sdm_query_points(sdm_map *m, const float *xyz, int64_t n, sdm_voxel_result *out, uint32_t *voxel_out,
+                            uint32_t flags);
+
+/* Segments a -> b (ab[6i..6i+5] = ax ay az bx by bz) are traversed through the lattice of map cells in ascending t,
+ * u(t) = u(a) + t (u(b) - u(a)), t in [0, 1], visiting the cells floor(u(t)) (a 3-D DDA, Amanatides-Woo); where two planes
+ * are crossed at the same t, x steps before y before z.  NOTE: segments use floor, points the map's truncation - the
+ * two differ only inside the one-voxel sliver below each lower map face (u in (-1, 0)), which is outside the map here.
+ * A cell blocks if occ >= 1, or, with SDM_QUERY_UNKNOWN_BLOCKS, if occ == -1 or it lies outside the map.  Without the
+ * flag, cells outside the map are skipped: the segment is clipped to the map first, so its cost is bounded by NX+NY+NZ
+ * cells however long it is.  A zero-length segment is the cell of a.  A non-finite coordinate gives no hit and
+ * cells = 0; with SDM_QUERY_UNKNOWN_BLOCKS it is a hit at t = 0 on voxel 0xffffffff. */
+typedef struct {  /* 16 bytes */
+  float t;        /* where the segment enters its first blocking cell, as a fraction of a->b in [0,1]; 0 if a lies in it;
+                     -1 = nothing blocks */
+  uint32_t voxel; /* storage index of that cell; 0xffffffff = outside the map, or no hit */
+  int32_t cells;  /* in-map cells visited up to and including the hit (all of them if no hit) */
+  uint16_t track; /* result of the blocking cell, as sdm_get_voxels holds it (0 / 0 / -1 if outside or no hit) */
+  uint8_t label;
+  int8_t occ;
+} sdm_segment_hit;
+sdm_status sdm_query_segments(sdm_map *m, const float *ab, int64_t n, sdm_segment_hit *out, uint32_t flags);
+
+/* Boxes (boxes[6i..6i+5] = min x y z, max x y z): per axis the cells floor(u(min)) .. floor(u(max)) inclusive, intersected
+ * with [0, N), counted by class.  A box with min > max on any axis, or with a non-finite coordinate, counts nothing
+ * (all zero, first_occupied 0xffffffff, clipped 0). */
+typedef struct {          /* 20 bytes; only cells inside the map are counted */
+  int32_t n_occupied;     /* occ >= 1 */
+  int32_t n_free;         /* occ == 0 */
+  int32_t n_unknown;      /* occ == -1 */
+  uint32_t first_occupied; /* smallest storage index among the occupied cells, 0xffffffff if none */
+  int32_t clipped;        /* 1 if the box reaches outside the map */
+} sdm_box_result;
+sdm_status sdm_query_boxes(sdm_map *m, const float *boxes, int64_t n, sdm_box_result *out, uint32_t flags);
+
 /* ---- owner sets of the object layer: ObjectParticleHashMap (object_layer.h:20-52) */
 sdm_status sdm_object_particle_count(sdm_map *m, int32_t track_id, int64_t *count);
 /* The keys of ObjectParticleHashMap::indices_map whose sets are not empty: every track id that owns at least one slot of

@@ -21,6 +21,12 @@ POINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("track", "<u2"), ("
 POINT_XYZRGB = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("one", "<f4"), ("b", "u1"), ("g", "u1"), ("r", "u1"), ("a", "u1"),
                          ("pad", "<u4", (3,))])
 assert LABELED_POINT.itemsize == 20 and OBJECT_MOVE.itemsize == 68 and VOXEL_RESULT.itemsize == 8 and POINT.itemsize == 16
+# the batched map queries (sdm.h: sdm_query_segments / sdm_query_boxes)
+SEGMENT_HIT = np.dtype([("t", "<f4"), ("voxel", "<u4"), ("cells", "<i4"), ("track", "<u2"), ("label", "u1"), ("occ", "i1")])
+BOX_RESULT = np.dtype([("n_occupied", "<i4"), ("n_free", "<i4"), ("n_unknown", "<i4"), ("first_occupied", "<u4"), ("clipped", "<i4")])
+assert SEGMENT_HIT.itemsize == 16 and BOX_RESULT.itemsize == 20
+QUERY_ON_DEVICE = 0x1
+QUERY_UNKNOWN_BLOCKS = 0x2
 
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
@@ -155,6 +161,9 @@ def load_library():
         "sdm_set_colours": [vp, vp],
         "sdm_get_freespace": [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), i32],
         "sdm_voxels_device_ptr": [vp, C.POINTER(vp)],
+        "sdm_query_points": [vp, vp, i64, vp, vp, u32],
+        "sdm_query_segments": [vp, vp, i64, vp, u32],
+        "sdm_query_boxes": [vp, vp, i64, vp, u32],
         "sdm_object_particle_count": [vp, i32, C.POINTER(i64)],
         "sdm_tracks_with_particles": [vp, vp, i32, C.POINTER(i32)],
         "sdm_comm_set_options": [vp, i32, i32],
@@ -460,6 +469,49 @@ class SdmMap:
         out = np.empty(self.v_count, VOXEL_RESULT)
         _check(self.L, self.L.sdm_get_voxels(self.h, _ptr(out)), "sdm_get_voxels")
         return out
+
+    # ---- batched map queries (sdm.h).  Host mode: numpy in, numpy structured arrays out, the call waits.  on_device=True:
+    # the arguments are integer device pointers plus n, as update(on_device=True) takes them (device_alloc / device_put
+    # buffers, or a tensor's data_ptr() where the tensor lives on the runtime the library uses - INTEGRATION.md 3); the
+    # kernel is enqueued on the map's stream and the call returns at once.  The caller must have finished writing the
+    # inputs on its own stream first, and reads the outputs after synchronize() (or in stream order on stream()).
+    def query_points(self, xyz, with_index=False, on_device=False, n=None, out=None, voxel_out=None):
+        """xyz: (n, 3) global positions -> VOXEL_RESULT per point (and the storage indices if with_index).
+        on_device: xyz, out (n VOXEL_RESULT) and voxel_out (n uint32, or None) are device pointers."""
+        if on_device:
+            _check(self.L, self.L.sdm_query_points(self.h, _ptr(int(xyz)), int(n), _ptr(int(out)), _ptr(int(voxel_out)) if voxel_out else None,
+                                                   QUERY_ON_DEVICE), "sdm_query_points")
+            return None
+        p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        res = np.empty(len(p), VOXEL_RESULT)
+        idx = np.empty(len(p), np.uint32) if with_index else None
+        _check(self.L, self.L.sdm_query_points(self.h, _ptr(p), len(p), _ptr(res), _ptr(idx), 0), "sdm_query_points")
+        return (res, idx) if with_index else res
+
+    def query_segments(self, a, b=None, unknown_blocks=False, on_device=False, n=None, out=None):
+        """a, b: (n, 3) end points -> SEGMENT_HIT per segment.  on_device: a is a device pointer to n rows of
+        (ax ay az bx by bz) floats, b is None, out a device pointer to n SEGMENT_HIT."""
+        fl = QUERY_UNKNOWN_BLOCKS if unknown_blocks else 0
+        if on_device:
+            assert b is None
+            _check(self.L, self.L.sdm_query_segments(self.h, _ptr(int(a)), int(n), _ptr(int(out)), fl | QUERY_ON_DEVICE), "sdm_query_segments")
+            return None
+        ab = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float32).reshape(-1, 3), np.asarray(b, np.float32).reshape(-1, 3)], axis=1))
+        res = np.empty(len(ab), SEGMENT_HIT)
+        _check(self.L, self.L.sdm_query_segments(self.h, _ptr(ab), len(ab), _ptr(res), fl), "sdm_query_segments")
+        return res
+
+    def query_boxes(self, lo, hi=None, on_device=False, n=None, out=None):
+        """lo, hi: (n, 3) box corners (min, max) -> BOX_RESULT per box.  on_device: lo is a device pointer to n rows of
+        (min xyz, max xyz) floats, hi is None, out a device pointer to n BOX_RESULT."""
+        if on_device:
+            assert hi is None
+            _check(self.L, self.L.sdm_query_boxes(self.h, _ptr(int(lo)), int(n), _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_boxes")
+            return None
+        bx = np.ascontiguousarray(np.concatenate([np.asarray(lo, np.float32).reshape(-1, 3), np.asarray(hi, np.float32).reshape(-1, 3)], axis=1))
+        res = np.empty(len(bx), BOX_RESULT)
+        _check(self.L, self.L.sdm_query_boxes(self.h, _ptr(bx), len(bx), _ptr(res), 0), "sdm_query_boxes")
+        return res
 
     def occupied(self, cap=None, zero_center=False, free=False, mark_fov=False):
         cap = cap or self.v_count

@@ -1,0 +1,279 @@
+// queries.hip — batched map queries (gfx950): points, segments, boxes (include/sdm.h, "batched map queries").
+//
+// All three read the result array of the occupancy sweep (State::res, 8 B per voxel, indexed by storage index) and
+// nothing else of the map; they write only the caller's outputs.  The grid geometry (Dims) and the ring state of the
+// last issued frame (Frame: map center, ring offsets) come by value, so a query enqueued between two frames answers for
+// the frame before it whatever the host does next.  Segments and boxes only need the second word of a result (track,
+// label, occ): they gather 4 bytes per cell.
+#include "sdm_internal.h"
+
+#pragma clang fp contract(off)
+
+static_assert(sizeof(sdm_segment_hit) == 16 && sizeof(sdm_box_result) == 20 && sizeof(sdm_voxel_result) == 8, "sdm.h layouts");
+
+namespace sdm {
+
+namespace {
+
+constexpr int QTPB = 256;
+constexpr uint32_t RES_UNKNOWN_W1 = 0xff000000u;  // second word of an "unobserved" result: track 0, label 0, occ -1
+constexpr uint32_t RES_UNKNOWN_W0 = 0xbf800000u;  // wsum -1.f
+
+__device__ __forceinline__ int8_t occ_of(uint32_t w1) { return (int8_t)(w1 >> 24); }
+
+// map-index coordinate of one axis: the float32 expression of global_pos_to_voxel, without its cast
+__device__ __forceinline__ float map_u(const Dims &d, const Frame &f, int a, float p) { return ((p - f.center[a]) - d.pmin[a]) * d.recip; }
+
+// storage index of in-map cell (ix, iy, iz): the ring correction of global_pos_to_voxel
+__device__ __forceinline__ uint32_t cell_voxel(const Dims &d, const Frame &f, int ix, int iy, int iz) {
+  return ring_to_voxel(d, axis_correct(ix + f.eq[0], d.NX), axis_correct(iy + f.eq[1], d.NY), axis_correct(iz + f.eq[2], d.NZ));
+}
+
+// ---- points: one lane per query, one 8-byte gather -----------------------------------------------------------------
+__global__ __launch_bounds__(QTPB) void k_query_points(Dims d, Frame f, const float *__restrict__ xyz, uint32_t n,
+                                                       const uint2 *__restrict__ res, uint2 *__restrict__ out,
+                                                       uint32_t *__restrict__ voxel_out) {
+  const uint32_t i = blockIdx.x * QTPB + threadIdx.x;
+  if (i >= n) return;
+  const float px = xyz[3 * (size_t)i], py = xyz[3 * (size_t)i + 1], pz = xyz[3 * (size_t)i + 2];
+  uint32_t rx, ry, rz;
+  const uint32_t v = global_pos_to_voxel(d, f, px, py, pz, rx, ry, rz);  // (NaN / inf fail its range test: outside)
+  const uint2 r = v != INVALID_INDEX ? res[v] : make_uint2(RES_UNKNOWN_W0, RES_UNKNOWN_W1);
+  out[i] = r;
+  if (voxel_out) voxel_out[i] = v;
+}
+
+// ---- segments: one lane per segment, a 3-D DDA in batches of SEG_K cells -------------------------------------------
+// The cells a segment visits follow from its end points alone; only "stop here" depends on the map.  So the DDA walks
+// SEG_K cells ahead, the SEG_K loads are issued together, and then their results are tested: one memory round trip per
+// SEG_K cells instead of one per cell (a 100-cell segment taken cell by cell would wait ~100 x 900 cycles).  Every load
+// of a batch feeds the stop mask below unconditionally, so none of them can be sunk behind an earlier cell's test.
+// The DDA runs in double: crossing parameters t = (plane - u_a) * (1 / (u_b - u_a)) are computed fresh from the end
+// points for every plane (no accumulated increments), so a cell sequence differs from the exact one only where two crossings lie
+// within rounding of each other.
+constexpr int SEG_K = 8;
+enum : int { SEG_CELL = 0, SEG_OUT = 1, SEG_END = 2 };
+
+__global__ __launch_bounds__(QTPB) void k_query_segments(Dims d, Frame f, const float *__restrict__ ab, uint32_t n,
+                                                         const uint2 *__restrict__ res, sdm_segment_hit *__restrict__ out,
+                                                         int unknown_blocks) {
+  const uint32_t i = blockIdx.x * QTPB + threadIdx.x;
+  if (i >= n) return;
+  const int N[3] = {(int)d.NX, (int)d.NY, (int)d.NZ};
+  float ua[3], ub[3];
+  bool finite = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    ua[a] = map_u(d, f, a, ab[6 * (size_t)i + a]);
+    ub[a] = map_u(d, f, a, ab[6 * (size_t)i + 3 + a]);
+    finite = finite && isfinite(ua[a]) && isfinite(ub[a]);
+  }
+  float hit_t = -1.f;
+  uint32_t hit_v = INVALID_INDEX, hit_w = RES_UNKNOWN_W1;
+  int cells = 0;
+  // the state of the walk: current cell c, the t at which it was entered, per axis the t of the next plane
+  int c[3] = {0, 0, 0}, step[3] = {0, 0, 0};
+  double A[3], inv[3], tn[3];
+  double t_cur = 0.0;
+  int kind = SEG_END;  // of the current cell
+  if (!finite) {
+    if (unknown_blocks) hit_t = 0.f;
+  } else {
+    bool inside = true, empty = false;
+    double t_in = -INFINITY, t_out = INFINITY;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      A[a] = (double)ua[a];
+      const double D = (double)ub[a] - A[a];
+      inside = inside && ua[a] >= 0.f && ua[a] < (float)N[a];
+      if (D == 0.0) {
+        empty = empty || !(ua[a] >= 0.f && ua[a] < (float)N[a]);
+        inv[a] = 0.0;
+      } else {
+        inv[a] = 1.0 / D;
+        const double t0 = (0.0 - A[a]) * inv[a], t1 = ((double)N[a] - A[a]) * inv[a];
+        t_in = fmax(t_in, fmin(t0, t1));
+        t_out = fmin(t_out, fmax(t0, t1));
+      }
+      step[a] = D > 0.0 ? 1 : (D < 0.0 ? -1 : 0);
+    }
+    if (inside) {
+      kind = SEG_CELL;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) c[a] = (int)floorf(ua[a]);
+    } else if (unknown_blocks) {
+      hit_t = 0.f;  // a lies outside the map, which blocks
+    } else if (!empty && t_in <= 1.0 && t_out > 0.0 && t_in < t_out) {
+      // clipped: the walk starts where the segment enters the map (rounding at the face is clamped back into the map)
+      kind = SEG_CELL;
+      t_cur = fmax(t_in, 0.0);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) c[a] = min(max((int)floor(A[a] + t_cur * ((double)ub[a] - A[a])), 0), N[a] - 1);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) tn[a] = step[a] == 0 ? INFINITY : ((double)(c[a] + (step[a] > 0)) - A[a]) * inv[a];
+  }
+  while (kind != SEG_END) {
+    uint32_t vox[SEG_K], w[SEG_K];
+    float tin[SEG_K];
+    int kd[SEG_K];
+#pragma unroll
+    for (int k = 0; k < SEG_K; ++k) {  // the next SEG_K cells: arithmetic only
+      kd[k] = kind;
+      tin[k] = (float)t_cur;
+      vox[k] = kind == SEG_CELL ? cell_voxel(d, f, c[0], c[1], c[2]) : INVALID_INDEX;
+      if (kind == SEG_CELL) {
+        int ax = 0;  // the plane crossed next: x before y before z at equal t
+        double tm = tn[0];
+        if (tn[1] < tm) { ax = 1; tm = tn[1]; }
+        if (tn[2] < tm) { ax = 2; tm = tn[2]; }
+        if (tm > 1.0) {
+          kind = SEG_END;
+        } else {
+          const int cn = (ax == 0 ? c[0] : ax == 1 ? c[1] : c[2]) + (ax == 0 ? step[0] : ax == 1 ? step[1] : step[2]);
+          const int na = ax == 0 ? N[0] : ax == 1 ? N[1] : N[2];
+#pragma unroll
+          for (int a = 0; a < 3; ++a)
+            if (a == ax) {
+              c[a] = cn;
+              tn[a] = ((double)(cn + (step[a] > 0)) - A[a]) * inv[a];
+            }
+          t_cur = tm;
+          if (cn < 0 || cn >= na) kind = SEG_OUT;
+        }
+      } else {
+        kind = SEG_END;  // (after the cell outside the map there is nothing: the map is convex)
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < SEG_K; ++k) w[k] = res[kd[k] == SEG_CELL ? vox[k] : 0u].y;  // SEG_K independent loads
+    uint32_t stop = 0;
+#pragma unroll
+    for (int k = 0; k < SEG_K; ++k) {
+      const int8_t o = occ_of(w[k]);
+      const bool blocks = o >= 1 || (unknown_blocks && o == -1);
+      stop |= (uint32_t)(kd[k] != SEG_CELL || blocks) << k;
+    }
+    if (!stop) {
+      cells += SEG_K;
+      continue;
+    }
+    const int first = __builtin_ctz(stop);
+    int fk = SEG_END;
+    float ft = 0.f;
+    uint32_t fv = INVALID_INDEX, fw = RES_UNKNOWN_W1;
+#pragma unroll
+    for (int k = 0; k < SEG_K; ++k)  // (selected by compile-time index: no register array indexed at run time)
+      if (k == first) {
+        fk = kd[k];
+        ft = tin[k];
+        fv = vox[k];
+        fw = w[k];
+      }
+    cells += first + (fk == SEG_CELL ? 1 : 0);
+    if (fk == SEG_CELL) {
+      hit_t = ft;
+      hit_v = fv;
+      hit_w = fw;
+    } else if (fk == SEG_OUT && unknown_blocks) {
+      hit_t = ft;
+    }
+    break;
+  }
+  sdm_segment_hit h;
+  h.t = hit_t;
+  h.voxel = hit_v;
+  h.cells = cells;
+  __builtin_memcpy(&h.track, &hit_w, 4);
+  uint4 v;
+  __builtin_memcpy(&v, &h, 16);
+  reinterpret_cast<uint4 *>(out)[i] = v;
+}
+
+// ---- boxes: one wave per box, lanes along x ------------------------------------------------------------------------
+// The box's cells are numbered x fastest, so consecutive lanes read consecutive cells of an x row (contiguous in storage
+// except where the ring wraps), and a narrow footprint still keeps all 64 lanes busy.  Each lane takes BOX_U cells per
+// round, loads first.  Counts are wave-wide ballots (popcount in scalar registers), first_occupied a min over the wave.
+constexpr int BOX_U = 4;
+
+__global__ __launch_bounds__(QTPB) void k_query_boxes(Dims d, Frame f, const float *__restrict__ boxes, uint32_t n,
+                                                      const uint2 *__restrict__ res, sdm_box_result *__restrict__ out) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t b = blockIdx.x * (QTPB / 64) + (threadIdx.x >> 6);
+  if (b >= n) return;
+  const int N[3] = {(int)d.NX, (int)d.NY, (int)d.NZ};
+  int lo[3], w[3];
+  bool valid = true, clipped = false, empty = false;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float pl = boxes[6 * (size_t)b + a], ph = boxes[6 * (size_t)b + 3 + a];
+    valid = valid && isfinite(pl) && isfinite(ph) && pl <= ph;
+    const float fl = floorf(map_u(d, f, a, pl)), fh = floorf(map_u(d, f, a, ph));
+    clipped = clipped || fl < 0.f || fh >= (float)N[a];
+    // (clamped in float - a coordinate far outside may overflow u to +-inf -: the casts see values inside the map only)
+    const int l = (int)fmaxf(fl, 0.f), h = (int)fminf(fh, (float)(N[a] - 1));
+    lo[a] = l;
+    w[a] = h - l + 1;
+    empty = empty || !(fl <= (float)(N[a] - 1) && fh >= 0.f);
+  }
+  uint32_t n_occ = 0, n_free = 0, n_unk = 0, first = INVALID_INDEX;
+  if (valid && !empty) {
+    const uint32_t wx = (uint32_t)w[0], wxy = wx * (uint32_t)w[1], total = wxy * (uint32_t)w[2];
+    for (uint32_t base = 0; base < total; base += 64u * BOX_U) {
+      uint32_t vox[BOX_U], r[BOX_U];
+      bool in[BOX_U];
+#pragma unroll
+      for (int u = 0; u < BOX_U; ++u) {
+        const uint32_t k = base + (uint32_t)u * 64u + lane;
+        in[u] = k < total;
+        const uint32_t z = k / wxy, rem = k - z * wxy, y = rem / wx, x = rem - y * wx;
+        vox[u] = in[u] ? cell_voxel(d, f, lo[0] + (int)x, lo[1] + (int)y, lo[2] + (int)z) : 0u;
+      }
+#pragma unroll
+      for (int u = 0; u < BOX_U; ++u) r[u] = res[vox[u]].y;
+#pragma unroll
+      for (int u = 0; u < BOX_U; ++u) {
+        const int8_t o = occ_of(r[u]);
+        const bool occ = in[u] && o >= 1;
+        n_occ += (uint32_t)__popcll(__ballot(occ));
+        n_free += (uint32_t)__popcll(__ballot(in[u] && o == 0));
+        n_unk += (uint32_t)__popcll(__ballot(in[u] && o == -1));
+        if (occ) first = min(first, vox[u]);
+      }
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) first = min(first, (uint32_t)__shfl_xor((int)first, s, 64));
+  }
+  if (lane == 0) {
+    sdm_box_result o;
+    o.n_occupied = (int32_t)n_occ;
+    o.n_free = (int32_t)n_free;
+    o.n_unknown = (int32_t)n_unk;
+    o.first_occupied = first;
+    o.clipped = valid && clipped ? 1 : 0;
+    out[b] = o;
+  }
+}
+
+}  // namespace
+
+void launch_query_points(const Dims &d, const Frame &f, const State &st, const float *xyz, uint32_t n, sdm_voxel_result *out,
+                         uint32_t *voxel_out, hipStream_t s) {
+  hipLaunchKernelGGL(k_query_points, dim3((n + QTPB - 1) / QTPB), dim3(QTPB), 0, s, d, f, xyz, n,
+                     reinterpret_cast<const uint2 *>(st.res), reinterpret_cast<uint2 *>(out), voxel_out);
+}
+
+void launch_query_segments(const Dims &d, const Frame &f, const State &st, const float *ab, uint32_t n, sdm_segment_hit *out,
+                           int unknown_blocks, hipStream_t s) {
+  hipLaunchKernelGGL(k_query_segments, dim3((n + QTPB - 1) / QTPB), dim3(QTPB), 0, s, d, f, ab, n,
+                     reinterpret_cast<const uint2 *>(st.res), out, unknown_blocks);
+}
+
+void launch_query_boxes(const Dims &d, const Frame &f, const State &st, const float *boxes, uint32_t n, sdm_box_result *out,
+                        hipStream_t s) {
+  constexpr uint32_t per_block = QTPB / 64;
+  hipLaunchKernelGGL(k_query_boxes, dim3((n + per_block - 1) / per_block), dim3(QTPB), 0, s, d, f, boxes, n,
+                     reinterpret_cast<const uint2 *>(st.res), out);
+}
+
+}  // namespace sdm

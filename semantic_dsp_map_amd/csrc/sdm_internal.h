@@ -653,4 +653,12 @@ int radix_sort_pairs(uint32_t *keys_a, uint32_t *vals_a, uint32_t *keys_b, uint3
 
 void launch_clear(const Dims &d, const State &st, hipStream_t s, bool fresh);
 
+// ---- batched map queries (queries.hip): read State::res only, write the caller's outputs; n > 0 ----------------------
+void launch_query_points(const Dims &d, const Frame &f, const State &st, const float *xyz, uint32_t n, sdm_voxel_result *out,
+                         uint32_t *voxel_out, hipStream_t s);
+void launch_query_segments(const Dims &d, const Frame &f, const State &st, const float *ab, uint32_t n, sdm_segment_hit *out,
+                           int unknown_blocks, hipStream_t s);
+void launch_query_boxes(const Dims &d, const Frame &f, const State &st, const float *boxes, uint32_t n, sdm_box_result *out,
+                        hipStream_t s);
+
 }  // namespace sdm
