@@ -489,6 +489,49 @@ typedef struct {          /* 20 bytes; only cells inside the map are counted */
 } sdm_box_result;
 sdm_status sdm_query_boxes(sdm_map *m, const float *boxes, int64_t n, sdm_box_result *out, uint32_t flags);
 
+/* ---- Euclidean distance field (ESDF) of the map block, and distance queries on it ----
+ * sdm_esdf_update enqueues, on the map's stream, an exact Euclidean distance transform of the result array of the last
+ * frame enqueued before the call, and returns without waiting.  The field is a snapshot: it answers for that frame -
+ * its map center and ring offsets are kept with it - until the next sdm_esdf_update, whatever frames, sdm_clear,
+ * sdm_load_state or sdm_set_ring_state come in between.
+ * Obstacles: cells with occ >= 1 (occupied or guessed occupied, as segments block); with SDM_ESDF_UNKNOWN_IS_OBSTACLE
+ * also occ == -1; with SDM_ESDF_STATIC_ONLY no cell whose winning track is movable (1 <= track <= max_movable_track;
+ * track 0 is static).  The map is a block, not a torus: the ring's wrap point is not a neighbour relation, and the
+ * space outside the map is never an obstacle, under any flag (unlike SDM_QUERY_UNKNOWN_BLOCKS for segments).
+ * Metric: between cell centres in map-index cells (cell (i, j, k) as above).  Per cell the field holds site, the
+ * map-index cell i | j << x_n | k << (x_n + y_n) of a nearest obstacle (any one where several are equally near), and
+ * d2 = |cell - site|^2, its exact squared distance in cells.  A field without any obstacle holds 0xffffffff in both.
+ * Memory: 8 bytes per voxel of device memory (4 B site, 4 B snapshot of each cell's result word track / label / occ),
+ * allocated at the first sdm_esdf_update and freed by sdm_destroy: 134 MB at 256^3, 1.07 GB at 512^3.  The build uses no
+ * scratch of the frames'.
+ * Errors: SDM_ERR_INVALID_ARGUMENT for unknown flag bits, a Z-slab shard (shard_count > 1), and sdm_get_esdf or
+ * sdm_query_distance before any sdm_esdf_update. */
+#define SDM_ESDF_UNKNOWN_IS_OBSTACLE 0x1u
+#define SDM_ESDF_STATIC_ONLY 0x2u
+sdm_status sdm_esdf_update(sdm_map *m, uint32_t flags);
+/* Host copies of the field in map-index order (x fastest, then y, then z), NX*NY*NZ entries each; any of the three may
+ * be NULL; waits.  origin = the global position of the min corner of cell (0,0,0) of the snapshot, center + pmin in
+ * float32. */
+sdm_status sdm_get_esdf(sdm_map *m, uint32_t *d2, uint32_t *site, float origin[3]);
+/* Distance of points xyz[3i..3i+2] (global frame) from the field's obstacles.  A point's cell is floor(u) per axis (as
+ * for segments and boxes), u taken with the snapshot's map center.  The distance is the trilinear interpolation of
+ * D(c) = sqrtf((float)d2(c)) * voxel_size between cell centres: per axis s = u - 0.5, i0 = floor(s), t = s - i0, corners
+ * clamp(i0, 0, N-1) and clamp(i0 + 1, 0, N-1) - so it is constant beyond the outermost cell centres, with gradient 0
+ * along that axis.  No answer (a point outside the map, a non-finite coordinate, a field without obstacles): d2
+ * 0xffffffff, distance -1, gradient 0, nearest NaN, track / label / occ 0 / 0 / -1.  Flags: SDM_QUERY_ON_DEVICE, as for
+ * the queries above; n == 0 launches nothing. */
+typedef struct {      /* 36 bytes */
+  float distance;     /* metres: the interpolated D; -1 = no answer */
+  float gradient[3];  /* d distance / d position of that interpolant, per metre; 0 where no answer */
+  float nearest[3];   /* centre of the nearest obstacle of the point's cell, global frame:
+                         (center + pmin) + ((float)site + 0.5f) * voxel_size; NaN where no answer */
+  uint32_t d2;        /* of the point's cell; 0xffffffff = no answer */
+  uint16_t track;     /* snapshot result of that nearest obstacle cell */
+  uint8_t label;
+  int8_t occ;         /* 1 or 2, or -1 when unknown cells count as obstacles */
+} sdm_distance_result;
+sdm_status sdm_query_distance(sdm_map *m, const float *xyz, int64_t n, sdm_distance_result *out, uint32_t flags);
+
 /* ---- owner sets of the object layer: ObjectParticleHashMap (object_layer.h:20-52) */
 sdm_status sdm_object_particle_count(sdm_map *m, int32_t track_id, int64_t *count);
 /* The keys of ObjectParticleHashMap::indices_map whose sets are not empty: every track id that owns at least one slot of

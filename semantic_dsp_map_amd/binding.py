@@ -27,6 +27,12 @@ BOX_RESULT = np.dtype([("n_occupied", "<i4"), ("n_free", "<i4"), ("n_unknown", "
 assert SEGMENT_HIT.itemsize == 16 and BOX_RESULT.itemsize == 20
 QUERY_ON_DEVICE = 0x1
 QUERY_UNKNOWN_BLOCKS = 0x2
+# the distance field (sdm.h: sdm_esdf_update / sdm_query_distance)
+DISTANCE_RESULT = np.dtype([("distance", "<f4"), ("gradient", "<f4", (3,)), ("nearest", "<f4", (3,)), ("d2", "<u4"), ("track", "<u2"),
+                            ("label", "u1"), ("occ", "i1")])
+assert DISTANCE_RESULT.itemsize == 36
+ESDF_UNKNOWN_IS_OBSTACLE = 0x1
+ESDF_STATIC_ONLY = 0x2
 
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
@@ -164,6 +170,9 @@ def load_library():
         "sdm_query_points": [vp, vp, i64, vp, vp, u32],
         "sdm_query_segments": [vp, vp, i64, vp, u32],
         "sdm_query_boxes": [vp, vp, i64, vp, u32],
+        "sdm_esdf_update": [vp, u32],
+        "sdm_get_esdf": [vp, vp, vp, vp],
+        "sdm_query_distance": [vp, vp, i64, vp, u32],
         "sdm_object_particle_count": [vp, i32, C.POINTER(i64)],
         "sdm_tracks_with_particles": [vp, vp, i32, C.POINTER(i32)],
         "sdm_comm_set_options": [vp, i32, i32],
@@ -511,6 +520,32 @@ class SdmMap:
         bx = np.ascontiguousarray(np.concatenate([np.asarray(lo, np.float32).reshape(-1, 3), np.asarray(hi, np.float32).reshape(-1, 3)], axis=1))
         res = np.empty(len(bx), BOX_RESULT)
         _check(self.L, self.L.sdm_query_boxes(self.h, _ptr(bx), len(bx), _ptr(res), 0), "sdm_query_boxes")
+        return res
+
+    # ---- the distance field (sdm.h).  esdf_update enqueues a build on the map's stream from the last frame's results;
+    # esdf() and query_distance() answer for that frame until the next build.
+    def esdf_update(self, unknown_is_obstacle=False, static_only=False):
+        fl = (ESDF_UNKNOWN_IS_OBSTACLE if unknown_is_obstacle else 0) | (ESDF_STATIC_ONLY if static_only else 0)
+        _check(self.L, self.L.sdm_esdf_update(self.h, fl), "sdm_esdf_update")
+
+    def esdf(self):
+        """-> (d2, site, origin): uint32 arrays shaped [NZ, NY, NX] in map-index order, origin the global position of the
+        min corner of cell (0, 0, 0) of the field's snapshot (float32[3])"""
+        c = self.cfg
+        shape = (1 << c.z_n, 1 << c.y_n, 1 << c.x_n)
+        d2, site, origin = np.empty(shape, np.uint32), np.empty(shape, np.uint32), np.empty(3, np.float32)
+        _check(self.L, self.L.sdm_get_esdf(self.h, _ptr(d2), _ptr(site), _ptr(origin)), "sdm_get_esdf")
+        return d2, site, origin
+
+    def query_distance(self, xyz, on_device=False, n=None, out=None):
+        """xyz: (n, 3) global positions -> DISTANCE_RESULT per point.  on_device: xyz and out (n DISTANCE_RESULT) are
+        device pointers, as for query_points."""
+        if on_device:
+            _check(self.L, self.L.sdm_query_distance(self.h, _ptr(int(xyz)), int(n), _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_distance")
+            return None
+        p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        res = np.empty(len(p), DISTANCE_RESULT)
+        _check(self.L, self.L.sdm_query_distance(self.h, _ptr(p), len(p), _ptr(res), 0), "sdm_query_distance")
         return res
 
     def occupied(self, cap=None, zero_center=False, free=False, mark_fov=False):

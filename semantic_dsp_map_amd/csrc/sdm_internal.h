@@ -661,4 +661,11 @@ void launch_query_segments(const Dims &d, const Frame &f, const State &st, const
 void launch_query_boxes(const Dims &d, const Frame &f, const State &st, const float *boxes, uint32_t n, sdm_box_result *out,
                         hipStream_t s);
 
+// ---- distance field (esdf.hip): the build reads State::res through f's ring correction and writes site / snap (V words
+// each, map-index order); the query reads only site / snap, f being the field's snapshot --------------------------------
+hipError_t launch_esdf_build(const Dims &d, const Frame &f, const State &st, uint32_t flags, uint32_t *site, uint32_t *snap,
+                             hipStream_t s);
+void launch_query_distance(const Dims &d, const Frame &f, const uint32_t *site, const uint32_t *snap, const float *xyz, uint32_t n,
+                           sdm_distance_result *out, hipStream_t s);
+
 }  // namespace sdm
