@@ -1252,7 +1252,7 @@ __global__ __launch_bounds__(TPB) DENSE_WAVES_ATTR void k_occupancy_dense(Dims d
   uint32_t n_eval = 0;
   if (!densebits) return;  // nothing of this wave's was left to this kernel (its hint is and stays 0)
   {
-  if (fused) {  // (lanes beyond the end of the map read the arrays' padding)
+  if (fused) {  // (lanes beyond the end of the map read the arrays' padding: both hold whole groups, sdm_create)
     meta_t[wave][lane] = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(st.vts + lvw) + lane);
     meta_f[wave][lane] = __builtin_nontemporal_load(reinterpret_cast<const v2u *>(st.vflag + lvw) + lane);
   }

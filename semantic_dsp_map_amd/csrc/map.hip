@@ -1023,8 +1023,11 @@ sdm_status sdm_create(const sdm_config *cfg, sdm_map **out) {
   // one record per voxel: w | ts | track | label (sdm_internal.h); one chunk of 64 records of padding behind the last, so
   // that the sweep's chunk-wide loads need no clamp at the end of the map (k_occupancy_dense)
   A(m->st.rec, rec_array_bytes(d.v_count, d.S));
-  A(m->st.vts, (size_t)d.v_count + 64);    // (+ one chunk: the sweep's chunk-wide loads need no clamp at the end of the map)
-  A(m->st.vflag, (size_t)d.v_count + 64);
+  // stamps and flags: whole 512-voxel groups plus one chunk - the sweep's chunk-wide loads need no clamp at the end of the
+  // map, and a wave of k_occupancy_dense on its fused path loads a whole group's (maps of 64, 128 or 256 voxels are less)
+  const size_t v_groups = ((size_t)d.v_count + 511) / 512 * 512;
+  A(m->st.vts, v_groups + 64);
+  A(m->st.vflag, v_groups + 64);
   m->st.tile_stride = (uint32_t)tile_mark_bytes(d);
   A(m->st.tile_dirty, 2 * (size_t)m->st.tile_stride);
   A(m->st.occ_need, ((size_t)d.v_count + 63) / 64 + 32);

@@ -42,11 +42,24 @@ def random_state(cfg, seed, run=1, kinds=(0.25, 0.25, 0.5)):
     return st
 
 
+def stamp_slabs(nx, ny, nz):
+    """Which slabs stamps_for re-stamps on axes of nx, ny, nz cells: x 3..5, y 10 and z 20..21 where the axes are long
+    enough (32 cells and more), else slabs at the same fractions of the axis (x 3/32 .. 6/32, y 10/32, z 20/32 .. 22/32),
+    at least one cell each and never the whole axis -> (x slice, y index, z slice)"""
+    def frac(n, a, b):
+        if n >= 32:
+            return slice(a, b)
+        lo = a * n // 32
+        return slice(lo, max(lo + 1, min(b * n // 32, n - 1)))
+    return frac(nx, 3, 6), (10 if ny >= 32 else 10 * ny // 32), frac(nz, 20, 22)
+
+
 def stamps_for(o):
     """The initial stamp arrays of a map with a few slabs re-stamped at frame 2 and 3 (slots with an older stamp in them
     are stale) and the ring state at frame 3."""
     sx, sy, sz = (a.copy() for a in o.stamps())
-    sx[3:6] = 2
-    sy[10] = 3
-    sz[20:22] = 2
+    xs, yi, zs = stamp_slabs(len(sx), len(sy), len(sz))
+    sx[xs] = 2
+    sy[yi] = 3
+    sz[zs] = 2
     return (sx, sy, sz), dict(o.ring_state(), global_time_stamp=3)
