@@ -152,7 +152,8 @@ typedef struct {
   int64_t n_birth_attempts;
   int64_t n_birth_success;
   int64_t n_resampled_voxels;
-  int64_t n_moved;
+  int64_t n_moved;          /* particles of moving objects the last update copied, over the whole map (every shard). At most
+                               min(slots of the whole map, 2^18) per frame, whatever shard_count is; more: SDM_ERR_CAPACITY */
   int64_t n_move_reinserted;
   int64_t n_frustum_voxels;
   int64_t n_occupied;

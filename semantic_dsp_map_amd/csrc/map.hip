@@ -753,6 +753,20 @@ sdm_status check_counters(sdm_map *m, Counters *out) {
               "moving objects' sets at once): the owner sets are incomplete until sdm_clear / sdm_load_state");
     return SDM_ERR_CAPACITY;
   }
+  if (c.overflow && c.n_halo_dropped > 0) {
+    char buf[200];
+    snprintf(buf, sizeof(buf), "export segments overflowed: %u slab-crossing copies beyond %u per destination shard were dropped "
+             "(raise halo_cap)", c.n_halo_dropped, m->sc.halo_cap);
+    set_error("capacity", __FILE__, __LINE__, buf);
+    return SDM_ERR_CAPACITY;
+  }
+  if (c.overflow && c.n_moved > m->sc.cap_move) {
+    char buf[160];
+    snprintf(buf, sizeof(buf), "moved-copy list overflowed: %u particles of moving objects in one frame, more than %u", c.n_moved,
+             m->sc.cap_move);
+    set_error("capacity", __FILE__, __LINE__, buf);
+    return SDM_ERR_CAPACITY;
+  }
   if (c.overflow) {
     set_error("capacity", __FILE__, __LINE__, "visible-particle or move list overflowed: more visible particles than sdm_config.max_visible, more in ONE image row than "
               "max(2 max_visible / height, 2 width slots) - raise max_visible -, or more than 2^20 in one pixel's bin");
@@ -1120,7 +1134,9 @@ sdm_status sdm_create(const sdm_config *cfg, sdm_map **out) {
   HIP_TRY(hipEventCreateWithFlags(&m->ev_copy, hipEventDisableTiming));
   A(sc.b_valid, hw + 1);
   A(sc.b_rank, hw + 1);
-  sc.cap_move = (uint32_t)std::min<size_t>(n_slots, (size_t)1 << 18);  // moved particles per frame (objects hold <= ~1e5)
+  // moved particles per frame (objects hold <= ~1e5).  A copy's rank is global - it counts the members of every shard
+  // (k_move_apply) - and indexes mv_copy / mv_next on every shard, so the capacity follows the whole map, not the slab
+  sc.cap_move = (uint32_t)std::min<size_t>((size_t)d.V * d.S, (size_t)1 << 18);
   A(m->d_counts_local, HALO_OBJ);
   const size_t mv_cnt_n = move_count_elems();
   A(sc.mv_cnt, mv_cnt_n);

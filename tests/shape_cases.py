@@ -72,12 +72,13 @@ def quat_mat(q):
                      [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]], np.float64)
 
 
-def drive(name, params, n_frames, seed):
+def drive(name, params, n_frames, seed, cfg=None):
     """random_frame's frames for case `name` on a free-running camera: steps of about one voxel on every axis (the ring
     follows the camera cell by cell, both ways), and at n_frames // 2 one jump of more than half the map on every axis.
-    Yields (t, depth, cloud, pos float32, q float32, moves, remove)."""
-    cfg = config(name)
-    T = rot_x(CASES[name]["tilt"])
+    `cfg` (name None): another grid and camera, untilted.  Yields (t, depth, cloud, pos float32, q float32, moves, remove)."""
+    tilt = CASES[name]["tilt"] if name is not None else 0.0
+    cfg = config(name) if cfg is None else cfg
+    T = rot_x(tilt)
     rng = np.random.default_rng(seed)
     size = cfg["voxel_size"]
     N = np.array([1 << cfg["x_n"], 1 << cfg["y_n"], 1 << cfg["z_n"]], np.float64)
@@ -88,7 +89,7 @@ def drive(name, params, n_frames, seed):
             pos = pos + (N // 2 + 3) * size * np.array([1.0, -1.0, 1.0])
         yaw += rng.normal(0, 0.08)
         depth, cloud, mv, remove = random_frame(rng, cfg, params, t, pos, yaw)
-        if CASES[name]["tilt"]:
+        if tilt:
             valid = cloud["is_valid"] != 0
             p = np.stack([cloud["x"], cloud["y"], cloud["z"]], 1).astype(np.float64)
             p = (p - pos) @ T.T + pos
@@ -134,10 +135,11 @@ def crafted_ring(cfg, steps):
                 birth_cursor=0, move_cursor=0)
 
 
-def crafted_state(cfg, ring, occupied=(), unknown=(), tracks=None, labels=None):
+def crafted_state(cfg, ring, occupied=(), unknown=(), tracks=None, labels=None, owner=None, slots=1):
     """a state for load_state: every cell observed and free (slot 0 stamped at GTS), except the map cells `unknown`
-    (never observed: occ -1) and `occupied` (one particle of weight W_OBSTACLE in slot 1, track / label per cell, default a
-    static building).  Cells are (x, y, z) map indices; they are placed with query_ref.Geometry.voxel."""
+    (never observed: occ -1) and `occupied` (a particle of weight W_OBSTACLE in each of slots 1 .. `slots`, track / label
+    per cell, default a static building; `owner`: the track whose object set holds them, default none).  Cells are
+    (x, y, z) map indices; they are placed with query_ref.Geometry.voxel."""
     from semantic_dsp_map_amd import binding
     geo = qr.Geometry(cfg, ring)
     S = 1 << cfg["p_n"]
@@ -152,14 +154,17 @@ def crafted_state(cfg, ring, occupied=(), unknown=(), tracks=None, labels=None):
         st["ts"][geo.voxel(unknown).astype(np.int64) * S] = 0
     occupied = np.asarray(occupied, np.int64).reshape(-1, 3)
     if len(occupied):
-        idx = geo.voxel(occupied).astype(np.int64) * S + 1
-        st["status"][idx] = ST_UPDATED
-        st["w"][idx] = W_OBSTACLE
-        st["ts"][idx] = GTS
-        st["track"][idx] = synth.TRACK_BUILDING if tracks is None else tracks
-        st["label"][idx] = synth.LABEL_BUILDING if labels is None else labels
         p = (geo.center + geo.pmin) + (occupied.astype(np.float32) + np.float32(0.5)) * size   # the cell's centre
-        st["px"][idx], st["py"][idx], st["pz"][idx] = p[:, 0], p[:, 1], p[:, 2]
+        for slot in range(1, slots + 1):
+            idx = geo.voxel(occupied).astype(np.int64) * S + slot
+            st["status"][idx] = ST_UPDATED
+            st["w"][idx] = W_OBSTACLE
+            st["ts"][idx] = GTS
+            st["track"][idx] = synth.TRACK_BUILDING if tracks is None else tracks
+            st["label"][idx] = synth.LABEL_BUILDING if labels is None else labels
+            st["px"][idx], st["py"][idx], st["pz"][idx] = p[:, 0], p[:, 1], p[:, 2]
+            if owner is not None:
+                st["owner"][idx] = owner
     return st
 
 

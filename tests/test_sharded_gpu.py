@@ -48,7 +48,10 @@ def all_to_all(shards, src_attr, dst_attr, piece):
     return src
 
 
-def run_frame(shards, frame, remove_tracks=None):
+def run_frame(shards, frame, remove_tracks=None, headers=False, sync=True):
+    """one frame through every shard, the test playing the collectives -> the slab-crossing copies exported; headers:
+    (that, hdr) with hdr[s, d] the raw count in the header of shard s's export segment towards d (beyond the segment's
+    capacity when copies were dropped); sync=False leaves the shards' sdm_synchronize to the caller"""
     depth, cloud, pos, q, moves = frame
     G = len(shards)
     has_moves = len(moves) > 0
@@ -64,9 +67,11 @@ def run_frame(shards, frame, remove_tracks=None):
         for s in shards:
             s.m.frame_moves()
     exported = 0
+    hdr = np.zeros((G, G), np.int64)
     if has_moves:
         src = all_to_all(shards, "send", "recv", shards[0].seg)
         exported = int(sum(int(x[:, :4].copy().view(np.uint32).sum()) for x in src))
+        hdr = np.stack([x[:, :4].copy().view(np.uint32)[:, 0] for x in src]).astype(np.int64)
     for s in shards:
         s.m.frame_predict()
     all_to_all(shards, "ck_part", "ck_stage", shards[0].chunk * 4)
@@ -75,9 +80,10 @@ def run_frame(shards, frame, remove_tracks=None):
     gather(shards, "ck_full", "ck_full", shards[0].chunk * 4, src_offset=lambda r: r * shards[0].chunk * 4)
     for s in shards:
         s.m.update_finish(s.ck_full, 1)
-    for s in shards:
-        s.m.synchronize()
-    return exported
+    if sync:
+        for s in shards:
+            s.m.synchronize()
+    return (exported, hdr) if headers else exported
 
 
 def compare_union(o, shards, t, S):
@@ -215,10 +221,11 @@ print("OK")
     assert r.returncode == 0 and "OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
-@pytest.mark.parametrize("G,params_name,seed", [(2, "vkitti2", 5), (4, "noisy3", 6)])
+@pytest.mark.parametrize("G,params_name,seed", [(2, "vkitti2", 5), (4, "noisy3", 6), (16, "vkitti2", 7), (32, "noisy3", 8)])
 def test_shards_match_oracle_on_random_frames(G, params_name, seed):
     """The seeded random frames of tests/test_fuzz_gpu.py (overlapping tracks, re-used owner slots, removals are left
-    out: the split frame entry points take none) through G Z-slab shards against the unsharded oracle, 50 frames."""
+    out: the split frame entry points take none) through G Z-slab shards against the unsharded oracle, 50 frames.  At
+    G = 16 and 32 a slab is two planes or one: copies are exported to shards that are not neighbours."""
     from tests.test_fuzz_gpu import random_frame
     cfg = synth.CONFIGS["T0"]
     params = synth.PARAMS[params_name]
@@ -230,18 +237,26 @@ def test_shards_match_oracle_on_random_frames(G, params_name, seed):
     pos = np.zeros(3)
     yaw = 0.0
     exported = 0
-    for t in range(50):
-        pos = pos + rng.normal(0, 0.35, 3) * np.array([1.0, 0.2, 1.0])
-        yaw += rng.normal(0, 0.08)
-        depth, cloud, mv, _ = random_frame(rng, cfg, params, t, pos, yaw)
-        frame = (depth, cloud, pos.astype(np.float32), synth.yaw_quat(yaw).astype(np.float32), mv)
-        o.update(*frame)
-        exported += run_frame(shards, frame)
-        if t % 10 == 9:
-            compare_union(o, shards, t, S)
-    assert exported > 0 and o.stats()["alias_events"] > 0
-    for s in shards:
-        s.m.close()
+    far = 0   # copies exported to a shard two slabs away or more (either way round the ring)
+    try:
+        for t in range(50):
+            pos = pos + rng.normal(0, 0.35, 3) * np.array([1.0, 0.2, 1.0])
+            yaw += rng.normal(0, 0.08)
+            depth, cloud, mv, _ = random_frame(rng, cfg, params, t, pos, yaw)
+            frame = (depth, cloud, pos.astype(np.float32), synth.yaw_quat(yaw).astype(np.float32), mv)
+            o.update(*frame)
+            n, hdr = run_frame(shards, frame, headers=True)
+            exported += n
+            ring = np.abs(np.subtract.outer(np.arange(G), np.arange(G)))
+            far += int(hdr[np.minimum(ring, G - ring) >= 2].sum())
+            if t % 10 == 9:
+                compare_union(o, shards, t, S)
+        assert exported > 0 and o.stats()["alias_events"] > 0
+        if G >= 32:
+            assert far > 0, "no copy crossed more than one slab"
+    finally:
+        for s in shards:
+            s.m.close()
 
 
 @pytest.mark.parametrize("G,params_name,seed", [(4, "vkitti2", 11), (4, "noisy3", 12)])
