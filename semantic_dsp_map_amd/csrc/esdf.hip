@@ -16,7 +16,7 @@
 // fits in 31 bits.
 // The distance query reads the field and the snapshot only, never State: the field answers for the frame it was built
 // from until the next build.
-#include "sdm_internal.h"
+#include "sdm_map.h"
 
 #pragma clang fp contract(off)
 
@@ -265,3 +265,86 @@ void launch_query_distance(const Dims &d, const Frame &f, const uint32_t *site, 
 }
 
 }  // namespace sdm
+
+// ---- the host side: the entry points behind include/sdm.h ---------------------------------------------------------
+// The build reads the result array in stream order and takes the host Frame of the last issued frame by value, as the
+// queries do; the Frame is kept with the field, so that the distance query and sdm_get_esdf answer for that frame.
+namespace {
+sdm_status esdf_check(sdm_map *m, const char *what, bool need_field) {
+  if (m->cfg.shard_count > 1) {
+    set_error(what, __FILE__, __LINE__, "the distance field of a Z-slab shard (shard_count > 1) is not supported: build it on a whole map");
+    return SDM_ERR_INVALID_ARGUMENT;
+  }
+  if (need_field && !m->esdf_valid) {
+    set_error(what, __FILE__, __LINE__, "no distance field: call sdm_esdf_update first");
+    return SDM_ERR_INVALID_ARGUMENT;
+  }
+  return SDM_OK;
+}
+}  // namespace
+extern "C" {
+
+sdm_status sdm_esdf_update(sdm_map *m, uint32_t flags) {
+  if (!m) return SDM_ERR_INVALID_ARGUMENT;
+  if (flags & ~(SDM_ESDF_UNKNOWN_IS_OBSTACLE | SDM_ESDF_STATIC_ONLY)) {
+    set_error("sdm_esdf_update", __FILE__, __LINE__, "unknown flag bits");
+    return SDM_ERR_INVALID_ARGUMENT;
+  }
+  const sdm_status e = esdf_check(m, "sdm_esdf_update", false);
+  if (e != SDM_OK) return e;
+  HIP_TRY(hipSetDevice(m->device));
+  if (!m->d_esdf_site) SDM_TRY(alloc_tracked(m, &m->d_esdf_site, m->d.V));
+  if (!m->d_esdf_snap) SDM_TRY(alloc_tracked(m, &m->d_esdf_snap, m->d.V));
+  const Frame f = m->f;
+  HIP_TRY(launch_esdf_build(m->d, f, m->st, flags, m->d_esdf_site, m->d_esdf_snap, m->stream));
+  m->esdf_f = f;
+  m->esdf_valid = true;
+  return SDM_OK;
+}
+
+sdm_status sdm_get_esdf(sdm_map *m, uint32_t *d2, uint32_t *site, float origin[3]) {
+  if (!m) return SDM_ERR_INVALID_ARGUMENT;
+  const sdm_status e = esdf_check(m, "sdm_get_esdf", true);
+  if (e != SDM_OK) return e;
+  HIP_TRY(hipSetDevice(m->device));
+  const Dims &d = m->d;
+  std::vector<uint32_t> own;
+  uint32_t *s = site;
+  if (d2 && !s) {
+    own.resize(d.V);
+    s = own.data();
+  }
+  if (s) HIP_TRY(hipMemcpyAsync(s, m->d_esdf_site, (size_t)d.V * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  if (d2) {
+    for (uint32_t c = 0; c < d.V; ++c) {
+      const uint32_t v = s[c];
+      if (v == INVALID_INDEX) {
+        d2[c] = INVALID_INDEX;
+        continue;
+      }
+      const int dx = (int)(c & (d.NX - 1)) - (int)(v & (d.NX - 1));
+      const int dy = (int)((c >> d.x_n) & (d.NY - 1)) - (int)((v >> d.x_n) & (d.NY - 1));
+      const int dz = (int)(c >> (d.x_n + d.y_n)) - (int)(v >> (d.x_n + d.y_n));
+      d2[c] = (uint32_t)(dx * dx + dy * dy + dz * dz);
+    }
+  }
+  if (origin)
+    for (int a = 0; a < 3; ++a) origin[a] = m->esdf_f.center[a] + d.pmin[a];
+  return SDM_OK;
+}
+
+sdm_status sdm_query_distance(sdm_map *m, const float *xyz, int64_t n, sdm_distance_result *out, uint32_t flags) {
+  sdm_status e = query_check(m, xyz, n, out, flags, SDM_QUERY_ON_DEVICE, "sdm_query_distance");
+  if (e != SDM_OK) return e;
+  e = esdf_check(m, "sdm_query_distance", true);
+  if (e != SDM_OK) return e;
+  const Frame f = m->esdf_f;
+  const uint32_t *site = m->d_esdf_site, *snap = m->d_esdf_snap;
+  return run_query(m, xyz, 12, out, sizeof(sdm_distance_result), nullptr, 0, n, flags,
+                   [m, f, site, snap](const void *in, void *o, void *, uint32_t c, hipStream_t s) {
+                     launch_query_distance(m->d, f, site, snap, static_cast<const float *>(in), c, static_cast<sdm_distance_result *>(o), s);
+                   });
+}
+
+}  // extern "C"

@@ -360,7 +360,7 @@ __global__ __launch_bounds__(TPB) void k_set_frame(FrameArgs *__restrict__ dst, 
 //   k_occupancy_scan + k_occupancy_dense  the non-incremental sweep (first sweep of a state: sdm_load_state,
 //                    sdm_set_params, sdm_clear, a wholesale stamp upload): every voxel gets its result, HBM-bound,
 //                    records of dense chunks fetched cooperatively.  On a map whose particles sit on surfaces:
-//                    k_occupancy_scan_lists + k_occupancy_listed + k_occupancy_dense (the host picks: map.hip, sweep_lists).
+//                    k_occupancy_scan_lists + k_occupancy_listed + k_occupancy_dense (the host picks: lifecycle.hip, sweep_lists).
 //                    On a map whose every group of 512 voxels was dense last time: k_occupancy_dense alone
 //                    (launch_occupancy, OCC_SKIP_SCAN).
 

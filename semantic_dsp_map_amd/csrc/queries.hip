@@ -5,7 +5,7 @@
 // last issued frame (Frame: map center, ring offsets) come by value, so a query enqueued between two frames answers for
 // the frame before it whatever the host does next.  Segments and boxes only need the second word of a result (track,
 // label, occ): they gather 4 bytes per cell.
-#include "sdm_internal.h"
+#include "sdm_map.h"
 
 #pragma clang fp contract(off)
 
@@ -277,3 +277,105 @@ void launch_query_boxes(const Dims &d, const Frame &f, const State &st, const fl
 }
 
 }  // namespace sdm
+
+// ---- the host side: the entry points behind include/sdm.h ---------------------------------------------------------
+// Host mode works through the queries in chunks of QUERY_CHUNK: inputs copied to the map's page-locked staging area and
+// up, the kernel, the outputs down, one wait per chunk.  Device mode launches per chunk too (the kernels count in 32 bits)
+// and does not wait.  Either way the kernels read the result array in stream order and the host Frame of the last issued
+// frame, taken by value at the call.
+namespace sdm {
+
+namespace {
+constexpr size_t QUERY_CHUNK = (size_t)1 << 20;
+size_t query_align(size_t b) { return (b + 255) & ~(size_t)255; }
+}  // namespace
+
+sdm_status query_check(sdm_map *m, const void *in, int64_t n, const void *out, uint32_t flags, uint32_t allowed, const char *what) {
+  if (!m) return SDM_ERR_INVALID_ARGUMENT;
+  if (!in || !out || n < 0 || (flags & ~allowed)) {
+    set_error(what, __FILE__, __LINE__, "null pointer, negative count or unknown flag bits");
+    return SDM_ERR_INVALID_ARGUMENT;
+  }
+  if (m->cfg.shard_count > 1) {
+    set_error(what, __FILE__, __LINE__, "queries on a Z-slab shard (shard_count > 1) are not supported: query a whole map");
+    return SDM_ERR_INVALID_ARGUMENT;
+  }
+  return SDM_OK;
+}
+
+// launch(in, out, out2, count, stream) enqueues one chunk; out2 (may be null) is a second output array
+sdm_status run_query(sdm_map *m, const void *in_v, size_t in_elem, void *out_v, size_t out_elem, void *out2_v, size_t out2_elem, int64_t n,
+                     uint32_t flags, const QueryLaunch &launch) {
+  if (n == 0) return SDM_OK;
+  HIP_TRY(hipSetDevice(m->device));
+  const unsigned char *in = static_cast<const unsigned char *>(in_v);
+  unsigned char *out = static_cast<unsigned char *>(out_v), *out2 = static_cast<unsigned char *>(out2_v);
+  if (!out2) out2_elem = 0;
+  if (flags & SDM_QUERY_ON_DEVICE) {
+    for (size_t off = 0; off < (size_t)n; off += QUERY_CHUNK) {
+      const uint32_t c = (uint32_t)std::min(QUERY_CHUNK, (size_t)n - off);
+      launch(in + off * in_elem, out + off * out_elem, out2 ? out2 + off * out2_elem : nullptr, c, m->stream);
+      HIP_TRY(hipGetLastError());
+    }
+    return SDM_OK;
+  }
+  const size_t chunk = std::min(QUERY_CHUNK, (size_t)n);
+  const size_t o_out = query_align(chunk * in_elem), o_out2 = o_out + query_align(chunk * out_elem);
+  const size_t need = o_out2 + query_align(chunk * out2_elem);
+  if (need > m->query_bytes) {
+    const size_t grown = std::max(need, (size_t)1 << 20);  // (both buffers, one capacity: it holds when the second is there)
+    SDM_TRY(regrow(m, &m->h_query, &m->query_bytes, grown, m->stream, true));
+    SDM_TRY(regrow(m, &m->d_query, &m->query_bytes, grown));
+  }
+  for (size_t off = 0; off < (size_t)n; off += chunk) {
+    const size_t c = std::min(chunk, (size_t)n - off);
+    memcpy(m->h_query, in + off * in_elem, c * in_elem);
+    HIP_TRY(hipMemcpyAsync(m->d_query, m->h_query, c * in_elem, hipMemcpyHostToDevice, m->stream));
+    launch(m->d_query, m->d_query + o_out, out2 ? m->d_query + o_out2 : nullptr, (uint32_t)c, m->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(m->h_query + o_out, m->d_query + o_out, c * out_elem, hipMemcpyDeviceToHost, m->stream));
+    if (out2) HIP_TRY(hipMemcpyAsync(m->h_query + o_out2, m->d_query + o_out2, c * out2_elem, hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    memcpy(out + off * out_elem, m->h_query + o_out, c * out_elem);
+    if (out2) memcpy(out2 + off * out2_elem, m->h_query + o_out2, c * out2_elem);
+  }
+  return SDM_OK;
+}
+}  // namespace sdm
+
+extern "C" {
+
+sdm_status sdm_query_points(sdm_map *m, const float *xyz, int64_t n, sdm_voxel_result *out, uint32_t *voxel_out, uint32_t flags) {
+  const sdm_status e = query_check(m, xyz, n, out, flags, SDM_QUERY_ON_DEVICE, "sdm_query_points");
+  if (e != SDM_OK) return e;
+  const Frame f = m->f;
+  return run_query(m, xyz, 12, out, sizeof(sdm_voxel_result), voxel_out, 4, n, flags,
+                   [m, f](const void *in, void *o, void *o2, uint32_t c, hipStream_t s) {
+                     launch_query_points(m->d, f, m->st, static_cast<const float *>(in), c, static_cast<sdm_voxel_result *>(o),
+                                         static_cast<uint32_t *>(o2), s);
+                   });
+}
+
+sdm_status sdm_query_segments(sdm_map *m, const float *ab, int64_t n, sdm_segment_hit *out, uint32_t flags) {
+  const sdm_status e = query_check(m, ab, n, out, flags, SDM_QUERY_ON_DEVICE | SDM_QUERY_UNKNOWN_BLOCKS, "sdm_query_segments");
+  if (e != SDM_OK) return e;
+  const Frame f = m->f;
+  const int unknown_blocks = (flags & SDM_QUERY_UNKNOWN_BLOCKS) ? 1 : 0;
+  return run_query(m, ab, 24, out, sizeof(sdm_segment_hit), nullptr, 0, n, flags,
+                   [m, f, unknown_blocks](const void *in, void *o, void *, uint32_t c, hipStream_t s) {
+                     launch_query_segments(m->d, f, m->st, static_cast<const float *>(in), c, static_cast<sdm_segment_hit *>(o),
+                                           unknown_blocks, s);
+                   });
+}
+
+sdm_status sdm_query_boxes(sdm_map *m, const float *boxes, int64_t n, sdm_box_result *out, uint32_t flags) {
+  const sdm_status e = query_check(m, boxes, n, out, flags, SDM_QUERY_ON_DEVICE, "sdm_query_boxes");
+  if (e != SDM_OK) return e;
+  const Frame f = m->f;
+  return run_query(m, boxes, 24, out, sizeof(sdm_box_result), nullptr, 0, n, flags,
+                   [m, f](const void *in, void *o, void *, uint32_t c, hipStream_t s) {
+                     launch_query_boxes(m->d, f, m->st, static_cast<const float *>(in), c, static_cast<sdm_box_result *>(o), s);
+                   });
+}
+
+}  // extern "C"

@@ -208,7 +208,7 @@ struct State {
   // OCC_LIST_SHARDS arrays (occ_unit_cap pairs each), its slot handed out by the shard's counter, which also counts the
   // tiles that listed anything; the sweep's last launch zeroes the counters and turns the tile count into
   // occ_shard[OCC_LIST_SHARDS].word, the word the host reads before the next non-incremental sweep: 2 = few tiles list
-  // anything (surfaces), the lists pay; 1 = none or most do, evaluate in the first launch (map.hip, sweep_lists).
+  // anything (surfaces), the lists pay; 1 = none or most do, evaluate in the first launch (lifecycle.hip, sweep_lists).
   uint16_t *occ_list = nullptr;
   uint32_t *occ_list_n = nullptr;
   uint2 *occ_unit = nullptr;

@@ -1,0 +1,288 @@
+// sdm_map.h — private to the host units of libsdm_hip (not installed): the map object behind the C ABI (include/sdm.h),
+// the error macros, who owns what a map allocates, and the host helpers that more than one unit uses.
+#pragma once
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "sdm_internal.h"
+#include "sdm_scratch.h"
+
+typedef struct ncclComm *ncclComm_t;  // (rccl.h's own declaration: only exchange.hip includes that header)
+
+namespace sdm {
+// the thread's last error (sdm_last_error): "what (file:line): detail"
+void set_error(const char *what, const char *file, int line, const char *detail);
+}  // namespace sdm
+
+#define HIP_TRY(expr)                                                        \
+  do {                                                                       \
+    hipError_t e_ = (expr);                                                  \
+    if (e_ != hipSuccess) {                                                  \
+      sdm::set_error(#expr, __FILE__, __LINE__, hipGetErrorString(e_));      \
+      return SDM_ERR_HIP;                                                    \
+    }                                                                        \
+  } while (0)
+#define NCCL_TRY(expr)                                                       \
+  do {                                                                       \
+    ncclResult_t r_ = (expr);                                                \
+    if (r_ != ncclSuccess) {                                                 \
+      sdm::set_error(#expr, __FILE__, __LINE__, ncclGetErrorString(r_));     \
+      return SDM_ERR_COMM;                                                   \
+    }                                                                        \
+  } while (0)
+#define SDM_TRY(expr) do { const sdm_status rc_ = (expr); if (rc_ != SDM_OK) return rc_; } while (0)
+
+using namespace sdm;
+
+struct sdm_map {
+  sdm_config cfg{};
+  sdm_params prm{};
+  Dims d{};
+  Frame f{};
+  Filter flt{};
+  BirthOrder bo{};
+  State st{};
+  Scratch sc{};
+  hipStream_t stream = nullptr;
+  hipStream_t own_stream = nullptr;
+  // side streams: the frustum reach set (pose only) and the birth candidates + sort (input cloud only) do not depend
+  // on the map state, so they run next to the object-move chain and join the main stream through events
+  hipStream_t s_frustum = nullptr, s_birth = nullptr, s_moves = nullptr;
+  // ev_state: the particles of the last frame are final (after its births, before its sweep); the next frame's
+  // member count of the moving objects starts there, next to the sweep
+  hipEvent_t ev_state = nullptr, ev_counts = nullptr;
+  hipEvent_t ev_vis = nullptr;      // the frame's visibility pass (and binning) has been issued up to here
+  bool vis_event_valid = false;
+  bool mv_pending = false;          // a member count has run whose k_move_apply has not (it resets the totals)
+  bool state_event_valid = false;
+  hipEvent_t ev_begin = nullptr, ev_frustum = nullptr, ev_birth = nullptr;
+  int birth_which = 0;
+  float *ck_user = nullptr;
+  bool fused_ck = false;  // single-GPU sdm_update: pass 1 writes ck+kappa directly
+  const float *ck_raw_last = nullptr;  // the last frame's summed ck image when pass 2 formed ck + kappa itself (sdm_get_ck_kappa finishes it on demand)
+  int32_t stop_after = 0;
+  uint32_t frame_flags = 0;
+  int n_moves = 0, n_remove = 0;
+  // object lists longer than the frame block holds (MAX_MOVE_OBJECTS / MAX_REMOVE_TRACKS): the whole lists, worked off in
+  // batches by sdm_frame_moves / sdm_frame_predict (whole maps, launch by launch)
+  std::vector<sdm_object_move> moves_all;
+  std::vector<int32_t> removes_all;
+  size_t mv_batch_next = 0;     // first object of the next batch of a long object list (0: none left)
+  bool mv_batch_ready = false;  // Z-slab shard: that batch's member count is issued, its counts await their exchange
+  uint32_t mv_seq = 0;            // frames with moving objects so far (FrameArgs::mv_seq)
+  uint32_t *d_track_bits = nullptr;  // sdm_tracks_with_particles: one bit per track id
+  int32_t *d_counts_local = nullptr;
+  // native RCCL path (sdm_comm_init): communicator + exchange buffers owned by the map
+  ncclComm_t comm = nullptr;
+  // the exchanges of a sharded frame WITHOUT RCCL (sdm_ipc_create / sdm_ipc_connect): every shard owns one receive arena -
+  // flags, gathered count rows, import segments, ck parts and summed ck chunks - that its peers have mapped through hipIpc;
+  // an exchange is one small kernel that writes this shard's pieces into the peers' arenas, raises a flag per peer and
+  // waits for the peers' flags in its own (k_ipc_exchange)
+  bool ipc = false;
+  unsigned char *ipc_arena = nullptr;
+  void *ipc_peer[16] = {};  // [shard]: that shard's arena as this process sees it ([own rank] = ipc_arena)
+  uint32_t ipc_seq[4] = {0, 0, 0, 0};  // exchanges issued so far, per kind: the value the flags of the next one carry
+  size_t ipc_off_counts = 0, ipc_off_halo = 0, ipc_off_stage = 0, ipc_off_full = 0, ipc_bytes = 0;
+  int ipc_fine_grained = 0;
+  float *d_ck_full_local = nullptr;      // the summed ck image in ordinary device memory (k_ipc_ck writes it, the weight update reads it)
+  int32_t *d_counts_all_local = nullptr; // the gathered count rows, likewise
+  uint32_t *d_ipc_sync = nullptr;        // k_ipc_ck's arrival and barrier counters
+  int32_t *d_counts_all = nullptr;
+  unsigned char *d_halo_send = nullptr, *d_halo_recv = nullptr;
+  float *d_ck_stage = nullptr, *d_ck_full = nullptr;  // chunk-owner exchange of the partial ck images (sdm_update_sharded)
+  uint32_t halo_cap_own = 0;
+  size_t ck_part_stride = 0;     // floats between the partial images handed to the next sdm_update_finish (0 = H*W)
+  int ck_exchange = 0;           // 0 chunk-owner reduction (all-to-all + sum + all-gather), 1 one all-gather of the whole partial images
+  float *d_ck_all = nullptr;     // ck_exchange 1: shard_count padded partial images
+  int comm_timeout_ms = 30000;   // sdm_synchronize gives a sharded frame this long before it aborts the communicator
+  uint32_t ck_chunk = 0;  // pixels per shard of the chunk-owner exchange: ceil(H*W / shard_count), a multiple of 64
+  // HIP events around every collective of the last sharded frame (sdm_comm_timing): [2k], [2k+1] bracket collective k
+  hipEvent_t ev_comm[8]{};
+  bool comm_timing = false, comm_timed[4]{};
+  bool sharded_frame = false;  // inside sdm_update_sharded
+  int32_t *counts_local_user = nullptr;
+  const int32_t *counts_all_user = nullptr;
+  int device = 0;
+
+  // host ring-buffer state (mc_ring/buffer.h:97-120)
+  std::vector<uint32_t> stamps_x, stamps_y, stamps_z;
+  int moved_steps[3]{}, eq_steps[3]{};
+  float map_center[3]{}, ego_center[3]{}, last_pos[3]{};
+  uint32_t global_time_stamp = 0;
+  float forgetting_function[5]{};
+  bool forgetting_initialized = false;
+  float cam_R[9]{}, cam_p[3]{};
+  // this frame's scalars (sdm_scratch.h): host copy, the two device blocks and the event that says "the side chains'
+  // block is written"
+  FrameArgs fa{};
+  FrameArgs *d_fa[3]{};        // [0] read by the main-stream kernels, [1] by the frustum chain that runs ahead of the frame, [2] by the member-count chain
+  FrameBeginLaunch fb{};       // arguments of k_frame_begin (the frame block travels with it)
+  hipEvent_t ev_fa = nullptr;
+  const float *cur_depth = nullptr;            // the inputs the last frame read (sdm_get_labeled_cloud)
+  const sdm_labeled_point *cur_cloud = nullptr;
+  // The launch sequence of a plain frame (sdm_update, device-resident inputs, one GPU) does not depend on the frame:
+  // it is captured once into a hipGraph and replayed with one kernel-node parameter update (the frame block) per frame.
+  // graph_mode (SDM_GRAPH): 0 never, 1 the branched graph, 3 the chain, 4 the pieces, 2 (default): by the host's speed
+  // at issuing launches, measured at creation - launch by launch, the pieces (GRAPH_PIECES_US) or the chain (GRAPH_CHAIN_US).
+  int graph_mode = 2;
+  bool use_graph = false;
+  int graph_shape = 0;             // GRAPH_PIECES / GRAPH_BRANCHED / GRAPH_CHAIN
+  hipGraphExec_t piece[5] = {};    // GRAPH_PIECES: frustum chain, birth chain, main stream part 1 / 2 / 3
+  double enqueue_us = 0.0;  // measured at creation: host time to issue a frame's worth of launches
+  double t_prepare_us = 0, t_setparams_us = 0, t_launch_us = 0, t_direct_us = 0;  // SDM_HOST_TIMING: host time per step of sdm_update
+  bool host_timing = false;
+  bool capturing = false;
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t graph_exec = nullptr;
+  hipGraphNode_t graph_set_node = nullptr;
+  Filter graph_flt{};          // the filter parameters baked into the captured launches
+  hipEvent_t cap_begin = nullptr, cap_frustum = nullptr, cap_birth = nullptr;
+  uint64_t n_graph_frames = 0, n_direct_frames = 0;
+  int restamped[3]{};        // slabs re-stamped by the last frame's ring shift, per axis
+  bool stamps_dirty = true;  // device copy of the stamp arrays needs a full upload
+  bool sweep_all = true;     // the next occupancy sweep evaluates every voxel that holds something, changed or not
+  // A non-incremental sweep hands the sparse voxels of its tiles to a launch of their own (State::occ_list) - or, where
+  // that launch would only cost its 4 us, evaluates them in its first launch: every such sweep leaves word of which it
+  // should have been (State::occ_shard: few tiles listed anything = surfaces, lists pay; none or most did, they do not),
+  // and the host picks the word up at its next wait (sweep_mode_latch).  Either way every voxel gets the same result.
+  bool sweep_lists = true;
+  // ... and whether its first launch found anything to do: on a map whose every group of 512 voxels is dense it does not
+  // (State::grp_hint), and the next non-incremental sweep is one launch (launch_occupancy, OCC_SKIP_SCAN).
+  bool sweep_skip_scan = false;
+  bool sweep_skip_allowed = true;  // SDM_SWEEP_SKIP_SCAN=0: always both launches (A/B)
+  bool sweep_rec_pending = false;
+  int sweep_lists_forced = -1;  // sdm_debug_sweep_lists
+  uint32_t sweep_epoch = 1;  // the number the next sweep looks for in State::tile_dirty (mark_tile): advanced by every sweep issued
+
+  // owned device buffers for inputs
+  float *d_depth = nullptr;
+  sdm_labeled_point *d_cloud = nullptr;
+  float *d_ck_part = nullptr;
+  // N1 inputs: static mask, label->instance table, object masks (grown on demand)
+  // sdm_update_raw: two sets of device-side inputs, filled alternately on a copy stream, so that the upload (and
+  // BOOST-mode reduction) of a frame runs beside the previous frame's kernels
+  struct RawInputs {
+    float *depth = nullptr;
+    uint8_t *static_mask = nullptr, *obj_masks = nullptr;
+    uint16_t *label_to_inst = nullptr;
+    uint16_t label_host[256];  // what label_to_inst holds (the table rarely changes: it is uploaded when it does)
+    bool label_valid = false;
+    double *bbox = nullptr;  // ZED2: per-object boxes
+    size_t obj_masks_cap = 0;  // bytes
+    hipEvent_t ev_free = nullptr;  // the frame that read this set has been issued up to its end
+  } raw[2];
+  int raw_next = 0;
+  hipStream_t s_copy = nullptr;
+  hipEvent_t ev_copy = nullptr;
+  unsigned char *d_src_stage = nullptr;  // BOOST mode: one input image at the sensor's size
+  size_t src_stage_bytes = 0;
+  unsigned long long *d_u64 = nullptr;
+  EmitScratch emit;  // compaction of the result lists (getters)
+  // page-locked landing area of the getters: [0] the list's length, from byte 16 on the points
+  unsigned char *h_emit = nullptr;
+  size_t h_emit_bytes = 0;
+  uint32_t *h_track_bits = nullptr;  // page-locked landing area of sdm_tracks_with_particles
+  size_t emit_guess = 1024;  // points fetched together with the length (the last list's length and a margin)
+  sdm_point *d_points = nullptr;
+  size_t points_cap = 0;
+  // host-mode staging of the batched queries (sdm_query_*): one chunk's inputs and outputs, on the device and page-locked;
+  // grown on demand, used by nothing else (a query between two frames changes nothing the next frame reads)
+  unsigned char *d_query = nullptr, *h_query = nullptr;
+  size_t query_bytes = 0;
+  // the distance field (sdm_esdf_update, esdf.hip): site and snapshot word per cell in map-index order, allocated by the
+  // first build; the Frame of the frame it was built from (its map center and ring offsets); no frame reads any of it
+  uint32_t *d_esdf_site = nullptr, *d_esdf_snap = nullptr;
+  Frame esdf_f{};
+  bool esdf_valid = false;
+  sdm_point_xyzrgb *d_points_rgb = nullptr;
+  size_t points_rgb_cap = 0;
+  ColourTables *d_colours = nullptr;
+  bool colours_set = false;
+  int nb_alloc = 0;
+  size_t sort_cap = 0;
+  int noise_n = 0;
+  int force_generic_flood = 0;
+
+  bool profiling = false;
+  hipEvent_t ev[9]{};
+  bool stage_ran[9]{};
+  // What the map owns, released by sdm_destroy: device memory, page-locked host memory, events (alloc_tracked, regrow,
+  // new_event below).  The kernels take the raw pointers by value (State / Scratch), so the fields above stay raw; a field
+  // that is null is simply not allocated yet.  Streams, graph executables, the communicator and the peers' arena mappings
+  // are not in these lists: the order in which they go matters (sdm_destroy, drop_graphs, exchange_teardown).
+  std::vector<void *> allocs, pinned;
+  std::vector<hipEvent_t> events;
+};
+
+namespace sdm {
+
+// ---- who owns what (lifecycle.hip) -----------------------------------------------------------------------------------
+sdm_status map_alloc(sdm_map *m, void **p, size_t bytes, bool pinned);  // *p: fresh memory, registered with the map
+void map_release(sdm_map *m, void **p);                                 // *p (registered, or null) is freed and cleared
+sdm_status new_event(sdm_map *m, hipEvent_t *e, unsigned flags);        // created and registered
+template <typename T>
+sdm_status alloc_tracked(sdm_map *m, T **p, size_t n, bool pinned = false) {
+  return map_alloc(m, (void **)p, std::max<size_t>(n, 1) * sizeof(T), pinned);
+}
+template <typename T>
+void release(sdm_map *m, T **p) {
+  map_release(m, (void **)p);
+}
+// A buffer that grows on demand: the old one goes - once `quiet`, a stream that may still be using it, has drained - and
+// one of n elements comes; *cap is what the caller compares its need with (0 while there is no buffer).
+template <typename T>
+sdm_status regrow(sdm_map *m, T **p, size_t *cap, size_t n, hipStream_t quiet = nullptr, bool pinned = false) {
+  if (quiet) HIP_TRY(hipStreamSynchronize(quiet));
+  *cap = 0;
+  release(m, p);
+  SDM_TRY(alloc_tracked(m, p, n, pinned));
+  *cap = n;
+  return SDM_OK;
+}
+// device temporaries of one call: freed on every exit from it
+struct DevTemps {
+  std::vector<void *> v;
+  template <typename T>
+  hipError_t alloc(T **p, size_t n) {
+    const hipError_t e = hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T));
+    if (e == hipSuccess) v.push_back((void *)*p);
+    return e;
+  }
+  ~DevTemps() { for (void *p : v) (void)hipFree(p); }
+};
+
+// ---- host helpers shared between the units ---------------------------------------------------------------------------
+inline bool stage_done(int32_t stop_after, int stage) { return stop_after != 0 && stop_after <= stage; }
+// lifecycle.hip
+enum { GRAPH_PIECES = 0, GRAPH_BRANCHED = 1, GRAPH_CHAIN = 2 };  // sdm_map::graph_shape
+void issue_mode_for(const sdm_map *m, int mode, bool *use_graph, int *shape);  // SDM_GRAPH / sdm_set_issue_mode -> how frames are issued
+hipError_t lazy_stream(int device, hipStream_t *s);
+void refresh_filter(sdm_map *m);
+void update_ego_center(sdm_map *m, const float pos[3]);
+void compute_extrinsic(sdm_map *m, const float pos[3], const float q[4]);
+void compute_frustum_box(sdm_map *m);
+void sync_frame_scalars(sdm_map *m);
+sdm_status upload_stamps(sdm_map *m);
+int sweep_mode(const sdm_map *m);
+sdm_status sweep_mode_latch(sdm_map *m);
+sdm_status check_counters(sdm_map *m, Counters *out);
+// affinity.cpp
+int bind_host_thread_to(int device);
+// frame.hip
+void drop_graphs(sdm_map *m);  // whatever was captured goes (the caller has made sure that none of it is running)
+// exchange.hip
+sdm_status exchange_counts(sdm_map *m, hipStream_t s);  // the all-gather of the member-count rows: RCCL or the peers' arenas
+sdm_status exchange_check(sdm_map *m);                  // (m->stream is idle) did an exchange through the arenas time out?
+sdm_status exchange_wait(sdm_map *m);                   // sdm_synchronize with a communicator: a bounded wait for the map's streams
+void exchange_teardown(sdm_map *m);                     // communicator, arena, peer mappings, exchange buffers: back to "none"
+// queries.hip: host mode works through a batch in chunks; launch(in, out, out2, count, stream) enqueues one chunk
+using QueryLaunch = std::function<void(const void *, void *, void *, uint32_t, hipStream_t)>;
+sdm_status query_check(sdm_map *m, const void *in, int64_t n, const void *out, uint32_t flags, uint32_t allowed, const char *what);
+sdm_status run_query(sdm_map *m, const void *in_v, size_t in_elem, void *out_v, size_t out_elem, void *out2_v, size_t out2_elem, int64_t n,
+                     uint32_t flags, const QueryLaunch &launch);
+
+}  // namespace sdm

@@ -35,7 +35,7 @@ def config(name):
 
 
 def sdm_create_accepts(cfg):
-    """sdm_create's rules on the grid (csrc/map.hip), restated"""
+    """sdm_create's rules on the grid (csrc/lifecycle.hip), restated"""
     n = [cfg["x_n"], cfg["y_n"], cfg["z_n"]]
     return (sum(n) + cfg["p_n"] <= 31 and all(2 <= v <= 9 for v in n) and 1 <= cfg["p_n"] <= 4 and cfg["voxel_size"] > 0
             and cfg["width"] > 0 and cfg["height"] > 0 and 0 <= cfg["window_half"] <= 7)

@@ -1,7 +1,7 @@
 """Z-slab shardings that sdm_create accepts and the rest of the suite does not build: slabs of one or two planes, shards
 of fewer voxels than one 64-voxel chunk or one 512-voxel group, shards that own no pixel of the ck image.  Plain numpy,
 importable without a GPU: the (grid, G) cases with the property each one is there for, the shard geometry restated from
-sdm_create (csrc/map.hip), and the crafted state of an object larger than one shard."""
+sdm_create (csrc/lifecycle.hip), and the crafted state of an object larger than one shard."""
 import numpy as np
 
 from semantic_dsp_map_amd import synth
@@ -44,7 +44,7 @@ def shape_of(name):
 
 
 def sdm_create_accepts_shard(cfg, rank, G):
-    """sdm_create's rules on the grid and the sharding (csrc/map.hip), restated"""
+    """sdm_create's rules on the grid and the sharding (csrc/lifecycle.hip), restated"""
     return sc.sdm_create_accepts(cfg) and G >= 1 and 0 <= rank < G and (1 << cfg["z_n"]) % G == 0
 
 

@@ -2,13 +2,10 @@
 # usage: tools/ab_build.sh <tag> [extra hipcc flags, e.g. -DSDM_X=1]  ->  build/ab/libsdm_<tag>.so
 # A/B variants of the library for one and the same GPU run (box-to-box spread is a few percent: variants are only
 # comparable inside one gpurun call); load one with SDM_LIB_PATH=build/ab/libsdm_<tag>.so.
+# Sources and flags are csrc/Makefile's; the variant's objects are built out of tree, the default build is not touched.
 set -e
 tag=$1; shift
-cd "$(dirname "$0")/../semantic_dsp_map_amd/csrc"
-make -s -j8
-mkdir -p ../../build/ab
-FLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wno-unused-function -Wno-unused-result -Wno-unused-value"
-for f in kernels moves map; do /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS "$@" -c $f.hip -o ../../build/ab/${f}_$tag.o & done; wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../build/ab/libsdm_$tag.so primitives.o ../../build/ab/kernels_$tag.o ../../build/ab/moves_$tag.o ../../build/ab/map_$tag.o objects.o -L/opt/rocm/lib -lrocrand -lrccl -Wl,-rpath,/opt/rocm/lib
-rm -f ../../build/ab/*_$tag.o
+root="$(cd "$(dirname "$0")/.." && pwd)"
+make -s -j8 -C "$root/semantic_dsp_map_amd/csrc" LIB="$root/build/ab/libsdm_$tag.so" OBJDIR="$root/build/ab/obj_$tag" EXTRA="$*"
+rm -rf "$root/build/ab/obj_$tag"
 echo built build/ab/libsdm_$tag.so
