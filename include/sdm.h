@@ -533,6 +533,51 @@ typedef struct {      /* 36 bytes */
 } sdm_distance_result;
 sdm_status sdm_query_distance(sdm_map *m, const float *xyz, int64_t n, sdm_distance_result *out, uint32_t flags);
 
+/* ---- instance table: the map by object - per winning track id its cells, box and moments ----
+ * sdm_instances_update enqueues, on the map's stream, one pass over the result array of the last frame enqueued before
+ * the call and returns without waiting.  Like the distance field the table is a snapshot: it keeps that frame's map
+ * center and answers for it until the next sdm_instances_update, whatever frames, sdm_clear, sdm_load_state or
+ * sdm_set_ring_state come in between.  Nothing of the map's state is modified and no scratch of the frames' is used.
+ * Counted cells: occ >= 1 (occupied or guessed occupied, as segments block and as the field's obstacles); with
+ * SDM_INSTANCES_MOVABLE_ONLY only cells whose winning track is movable (1 <= track <= max_movable_track), with
+ * SDM_INSTANCES_OBSERVED_ONLY only occ == 1.  An instance is the set of counted cells with one winning track id; track 0
+ * is an instance like any other unless SDM_INSTANCES_MOVABLE_ONLY is set.  Tracks without a counted cell have no entry.
+ * Cells are map-index cells (cell (i, j, k) of the query block above), not storage indices: the ring's wrap point never
+ * splits a box.  Every accumulated field is an integer sum, minimum or maximum (wsum_max: a float maximum), so the
+ * table is bitwise the same from run to run.  The float triples follow from the integer fields by the formulas below,
+ * one IEEE operation at a time: box_* in float32, centroid in double and rounded once; origin = center + pmin in
+ * float32, what sdm_get_esdf returns.
+ * Memory: 17.6 MB of device memory (8.1 MB of accumulators for the 65536 track ids and the 256 label counters, 9.4 MB
+ * for the table itself), allocated by the first sdm_instances_update and freed by sdm_destroy.
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map, unknown flag bits, cap < 0, a NULL n_out (or a NULL out with
+ * cap > 0), a Z-slab shard (shard_count > 1), and either getter before any sdm_instances_update. */
+#define SDM_INSTANCES_MOVABLE_ONLY  0x1u  /* count only cells with 1 <= track <= max_movable_track */
+#define SDM_INSTANCES_OBSERVED_ONLY 0x2u  /* count only occ == 1 (leave out guessed-occupied cells, occ == 2) */
+typedef struct {            /* 144 bytes, every field naturally aligned */
+  uint16_t track;           /* the instance: the winning track id of its cells */
+  uint8_t  label;           /* label of first_cell */
+  uint8_t  mixed_labels;    /* 1 if the counted cells do not all carry the same label */
+  uint32_t n_cells;         /* counted cells of this track (> 0: absent tracks have no entry) */
+  uint32_t n_guessed;       /* of them, cells with occ == 2 */
+  uint32_t first_cell;      /* smallest map-index cell word i | j << x_n | k << (x_n + y_n) among them */
+  uint16_t cell_min[3];     /* axis-aligned box in map-index cells, inclusive, x y z */
+  uint16_t cell_max[3];
+  float    wsum_max;        /* largest sdm_voxel_result.wsum among them (float comparison) */
+  uint64_t cell_sum[3];     /* sum of i, of j, of k */
+  uint64_t cell_sq[6];      /* sum of ii, jj, kk, ij, ik, jk */
+  float    box_min[3];      /* global frame, metres: origin + (float)cell_min * voxel_size */
+  float    box_max[3];      /* origin + (float)(cell_max + 1) * voxel_size */
+  float    centroid[3];     /* (float)((double)origin + ((double)cell_sum / (double)n_cells + 0.5) * (double)voxel_size) */
+  uint32_t pad;             /* 0 */
+} sdm_instance;
+sdm_status sdm_instances_update(sdm_map *m, uint32_t flags);
+/* Waits; writes at most `cap` entries in ascending track id and sets *n_out to how many there are (it may exceed cap,
+ * as with sdm_tracks_with_particles; nothing beyond min(cap, *n_out) entries is written).  out may be NULL with cap 0;
+ * origin (the global position of the min corner of cell (0,0,0) of the snapshot) may be NULL. */
+sdm_status sdm_get_instances(sdm_map *m, sdm_instance *out, int32_t cap, int32_t *n_out, float origin[3]);
+/* Counted cells per label id, under the flags of the last sdm_instances_update (how much "Road", how much "Car").  Waits. */
+sdm_status sdm_get_label_cells(sdm_map *m, uint32_t out[256]);
+
 /* ---- owner sets of the object layer: ObjectParticleHashMap (object_layer.h:20-52) */
 sdm_status sdm_object_particle_count(sdm_map *m, int32_t track_id, int64_t *count);
 /* The keys of ObjectParticleHashMap::indices_map whose sets are not empty: every track id that owns at least one slot of

@@ -403,6 +403,25 @@ class SemanticDSPMap {
     for (const auto &kv : label_colours) label_color_[kv.first] = kv.second;
     pushColours();
   }
+  /// The map by object (sdm.h, "instance table"): builds the table from the results of the last update() and fetches it -
+  /// per winning track id its cell count, box, centroid and second moments, ascending track id.  movable_only: only the
+  /// tracks 1 .. g_max_movable_object_instance_id, the objects a planner treats apart from the static field.  origin
+  /// (3 floats, may be null): the global position of the min corner of map cell (0, 0, 0).  Returns the number of
+  /// instances; 0 (and an empty vector) before the first update() or when a call fails.
+  size_t instances(std::vector<sdm_instance> &out, bool movable_only = true, float *origin = nullptr) {
+    out.clear();
+    if (!map_) return 0;
+    if (!check(sdm_instances_update(map_, movable_only ? SDM_INSTANCES_MOVABLE_ONLY : 0u), "sdm_instances_update")) return 0;
+    int32_t n = 0;
+    out.resize(64);
+    if (!check(sdm_get_instances(map_, out.data(), (int32_t)out.size(), &n, origin), "sdm_get_instances")) n = 0;
+    if ((size_t)n > out.size()) {
+      out.resize((size_t)n);
+      if (!check(sdm_get_instances(map_, out.data(), (int32_t)out.size(), &n, origin), "sdm_get_instances")) n = 0;
+    }
+    out.resize((size_t)n);
+    return out.size();
+  }
 
   // ---- the reference's public interface ----
   /// semantic_dsp_map.h:74-81

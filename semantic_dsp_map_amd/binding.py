@@ -33,6 +33,14 @@ DISTANCE_RESULT = np.dtype([("distance", "<f4"), ("gradient", "<f4", (3,)), ("ne
 assert DISTANCE_RESULT.itemsize == 36
 ESDF_UNKNOWN_IS_OBSTACLE = 0x1
 ESDF_STATIC_ONLY = 0x2
+# the instance table (sdm.h: sdm_instances_update / sdm_get_instances / sdm_get_label_cells)
+INSTANCE = np.dtype([("track", "<u2"), ("label", "u1"), ("mixed_labels", "u1"), ("n_cells", "<u4"), ("n_guessed", "<u4"),
+                     ("first_cell", "<u4"), ("cell_min", "<u2", (3,)), ("cell_max", "<u2", (3,)), ("wsum_max", "<f4"),
+                     ("cell_sum", "<u8", (3,)), ("cell_sq", "<u8", (6,)), ("box_min", "<f4", (3,)), ("box_max", "<f4", (3,)),
+                     ("centroid", "<f4", (3,)), ("pad", "<u4")])
+assert INSTANCE.itemsize == 144
+INSTANCES_MOVABLE_ONLY = 0x1
+INSTANCES_OBSERVED_ONLY = 0x2
 
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
@@ -173,6 +181,9 @@ def load_library():
         "sdm_esdf_update": [vp, u32],
         "sdm_get_esdf": [vp, vp, vp, vp],
         "sdm_query_distance": [vp, vp, i64, vp, u32],
+        "sdm_instances_update": [vp, u32],
+        "sdm_get_instances": [vp, vp, i32, C.POINTER(i32), vp],
+        "sdm_get_label_cells": [vp, vp],
         "sdm_object_particle_count": [vp, i32, C.POINTER(i64)],
         "sdm_tracks_with_particles": [vp, vp, i32, C.POINTER(i32)],
         "sdm_comm_set_options": [vp, i32, i32],
@@ -547,6 +558,29 @@ class SdmMap:
         res = np.empty(len(p), DISTANCE_RESULT)
         _check(self.L, self.L.sdm_query_distance(self.h, _ptr(p), len(p), _ptr(res), 0), "sdm_query_distance")
         return res
+
+    # ---- the instance table (sdm.h).  instances_update enqueues a build on the map's stream from the last frame's
+    # results; instances() and label_cells() answer for that frame until the next build.
+    def instances_update(self, movable_only=False, observed_only=False):
+        fl = (INSTANCES_MOVABLE_ONLY if movable_only else 0) | (INSTANCES_OBSERVED_ONLY if observed_only else 0)
+        _check(self.L, self.L.sdm_instances_update(self.h, fl), "sdm_instances_update")
+
+    def instances(self, cap=64):
+        """-> (table, origin): INSTANCE entries in ascending track id, origin the global position of the min corner of
+        cell (0, 0, 0) of the table's snapshot (float32[3]).  cap: the first guess of the table's length."""
+        origin, n = np.empty(3, np.float32), C.c_int32(0)
+        while True:
+            out = np.empty(cap, INSTANCE)
+            _check(self.L, self.L.sdm_get_instances(self.h, _ptr(out), cap, C.byref(n), _ptr(origin)), "sdm_get_instances")
+            if n.value <= cap:
+                return out[:n.value].copy(), origin
+            cap = n.value
+
+    def label_cells(self):
+        """counted cells per label id (256 uint32) under the flags of the last instances_update"""
+        out = np.empty(256, np.uint32)
+        _check(self.L, self.L.sdm_get_label_cells(self.h, _ptr(out)), "sdm_get_label_cells")
+        return out
 
     def occupied(self, cap=None, zero_center=False, free=False, mark_fov=False):
         cap = cap or self.v_count

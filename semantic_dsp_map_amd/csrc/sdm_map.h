@@ -198,6 +198,14 @@ struct sdm_map {
   uint32_t *d_esdf_site = nullptr, *d_esdf_snap = nullptr;
   Frame esdf_f{};
   bool esdf_valid = false;
+  // the instance table (sdm_instances_update, instances.hip): the accumulators (empty between builds), the table of the
+  // last build, its count and label counters, allocated by the first build; the Frame and flags of that build
+  unsigned char *d_inst_acc = nullptr;
+  sdm_instance *d_inst_out = nullptr;
+  uint32_t *d_inst_meta = nullptr;
+  Frame inst_f{};
+  uint32_t inst_flags = 0;
+  bool inst_valid = false;
   sdm_point_xyzrgb *d_points_rgb = nullptr;
   size_t points_rgb_cap = 0;
   ColourTables *d_colours = nullptr;
