@@ -578,6 +578,61 @@ sdm_status sdm_get_instances(sdm_map *m, sdm_instance *out, int32_t cap, int32_t
 /* Counted cells per label id, under the flags of the last sdm_instances_update (how much "Road", how much "Car").  Waits. */
 sdm_status sdm_get_label_cells(sdm_map *m, uint32_t out[256]);
 
+/* ---- frontiers: where known free space borders never-observed space, in connected clusters ----
+ * sdm_frontiers_update enqueues, on the map's stream, a build from the result array of the last frame enqueued before
+ * the call and returns without waiting.  Like the distance field and the instance table the result is a snapshot: it
+ * keeps that frame's map center and ring offsets and answers for it until the next sdm_frontiers_update, whatever
+ * frames, sdm_clear, sdm_load_state or sdm_set_ring_state come in between.  Nothing of the map's state is modified and no
+ * scratch of the frames', the field's or the table's is used.
+ * Frontier cell: a map-index cell (cell (i, j, k) of the query block above) with occ == 0 of whose six face neighbours
+ * at least one lies inside the map and has occ == -1.  The space outside the map is never unknown here (as it is never
+ * an obstacle for the distance field), neighbours are taken in map-index space - the ring's wrap point is not a
+ * neighbour relation, the map is not a torus - and unknown_faces of a cell is how many of the six are unknown (1..6).
+ * Cluster: a connected component of frontier cells under 26-connectivity (face, edge or corner), under 6-connectivity
+ * with SDM_FRONTIERS_FACE_CONNECTED.  Its identity is first_cell, the smallest map-index cell word
+ * i | j << x_n | k << (x_n + y_n) among its cells; the table ascends in first_cell.  min_cells <= 1 keeps every cluster;
+ * a larger value leaves the clusters with fewer cells out of the table - their cells stay in the cell list, with
+ * cluster == 0xffffffff.
+ * Everything accumulated is an integer sum, minimum or maximum, and a cluster's label is its smallest cell: tables and
+ * lists are bitwise the same from run to run.  The float triples follow from the integer fields by sdm_instance's
+ * formulas, one IEEE operation at a time: box_* in float32, centroid in double and rounded once, origin = center + pmin
+ * in float32.
+ * max_cells is the capacity of the cell list, 0 = V / 16 cells (V = NX*NY*NZ; at most V).  Memory: V * 7 / 16 bytes for
+ * the bitmasks and their prefix, and SDM_FRONTIERS_BYTES_PER_CELL = 169 bytes of device memory per cell of capacity
+ * (56 B accumulator, 96 B table entry - every cell may be a cluster of its own -, 16 B cell / cluster / root / rank words,
+ * 1 B unknown_faces): 7.3 MB + 177 MB at 256^3 with the default capacity.  Allocated at the first sdm_frontiers_update,
+ * grown by one that asks for more cells, freed by sdm_destroy.  A frame with more frontier cells than the capacity:
+ * both getters return SDM_ERR_CAPACITY and sdm_get_frontier_cells still sets *n_out to the true count; nothing is
+ * written out of bounds and nothing is truncated; an update with max_cells >= that count then succeeds.
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map, unknown flag bits, cap < 0 or max_cells < 0, a NULL n_out (or a NULL
+ * out with cap > 0), a Z-slab shard (shard_count > 1), and either getter before any sdm_frontiers_update. */
+#define SDM_FRONTIERS_FACE_CONNECTED 0x1u  /* clusters under 6-connectivity instead of 26-connectivity */
+#define SDM_FRONTIERS_BYTES_PER_CELL 169
+typedef struct {              /* 96 bytes, every field naturally aligned */
+  uint32_t first_cell;        /* the cluster: the smallest map-index cell word among its cells */
+  uint32_t n_cells;
+  uint32_t n_unknown_faces;   /* sum of unknown_faces over its cells */
+  uint32_t first_index;       /* position of first_cell in the cell list (the cluster's first entry there) */
+  uint16_t cell_min[3];       /* axis-aligned box in map-index cells, inclusive, x y z */
+  uint16_t cell_max[3];
+  uint32_t pad0;              /* 0 */
+  uint64_t cell_sum[3];       /* sum of i, of j, of k */
+  float    box_min[3];        /* global frame, metres: origin + (float)cell_min * voxel_size */
+  float    box_max[3];        /* origin + (float)(cell_max + 1) * voxel_size */
+  float    centroid[3];       /* (float)((double)origin + ((double)cell_sum / (double)n_cells + 0.5) * (double)voxel_size) */
+  uint32_t pad1;              /* 0 */
+} sdm_frontier_cluster;
+sdm_status sdm_frontiers_update(sdm_map *m, uint32_t flags, int32_t min_cells, int64_t max_cells);
+/* Waits; writes at most `cap` entries in ascending first_cell and sets *n_out to how many there are (it may exceed cap,
+ * as with sdm_get_instances; nothing beyond min(cap, *n_out) entries is written).  out may be NULL with cap 0; origin
+ * (the global position of the min corner of cell (0,0,0) of the snapshot) may be NULL. */
+sdm_status sdm_get_frontier_clusters(sdm_map *m, sdm_frontier_cluster *out, int32_t cap, int32_t *n_out, float origin[3]);
+/* Waits; the frontier cells in ascending map-index cell word, at most `cap` of them: per cell its word, the index of its
+ * cluster in the table (0xffffffff: a cluster below min_cells) and unknown_faces.  Any of the three arrays may be NULL.
+ * *n_out = how many cells there are (it may exceed cap). */
+sdm_status sdm_get_frontier_cells(sdm_map *m, uint32_t *cell, uint32_t *cluster, uint8_t *unknown_faces,
+                                  int64_t cap, int64_t *n_out);
+
 /* ---- owner sets of the object layer: ObjectParticleHashMap (object_layer.h:20-52) */
 sdm_status sdm_object_particle_count(sdm_map *m, int32_t track_id, int64_t *count);
 /* The keys of ObjectParticleHashMap::indices_map whose sets are not empty: every track id that owns at least one slot of

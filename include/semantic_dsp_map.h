@@ -422,6 +422,27 @@ class SemanticDSPMap {
     out.resize((size_t)n);
     return out.size();
   }
+  /// Where to explore (sdm.h, "frontiers"): builds the frontiers from the results of the last update() and fetches the
+  /// table - per connected cluster (26-connectivity) of free cells that border never-observed space its first cell, cell
+  /// count, unknown faces, box and centroid, ascending first cell.  min_cells: clusters with fewer cells are left out.
+  /// The cell list takes the library's default capacity (a sixteenth of the map's cells).  origin (3 floats, may be
+  /// null): the global position of the min corner of map cell (0, 0, 0).  The table is fetched into the room `out`
+  /// already has (64 entries if it has none) and once more if there are more clusters than that.  Returns the number of
+  /// clusters; 0 (and an empty vector) before the first update() or when a call fails.
+  size_t frontiers(std::vector<sdm_frontier_cluster> &out, int min_cells = 1, float *origin = nullptr) {
+    out.clear();
+    if (!map_) return 0;
+    if (!check(sdm_frontiers_update(map_, 0u, (int32_t)min_cells, 0), "sdm_frontiers_update")) return 0;
+    int32_t n = 0;
+    out.resize(out.capacity() ? out.capacity() : 64);  // the first guess: what the vector already holds room for
+    if (!check(sdm_get_frontier_clusters(map_, out.data(), (int32_t)out.size(), &n, origin), "sdm_get_frontier_clusters")) n = 0;
+    if ((size_t)n > out.size()) {
+      out.resize((size_t)n);
+      if (!check(sdm_get_frontier_clusters(map_, out.data(), (int32_t)out.size(), &n, origin), "sdm_get_frontier_clusters")) n = 0;
+    }
+    out.resize((size_t)n);
+    return out.size();
+  }
 
   // ---- the reference's public interface ----
   /// semantic_dsp_map.h:74-81

@@ -41,6 +41,13 @@ INSTANCE = np.dtype([("track", "<u2"), ("label", "u1"), ("mixed_labels", "u1"), 
 assert INSTANCE.itemsize == 144
 INSTANCES_MOVABLE_ONLY = 0x1
 INSTANCES_OBSERVED_ONLY = 0x2
+# the frontiers (sdm.h: sdm_frontiers_update / sdm_get_frontier_clusters / sdm_get_frontier_cells)
+FRONTIER_CLUSTER = np.dtype([("first_cell", "<u4"), ("n_cells", "<u4"), ("n_unknown_faces", "<u4"), ("first_index", "<u4"),
+                             ("cell_min", "<u2", (3,)), ("cell_max", "<u2", (3,)), ("pad0", "<u4"), ("cell_sum", "<u8", (3,)),
+                             ("box_min", "<f4", (3,)), ("box_max", "<f4", (3,)), ("centroid", "<f4", (3,)), ("pad1", "<u4")])
+assert FRONTIER_CLUSTER.itemsize == 96
+FRONTIERS_FACE_CONNECTED = 0x1
+FRONTIER_NO_CLUSTER = 0xFFFFFFFF
 
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
@@ -184,6 +191,9 @@ def load_library():
         "sdm_instances_update": [vp, u32],
         "sdm_get_instances": [vp, vp, i32, C.POINTER(i32), vp],
         "sdm_get_label_cells": [vp, vp],
+        "sdm_frontiers_update": [vp, u32, i32, i64],
+        "sdm_get_frontier_clusters": [vp, vp, i32, C.POINTER(i32), vp],
+        "sdm_get_frontier_cells": [vp, vp, vp, vp, i64, C.POINTER(i64)],
         "sdm_object_particle_count": [vp, i32, C.POINTER(i64)],
         "sdm_tracks_with_particles": [vp, vp, i32, C.POINTER(i32)],
         "sdm_comm_set_options": [vp, i32, i32],
@@ -581,6 +591,33 @@ class SdmMap:
         out = np.empty(256, np.uint32)
         _check(self.L, self.L.sdm_get_label_cells(self.h, _ptr(out)), "sdm_get_label_cells")
         return out
+
+    # ---- the frontiers (sdm.h).  frontiers_update enqueues a build on the map's stream from the last frame's results;
+    # frontiers() and frontier_cells() answer for that frame until the next build.
+    def frontiers_update(self, face_connected=False, min_cells=1, max_cells=0):
+        fl = FRONTIERS_FACE_CONNECTED if face_connected else 0
+        _check(self.L, self.L.sdm_frontiers_update(self.h, fl, int(min_cells), int(max_cells)), "sdm_frontiers_update")
+
+    def frontiers(self, cap=64):
+        """-> (table, origin): FRONTIER_CLUSTER entries in ascending first_cell, origin the global position of the min
+        corner of cell (0, 0, 0) of the snapshot (float32[3]).  cap: the first guess of the table's length."""
+        origin, n = np.empty(3, np.float32), C.c_int32(0)
+        while True:
+            out = np.empty(cap, FRONTIER_CLUSTER)
+            _check(self.L, self.L.sdm_get_frontier_clusters(self.h, _ptr(out), cap, C.byref(n), _ptr(origin)), "sdm_get_frontier_clusters")
+            if n.value <= cap:
+                return out[:n.value].copy(), origin
+            cap = n.value
+
+    def frontier_cells(self):
+        """-> (cell, cluster, unknown_faces): the frontier cells in ascending map-index cell word (uint32), per cell the
+        index of its cluster in the table (FRONTIER_NO_CLUSTER: below min_cells) and its number of unknown faces (uint8)"""
+        n = C.c_int64(0)
+        _check(self.L, self.L.sdm_get_frontier_cells(self.h, None, None, None, 0, C.byref(n)), "sdm_get_frontier_cells")
+        k = n.value
+        cell, cluster, faces = np.empty(k, np.uint32), np.empty(k, np.uint32), np.empty(k, np.uint8)
+        _check(self.L, self.L.sdm_get_frontier_cells(self.h, _ptr(cell), _ptr(cluster), _ptr(faces), k, C.byref(n)), "sdm_get_frontier_cells")
+        return cell, cluster, faces
 
     def occupied(self, cap=None, zero_center=False, free=False, mark_fov=False):
         cap = cap or self.v_count

@@ -206,6 +206,17 @@ struct sdm_map {
   Frame inst_f{};
   uint32_t inst_flags = 0;
   bool inst_valid = false;
+  // the frontiers (sdm_frontiers_update, frontiers.hip): the free / unknown / frontier bitmasks and the words' prefix; the
+  // per-cell arrays, accumulators (empty between builds) and cluster table, laid out for front_alloc cells of which
+  // front_cap are in use; the build's counters; a scan scratch of its own.  Allocated by the first build, the cells
+  // grown by one that asks for more; the Frame and flags of the last build
+  unsigned char *d_front_bits = nullptr, *d_front_cells = nullptr;
+  uint32_t *d_front_meta = nullptr, *d_front_scan = nullptr;
+  size_t front_alloc = 0;
+  int64_t front_cap = 0;
+  Frame front_f{};
+  uint32_t front_flags = 0;
+  bool front_valid = false;
   sdm_point_xyzrgb *d_points_rgb = nullptr;
   size_t points_rgb_cap = 0;
   ColourTables *d_colours = nullptr;
