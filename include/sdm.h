@@ -695,6 +695,31 @@ sdm_status sdm_debug_alias_cap(sdm_map *m, int32_t cap);
 sdm_status sdm_test_scan(const uint32_t *in, uint32_t *out, int64_t n);
 sdm_status sdm_test_sort_pairs(const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out,
                                uint32_t *vals_out, int64_t n, int32_t nbits);
+/* The same two primitives through their whole contract (csrc/sdm_internal.h): a SEQUENCE of n_calls calls issued back to
+ * back on one stream, without a host synchronisation between them, on ONE scratch buffer that is sized for the longest
+ * capacity of the sequence with no slack, zeroed once before the first call and followed by SDM_TEST_GUARD_WORDS words
+ * of a canary.  Call i works on `capacity[i]` words, slice i of the concatenated arrays (sum of the capacities long).
+ * Without SDM_TEST_COUNT_ON_DEVICE its length is count[i] (<= capacity[i]); with it the call is launched at the
+ * capacity and count[i] (any value) is read on the device.  *guard_ok = every guard word survived.  scratch_out, if not
+ * null, receives the scratch as the last call left it: sdm_test_scratch_elems words for the longest capacity.
+ *
+ * sdm_test_scan_seq: `out` is uploaded before the calls and downloaded after them, so the caller sees what the scan left
+ * alone.  With SDM_TEST_IN_PLACE the scan runs with out == in on a copy of `in`, and `out` receives that buffer.
+ * Sequences whose calls would not all take the same form of the scan (one launch / two launches) are refused: a scratch
+ * region may only ever see one of them.
+ *
+ * sdm_test_sort_pairs_seq: keys_in / vals_in are uploaded as the first pair of buffers, keys_out / vals_out as the
+ * second; which[i] is what radix_sort_pairs returned for call i (0 = first pair, 1 = second), and slice i of keys_out /
+ * vals_out receives the whole slice of THAT pair.  Keys must be < 2^nbits[i]. */
+#define SDM_TEST_IN_PLACE 1u
+#define SDM_TEST_COUNT_ON_DEVICE 2u
+#define SDM_TEST_GUARD_WORDS 64
+sdm_status sdm_test_scratch_elems(int32_t sort, int64_t n, int64_t *elems);
+sdm_status sdm_test_scan_seq(int32_t n_calls, const int64_t *capacity, const int64_t *count, uint32_t flags,
+                             const uint32_t *in, uint32_t *out, int32_t *guard_ok, uint32_t *scratch_out);
+sdm_status sdm_test_sort_pairs_seq(int32_t n_calls, const int64_t *capacity, const int64_t *count, const int32_t *nbits,
+                                   uint32_t flags, const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out,
+                                   uint32_t *vals_out, int32_t *which, int32_t *guard_ok, uint32_t *scratch_out);
 
 const char *sdm_last_error(void);
 const char *sdm_version(void);

@@ -222,6 +222,9 @@ def load_library():
         "sdm_debug_alias_cap": [vp, i32],
         "sdm_test_scan": [vp, vp, i64],
         "sdm_test_sort_pairs": [vp, vp, vp, vp, i64, i32],
+        "sdm_test_scratch_elems": [i32, i64, C.POINTER(i64)],
+        "sdm_test_scan_seq": [i32, vp, vp, u32, vp, vp, C.POINTER(i32), vp],
+        "sdm_test_sort_pairs_seq": [i32, vp, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(i32), vp],
     }
     for name, argtypes in sig.items():
         fn = getattr(L, name)
@@ -800,3 +803,57 @@ def test_sort_pairs(keys, vals, nbits):
     ko, vo = np.empty_like(keys), np.empty_like(vals)
     _check(L, L.sdm_test_sort_pairs(_ptr(keys), _ptr(vals), _ptr(ko), _ptr(vo), keys.size, nbits), "sdm_test_sort_pairs")
     return ko, vo
+
+
+TEST_IN_PLACE, TEST_COUNT_ON_DEVICE, TEST_GUARD_WORDS = 1, 2, 64  # sdm.h, SDM_TEST_*
+
+
+def test_scratch_elems(sort, n):
+    """words of scratch the scan (sort = False) or the sort (True) asks for at n elements (sdm_test_scratch_elems)"""
+    L = load_library()
+    v = C.c_int64(0)
+    _check(L, L.sdm_test_scratch_elems(int(bool(sort)), int(n), C.byref(v)), "sdm_test_scratch_elems")
+    return v.value
+
+
+def _seq_args(capacity, count, arrays):
+    capacity = np.ascontiguousarray(capacity, dtype=np.int64)
+    count = capacity.copy() if count is None else np.ascontiguousarray(count, dtype=np.int64)
+    if capacity.ndim != 1 or capacity.size == 0 or count.shape != capacity.shape:
+        raise ValueError("one capacity and one count per call")
+    arrays = [np.ascontiguousarray(a, dtype=np.uint32) for a in arrays]
+    if any(a.shape != (int(capacity.sum()),) for a in arrays):
+        raise ValueError("the arrays hold one slice of `capacity` words per call")
+    return capacity, count, arrays
+
+
+def test_scan_seq(capacity, a, out, count=None, in_place=False, count_on_device=False, want_scratch=False):
+    """sdm_test_scan_seq: scans of the slices of `a` (capacity[i] words each) back to back on one scratch.  `out` is what the
+    output buffer holds before the calls.  Returns (the output buffer after them, guard words intact, the scratch as the last
+    call left it or None)."""
+    L = load_library()
+    capacity, count, (a, out) = _seq_args(capacity, count, [a, out])
+    out = out.copy()
+    flags = (TEST_IN_PLACE if in_place else 0) | (TEST_COUNT_ON_DEVICE if count_on_device else 0)
+    scratch = np.empty(test_scratch_elems(False, capacity.max()), np.uint32) if want_scratch else None
+    ok = C.c_int32(0)
+    _check(L, L.sdm_test_scan_seq(capacity.size, _ptr(capacity), _ptr(count), flags, _ptr(a), _ptr(out), C.byref(ok), _ptr(scratch)),
+           "sdm_test_scan_seq")
+    return out, bool(ok.value), scratch
+
+
+def test_sort_pairs_seq(capacity, nbits, keys, vals, keys_out, vals_out, count=None, count_on_device=False, want_scratch=False):
+    """sdm_test_sort_pairs_seq: sorts of the slices of (keys, vals) back to back on one scratch; keys_out / vals_out are what
+    the second pair of buffers holds before the calls.  Returns (keys, vals of the pair each call named, the value each call
+    returned, guard words intact, the scratch as the last call left it or None)."""
+    L = load_library()
+    capacity, count, (keys, vals, keys_out, vals_out) = _seq_args(capacity, count, [keys, vals, keys_out, vals_out])
+    nbits = np.ascontiguousarray(np.broadcast_to(np.asarray(nbits, np.int32), capacity.shape))
+    keys_out, vals_out = keys_out.copy(), vals_out.copy()
+    which = np.zeros(capacity.size, np.int32)
+    scratch = np.empty(test_scratch_elems(True, capacity.max()), np.uint32) if want_scratch else None
+    ok = C.c_int32(0)
+    _check(L, L.sdm_test_sort_pairs_seq(capacity.size, _ptr(capacity), _ptr(count), _ptr(nbits),
+                                        TEST_COUNT_ON_DEVICE if count_on_device else 0, _ptr(keys), _ptr(vals), _ptr(keys_out),
+                                        _ptr(vals_out), _ptr(which), C.byref(ok), _ptr(scratch)), "sdm_test_sort_pairs_seq")
+    return keys_out, vals_out, which, bool(ok.value), scratch

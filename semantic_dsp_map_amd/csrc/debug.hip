@@ -167,4 +167,135 @@ sdm_status sdm_test_sort_pairs(const uint32_t *keys_in, const uint32_t *vals_in,
   return SDM_OK;
 }
 
+// ---- the same two through their whole contract (sdm.h): a sequence of calls on one scratch without slack --------------
+}  // extern "C"
+namespace {
+
+constexpr uint32_t SEQ_CANARY = 0xC0FFEE5Au;
+constexpr size_t SEQ_MAX_WORDS = (size_t)1 << 28;  // all slices of one array together: 1 GiB
+
+// the slices of a sequence: capacities > 0; counts <= capacity unless they are read on the device, where any uint32 goes
+bool seq_layout(int32_t n_calls, const int64_t *capacity, const int64_t *count, bool on_device, std::vector<size_t> *first,
+                size_t *total, size_t *longest) {
+  if (n_calls <= 0 || !capacity || !count) return false;
+  *total = *longest = 0;
+  first->clear();
+  for (int32_t i = 0; i < n_calls; ++i) {
+    if (capacity[i] <= 0 || (size_t)capacity[i] > SEQ_MAX_WORDS || count[i] < 0 || count[i] > 0xffffffffll) return false;
+    if (!on_device && count[i] > capacity[i]) return false;
+    first->push_back(*total);
+    *total += (size_t)capacity[i];
+    *longest = std::max(*longest, (size_t)capacity[i]);
+  }
+  return *total <= SEQ_MAX_WORDS;
+}
+
+// the scratch of a sequence: exactly n words, zero, and SDM_TEST_GUARD_WORDS of the canary right behind them
+hipError_t seq_scratch(DevTemps &tmp, size_t n, uint32_t **scr) {
+  std::vector<uint32_t> h(n + SDM_TEST_GUARD_WORDS, 0u);
+  std::fill(h.begin() + n, h.end(), SEQ_CANARY);
+  hipError_t e = tmp.alloc(scr, h.size());
+  if (e == hipSuccess) e = hipMemcpy(*scr, h.data(), h.size() * 4, hipMemcpyHostToDevice);
+  return e;
+}
+hipError_t seq_scratch_read(const uint32_t *scr, size_t n, int32_t *guard_ok, uint32_t *scratch_out) {
+  uint32_t g[SDM_TEST_GUARD_WORDS];
+  hipError_t e = hipMemcpy(g, scr + n, sizeof(g), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return e;
+  *guard_ok = 1;
+  for (uint32_t w : g)
+    if (w != SEQ_CANARY) *guard_ok = 0;
+  if (scratch_out) e = hipMemcpy(scratch_out, scr, n * 4, hipMemcpyDeviceToHost);
+  return e;
+}
+hipError_t seq_counts(DevTemps &tmp, int32_t n_calls, const int64_t *count, uint32_t **dcount) {
+  std::vector<uint32_t> h(n_calls);
+  for (int32_t i = 0; i < n_calls; ++i) h[i] = (uint32_t)count[i];
+  hipError_t e = tmp.alloc(dcount, h.size());
+  if (e == hipSuccess) e = hipMemcpy(*dcount, h.data(), h.size() * 4, hipMemcpyHostToDevice);
+  return e;
+}
+
+}  // namespace
+extern "C" {
+
+sdm_status sdm_test_scratch_elems(int32_t sort, int64_t n, int64_t *elems) {
+  if (n <= 0 || !elems) return SDM_ERR_INVALID_ARGUMENT;
+  *elems = (int64_t)(sort ? sort_scratch_elems((size_t)n) : scan_scratch_elems((size_t)n));
+  return SDM_OK;
+}
+
+sdm_status sdm_test_scan_seq(int32_t n_calls, const int64_t *capacity, const int64_t *count, uint32_t flags, const uint32_t *in,
+                             uint32_t *out, int32_t *guard_ok, uint32_t *scratch_out) {
+  if (!in || !out || !guard_ok || (flags & ~(SDM_TEST_IN_PLACE | SDM_TEST_COUNT_ON_DEVICE))) return SDM_ERR_INVALID_ARGUMENT;
+  const bool on_device = flags & SDM_TEST_COUNT_ON_DEVICE, in_place = flags & SDM_TEST_IN_PLACE;
+  std::vector<size_t> first;
+  size_t total, longest;
+  if (!seq_layout(n_calls, capacity, count, on_device, &first, &total, &longest)) return SDM_ERR_INVALID_ARGUMENT;
+  // one form of the scan per scratch region (sdm_internal.h): the form of the longest capacity, which sizes the scratch
+  for (int32_t i = 0; i < n_calls; ++i) {
+    const size_t n = on_device ? (size_t)capacity[i] : (size_t)count[i];
+    if (n && scan_is_one_launch(n) != scan_is_one_launch(longest)) return SDM_ERR_INVALID_ARGUMENT;
+  }
+  const size_t scr_n = scan_scratch_elems(longest);
+  uint32_t *din, *dout, *scr, *dcount;
+  DevTemps tmp;
+  HIP_TRY(tmp.alloc(&din, total));
+  HIP_TRY(hipMemcpy(din, in, total * 4, hipMemcpyHostToDevice));
+  if (in_place) {
+    dout = din;
+  } else {
+    HIP_TRY(tmp.alloc(&dout, total));
+    HIP_TRY(hipMemcpy(dout, out, total * 4, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(seq_scratch(tmp, scr_n, &scr));
+  HIP_TRY(seq_counts(tmp, n_calls, count, &dcount));
+  for (int32_t i = 0; i < n_calls; ++i)
+    exclusive_scan_u32(din + first[i], dout + first[i], on_device ? (size_t)capacity[i] : (size_t)count[i], scr, nullptr,
+                       on_device ? dcount + i : nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, dout, total * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(seq_scratch_read(scr, scr_n, guard_ok, scratch_out));
+  return SDM_OK;
+}
+
+sdm_status sdm_test_sort_pairs_seq(int32_t n_calls, const int64_t *capacity, const int64_t *count, const int32_t *nbits,
+                                   uint32_t flags, const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out,
+                                   uint32_t *vals_out, int32_t *which, int32_t *guard_ok, uint32_t *scratch_out) {
+  if (!nbits || !keys_in || !vals_in || !keys_out || !vals_out || !which || !guard_ok || (flags & ~SDM_TEST_COUNT_ON_DEVICE))
+    return SDM_ERR_INVALID_ARGUMENT;
+  const bool on_device = flags & SDM_TEST_COUNT_ON_DEVICE;
+  std::vector<size_t> first;
+  size_t total, longest;
+  if (!seq_layout(n_calls, capacity, count, on_device, &first, &total, &longest)) return SDM_ERR_INVALID_ARGUMENT;
+  for (int32_t i = 0; i < n_calls; ++i)
+    if (nbits[i] <= 0 || nbits[i] > 32) return SDM_ERR_INVALID_ARGUMENT;
+  const size_t scr_n = sort_scratch_elems(longest);
+  uint32_t *ka, *va, *kb, *vb, *scr, *dcount;
+  DevTemps tmp;
+  HIP_TRY(tmp.alloc(&ka, total));
+  HIP_TRY(tmp.alloc(&va, total));
+  HIP_TRY(tmp.alloc(&kb, total));
+  HIP_TRY(tmp.alloc(&vb, total));
+  HIP_TRY(hipMemcpy(ka, keys_in, total * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(va, vals_in, total * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(kb, keys_out, total * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(vb, vals_out, total * 4, hipMemcpyHostToDevice));
+  HIP_TRY(seq_scratch(tmp, scr_n, &scr));
+  HIP_TRY(seq_counts(tmp, n_calls, count, &dcount));
+  for (int32_t i = 0; i < n_calls; ++i)
+    which[i] = radix_sort_pairs(ka + first[i], va + first[i], kb + first[i], vb + first[i],
+                                on_device ? (size_t)capacity[i] : (size_t)count[i], nbits[i], scr, nullptr,
+                                on_device ? dcount + i : nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  for (int32_t i = 0; i < n_calls; ++i) {
+    HIP_TRY(hipMemcpy(keys_out + first[i], (which[i] ? kb : ka) + first[i], (size_t)capacity[i] * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(vals_out + first[i], (which[i] ? vb : va) + first[i], (size_t)capacity[i] * 4, hipMemcpyDeviceToHost));
+  }
+  HIP_TRY(seq_scratch_read(scr, scr_n, guard_ok, scratch_out));
+  return SDM_OK;
+}
+
 }  // extern "C"

@@ -415,7 +415,6 @@ Front front_of(const sdm_map *m) {
 // the two.  The words' scan has one length per map and a region of its own; the flags' scan runs over capacity + 1
 // entries, which differs from build to build, and has one region for each form.  (Regions begin at even words: the
 // one-launch form keeps 8-byte words behind its two counters.)
-bool scan_is_one_launch(size_t n) { return scan_scratch_elems(n) > (n + 2047) / 2048 + 1; }  // 2 * tiles + 8 against tiles + 1
 struct ScanScratch {
   size_t words, flags_one, flags_two, total;  // offsets in uint32
 };

@@ -259,6 +259,7 @@ size_t scan_scratch_elems(size_t n) {
   const size_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
   return tiles <= (size_t)SCAN_ONEPASS_MAX_TILES ? 2 * tiles + 8 : tiles + 1;
 }
+bool scan_is_one_launch(size_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE <= (size_t)SCAN_ONEPASS_MAX_TILES; }
 
 void exclusive_scan_u32(const uint32_t *in, uint32_t *out, size_t n, uint32_t *scratch, hipStream_t s, const uint32_t *n_dev) {
   if (n == 0) return;
