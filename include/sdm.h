@@ -633,6 +633,54 @@ sdm_status sdm_get_frontier_clusters(sdm_map *m, sdm_frontier_cluster *out, int3
 sdm_status sdm_get_frontier_cells(sdm_map *m, uint32_t *cell, uint32_t *cluster, uint8_t *unknown_faces,
                                   int64_t cap, int64_t *n_out);
 
+/* ---- view scoring: how much unknown space would a camera at this pose see? (next-best-view exploration) ----
+ * A view is a camera pose and a range.  Its rays are a table the caller passes once per call: `dirs` holds n_rays
+ * camera-frame vectors, three floats each, NOT normalised - (x/z, y/z, 1) gives a ray whose end lies at planar depth
+ * `range`, as depth_max is meant.  Ray r of view v is the segment from a = pos to b = pos + range * (R(q) d_r), computed
+ * in float32 one IEEE operation at a time (no contraction), in this order: with q = (w, x, y, z), used as given,
+ *   R = | 1 - 2 (y y + z z)   2 (x y - w z)       2 (x z + w y)     |
+ *       | 2 (x y + w z)       1 - 2 (x x + z z)   2 (y z - w x)     |
+ *       | 2 (x z - w y)       2 (y z + w x)       1 - 2 (x x + y y) |
+ * (R d)_i = (R_i0 d_0 + R_i1 d_1) + R_i2 d_2, then b_i = pos_i + range * (R d)_i.  range <= 0 is not an error: b = a, the
+ * zero-length segment, the cell of a.  The segment is walked exactly as sdm_query_segments walks it without
+ * SDM_QUERY_UNKNOWN_BLOCKS: clipped to the map, only cells with occ >= 1 block, unknown cells are passed through and
+ * counted, space outside the map is nothing, x steps before y before z at equal t.  rays_out[v * n_rays + r] is bit for
+ * bit what sdm_query_segments returns for (a, b); ray_unknown_out[v * n_rays + r] is the number of cells with occ == -1
+ * among that ray's `cells`.  Either may be NULL.  A non-finite pos, q or range gives an all-zero gain and "no hit" rays
+ * with cells = 0; a non-finite d_r does for that ray only.
+ * Distinct counts: a cell counts once per view, however many of its rays visit it - the rays of a camera share their
+ * cells near the origin, and a sum over rays would count a nearby cell hundreds of times.  The blocking cell of a ray
+ * counts towards n_occupied, every cell before it towards n_unknown or n_free by its occ.  All counters and sums are
+ * integers: the result is bitwise the same from run to run whatever order the rays finish in.
+ * Like the other queries: reads the results of the last frame enqueued before the call, in stream order on the map's
+ * stream; never modifies map state; uses no scratch of the frames', the field's, the table's or the frontiers'.  With
+ * SDM_QUERY_ON_DEVICE all five pointers are device pointers and the call returns without waiting; without it inputs and
+ * outputs are host memory, staged in chunks of whole views, and the call waits.  n_views == 0 launches nothing.
+ * Memory: one bitmask of V / 8 bytes (V = NX*NY*NZ) per view in flight, in a pool of min(256, max(1, 64 MiB / (V / 8)))
+ * masks - 64 MiB at 256^3 (32 views in flight) and at 512^3 (4), 256 * V / 8 bytes on maps of up to 2^21 cells -
+ * allocated at the first sdm_query_views, freed by sdm_destroy and all zero whenever a call's work has completed.  A call
+ * with more views than masks works through them in batches.
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map, views, dirs or out, n_views < 0, n_rays < 1 or > SDM_VIEW_MAX_RAYS,
+ * n_views * n_rays >= 2^31, unknown flag bits (only SDM_QUERY_ON_DEVICE is known), or a Z-slab shard (shard_count > 1). */
+#define SDM_VIEW_MAX_RAYS 65536
+typedef struct {   /* 32 bytes */
+  float pos[3];    /* camera position, global frame */
+  float q[4];      /* camera orientation (w, x, y, z), as sdm_update's cam_q; used as given, not normalised */
+  float range;     /* metres; scales the ray table */
+} sdm_view;
+typedef struct {          /* 40 bytes, every field naturally aligned */
+  uint32_t n_unknown;     /* DISTINCT in-map cells with occ == -1 that at least one ray of the view visits */
+  uint32_t n_free;        /* distinct visited cells with occ == 0 */
+  uint32_t n_occupied;    /* distinct cells with occ >= 1 in which at least one ray ends */
+  uint32_t rays_hit;      /* rays that end in a blocking cell */
+  uint32_t rays_in_map;   /* rays that visit at least one in-map cell */
+  uint32_t pad;           /* 0 */
+  uint64_t ray_cells;     /* sum over the rays of cells visited (= sum of sdm_segment_hit.cells) */
+  uint64_t ray_unknown;   /* sum over the rays of visited cells with occ == -1 (not distinct) */
+} sdm_view_gain;
+sdm_status sdm_query_views(sdm_map *m, const sdm_view *views, int64_t n_views, const float *dirs, int32_t n_rays,
+                           sdm_view_gain *out, sdm_segment_hit *rays_out, int32_t *ray_unknown_out, uint32_t flags);
+
 /* ---- owner sets of the object layer: ObjectParticleHashMap (object_layer.h:20-52) */
 sdm_status sdm_object_particle_count(sdm_map *m, int32_t track_id, int64_t *count);
 /* The keys of ObjectParticleHashMap::indices_map whose sets are not empty: every track id that owns at least one slot of
@@ -690,6 +738,9 @@ sdm_status sdm_debug_sweep_mode(sdm_map *m, int32_t *mode_out);
 /* Test hook.  The table of older owner-set memberships (sdm_stats.alias_entries) takes 65536 entries; `cap` (1..65536)
  * makes it report its overflow earlier, so that a test can reach it on a small map.  Call before the map's first frame. */
 sdm_status sdm_debug_alias_cap(sdm_map *m, int32_t cap);
+/* Test hook.  sdm_query_views keeps at most max_views_in_flight views in flight (never more than its pool has masks);
+ * <= 0: the library's choice.  A test on a small map can so force a call to take several batches. */
+sdm_status sdm_debug_view_batch(sdm_map *m, int32_t max_views_in_flight);
 
 /* ---- device-side unit tests of the hand-written primitives (tests/test_primitives_gpu.py) */
 sdm_status sdm_test_scan(const uint32_t *in, uint32_t *out, int64_t n);

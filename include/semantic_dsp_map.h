@@ -443,6 +443,37 @@ class SemanticDSPMap {
     out.resize((size_t)n);
     return out.size();
   }
+  /// What would a camera there see (sdm.h, "view scoring")?  Scores candidate poses against the results of the last
+  /// update(): per view the distinct unknown, free and occupied cells its rays visit.  The rays are those of this map's
+  /// own camera through every stride-th pixel, ((u - cx) / fx, (v - cy) / fy, 1) in float32 for u = 0, stride, ... < width
+  /// and v = 0, stride, ... < height, rows first: a view's range is then the planar depth its rays end at, as depth_max
+  /// is meant.  The table is built from the preset's intrinsics at the first call and kept until the stride changes.
+  /// Returns the number of views scored; 0 (and an empty vector) before the first update() or when the call fails.
+  size_t scoreViews(const std::vector<sdm_view> &views, int stride, std::vector<sdm_view_gain> &out) {
+    out.clear();
+    if (!map_ || views.empty() || stride < 1) return 0;
+    const std::vector<float> &rays = viewRays(stride);
+    out.resize(views.size());
+    if (!check(sdm_query_views(map_, views.data(), (int64_t)views.size(), rays.data(), (int32_t)(rays.size() / 3), out.data(), nullptr,
+                               nullptr, 0u),
+               "sdm_query_views"))
+      out.clear();
+    return out.size();
+  }
+  /// the ray table scoreViews uses at `stride`: three floats per ray
+  const std::vector<float> &viewRays(int stride) {
+    if (stride != view_rays_stride_ || view_rays_.empty()) {
+      view_rays_.clear();
+      for (int v = 0; v < preset_.height; v += stride)
+        for (int u = 0; u < preset_.width; u += stride) {
+          view_rays_.push_back(((float)u - preset_.cx) / preset_.fx);
+          view_rays_.push_back(((float)v - preset_.cy) / preset_.fy);
+          view_rays_.push_back(1.f);
+        }
+      view_rays_stride_ = stride;
+    }
+    return view_rays_;
+  }
 
   // ---- the reference's public interface ----
   /// semantic_dsp_map.h:74-81
@@ -620,6 +651,8 @@ class SemanticDSPMap {
   std::vector<float> noise_table_;
   SdmUpdateTimes times_;
   bool tables_from_reference_ = false;
+  std::vector<float> view_rays_;  // scoreViews' ray table at view_rays_stride_
+  int view_rays_stride_ = 0;
 
   /// a frame that did not reach the map: its removals are offered again
   void frameLost(const std::vector<int32_t> &removals) {

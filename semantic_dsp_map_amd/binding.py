@@ -49,6 +49,13 @@ assert FRONTIER_CLUSTER.itemsize == 96
 FRONTIERS_FACE_CONNECTED = 0x1
 FRONTIER_NO_CLUSTER = 0xFFFFFFFF
 
+# view scoring (sdm.h: sdm_query_views)
+VIEW = np.dtype([("pos", "<f4", (3,)), ("q", "<f4", (4,)), ("range", "<f4")])
+VIEW_GAIN = np.dtype([("n_unknown", "<u4"), ("n_free", "<u4"), ("n_occupied", "<u4"), ("rays_hit", "<u4"), ("rays_in_map", "<u4"),
+                      ("pad", "<u4"), ("ray_cells", "<u8"), ("ray_unknown", "<u8")])
+assert VIEW.itemsize == 32 and VIEW_GAIN.itemsize == 40
+VIEW_MAX_RAYS = 65536
+
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
                 ("forget", np.uint8), ("owner", np.uint16)]
@@ -194,6 +201,8 @@ def load_library():
         "sdm_frontiers_update": [vp, u32, i32, i64],
         "sdm_get_frontier_clusters": [vp, vp, i32, C.POINTER(i32), vp],
         "sdm_get_frontier_cells": [vp, vp, vp, vp, i64, C.POINTER(i64)],
+        "sdm_query_views": [vp, vp, i64, vp, i32, vp, vp, vp, u32],
+        "sdm_debug_view_batch": [vp, i32],
         "sdm_object_particle_count": [vp, i32, C.POINTER(i64)],
         "sdm_tracks_with_particles": [vp, vp, i32, C.POINTER(i32)],
         "sdm_comm_set_options": [vp, i32, i32],
@@ -622,6 +631,31 @@ class SdmMap:
         _check(self.L, self.L.sdm_get_frontier_cells(self.h, _ptr(cell), _ptr(cluster), _ptr(faces), k, C.byref(n)), "sdm_get_frontier_cells")
         return cell, cluster, faces
 
+    # ---- view scoring (sdm.h).  Like the batched queries: host mode takes numpy and waits, on_device=True takes device
+    # pointers, enqueues on the map's stream and returns at once.
+    def query_views(self, views, dirs, with_rays=False, on_device=False, n_views=None, n_rays=None, out=None, rays_out=None,
+                    ray_unknown_out=None):
+        """views: VIEW records, dirs: (n_rays, 3) camera-frame ray vectors -> VIEW_GAIN per view; with_rays: also the
+        SEGMENT_HIT and the unknown-cell count of every ray, shaped (n_views, n_rays).  on_device: views, dirs, out
+        (n_views VIEW_GAIN), rays_out (n_views * n_rays SEGMENT_HIT, or None) and ray_unknown_out (int32, or None) are
+        device pointers, n_views and n_rays their lengths."""
+        if on_device:
+            _check(self.L, self.L.sdm_query_views(self.h, _ptr(int(views)), int(n_views), _ptr(int(dirs)), int(n_rays), _ptr(int(out)),
+                                                  _ptr(int(rays_out)) if rays_out else None,
+                                                  _ptr(int(ray_unknown_out)) if ray_unknown_out else None, QUERY_ON_DEVICE), "sdm_query_views")
+            return None
+        v = np.ascontiguousarray(views, dtype=VIEW).reshape(-1)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        gain = np.empty(len(v), VIEW_GAIN)
+        rays = np.empty((len(v), len(d)), SEGMENT_HIT) if with_rays else None
+        unk = np.empty((len(v), len(d)), np.int32) if with_rays else None
+        _check(self.L, self.L.sdm_query_views(self.h, _ptr(v), len(v), _ptr(d), len(d), _ptr(gain), _ptr(rays), _ptr(unk), 0), "sdm_query_views")
+        return (gain, rays, unk) if with_rays else gain
+
+    def set_view_batch(self, max_views_in_flight):
+        """Test hook: query_views keeps at most this many views in flight (<= 0: the library's choice) (sdm_debug_view_batch)."""
+        _check(self.L, self.L.sdm_debug_view_batch(self.h, int(max_views_in_flight)), "sdm_debug_view_batch")
+
     def occupied(self, cap=None, zero_center=False, free=False, mark_fov=False):
         cap = cap or self.v_count
         out = np.empty(cap, POINT)
@@ -778,6 +812,20 @@ class SdmMap:
         ms = C.c_float()
         _check(self.L, self.L.sdm_time_occupancy_sweep(self.h, iters, C.byref(ms)), "sdm_time_occupancy_sweep")
         return ms.value
+
+
+def pinhole_rays(cfg, stride=1):
+    """The camera-frame ray table of every `stride`-th pixel centre of cfg's pinhole camera: ((u - cx) / fx, (v - cy) / fy, 1)
+    in float32, shaped (rows, columns, 3), rows v = 0, stride, ... and columns u = 0, stride, ...  With a view's range
+    r the ray of pixel (u, v) ends at planar depth r (query_views)."""
+    get = (lambda k: cfg[k]) if isinstance(cfg, dict) else (lambda k: getattr(cfg, k))
+    u = np.arange(0, int(get("width")), int(stride), dtype=np.float32)
+    v = np.arange(0, int(get("height")), int(stride), dtype=np.float32)
+    x = (u - np.float32(get("cx"))) / np.float32(get("fx"))
+    y = (v - np.float32(get("cy"))) / np.float32(get("fy"))
+    out = np.empty((len(v), len(u), 3), np.float32)
+    out[..., 0], out[..., 1], out[..., 2] = x[None, :], y[:, None], 1.0
+    return out
 
 
 def comm_unique_id():

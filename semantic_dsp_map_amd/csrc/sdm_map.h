@@ -217,6 +217,14 @@ struct sdm_map {
   Frame front_f{};
   uint32_t front_flags = 0;
   bool front_valid = false;
+  // view scoring (sdm_query_views, views.hip): a pool of view_pool_masks bitmasks of V / 8 bytes, one per view in flight,
+  // allocated by the first call and zero between calls; view_batch: sdm_debug_view_batch's bound on the views in flight
+  // (0: as many as the pool has masks); view_clear_rewalk: a batch's masks are cleared by walking its rays again
+  // instead of zeroing them whole
+  uint32_t *d_view_pool = nullptr;
+  uint32_t view_pool_masks = 0;
+  int32_t view_batch = 0;
+  bool view_clear_rewalk = false;
   sdm_point_xyzrgb *d_points_rgb = nullptr;
   size_t points_rgb_cap = 0;
   ColourTables *d_colours = nullptr;

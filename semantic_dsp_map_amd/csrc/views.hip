@@ -1,0 +1,333 @@
+// views.hip — view scoring for next-best-view exploration (gfx950): sdm_query_views (include/sdm.h, "view scoring").
+//
+// A view is a camera pose and a range; its rays are the caller's table of camera-frame directions.  Every ray is the
+// segment sdm_query_segments would walk (clipped to the map, occ >= 1 blocks, unknown cells passed through), and per view
+// the kernel counts the DISTINCT cells its rays visit, by class.  Like the other queries it reads the result array of the
+// occupancy sweep (State::res) in stream order and the Frame of the last issued frame by value, and writes only the
+// caller's outputs - and a pool of bitmasks of its own, one bit per voxel and view in flight, which every call leaves
+// zeroed.
+//
+// The walk restates k_query_segments' (queries.hip) statement for statement - the DDA in double, SEG_K cells computed
+// ahead, their SEG_K loads issued together - rather than sharing it through a header: that kernel's registers and ISA
+// stay exactly what its tests hold it to, and tests/test_views_gpu.py holds the two walks together ray by ray, bit by bit.
+#include <cstdlib>
+
+#include "sdm_map.h"
+
+#pragma clang fp contract(off)
+
+static_assert(sizeof(sdm_view) == 32 && sizeof(sdm_view_gain) == 40 && sizeof(sdm_segment_hit) == 16, "sdm.h layouts");
+
+namespace sdm {
+
+namespace {
+
+constexpr int VTPB = 256;
+constexpr uint32_t RES_UNKNOWN_W1 = 0xff000000u;  // second word of an "unobserved" result: track 0, label 0, occ -1
+constexpr int SEG_K = 8;
+enum : int { SEG_CELL = 0, SEG_OUT = 1, SEG_END = 2 };
+enum : int { VIEW_MARK = 0, VIEW_CLEAR = 1 };
+
+__device__ __forceinline__ int8_t occ_of(uint32_t w1) { return (int8_t)(w1 >> 24); }
+__device__ __forceinline__ float map_u(const Dims &d, const Frame &f, int a, float p) { return ((p - f.center[a]) - d.pmin[a]) * d.recip; }
+__device__ __forceinline__ uint32_t cell_voxel(const Dims &d, const Frame &f, int ix, int iy, int iz) {
+  return ring_to_voxel(d, axis_correct(ix + f.eq[0], d.NX), axis_correct(iy + f.eq[1], d.NY), axis_correct(iz + f.eq[2], d.NZ));
+}
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) v += (uint32_t)__shfl_xor((int)v, s, 64);
+  return v;
+}
+
+// One lane per ray, a block row per view (blockIdx.y = the view within the batch = its mask in the pool).
+// VIEW_MARK: a lane sets the bits of the cells of a batch with returned atomics, all issued together; where the bit was
+// clear it is the first of the view to visit that cell and counts it by its class.  The atomics carry agent scope: the
+// workgroups of a view sit on different XCDs, whose L2s do not see each other's plain writes, while a returned atomic is
+// executed at the memory side.  Cells behind the blocking one are not marked: the number of cells to mark follows from the
+// stop mask, before any atomic.  Counts are summed over the wave, then one set of atomic adds per wave goes to the view.
+// VIEW_CLEAR: the same walk stores zero words over the cells the first pass marked (the alternative to zeroing the whole
+// masks; DESIGN.md 5f has both measured).
+template <int MODE>
+__global__ __launch_bounds__(VTPB) void k_view_rays(Dims d, Frame f, const sdm_view *__restrict__ views, const float *__restrict__ dirs,
+                                                    uint32_t n_rays, const uint2 *__restrict__ res, uint32_t *__restrict__ pool,
+                                                    uint32_t mask_words, sdm_view_gain *__restrict__ gain,
+                                                    sdm_segment_hit *__restrict__ rays_out, int32_t *__restrict__ unk_out) {
+  const uint32_t r = blockIdx.x * VTPB + threadIdx.x;
+  const uint32_t v = blockIdx.y;
+  const bool live = r < n_rays;
+  uint32_t *__restrict__ mask = pool + (size_t)v * mask_words;
+  const int N[3] = {(int)d.NX, (int)d.NY, (int)d.NZ};
+  // the ray: a = pos, b = pos + range * (R(q) d), float32, one operation at a time (sdm.h pins the order)
+  const float px = views[v].pos[0], py = views[v].pos[1], pz = views[v].pos[2];
+  const float qw = views[v].q[0], qx = views[v].q[1], qy = views[v].q[2], qz = views[v].q[3];
+  const float range = views[v].range;
+  float dx = 0.f, dy = 0.f, dz = 0.f;
+  if (live) {
+    dx = dirs[3 * (size_t)r];
+    dy = dirs[3 * (size_t)r + 1];
+    dz = dirs[3 * (size_t)r + 2];
+  }
+  const bool given = live && isfinite(px) && isfinite(py) && isfinite(pz) && isfinite(qw) && isfinite(qx) && isfinite(qy) && isfinite(qz) &&
+                     isfinite(range) && isfinite(dx) && isfinite(dy) && isfinite(dz);
+  const float R[9] = {1.f - 2.f * (qy * qy + qz * qz), 2.f * (qx * qy - qw * qz), 2.f * (qx * qz + qw * qy),
+                      2.f * (qx * qy + qw * qz), 1.f - 2.f * (qx * qx + qz * qz), 2.f * (qy * qz - qw * qx),
+                      2.f * (qx * qz - qw * qy), 2.f * (qy * qz + qw * qx), 1.f - 2.f * (qx * qx + qy * qy)};
+  const float pa[3] = {px, py, pz};
+  float ua[3], ub[3];
+  bool finite = given;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float rd = (R[3 * a] * dx + R[3 * a + 1] * dy) + R[3 * a + 2] * dz;
+    const float pb = range > 0.f ? pa[a] + range * rd : pa[a];  // (range <= 0: the zero-length segment, the cell of a)
+    ua[a] = map_u(d, f, a, pa[a]);
+    ub[a] = map_u(d, f, a, pb);
+    finite = finite && isfinite(ua[a]) && isfinite(ub[a]);
+  }
+  float hit_t = -1.f;
+  uint32_t hit_v = INVALID_INDEX, hit_w = RES_UNKNOWN_W1;
+  int cells = 0;
+  uint32_t n_unk = 0, n_free = 0, n_occ = 0, r_unk = 0;
+  // the state of the walk: current cell c, the t at which it was entered, per axis the t of the next plane
+  int c[3] = {0, 0, 0}, step[3] = {0, 0, 0};
+  double A[3], inv[3], tn[3];
+  double t_cur = 0.0;
+  int kind = SEG_END;  // of the current cell
+  if (finite) {
+    bool inside = true, empty = false;
+    double t_in = -INFINITY, t_out = INFINITY;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      A[a] = (double)ua[a];
+      const double D = (double)ub[a] - A[a];
+      inside = inside && ua[a] >= 0.f && ua[a] < (float)N[a];
+      if (D == 0.0) {
+        empty = empty || !(ua[a] >= 0.f && ua[a] < (float)N[a]);
+        inv[a] = 0.0;
+      } else {
+        inv[a] = 1.0 / D;
+        const double t0 = (0.0 - A[a]) * inv[a], t1 = ((double)N[a] - A[a]) * inv[a];
+        t_in = fmax(t_in, fmin(t0, t1));
+        t_out = fmin(t_out, fmax(t0, t1));
+      }
+      step[a] = D > 0.0 ? 1 : (D < 0.0 ? -1 : 0);
+    }
+    if (inside) {
+      kind = SEG_CELL;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) c[a] = (int)floorf(ua[a]);
+    } else if (!empty && t_in <= 1.0 && t_out > 0.0 && t_in < t_out) {
+      // clipped: the walk starts where the segment enters the map (rounding at the face is clamped back into the map)
+      kind = SEG_CELL;
+      t_cur = fmax(t_in, 0.0);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) c[a] = min(max((int)floor(A[a] + t_cur * ((double)ub[a] - A[a])), 0), N[a] - 1);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) tn[a] = step[a] == 0 ? INFINITY : ((double)(c[a] + (step[a] > 0)) - A[a]) * inv[a];
+  }
+  while (kind != SEG_END) {
+    uint32_t vox[SEG_K], w[SEG_K];
+    float tin[SEG_K];
+    int kd[SEG_K];
+#pragma unroll
+    for (int k = 0; k < SEG_K; ++k) {  // the next SEG_K cells: arithmetic only
+      kd[k] = kind;
+      tin[k] = (float)t_cur;
+      vox[k] = kind == SEG_CELL ? cell_voxel(d, f, c[0], c[1], c[2]) : INVALID_INDEX;
+      if (kind == SEG_CELL) {
+        int ax = 0;  // the plane crossed next: x before y before z at equal t
+        double tm = tn[0];
+        if (tn[1] < tm) { ax = 1; tm = tn[1]; }
+        if (tn[2] < tm) { ax = 2; tm = tn[2]; }
+        if (tm > 1.0) {
+          kind = SEG_END;
+        } else {
+          const int cn = (ax == 0 ? c[0] : ax == 1 ? c[1] : c[2]) + (ax == 0 ? step[0] : ax == 1 ? step[1] : step[2]);
+          const int na = ax == 0 ? N[0] : ax == 1 ? N[1] : N[2];
+#pragma unroll
+          for (int a = 0; a < 3; ++a)
+            if (a == ax) {
+              c[a] = cn;
+              tn[a] = ((double)(cn + (step[a] > 0)) - A[a]) * inv[a];
+            }
+          t_cur = tm;
+          if (cn < 0 || cn >= na) kind = SEG_OUT;
+        }
+      } else {
+        kind = SEG_END;  // (after the cell outside the map there is nothing: the map is convex)
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < SEG_K; ++k) w[k] = res[kd[k] == SEG_CELL ? vox[k] : 0u].y;  // SEG_K independent loads
+    uint32_t blocked = 0, ended = 0;
+#pragma unroll
+    for (int k = 0; k < SEG_K; ++k) {
+      blocked |= (uint32_t)(kd[k] == SEG_CELL && occ_of(w[k]) >= 1) << k;
+      ended |= (uint32_t)(kd[k] != SEG_CELL) << k;
+    }
+    const uint32_t stop = blocked | ended;
+    const int first = stop ? __builtin_ctz(stop) : SEG_K;
+    const bool hit = stop && ((blocked >> first) & 1u);
+    const int nm = first + (hit ? 1 : 0);  // cells of this batch the ray visits: all in the map, the last one may block
+    if (MODE == VIEW_MARK) {
+      uint32_t old[SEG_K];
+#pragma unroll
+      for (int k = 0; k < SEG_K; ++k) {  // up to SEG_K returned atomics in flight
+        old[k] = 0xffffffffu;
+        if (k < nm) old[k] = __hip_atomic_fetch_or(mask + (vox[k] >> 5), 1u << (vox[k] & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+#pragma unroll
+      for (int k = 0; k < SEG_K; ++k) {
+        const int8_t o = occ_of(w[k]);
+        const bool visited = k < nm, fresh = visited && !((old[k] >> (vox[k] & 31u)) & 1u);
+        n_unk += (uint32_t)(fresh && o == -1);
+        n_free += (uint32_t)(fresh && o == 0);
+        n_occ += (uint32_t)(fresh && o >= 1);
+        r_unk += (uint32_t)(visited && o == -1);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < SEG_K; ++k)
+        if (k < nm) mask[vox[k] >> 5] = 0u;
+    }
+    cells += nm;
+    if (!stop) continue;
+    if (hit) {
+#pragma unroll
+      for (int k = 0; k < SEG_K; ++k)  // (selected by compile-time index: no register array indexed at run time)
+        if (k == first) {
+          hit_t = tin[k];
+          hit_v = vox[k];
+          hit_w = w[k];
+        }
+    }
+    break;
+  }
+  if (MODE == VIEW_CLEAR) return;
+  if (live) {
+    const size_t i = (size_t)v * n_rays + r;
+    if (rays_out) {
+      sdm_segment_hit h;
+      h.t = hit_t;
+      h.voxel = hit_v;
+      h.cells = cells;
+      __builtin_memcpy(&h.track, &hit_w, 4);
+      uint4 o;
+      __builtin_memcpy(&o, &h, 16);
+      reinterpret_cast<uint4 *>(rays_out)[i] = o;
+    }
+    if (unk_out) unk_out[i] = (int32_t)r_unk;
+  }
+  // the wave's sums (lanes past the last ray carry zeros), one set of adds per wave that has anything
+  const uint32_t s_unk = wave_sum(n_unk), s_free = wave_sum(n_free), s_occ = wave_sum(n_occ);
+  const uint32_t s_hit = wave_sum((uint32_t)(hit_v != INVALID_INDEX)), s_in = wave_sum((uint32_t)(cells > 0));
+  const uint32_t s_cells = wave_sum((uint32_t)cells), s_runk = wave_sum(r_unk);
+  if ((threadIdx.x & 63u) == 0 && s_cells) {
+    sdm_view_gain *g = gain + v;
+    if (s_unk) atomicAdd(&g->n_unknown, s_unk);
+    if (s_free) atomicAdd(&g->n_free, s_free);
+    if (s_occ) atomicAdd(&g->n_occupied, s_occ);
+    if (s_hit) atomicAdd(&g->rays_hit, s_hit);
+    atomicAdd(&g->rays_in_map, s_in);
+    atomicAdd(reinterpret_cast<unsigned long long *>(&g->ray_cells), (unsigned long long)s_cells);
+    if (s_runk) atomicAdd(reinterpret_cast<unsigned long long *>(&g->ray_unknown), (unsigned long long)s_runk);
+  }
+}
+
+constexpr size_t VIEW_POOL_BYTES = (size_t)64 << 20;  // what the pool may take; at least one mask, at most VIEW_POOL_MASKS
+constexpr uint32_t VIEW_POOL_MASKS = 256;
+constexpr size_t VIEW_CHUNK_RAYS = (size_t)1 << 20;   // host mode: rays per staged chunk (whole views; at least one)
+size_t view_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// `n` views from device memory, in batches of as many as the pool has masks (or the test hook allows)
+sdm_status views_enqueue(sdm_map *m, const Frame &f, const sdm_view *views, const float *dirs, uint32_t n_rays, size_t n, sdm_view_gain *out,
+                         sdm_segment_hit *rays_out, int32_t *unk_out) {
+  const uint32_t mask_words = m->d.V / 32u;
+  if (!m->d_view_pool) {
+    const size_t mask_bytes = (size_t)mask_words * 4;
+    m->view_pool_masks = (uint32_t)std::min<size_t>(VIEW_POOL_MASKS, std::max<size_t>(1, VIEW_POOL_BYTES / mask_bytes));
+    SDM_TRY(alloc_tracked(m, &m->d_view_pool, (size_t)m->view_pool_masks * mask_words));
+    HIP_TRY(hipMemsetAsync(m->d_view_pool, 0, (size_t)m->view_pool_masks * mask_bytes, m->stream));  // zero; every call leaves it zero again
+  }
+  const char *e = getenv("SDM_VIEW_CLEAR");  // A/B (tools/probes/views_probe.py): "rewalk" or "memset", looked up per call
+  const bool rewalk = e ? strcmp(e, "rewalk") == 0 : m->view_clear_rewalk;
+  const uint32_t B = m->view_batch > 0 ? std::min<uint32_t>(m->view_pool_masks, (uint32_t)m->view_batch) : m->view_pool_masks;
+  const uint2 *res = reinterpret_cast<const uint2 *>(m->st.res);
+  HIP_TRY(hipMemsetAsync(out, 0, n * sizeof(sdm_view_gain), m->stream));
+  for (size_t v0 = 0; v0 < n; v0 += B) {
+    const uint32_t nb = (uint32_t)std::min<size_t>(B, n - v0);
+    const dim3 grid((n_rays + VTPB - 1) / VTPB, nb);
+    sdm_segment_hit *ro = rays_out ? rays_out + v0 * n_rays : nullptr;
+    int32_t *uo = unk_out ? unk_out + v0 * n_rays : nullptr;
+    hipLaunchKernelGGL(k_view_rays<VIEW_MARK>, grid, dim3(VTPB), 0, m->stream, m->d, f, views + v0, dirs, n_rays, res, m->d_view_pool, mask_words,
+                       out + v0, ro, uo);
+    HIP_TRY(hipGetLastError());
+    if (rewalk) {
+      hipLaunchKernelGGL(k_view_rays<VIEW_CLEAR>, grid, dim3(VTPB), 0, m->stream, m->d, f, views + v0, dirs, n_rays, res, m->d_view_pool,
+                         mask_words, (sdm_view_gain *)nullptr, (sdm_segment_hit *)nullptr, (int32_t *)nullptr);
+      HIP_TRY(hipGetLastError());
+    } else {
+      HIP_TRY(hipMemsetAsync(m->d_view_pool, 0, (size_t)nb * mask_words * 4, m->stream));
+    }
+  }
+  return SDM_OK;
+}
+
+}  // namespace
+
+}  // namespace sdm
+
+extern "C" {
+
+sdm_status sdm_query_views(sdm_map *m, const sdm_view *views, int64_t n_views, const float *dirs, int32_t n_rays, sdm_view_gain *out,
+                           sdm_segment_hit *rays_out, int32_t *ray_unknown_out, uint32_t flags) {
+  const sdm_status e = query_check(m, views, n_views, out, flags, SDM_QUERY_ON_DEVICE, "sdm_query_views");
+  if (e != SDM_OK) return e;
+  if (!dirs || n_rays < 1 || n_rays > SDM_VIEW_MAX_RAYS || n_views > (((int64_t)1 << 31) - 1) / n_rays) {
+    set_error("sdm_query_views", __FILE__, __LINE__, "null ray table, n_rays outside 1 .. 65536, or n_views * n_rays >= 2^31");
+    return SDM_ERR_INVALID_ARGUMENT;
+  }
+  if (n_views == 0) return SDM_OK;
+  HIP_TRY(hipSetDevice(m->device));
+  const Frame f = m->f;
+  const size_t n = (size_t)n_views, nr = (size_t)n_rays;
+  if (flags & SDM_QUERY_ON_DEVICE) return views_enqueue(m, f, views, dirs, (uint32_t)n_rays, n, out, rays_out, ray_unknown_out);
+  // host mode: the ray table goes up once, the views in chunks of whole views through the queries' staging area
+  const size_t chunk = std::min(n, std::max<size_t>(1, VIEW_CHUNK_RAYS / nr));
+  const size_t o_views = view_align(nr * 12), o_out = o_views + view_align(chunk * sizeof(sdm_view));
+  const size_t o_rays = o_out + view_align(chunk * sizeof(sdm_view_gain));
+  const size_t o_unk = o_rays + (rays_out ? view_align(chunk * nr * sizeof(sdm_segment_hit)) : 0);
+  const size_t need = o_unk + (ray_unknown_out ? view_align(chunk * nr * 4) : 0);
+  if (need > m->query_bytes) {
+    const size_t grown = std::max(need, (size_t)1 << 20);
+    SDM_TRY(regrow(m, &m->h_query, &m->query_bytes, grown, m->stream, true));
+    SDM_TRY(regrow(m, &m->d_query, &m->query_bytes, grown));
+  }
+  unsigned char *hq = m->h_query, *dq = m->d_query;
+  memcpy(hq, dirs, nr * 12);
+  HIP_TRY(hipMemcpyAsync(dq, hq, nr * 12, hipMemcpyHostToDevice, m->stream));
+  for (size_t off = 0; off < n; off += chunk) {
+    const size_t c = std::min(chunk, n - off);
+    memcpy(hq + o_views, views + off, c * sizeof(sdm_view));
+    HIP_TRY(hipMemcpyAsync(dq + o_views, hq + o_views, c * sizeof(sdm_view), hipMemcpyHostToDevice, m->stream));
+    SDM_TRY(views_enqueue(m, f, reinterpret_cast<const sdm_view *>(dq + o_views), reinterpret_cast<const float *>(dq), (uint32_t)n_rays, c,
+                          reinterpret_cast<sdm_view_gain *>(dq + o_out), rays_out ? reinterpret_cast<sdm_segment_hit *>(dq + o_rays) : nullptr,
+                          ray_unknown_out ? reinterpret_cast<int32_t *>(dq + o_unk) : nullptr));
+    HIP_TRY(hipMemcpyAsync(hq + o_out, dq + o_out, c * sizeof(sdm_view_gain), hipMemcpyDeviceToHost, m->stream));
+    if (rays_out) HIP_TRY(hipMemcpyAsync(hq + o_rays, dq + o_rays, c * nr * sizeof(sdm_segment_hit), hipMemcpyDeviceToHost, m->stream));
+    if (ray_unknown_out) HIP_TRY(hipMemcpyAsync(hq + o_unk, dq + o_unk, c * nr * 4, hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    memcpy(out + off, hq + o_out, c * sizeof(sdm_view_gain));
+    if (rays_out) memcpy(rays_out + off * nr, hq + o_rays, c * nr * sizeof(sdm_segment_hit));
+    if (ray_unknown_out) memcpy(ray_unknown_out + off * nr, hq + o_unk, c * nr * 4);
+  }
+  return SDM_OK;
+}
+
+sdm_status sdm_debug_view_batch(sdm_map *m, int32_t max_views_in_flight) {
+  if (!m) return SDM_ERR_INVALID_ARGUMENT;
+  m->view_batch = max_views_in_flight > 0 ? max_views_in_flight : 0;
+  return SDM_OK;
+}
+
+}  // extern "C"
