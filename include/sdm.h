@@ -681,6 +681,81 @@ typedef struct {          /* 40 bytes, every field naturally aligned */
 sdm_status sdm_query_views(sdm_map *m, const sdm_view *views, int64_t n_views, const float *dirs, int32_t n_rays,
                            sdm_view_gain *out, sdm_segment_hit *rays_out, int32_t *ray_unknown_out, uint32_t flags);
 
+/* ---- travel cost: how far is it from the robot to a cell, and by which cells? (the denominator of a view's utility) ----
+ * sdm_reach_update builds, on the map's stream, a shortest-path field over the traversable cells of the map block from a
+ * set of start cells.  Unlike the other builds IT WAITS: it returns when the field is complete - how much work there is
+ * depends on the map's topology, the host decides when the relaxation is done, and no kernel ever waits for another
+ * workgroup.  Like them the result is a snapshot that keeps its frame's map center and ring offsets and answers for it
+ * until the next sdm_reach_update; nothing of the map's state is modified and no scratch of the frames', the distance
+ * field's, the instance table's, the frontiers' or view scoring's is used.
+ * Cells are map-index cells (i, j, k), cell word i | j << x_n | k << (x_n + y_n), as for the field, the table and the
+ * frontiers.  The ring's wrap point is not a neighbour relation, the map is a block and no torus, and nothing outside
+ * the map is traversable.
+ * Traversable cell: occ == 0; with SDM_REACH_THROUGH_UNKNOWN also occ == -1; occ >= 1 never.
+ * Clearance: min_d2 is a squared clearance in cells.  min_d2 == 0: the classes come from the result array of the last
+ * frame enqueued before the call.  min_d2 > 0: the build reads the distance field's snapshot instead - the snapshot
+ * word for the class, the site for d2 - and a cell must also have d2 >= min_d2 (a field without obstacles has
+ * d2 = 0xffffffff, which passes); the reach field then inherits that field's frame, not the current one; without an
+ * sdm_esdf_update before it the call is SDM_ERR_INVALID_ARGUMENT.  The field's own flags (UNKNOWN_IS_OBSTACLE,
+ * STATIC_ONLY) are the caller's choice and change nothing in this rule.
+ * Moves: the offsets o = (dx, dy, dz) in {-1, 0, 1}^3 without 0, numbered n = (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1); 13 is
+ * the centre and unused.  With SDM_REACH_FACE_CONNECTED only the six face moves exist.  A move c -> c + o is allowed
+ * when every cell c + s with s_a in {0, o_a} per axis - 2, 4 or 8 cells - lies inside the map and is traversable: no
+ * diagonal squeezes between two blocked cells, and the rule is symmetric.  A move weighs 10, 14 or 17 for one, two or
+ * three non-zero components (SDM_REACH_COST_PER_CELL = 10).
+ * Field: cost(c), uint32, is the smallest weight sum over the paths of allowed moves from any start cell to c; a start
+ * cell has cost 0; 0xffffffff = unreachable or not traversable.  With max_cost > 0 the cells whose true cost exceeds
+ * max_cost read 0xffffffff (a truncated search, still exact); max_cost == 0: no limit.  The largest possible cost is
+ * below 17 * V (< 2^32 at 512^3).  The field is the unique fixed point of a min-plus relaxation over integers: it is
+ * bitwise the same whatever order the device relaxes in.
+ * Starts: n_starts host entries, as points (start_xyz, three floats each, the cell of floor(u) per axis as for the
+ * distance query) or as cell words (start_cells); exactly one of the two pointers is non-NULL, also with n_starts == 0.
+ * Entries outside the map, non-finite ones and ones on cells that are not traversable are
+ * ignored; duplicates are fine; no usable start is no error: every cell is unreachable.
+ * Path descent: from a cell with 0 < cost < 0xffffffff the next cell is c + o for the smallest move number n whose move
+ * is allowed and has cost(c + o) + w(o) == cost(c) (one exists by construction; the allowed test is needed: a neighbour
+ * can satisfy the equation across a forbidden diagonal).  A path is the cell words from the goal to a start, both
+ * included; its length is at most cost / 10 + 1.
+ * sdm_query_reach / sdm_reach_paths answer for the field of the last build; goals are points (xyz) or cell words (cells),
+ * exactly one of the two non-NULL; SDM_QUERY_ON_DEVICE as for the other queries (device pointers, enqueued, no wait),
+ * host mode through the queries' staging area.  len_out[g] is the true length of goal g's path, 0 where there is none;
+ * it may exceed max_len: only the first min(len, max_len) cells, counted from the goal, are written to row g of
+ * cells_out (n rows of max_len words), the rest of the row is left untouched.
+ * Memory: 4 B per voxel of cost, V / 8 bytes of traversable mask, and the activity bookkeeping of the relaxation - one
+ * bit and one list word per tile of up to 8 x 8 x 8 cells (V / 512 tiles on maps without 4-cell axes): 64 MiB + 2 MiB +
+ * 132 KiB at 256^3.  Allocated at the first sdm_reach_update, freed by sdm_destroy.
+ * The build issues its rounds eight at a time between two looks at the count of active tiles; the environment variable
+ * SDM_REACH_BATCH=k (k >= 1, read at every build) makes it k, for tools/probes/reach_probe.py.  The field does not depend on it.
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map, no or both start / goal pointers, unknown flag bits, negative counts,
+ * max_len < 0, a NULL output, a Z-slab shard (shard_count > 1), min_d2 > 0 without a distance field, and the getter or a
+ * query before any sdm_reach_update.  SDM_ERR_NOT_CONVERGED if the relaxation has not come to rest after V rounds: a
+ * defect, never a result. */
+#define SDM_REACH_FACE_CONNECTED  0x1u  /* the six face moves only */
+#define SDM_REACH_THROUGH_UNKNOWN 0x2u  /* cells with occ == -1 are traversable too */
+#define SDM_REACH_COST_PER_CELL   10
+typedef struct {            /* 32 bytes */
+  uint32_t n_starts_used;   /* distinct start cells that were traversable */
+  uint32_t n_traversable, n_reached, max_cost_reached;
+  uint32_t rounds;          /* relaxation rounds the build took (diagnostic; not part of the bitwise contract) */
+  uint32_t flags, min_d2, max_cost;
+} sdm_reach_info;
+typedef struct {            /* 16 bytes */
+  uint32_t cost;            /* 0xffffffff: no path */
+  float    metres;          /* (float)cost * (voxel_size * 0.1f), float32, no contraction; -1 where cost is 0xffffffff */
+  uint32_t cell;            /* the goal's cell word; 0xffffffff outside the map / non-finite */
+  uint8_t  next;            /* move number of the first descent step; 13 at a start; 255 where no path */
+  uint8_t  status;          /* 0 reached, 1 traversable but unreachable (or beyond max_cost), 2 not traversable, 3 outside / non-finite */
+  uint16_t pad;             /* 0 */
+} sdm_reach_result;
+sdm_status sdm_reach_update(sdm_map *m, const float *start_xyz, const uint32_t *start_cells, int64_t n_starts,
+                            uint32_t min_d2, uint32_t max_cost, uint32_t flags);
+/* Waits; cost in map-index order, x fastest (V words); either of cost and info may be NULL, and so may origin (the global
+ * position of the min corner of cell (0,0,0) of the snapshot). */
+sdm_status sdm_get_reach(sdm_map *m, uint32_t *cost, sdm_reach_info *info, float origin[3]);
+sdm_status sdm_query_reach(sdm_map *m, const float *xyz, const uint32_t *cells, int64_t n, sdm_reach_result *out, uint32_t flags);
+sdm_status sdm_reach_paths(sdm_map *m, const float *xyz, const uint32_t *cells, int64_t n, int32_t max_len,
+                           uint32_t *cells_out, int32_t *len_out, uint32_t flags);
+
 /* ---- owner sets of the object layer: ObjectParticleHashMap (object_layer.h:20-52) */
 sdm_status sdm_object_particle_count(sdm_map *m, int32_t track_id, int64_t *count);
 /* The keys of ObjectParticleHashMap::indices_map whose sets are not empty: every track id that owns at least one slot of
@@ -738,6 +813,8 @@ sdm_status sdm_debug_sweep_mode(sdm_map *m, int32_t *mode_out);
 /* Test hook.  The table of older owner-set memberships (sdm_stats.alias_entries) takes 65536 entries; `cap` (1..65536)
  * makes it report its overflow earlier, so that a test can reach it on a small map.  Call before the map's first frame. */
 sdm_status sdm_debug_alias_cap(sdm_map *m, int32_t cap);
+/* Diagnostic (tools/probes/reach_probe.py): the tiles relaxed by the last sdm_reach_update, summed over its rounds. */
+sdm_status sdm_debug_reach_tiles(sdm_map *m, int64_t *tiles_out);
 /* Test hook.  sdm_query_views keeps at most max_views_in_flight views in flight (never more than its pool has masks);
  * <= 0: the library's choice.  A test on a small map can so force a call to take several batches. */
 sdm_status sdm_debug_view_batch(sdm_map *m, int32_t max_views_in_flight);

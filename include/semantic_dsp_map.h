@@ -460,6 +460,57 @@ class SemanticDSPMap {
       out.clear();
     return out.size();
   }
+  /// How far is it to get there (sdm.h, "travel cost")?  Builds the travel-cost field from `start` (a global position,
+  /// the robot's) over the results of the last update() and answers for every goal position: cost (ten per cell along a
+  /// face, 14 and 17 along diagonals, never squeezing between two blocked cells), the same in metres, the goal's cell,
+  /// the first step of the way back and a status.  through_unknown: never-observed cells can be crossed as well as free
+  /// ones.  max_metres > 0 bounds the search: goals farther than that read "unreachable".  clearance_cells > 0 keeps the
+  /// path that many cells away from every obstacle; it needs, and builds, the distance field of the same frame with flags 0 - a field the caller
+  /// built before, with whatever flags, is replaced: build it again after this call if it is still wanted.  paths
+  /// (may be null): per goal the cell words from the goal to the start, empty where there is no path.  The call waits
+  /// for the build.  Returns the number of goals answered; 0 (and an empty vector) before the first update() or when a
+  /// call fails.
+  size_t reach(const Eigen::Vector3d &start, const std::vector<Eigen::Vector3d> &goals, std::vector<sdm_reach_result> &costs_out,
+               bool through_unknown = false, float max_metres = 0.f, int clearance_cells = 0,
+               std::vector<std::vector<uint32_t>> *paths = nullptr) {
+    costs_out.clear();
+    if (paths) paths->clear();
+    if (!map_ || goals.empty()) return 0;
+    const float s[3] = {(float)start.x(), (float)start.y(), (float)start.z()};
+    // (0 would mean "no budget": a positive max_metres below a cost unit asks for one; 4294967040 is the largest float below 2^32)
+    const uint32_t budget = max_metres > 0.f ? (uint32_t)std::min(std::max(max_metres / (preset_.voxel_size * 0.1f), 1.f), 4294967040.f) : 0u;
+    const uint32_t min_d2 = clearance_cells > 0 ? (uint32_t)clearance_cells * (uint32_t)clearance_cells : 0u;
+    if (min_d2 && !check(sdm_esdf_update(map_, 0u), "sdm_esdf_update")) return 0;
+    if (!check(sdm_reach_update(map_, s, nullptr, 1, min_d2, budget, through_unknown ? SDM_REACH_THROUGH_UNKNOWN : 0u), "sdm_reach_update"))
+      return 0;
+    std::vector<float> xyz(3 * goals.size());
+    for (size_t i = 0; i < goals.size(); ++i) {
+      xyz[3 * i] = (float)goals[i].x();
+      xyz[3 * i + 1] = (float)goals[i].y();
+      xyz[3 * i + 2] = (float)goals[i].z();
+    }
+    costs_out.resize(goals.size());
+    if (!check(sdm_query_reach(map_, xyz.data(), nullptr, (int64_t)goals.size(), costs_out.data(), 0u), "sdm_query_reach")) {
+      costs_out.clear();
+      return 0;
+    }
+    if (paths) {
+      uint32_t longest = 0;
+      for (const sdm_reach_result &r : costs_out)
+        if (r.cost != 0xffffffffu) longest = std::max(longest, r.cost / (uint32_t)SDM_REACH_COST_PER_CELL + 1u);  // a path's longest
+      std::vector<uint32_t> rows(goals.size() * (size_t)longest);
+      std::vector<int32_t> lens(goals.size());
+      if (!check(sdm_reach_paths(map_, xyz.data(), nullptr, (int64_t)goals.size(), (int32_t)longest, rows.empty() ? nullptr : rows.data(),
+                                 lens.data(), 0u),
+                 "sdm_reach_paths")) {
+        costs_out.clear();
+        return 0;
+      }
+      paths->resize(goals.size());
+      for (size_t i = 0; i < goals.size(); ++i) (*paths)[i].assign(rows.begin() + i * longest, rows.begin() + i * longest + lens[i]);
+    }
+    return costs_out.size();
+  }
   /// the ray table scoreViews uses at `stride`: three floats per ray
   const std::vector<float> &viewRays(int stride) {
     if (stride != view_rays_stride_ || view_rays_.empty()) {

@@ -55,6 +55,15 @@ VIEW_GAIN = np.dtype([("n_unknown", "<u4"), ("n_free", "<u4"), ("n_occupied", "<
                       ("pad", "<u4"), ("ray_cells", "<u8"), ("ray_unknown", "<u8")])
 assert VIEW.itemsize == 32 and VIEW_GAIN.itemsize == 40
 VIEW_MAX_RAYS = 65536
+# the travel-cost field (sdm.h: sdm_reach_update / sdm_get_reach / sdm_query_reach / sdm_reach_paths)
+REACH_INFO = np.dtype([("n_starts_used", "<u4"), ("n_traversable", "<u4"), ("n_reached", "<u4"), ("max_cost_reached", "<u4"),
+                       ("rounds", "<u4"), ("flags", "<u4"), ("min_d2", "<u4"), ("max_cost", "<u4")])
+REACH_RESULT = np.dtype([("cost", "<u4"), ("metres", "<f4"), ("cell", "<u4"), ("next", "u1"), ("status", "u1"), ("pad", "<u2")])
+assert REACH_INFO.itemsize == 32 and REACH_RESULT.itemsize == 16
+REACH_FACE_CONNECTED = 0x1
+REACH_THROUGH_UNKNOWN = 0x2
+REACH_COST_PER_CELL = 10
+REACH_NO_COST = 0xFFFFFFFF
 
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
@@ -203,6 +212,11 @@ def load_library():
         "sdm_get_frontier_cells": [vp, vp, vp, vp, i64, C.POINTER(i64)],
         "sdm_query_views": [vp, vp, i64, vp, i32, vp, vp, vp, u32],
         "sdm_debug_view_batch": [vp, i32],
+        "sdm_reach_update": [vp, vp, vp, i64, u32, u32, u32],
+        "sdm_get_reach": [vp, vp, vp, vp],
+        "sdm_query_reach": [vp, vp, vp, i64, vp, u32],
+        "sdm_reach_paths": [vp, vp, vp, i64, i32, vp, vp, u32],
+        "sdm_debug_reach_tiles": [vp, C.POINTER(i64)],
         "sdm_object_particle_count": [vp, i32, C.POINTER(i64)],
         "sdm_tracks_with_particles": [vp, vp, i32, C.POINTER(i32)],
         "sdm_comm_set_options": [vp, i32, i32],
@@ -655,6 +669,62 @@ class SdmMap:
     def set_view_batch(self, max_views_in_flight):
         """Test hook: query_views keeps at most this many views in flight (<= 0: the library's choice) (sdm_debug_view_batch)."""
         _check(self.L, self.L.sdm_debug_view_batch(self.h, int(max_views_in_flight)), "sdm_debug_view_batch")
+
+    # ---- the travel-cost field (sdm.h).  reach_update builds the field from the last frame's results (or, with min_d2 > 0,
+    # from the distance field's snapshot) and WAITS until it is complete; reach(), query_reach() and reach_paths() answer
+    # for that build until the next one.
+    def reach_update(self, starts=None, start_cells=None, min_d2=0, max_cost=0, face_connected=False, through_unknown=False):
+        """starts: (n, 3) global positions, or start_cells: n map-index cell words (exactly one of the two)"""
+        fl = (REACH_FACE_CONNECTED if face_connected else 0) | (REACH_THROUGH_UNKNOWN if through_unknown else 0)
+        p = None if starts is None else np.ascontiguousarray(starts, dtype=np.float32).reshape(-1, 3)
+        w = None if start_cells is None else np.ascontiguousarray(start_cells, dtype=np.uint32).reshape(-1)
+        n = len(p) if p is not None else len(w) if w is not None else 0
+        _check(self.L, self.L.sdm_reach_update(self.h, _ptr(p), _ptr(w), n, int(min_d2), int(max_cost), fl), "sdm_reach_update")
+
+    def reach(self):
+        """-> (cost, info, origin): cost uint32 shaped [NZ, NY, NX] in map-index order, info a REACH_INFO record, origin the
+        global position of the min corner of cell (0, 0, 0) of the snapshot (float32[3])"""
+        c = self.cfg
+        cost = np.empty((1 << c.z_n, 1 << c.y_n, 1 << c.x_n), np.uint32)
+        info, origin = np.zeros(1, REACH_INFO), np.empty(3, np.float32)
+        _check(self.L, self.L.sdm_get_reach(self.h, _ptr(cost), _ptr(info), _ptr(origin)), "sdm_get_reach")
+        return cost, info[0], origin
+
+    def query_reach(self, xyz=None, cells=None, on_device=False, n=None, out=None):
+        """goals as (n, 3) global positions or as n cell words -> REACH_RESULT per goal.  on_device: the one given of xyz /
+        cells and out (n REACH_RESULT) are device pointers."""
+        if on_device:
+            _check(self.L, self.L.sdm_query_reach(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
+                                                  _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_reach")
+            return None
+        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.uint32).reshape(-1)
+        n = len(p) if p is not None else len(w) if w is not None else 0
+        res = np.empty(n, REACH_RESULT)
+        _check(self.L, self.L.sdm_query_reach(self.h, _ptr(p), _ptr(w), n, _ptr(res), 0), "sdm_query_reach")
+        return res
+
+    def reach_paths(self, xyz=None, cells=None, max_len=0, on_device=False, n=None, cells_out=None, len_out=None, fill=REACH_NO_COST):
+        """-> (cells_out, len_out): row g holds the first min(len, max_len) cell words of goal g's path, goal first, and
+        `fill` behind them; len_out the true lengths (int32, 0: no path).  on_device: the pointers are device pointers
+        (cells_out n * max_len uint32, len_out n int32) and nothing is returned."""
+        if on_device:
+            _check(self.L, self.L.sdm_reach_paths(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
+                                                  int(max_len), _ptr(int(cells_out)) if cells_out else None, _ptr(int(len_out)),
+                                                  QUERY_ON_DEVICE), "sdm_reach_paths")
+            return None
+        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.uint32).reshape(-1)
+        n = len(p) if p is not None else len(w) if w is not None else 0
+        rows, lens = np.full((n, int(max_len)), fill, np.uint32), np.zeros(n, np.int32)
+        _check(self.L, self.L.sdm_reach_paths(self.h, _ptr(p), _ptr(w), n, int(max_len), _ptr(rows), _ptr(lens), 0), "sdm_reach_paths")
+        return rows, lens
+
+    def reach_tiles(self):
+        """Diagnostic: the tiles the last reach_update relaxed, summed over its rounds (sdm_debug_reach_tiles)."""
+        n = C.c_int64(0)
+        _check(self.L, self.L.sdm_debug_reach_tiles(self.h, C.byref(n)), "sdm_debug_reach_tiles")
+        return n.value
 
     def occupied(self, cap=None, zero_center=False, free=False, mark_fov=False):
         cap = cap or self.v_count

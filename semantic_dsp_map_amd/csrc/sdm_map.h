@@ -225,6 +225,14 @@ struct sdm_map {
   uint32_t view_pool_masks = 0;
   int32_t view_batch = 0;
   bool view_clear_rewalk = false;
+  // the travel-cost field (sdm_reach_update, reach.hip): the cost per cell and the traversable bitmask in map-index
+  // order, the tiles' activity bitmask and the list of a round's active tiles, the build's counters (and their
+  // page-locked landing area), allocated by the first build; the Frame and arguments of the last build
+  uint32_t *d_reach_cost = nullptr, *d_reach_trav = nullptr, *d_reach_act = nullptr, *d_reach_list = nullptr;
+  uint32_t *d_reach_meta = nullptr, *h_reach_meta = nullptr;
+  Frame reach_f{};
+  uint32_t reach_flags = 0, reach_min_d2 = 0, reach_max_cost = 0;
+  bool reach_valid = false;
   sdm_point_xyzrgb *d_points_rgb = nullptr;
   size_t points_rgb_cap = 0;
   ColourTables *d_colours = nullptr;
