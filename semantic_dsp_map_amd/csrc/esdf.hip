@@ -16,6 +16,7 @@
 // fits in 31 bits.
 // The distance query reads the field and the snapshot only, never State: the field answers for the frame it was built
 // from until the next build.
+#include "sdm_layer.h"
 #include "sdm_map.h"
 
 #pragma clang fp contract(off)
@@ -31,9 +32,10 @@ constexpr int EX_CHUNKS = 8;     // NX <= 512 = 8 x 64
 constexpr int ENV_U = 32;        // k_esdf_env: rows loaded together (8 measured the same: DESIGN.md 5c)
 constexpr int ENV_NONE = 1 << 20;
 constexpr int QTPB = 256;
+constexpr LayerName ESDF = {"the distance field", "distance field", "sdm_esdf_update", false};
 
 __device__ __forceinline__ bool esdf_obstacle(uint32_t w1, uint32_t flags, int max_movable) {
-  const int occ = (int8_t)(w1 >> 24);
+  const int occ = (int8_t)(w1 >> 24);  // (not occ_of: the kernels' registers stay as they were)
   const int track = (int)(w1 & 0xffffu);
   const bool obst = occ >= 1 || ((flags & SDM_ESDF_UNKNOWN_IS_OBSTACLE) && occ == -1);
   const bool movable = (flags & SDM_ESDF_STATIC_ONLY) && track >= 1 && track <= max_movable;
@@ -181,7 +183,7 @@ __global__ __launch_bounds__(QTPB) void k_query_distance(Dims d, Frame f, const 
   bool ok = true;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const float u = ((xyz[3 * (size_t)i + a] - f.center[a]) - d.pmin[a]) * d.recip;
+    const float u = map_u(d, f, a, xyz[3 * (size_t)i + a]);
     ok = ok && u >= 0.f && u < (float)N[a];  // (NaN and +-inf fail it)
     const float uu = ok ? u : 0.5f;           // (no cast of a value outside the map)
     cell[a] = (int)floorf(uu);
@@ -204,7 +206,7 @@ __global__ __launch_bounds__(QTPB) void k_query_distance(Dims d, Frame f, const 
     r.gradient[0] = r.gradient[1] = r.gradient[2] = 0.f;
     r.nearest[0] = r.nearest[1] = r.nearest[2] = __builtin_nanf("");
     r.d2 = INVALID_INDEX;
-    const uint32_t w = 0xff000000u;  // track 0, label 0, occ -1
+    const uint32_t w = RES_UNKNOWN_W1;
     __builtin_memcpy(&r.track, &w, 4);
   } else {
     const uint32_t w = snap[sc];  // (issued before the arithmetic that does not need it)
@@ -269,19 +271,6 @@ void launch_query_distance(const Dims &d, const Frame &f, const uint32_t *site, 
 // ---- the host side: the entry points behind include/sdm.h ---------------------------------------------------------
 // The build reads the result array in stream order and takes the host Frame of the last issued frame by value, as the
 // queries do; the Frame is kept with the field, so that the distance query and sdm_get_esdf answer for that frame.
-namespace {
-sdm_status esdf_check(sdm_map *m, const char *what, bool need_field) {
-  if (m->cfg.shard_count > 1) {
-    set_error(what, __FILE__, __LINE__, "the distance field of a Z-slab shard (shard_count > 1) is not supported: build it on a whole map");
-    return SDM_ERR_INVALID_ARGUMENT;
-  }
-  if (need_field && !m->esdf_valid) {
-    set_error(what, __FILE__, __LINE__, "no distance field: call sdm_esdf_update first");
-    return SDM_ERR_INVALID_ARGUMENT;
-  }
-  return SDM_OK;
-}
-}  // namespace
 extern "C" {
 
 sdm_status sdm_esdf_update(sdm_map *m, uint32_t flags) {
@@ -290,22 +279,19 @@ sdm_status sdm_esdf_update(sdm_map *m, uint32_t flags) {
     set_error("sdm_esdf_update", __FILE__, __LINE__, "unknown flag bits");
     return SDM_ERR_INVALID_ARGUMENT;
   }
-  const sdm_status e = esdf_check(m, "sdm_esdf_update", false);
-  if (e != SDM_OK) return e;
+  SDM_TRY(layer_check(m, "sdm_esdf_update", nullptr, ESDF));
   HIP_TRY(hipSetDevice(m->device));
-  if (!m->d_esdf_site) SDM_TRY(alloc_tracked(m, &m->d_esdf_site, m->d.V));
-  if (!m->d_esdf_snap) SDM_TRY(alloc_tracked(m, &m->d_esdf_snap, m->d.V));
+  if (!m->esdf.site) SDM_TRY(alloc_tracked(m, &m->esdf.site, m->d.V));
+  if (!m->esdf.snap) SDM_TRY(alloc_tracked(m, &m->esdf.snap, m->d.V));
   const Frame f = m->f;
-  HIP_TRY(launch_esdf_build(m->d, f, m->st, flags, m->d_esdf_site, m->d_esdf_snap, m->stream));
-  m->esdf_f = f;
-  m->esdf_valid = true;
+  HIP_TRY(launch_esdf_build(m->d, f, m->st, flags, m->esdf.site, m->esdf.snap, m->stream));
+  m->esdf.built(f, flags);
   return SDM_OK;
 }
 
 sdm_status sdm_get_esdf(sdm_map *m, uint32_t *d2, uint32_t *site, float origin[3]) {
   if (!m) return SDM_ERR_INVALID_ARGUMENT;
-  const sdm_status e = esdf_check(m, "sdm_get_esdf", true);
-  if (e != SDM_OK) return e;
+  SDM_TRY(layer_check(m, "sdm_get_esdf", &m->esdf, ESDF));
   HIP_TRY(hipSetDevice(m->device));
   const Dims &d = m->d;
   std::vector<uint32_t> own;
@@ -314,7 +300,7 @@ sdm_status sdm_get_esdf(sdm_map *m, uint32_t *d2, uint32_t *site, float origin[3
     own.resize(d.V);
     s = own.data();
   }
-  if (s) HIP_TRY(hipMemcpyAsync(s, m->d_esdf_site, (size_t)d.V * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+  if (s) HIP_TRY(hipMemcpyAsync(s, m->esdf.site, (size_t)d.V * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
   HIP_TRY(hipStreamSynchronize(m->stream));
   if (d2) {
     for (uint32_t c = 0; c < d.V; ++c) {
@@ -329,18 +315,15 @@ sdm_status sdm_get_esdf(sdm_map *m, uint32_t *d2, uint32_t *site, float origin[3
       d2[c] = (uint32_t)(dx * dx + dy * dy + dz * dz);
     }
   }
-  if (origin)
-    for (int a = 0; a < 3; ++a) origin[a] = m->esdf_f.center[a] + d.pmin[a];
+  layer_origin(m, m->esdf, origin);
   return SDM_OK;
 }
 
 sdm_status sdm_query_distance(sdm_map *m, const float *xyz, int64_t n, sdm_distance_result *out, uint32_t flags) {
-  sdm_status e = query_check(m, xyz, n, out, flags, SDM_QUERY_ON_DEVICE, "sdm_query_distance");
-  if (e != SDM_OK) return e;
-  e = esdf_check(m, "sdm_query_distance", true);
-  if (e != SDM_OK) return e;
-  const Frame f = m->esdf_f;
-  const uint32_t *site = m->d_esdf_site, *snap = m->d_esdf_snap;
+  SDM_TRY(query_check(m, xyz, n, out, flags, SDM_QUERY_ON_DEVICE, "sdm_query_distance"));
+  SDM_TRY(layer_check(m, "sdm_query_distance", &m->esdf, ESDF));
+  const Frame f = m->esdf.f;
+  const uint32_t *site = m->esdf.site, *snap = m->esdf.snap;
   return run_query(m, xyz, 12, out, sizeof(sdm_distance_result), nullptr, 0, n, flags,
                    [m, f, site, snap](const void *in, void *o, void *, uint32_t c, hipStream_t s) {
                      launch_query_distance(m->d, f, site, snap, static_cast<const float *>(in), c, static_cast<sdm_distance_result *>(o), s);

@@ -37,6 +37,7 @@
 //               empty accumulators.
 // The number of cells is only known on the device, and sdm_frontiers_update does not wait: the kernels over cells run on a
 // fixed grid and stride over the n they read from meta[].
+#include "sdm_layer.h"
 #include "sdm_map.h"
 
 #pragma clang fp contract(off)
@@ -64,7 +65,7 @@ struct FAcc {  // per root; all zero = no cell yet
 };
 static_assert(sizeof(FAcc) == 56, "bytes per cell in sdm.h");
 
-struct Front {  // everything a build touches (sdm_map::d_front_bits, d_front_cells, d_front_meta)
+struct Front {  // everything a build touches (sdm_map::front: bits, cells, meta)
   u64 *free_m, *unk_m, *front_m;  // [nw]
   uint32_t *pre;                  // [nw]: popcounts, then their exclusive scan
   FAcc *acc;                      // [cap]
@@ -95,15 +96,14 @@ __global__ __launch_bounds__(FC_TPB) void k_frontier_classify(Dims d, Frame f, c
     if (chunk < nw) {
       const uint32_t c = (chunk << 6) + lane;
       const uint32_t x = c & (d.NX - 1), y = (c >> d.x_n) & (d.NY - 1), z = c >> xy_n;
-      w[u] = res[ring_to_voxel(d, axis_correct((int)x + f.eq[0], d.NX), axis_correct((int)y + f.eq[1], d.NY),
-                               axis_correct((int)z + f.eq[2], d.NZ))].y;
+      w[u] = res[cell_voxel(d, f, (int)x, (int)y, (int)z)].y;
     }
   }
 #pragma unroll
   for (int u = 0; u < FC_U; ++u) {
     const uint32_t chunk = first + (uint32_t)u;
     if (chunk >= nw) break;  // (wave-uniform)
-    const int occ = (int8_t)(w[u] >> 24);
+    const int occ = occ_of(w[u]);
     const u64 fm = __ballot(occ == 0), um = __ballot(occ == -1);
     if (lane == 0) {
       free_m[chunk] = fm;
@@ -389,14 +389,14 @@ Front front_of(const sdm_map *m) {
   const Dims &d = m->d;
   Front g;
   g.nw = d.V >> 6;
-  g.cap = (uint32_t)m->front_cap;
+  g.cap = (uint32_t)m->front.cap;
   g.x_n = d.x_n, g.y_n = d.y_n, g.z_n = d.z_n;
-  g.free_m = reinterpret_cast<u64 *>(m->d_front_bits);
+  g.free_m = reinterpret_cast<u64 *>(m->front.bits);
   g.unk_m = g.free_m + g.nw;
   g.front_m = g.unk_m + g.nw;
   g.pre = reinterpret_cast<uint32_t *>(g.front_m + g.nw);
-  const size_t alloc = m->front_alloc;  // the arrays are laid out for the cells allocated, of which cap are in use
-  unsigned char *p = m->d_front_cells;
+  const size_t alloc = m->front.alloc;  // the arrays are laid out for the cells allocated, of which cap are in use
+  unsigned char *p = m->front.cells;
   g.acc = reinterpret_cast<FAcc *>(p);
   p += alloc * sizeof(FAcc);
   g.table = reinterpret_cast<sdm_frontier_cluster *>(p);
@@ -406,7 +406,7 @@ Front front_of(const sdm_map *m) {
   g.root = g.parent + alloc;
   g.idx = g.root + alloc;
   g.faces = reinterpret_cast<uint8_t *>(g.idx + alloc + 1);
-  g.meta = m->d_front_meta;
+  g.meta = m->front.meta;
   return g;
 }
 
@@ -471,28 +471,18 @@ hipError_t launch_frontiers_build(const Dims &d, const Frame &f, const State &st
 // Like the distance field and the instance table, the build reads the result array in stream order and takes the host
 // Frame of the last issued frame by value; the Frame stays with the table (sdm_get_frontier_clusters' origin).
 namespace {
-sdm_status frontiers_check(sdm_map *m, const char *what, bool need_build) {
-  if (m->cfg.shard_count > 1) {
-    set_error(what, __FILE__, __LINE__, "the frontiers of a Z-slab shard (shard_count > 1) are not supported: build them on a whole map");
-    return SDM_ERR_INVALID_ARGUMENT;
-  }
-  if (need_build && !m->front_valid) {
-    set_error(what, __FILE__, __LINE__, "no frontiers: call sdm_frontiers_update first");
-    return SDM_ERR_INVALID_ARGUMENT;
-  }
-  return SDM_OK;
-}
+constexpr LayerName FRONTIERS = {"the frontiers", "frontiers", "sdm_frontiers_update", true};
 
 // waits; the build's counters (META_*)
 sdm_status frontiers_meta(sdm_map *m, const char *what, uint32_t (&meta)[META_WORDS], bool *over) {
   HIP_TRY(hipSetDevice(m->device));
-  HIP_TRY(hipMemcpyAsync(meta, m->d_front_meta, sizeof(meta), hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipMemcpyAsync(meta, m->front.meta, sizeof(meta), hipMemcpyDeviceToHost, m->stream));
   HIP_TRY(hipStreamSynchronize(m->stream));
-  *over = (int64_t)meta[META_N] > m->front_cap;
+  *over = (int64_t)meta[META_N] > m->front.cap;
   if (*over) {
     char msg[160];
     std::snprintf(msg, sizeof(msg), "%u frontier cells, the cell list holds %lld: call sdm_frontiers_update with a larger max_cells",
-                  meta[META_N], (long long)m->front_cap);
+                  meta[META_N], (long long)m->front.cap);
     set_error(what, __FILE__, __LINE__, msg);
   }
   return SDM_OK;
@@ -510,30 +500,29 @@ sdm_status sdm_frontiers_update(sdm_map *m, uint32_t flags, int32_t min_cells, i
     set_error("sdm_frontiers_update", __FILE__, __LINE__, "max_cells < 0");
     return SDM_ERR_INVALID_ARGUMENT;
   }
-  const sdm_status e = frontiers_check(m, "sdm_frontiers_update", false);
-  if (e != SDM_OK) return e;
+  SDM_TRY(layer_check(m, "sdm_frontiers_update", nullptr, FRONTIERS));
   HIP_TRY(hipSetDevice(m->device));
   const Dims &d = m->d;
   const size_t nw = d.V >> 6;
   const size_t cap = max_cells == 0 ? std::max<size_t>(d.V / 16, 1) : (size_t)std::min<int64_t>(max_cells, (int64_t)d.V);
-  if (!m->d_front_bits) SDM_TRY(alloc_tracked(m, &m->d_front_bits, nw * (3 * 8 + 4)));
-  if (!m->d_front_meta) SDM_TRY(alloc_tracked(m, &m->d_front_meta, META_WORDS));
-  if (!m->d_front_scan) {
+  if (!m->front.bits) SDM_TRY(alloc_tracked(m, &m->front.bits, nw * (3 * 8 + 4)));
+  if (!m->front.meta) SDM_TRY(alloc_tracked(m, &m->front.meta, META_WORDS));
+  if (!m->front.scan) {
     const size_t elems = front_scan_layout(d).total;
-    SDM_TRY(alloc_tracked(m, &m->d_front_scan, elems));
-    HIP_TRY(hipMemsetAsync(m->d_front_scan, 0, elems * sizeof(uint32_t), m->stream));  // (the scans leave it zeroed)
+    SDM_TRY(alloc_tracked(m, &m->front.scan, elems));
+    HIP_TRY(hipMemsetAsync(m->front.scan, 0, elems * sizeof(uint32_t), m->stream));  // (the scans leave it zeroed)
   }
-  if (cap > m->front_alloc) {  // a longer cell list: the old one goes once the builds that use it have run
-    SDM_TRY(regrow(m, &m->d_front_cells, &m->front_alloc, cells_bytes(cap), m->d_front_cells ? m->stream : nullptr));
-    m->front_alloc = cap;
-    HIP_TRY(hipMemsetAsync(m->d_front_cells, 0, cap * sizeof(FAcc), m->stream));  // empty; every build leaves them empty again
+  if (cap > m->front.alloc) {  // a longer cell list: the old one goes once the builds that use it have run
+    size_t bytes = 0;
+    m->front.alloc = 0;  // (cells; there is no list while it is replaced)
+    SDM_TRY(regrow(m, &m->front.cells, &bytes, cells_bytes(cap), m->front.cells ? m->stream : nullptr));
+    m->front.alloc = cap;
+    HIP_TRY(hipMemsetAsync(m->front.cells, 0, cap * sizeof(FAcc), m->stream));  // empty; every build leaves them empty again
   }
-  m->front_cap = (int64_t)cap;
+  m->front.cap = (int64_t)cap;
   const Frame f = m->f;
-  HIP_TRY(launch_frontiers_build(d, f, m->st, front_of(m), flags, (uint32_t)std::max<int32_t>(min_cells, 1), m->d_front_scan, m->stream));
-  m->front_f = f;
-  m->front_flags = flags;
-  m->front_valid = true;
+  HIP_TRY(launch_frontiers_build(d, f, m->st, front_of(m), flags, (uint32_t)std::max<int32_t>(min_cells, 1), m->front.scan, m->stream));
+  m->front.built(f, flags);
   return SDM_OK;
 }
 
@@ -543,8 +532,7 @@ sdm_status sdm_get_frontier_clusters(sdm_map *m, sdm_frontier_cluster *out, int3
     set_error("sdm_get_frontier_clusters", __FILE__, __LINE__, "cap < 0, no n_out, or no out for cap > 0");
     return SDM_ERR_INVALID_ARGUMENT;
   }
-  const sdm_status e = frontiers_check(m, "sdm_get_frontier_clusters", true);
-  if (e != SDM_OK) return e;
+  SDM_TRY(layer_check(m, "sdm_get_frontier_clusters", &m->front, FRONTIERS));
   uint32_t meta[META_WORDS];
   bool over = false;
   SDM_TRY(frontiers_meta(m, "sdm_get_frontier_clusters", meta, &over));
@@ -556,8 +544,7 @@ sdm_status sdm_get_frontier_clusters(sdm_map *m, sdm_frontier_cluster *out, int3
     HIP_TRY(hipStreamSynchronize(m->stream));
   }
   *n_out = (int32_t)n;
-  if (origin)
-    for (int a = 0; a < 3; ++a) origin[a] = m->front_f.center[a] + m->d.pmin[a];
+  layer_origin(m, m->front, origin);
   return SDM_OK;
 }
 
@@ -567,8 +554,7 @@ sdm_status sdm_get_frontier_cells(sdm_map *m, uint32_t *cell, uint32_t *cluster,
     set_error("sdm_get_frontier_cells", __FILE__, __LINE__, "cap < 0 or no n_out");
     return SDM_ERR_INVALID_ARGUMENT;
   }
-  const sdm_status e = frontiers_check(m, "sdm_get_frontier_cells", true);
-  if (e != SDM_OK) return e;
+  SDM_TRY(layer_check(m, "sdm_get_frontier_cells", &m->front, FRONTIERS));
   uint32_t meta[META_WORDS];
   bool over = false;
   SDM_TRY(frontiers_meta(m, "sdm_get_frontier_cells", meta, &over));

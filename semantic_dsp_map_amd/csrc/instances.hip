@@ -28,6 +28,7 @@
 //   k_instances_finalize    one workgroup: scans the 65536 track bits (8 KB), gives every set bit its rank (ascending
 //               track id), and one thread per instance reads its accumulators, writes the sdm_instance and stores zeros
 //               back, so the next build starts from empty accumulators.  Also moves the 256 label counters.
+#include "sdm_layer.h"
 #include "sdm_map.h"
 
 #pragma clang fp contract(off)
@@ -45,6 +46,7 @@ constexpr int IA_GRID = 256;     // workgroups at most: every one of them flushe
 constexpr int IA_SLOTS = 64;     // LDS accumulators per workgroup
 constexpr int IA_FEW = 4;        // at the end of a run: up to this many lanes of a wave send a track's cells themselves
 constexpr uint32_t N_TRACKS = 65536;
+constexpr LayerName INSTANCES = {"the instance table", "instance table", "sdm_instances_update", false};
 static_assert((IA_WAVES * IA_U * 64) % 512 == 0, "a step of a workgroup is whole x rows (x_n <= 9)");
 // fields of an accumulator: A64 64-bit ones (0..8 sums, 9 the first-cell maximum), A32 32-bit ones (0..1 sums, 2..10 maxima)
 constexpr int A64 = 10, A32 = 11;
@@ -53,7 +55,7 @@ enum { C_N = 0, C_GUESSED, M_NMINX, M_NMINY, M_NMINZ, M_MAXX, M_MAXY, M_MAXZ, M_
 constexpr size_t ACC64_WORDS = (size_t)A64 * N_TRACKS, ACC32_WORDS = (size_t)A32 * N_TRACKS;
 constexpr size_t ACC_BYTES = ACC64_WORDS * 8 + ACC32_WORDS * 4 + (N_TRACKS / 32) * 4 + 256 * 4;
 
-struct Acc {  // the global accumulators (one allocation, sdm_map::d_inst_acc)
+struct Acc {  // the global accumulators (one allocation, sdm_map::inst.acc)
   unsigned long long *a64;  // [A64][N_TRACKS]
   uint32_t *a32;            // [A32][N_TRACKS]
   uint32_t *bits;           // [N_TRACKS / 32]: tracks with cells
@@ -69,7 +71,7 @@ struct LaneAcc {
 };
 
 __device__ __forceinline__ bool counted_cell(uint32_t w1, uint32_t flags, int max_movable) {
-  const int occ = (int8_t)(w1 >> 24);
+  const int occ = (int8_t)(w1 >> 24);  // (not occ_of: the kernels' registers stay as they were)
   const int track = (int)(w1 & 0xffffu);
   if (occ < 1) return false;
   if ((flags & SDM_INSTANCES_OBSERVED_ONLY) && occ != 1) return false;
@@ -201,8 +203,7 @@ __global__ __launch_bounds__(IA_TPB) void k_instances_accumulate(Dims d, Frame f
         const uint32_t c = c0 + lane;
         if (c < d.V) {
           const uint32_t x = c & (d.NX - 1), y = (c >> d.x_n) & (d.NY - 1), z = c >> xy_n;
-          w[u] = res[ring_to_voxel(d, axis_correct((int)x + f.eq[0], d.NX), axis_correct((int)y + f.eq[1], d.NY),
-                                   axis_correct((int)z + f.eq[2], d.NZ))];
+          w[u] = res[cell_voxel(d, f, (int)x, (int)y, (int)z)];
         }
       }
     }
@@ -216,7 +217,7 @@ __global__ __launch_bounds__(IA_TPB) void k_instances_accumulate(Dims d, Frame f
     const bool counted = counted_cell(w.y, flags, d.max_movable);
     if (!__ballot(counted)) return;
     if (!counted) return;
-    const uint32_t guessed = (int8_t)(w.y >> 24) == 2 ? 1u : 0u;
+    const uint32_t guessed = occ_of(w.y) == 2 ? 1u : 0u;
     const uint32_t wim = float_image(w.x);
     atomicAdd(lab + label, 1u);
     if (WIDE) {
@@ -415,21 +416,7 @@ hipError_t launch_instances_build(const Dims &d, const Frame &f, const State &st
 
 // ---- the host side: the entry points behind include/sdm.h ---------------------------------------------------------
 // Like the distance field, the build reads the result array in stream order and takes the host Frame of the last issued
-// frame by value; the Frame stays with the table (sdm_get_instances' origin).  d_inst_meta: [0] the number of
-// instances, [1..256] the label counters.
-namespace {
-sdm_status instances_check(sdm_map *m, const char *what, bool need_table) {
-  if (m->cfg.shard_count > 1) {
-    set_error(what, __FILE__, __LINE__, "the instance table of a Z-slab shard (shard_count > 1) is not supported: build it on a whole map");
-    return SDM_ERR_INVALID_ARGUMENT;
-  }
-  if (need_table && !m->inst_valid) {
-    set_error(what, __FILE__, __LINE__, "no instance table: call sdm_instances_update first");
-    return SDM_ERR_INVALID_ARGUMENT;
-  }
-  return SDM_OK;
-}
-}  // namespace
+// frame by value; the Frame stays with the table (sdm_get_instances' origin).
 extern "C" {
 
 sdm_status sdm_instances_update(sdm_map *m, uint32_t flags) {
@@ -438,20 +425,17 @@ sdm_status sdm_instances_update(sdm_map *m, uint32_t flags) {
     set_error("sdm_instances_update", __FILE__, __LINE__, "unknown flag bits");
     return SDM_ERR_INVALID_ARGUMENT;
   }
-  const sdm_status e = instances_check(m, "sdm_instances_update", false);
-  if (e != SDM_OK) return e;
+  SDM_TRY(layer_check(m, "sdm_instances_update", nullptr, INSTANCES));
   HIP_TRY(hipSetDevice(m->device));
-  if (!m->d_inst_acc) {
-    SDM_TRY(alloc_tracked(m, &m->d_inst_acc, ACC_BYTES));
-    HIP_TRY(hipMemsetAsync(m->d_inst_acc, 0, ACC_BYTES, m->stream));  // empty; every build leaves them empty again
+  if (!m->inst.acc) {
+    SDM_TRY(alloc_tracked(m, &m->inst.acc, ACC_BYTES));
+    HIP_TRY(hipMemsetAsync(m->inst.acc, 0, ACC_BYTES, m->stream));  // empty; every build leaves them empty again
   }
-  if (!m->d_inst_out) SDM_TRY(alloc_tracked(m, &m->d_inst_out, N_TRACKS));
-  if (!m->d_inst_meta) SDM_TRY(alloc_tracked(m, &m->d_inst_meta, 257));
+  if (!m->inst.out) SDM_TRY(alloc_tracked(m, &m->inst.out, N_TRACKS));
+  if (!m->inst.meta) SDM_TRY(alloc_tracked(m, &m->inst.meta, 257));
   const Frame f = m->f;
-  HIP_TRY(launch_instances_build(m->d, f, m->st, flags, m->d_inst_acc, m->d_inst_out, m->d_inst_meta, m->stream));
-  m->inst_f = f;
-  m->inst_flags = flags;
-  m->inst_valid = true;
+  HIP_TRY(launch_instances_build(m->d, f, m->st, flags, m->inst.acc, m->inst.out, m->inst.meta, m->stream));
+  m->inst.built(f, flags);
   return SDM_OK;
 }
 
@@ -461,20 +445,18 @@ sdm_status sdm_get_instances(sdm_map *m, sdm_instance *out, int32_t cap, int32_t
     set_error("sdm_get_instances", __FILE__, __LINE__, "cap < 0, no n_out, or no out for cap > 0");
     return SDM_ERR_INVALID_ARGUMENT;
   }
-  const sdm_status e = instances_check(m, "sdm_get_instances", true);
-  if (e != SDM_OK) return e;
+  SDM_TRY(layer_check(m, "sdm_get_instances", &m->inst, INSTANCES));
   HIP_TRY(hipSetDevice(m->device));
   uint32_t n = 0;
-  HIP_TRY(hipMemcpyAsync(&n, m->d_inst_meta, sizeof(n), hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipMemcpyAsync(&n, m->inst.meta, sizeof(n), hipMemcpyDeviceToHost, m->stream));
   HIP_TRY(hipStreamSynchronize(m->stream));
   const size_t take = std::min<size_t>(n, (size_t)cap);
   if (take) {
-    HIP_TRY(hipMemcpyAsync(out, m->d_inst_out, take * sizeof(sdm_instance), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipMemcpyAsync(out, m->inst.out, take * sizeof(sdm_instance), hipMemcpyDeviceToHost, m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));
   }
   *n_out = (int32_t)n;
-  if (origin)
-    for (int a = 0; a < 3; ++a) origin[a] = m->inst_f.center[a] + m->d.pmin[a];
+  layer_origin(m, m->inst, origin);
   return SDM_OK;
 }
 
@@ -484,10 +466,9 @@ sdm_status sdm_get_label_cells(sdm_map *m, uint32_t out[256]) {
     set_error("sdm_get_label_cells", __FILE__, __LINE__, "no out");
     return SDM_ERR_INVALID_ARGUMENT;
   }
-  const sdm_status e = instances_check(m, "sdm_get_label_cells", true);
-  if (e != SDM_OK) return e;
+  SDM_TRY(layer_check(m, "sdm_get_label_cells", &m->inst, INSTANCES));
   HIP_TRY(hipSetDevice(m->device));
-  HIP_TRY(hipMemcpyAsync(out, m->d_inst_meta + 1, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipMemcpyAsync(out, m->inst.meta + 1, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
   HIP_TRY(hipStreamSynchronize(m->stream));
   return SDM_OK;
 }

@@ -5,6 +5,7 @@
 // last issued frame (Frame: map center, ring offsets) come by value, so a query enqueued between two frames answers for
 // the frame before it whatever the host does next.  Segments and boxes only need the second word of a result (track,
 // label, occ): they gather 4 bytes per cell.
+#include "sdm_layer.h"
 #include "sdm_map.h"
 
 #pragma clang fp contract(off)
@@ -16,19 +17,6 @@ namespace sdm {
 namespace {
 
 constexpr int QTPB = 256;
-constexpr uint32_t RES_UNKNOWN_W1 = 0xff000000u;  // second word of an "unobserved" result: track 0, label 0, occ -1
-constexpr uint32_t RES_UNKNOWN_W0 = 0xbf800000u;  // wsum -1.f
-
-__device__ __forceinline__ int8_t occ_of(uint32_t w1) { return (int8_t)(w1 >> 24); }
-
-// map-index coordinate of one axis: the float32 expression of global_pos_to_voxel, without its cast
-__device__ __forceinline__ float map_u(const Dims &d, const Frame &f, int a, float p) { return ((p - f.center[a]) - d.pmin[a]) * d.recip; }
-
-// storage index of in-map cell (ix, iy, iz): the ring correction of global_pos_to_voxel
-__device__ __forceinline__ uint32_t cell_voxel(const Dims &d, const Frame &f, int ix, int iy, int iz) {
-  return ring_to_voxel(d, axis_correct(ix + f.eq[0], d.NX), axis_correct(iy + f.eq[1], d.NY), axis_correct(iz + f.eq[2], d.NZ));
-}
-
 // ---- points: one lane per query, one 8-byte gather -----------------------------------------------------------------
 __global__ __launch_bounds__(QTPB) void k_query_points(Dims d, Frame f, const float *__restrict__ xyz, uint32_t n,
                                                        const uint2 *__restrict__ res, uint2 *__restrict__ out,
@@ -241,8 +229,7 @@ __global__ __launch_bounds__(QTPB) void k_query_boxes(Dims d, Frame f, const flo
         if (occ) first = min(first, vox[u]);
       }
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) first = min(first, (uint32_t)__shfl_xor((int)first, s, 64));
+    first = wave_min(first);
   }
   if (lane == 0) {
     sdm_box_result o;
@@ -280,14 +267,13 @@ void launch_query_boxes(const Dims &d, const Frame &f, const State &st, const fl
 
 // ---- the host side: the entry points behind include/sdm.h ---------------------------------------------------------
 // Host mode works through the queries in chunks of QUERY_CHUNK: inputs copied to the map's page-locked staging area and
-// up, the kernel, the outputs down, one wait per chunk.  Device mode launches per chunk too (the kernels count in 32 bits)
-// and does not wait.  Either way the kernels read the result array in stream order and the host Frame of the last issued
-// frame, taken by value at the call.
+// up, the kernel, the outputs down, one wait per chunk (run_staged: every host-mode batched call goes through it).  Device
+// mode launches per chunk too (the kernels count in 32 bits) and does not wait.  Either way the kernels read the result
+// array in stream order and the host Frame of the last issued frame, taken by value at the call.
 namespace sdm {
 
 namespace {
 constexpr size_t QUERY_CHUNK = (size_t)1 << 20;
-size_t query_align(size_t b) { return (b + 255) & ~(size_t)255; }
 }  // namespace
 
 sdm_status query_check(sdm_map *m, const void *in, int64_t n, const void *out, uint32_t flags, uint32_t allowed, const char *what) {
@@ -303,15 +289,81 @@ sdm_status query_check(sdm_map *m, const void *in, int64_t n, const void *out, u
   return SDM_OK;
 }
 
-// launch(in, out, out2, count, stream) enqueues one chunk; out2 (may be null) is a second output array
+sdm_status layer_check(sdm_map *m, const char *what, const Derived *need, const LayerName &name) {
+  char msg[160];
+  if (m->cfg.shard_count > 1) {
+    std::snprintf(msg, sizeof(msg), "%s of a Z-slab shard (shard_count > 1) %s not supported: build %s on a whole map", name.the_layer,
+                  name.plural ? "are" : "is", name.plural ? "them" : "it");
+  } else if (need && !need->valid) {
+    std::snprintf(msg, sizeof(msg), "no %s: call %s first", name.build, name.update);
+  } else {
+    return SDM_OK;
+  }
+  set_error(what, __FILE__, __LINE__, msg);
+  return SDM_ERR_INVALID_ARGUMENT;
+}
+
+void layer_origin(const sdm_map *m, const Derived &l, float origin[3]) {
+  if (origin)
+    for (int a = 0; a < 3; ++a) origin[a] = l.f.center[a] + m->d.pmin[a];
+}
+
+// The staging area holds the preamble and one chunk of every column, each at a multiple of 256 bytes, in the order given.
+sdm_status run_staged(sdm_map *m, size_t n, size_t chunk, const void *pre, size_t pre_bytes, const std::vector<StageCol> &cols,
+                      const StageLaunch &launch, const StageCopyOut &copy_out) {
+  auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t k_n = cols.size();
+  std::vector<size_t> at(k_n);
+  size_t need = align(pre_bytes);
+  for (size_t k = 0; k < k_n; ++k) {
+    at[k] = need;
+    need += align(chunk * cols[k].elem);
+  }
+  QueryStage &st = m->stage;
+  if (need > st.bytes) {  // both buffers grow together; the pinned one goes once the stream that may use it has drained
+    const size_t grown = std::max(need, (size_t)1 << 20);
+    size_t cap = 0;
+    st.bytes = 0;  // (non-zero only while both are there)
+    SDM_TRY(regrow(m, &st.h, &cap, grown, m->stream, true));
+    SDM_TRY(regrow(m, &st.d, &cap, grown));
+    st.bytes = grown;
+  }
+  std::vector<unsigned char *> dev(k_n), host(k_n);
+  for (size_t k = 0; k < k_n; ++k) {
+    dev[k] = cols[k].elem ? st.d + at[k] : nullptr;
+    host[k] = cols[k].elem ? st.h + at[k] : nullptr;
+  }
+  if (pre_bytes) {
+    memcpy(st.h, pre, pre_bytes);
+    HIP_TRY(hipMemcpyAsync(st.d, st.h, pre_bytes, hipMemcpyHostToDevice, m->stream));
+  }
+  for (size_t off = 0; off < n; off += chunk) {
+    const size_t c = std::min(chunk, n - off);
+    for (size_t k = 0; k < k_n; ++k) {
+      if (cols[k].kind != StageCol::IN || !cols[k].elem) continue;
+      memcpy(host[k], static_cast<const unsigned char *>(cols[k].host) + off * cols[k].elem, c * cols[k].elem);
+      HIP_TRY(hipMemcpyAsync(dev[k], host[k], c * cols[k].elem, hipMemcpyHostToDevice, m->stream));
+    }
+    SDM_TRY(launch(st.d, dev.data(), c));
+    for (size_t k = 0; k < k_n; ++k)
+      if (cols[k].kind != StageCol::IN && cols[k].elem)
+        HIP_TRY(hipMemcpyAsync(host[k], dev[k], c * cols[k].elem, hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    for (size_t k = 0; k < k_n; ++k)
+      if (cols[k].kind == StageCol::OUT && cols[k].elem) memcpy(static_cast<unsigned char *>(cols[k].host) + off * cols[k].elem, host[k], c * cols[k].elem);
+    if (copy_out) copy_out(host.data(), off, c);
+  }
+  return SDM_OK;
+}
+
 sdm_status run_query(sdm_map *m, const void *in_v, size_t in_elem, void *out_v, size_t out_elem, void *out2_v, size_t out2_elem, int64_t n,
                      uint32_t flags, const QueryLaunch &launch) {
   if (n == 0) return SDM_OK;
   HIP_TRY(hipSetDevice(m->device));
-  const unsigned char *in = static_cast<const unsigned char *>(in_v);
-  unsigned char *out = static_cast<unsigned char *>(out_v), *out2 = static_cast<unsigned char *>(out2_v);
-  if (!out2) out2_elem = 0;
+  if (!out2_v) out2_elem = 0;
   if (flags & SDM_QUERY_ON_DEVICE) {
+    const unsigned char *in = static_cast<const unsigned char *>(in_v);
+    unsigned char *out = static_cast<unsigned char *>(out_v), *out2 = static_cast<unsigned char *>(out2_v);
     for (size_t off = 0; off < (size_t)n; off += QUERY_CHUNK) {
       const uint32_t c = (uint32_t)std::min(QUERY_CHUNK, (size_t)n - off);
       launch(in + off * in_elem, out + off * out_elem, out2 ? out2 + off * out2_elem : nullptr, c, m->stream);
@@ -319,35 +371,20 @@ sdm_status run_query(sdm_map *m, const void *in_v, size_t in_elem, void *out_v, 
     }
     return SDM_OK;
   }
-  const size_t chunk = std::min(QUERY_CHUNK, (size_t)n);
-  const size_t o_out = query_align(chunk * in_elem), o_out2 = o_out + query_align(chunk * out_elem);
-  const size_t need = o_out2 + query_align(chunk * out2_elem);
-  if (need > m->query_bytes) {
-    const size_t grown = std::max(need, (size_t)1 << 20);  // (both buffers, one capacity: it holds when the second is there)
-    SDM_TRY(regrow(m, &m->h_query, &m->query_bytes, grown, m->stream, true));
-    SDM_TRY(regrow(m, &m->d_query, &m->query_bytes, grown));
-  }
-  for (size_t off = 0; off < (size_t)n; off += chunk) {
-    const size_t c = std::min(chunk, (size_t)n - off);
-    memcpy(m->h_query, in + off * in_elem, c * in_elem);
-    HIP_TRY(hipMemcpyAsync(m->d_query, m->h_query, c * in_elem, hipMemcpyHostToDevice, m->stream));
-    launch(m->d_query, m->d_query + o_out, out2 ? m->d_query + o_out2 : nullptr, (uint32_t)c, m->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(m->h_query + o_out, m->d_query + o_out, c * out_elem, hipMemcpyDeviceToHost, m->stream));
-    if (out2) HIP_TRY(hipMemcpyAsync(m->h_query + o_out2, m->d_query + o_out2, c * out2_elem, hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    memcpy(out + off * out_elem, m->h_query + o_out, c * out_elem);
-    if (out2) memcpy(out2 + off * out2_elem, m->h_query + o_out2, c * out2_elem);
-  }
-  return SDM_OK;
+  return run_staged(m, (size_t)n, std::min(QUERY_CHUNK, (size_t)n), nullptr, 0,
+                    {{StageCol::IN, const_cast<void *>(in_v), in_elem}, {StageCol::OUT, out_v, out_elem}, {StageCol::OUT, out2_v, out2_elem}},
+                    [&](const unsigned char *, unsigned char *const *col, size_t c) -> sdm_status {
+                      launch(col[0], col[1], col[2], (uint32_t)c, m->stream);
+                      HIP_TRY(hipGetLastError());
+                      return SDM_OK;
+                    });
 }
 }  // namespace sdm
 
 extern "C" {
 
 sdm_status sdm_query_points(sdm_map *m, const float *xyz, int64_t n, sdm_voxel_result *out, uint32_t *voxel_out, uint32_t flags) {
-  const sdm_status e = query_check(m, xyz, n, out, flags, SDM_QUERY_ON_DEVICE, "sdm_query_points");
-  if (e != SDM_OK) return e;
+  SDM_TRY(query_check(m, xyz, n, out, flags, SDM_QUERY_ON_DEVICE, "sdm_query_points"));
   const Frame f = m->f;
   return run_query(m, xyz, 12, out, sizeof(sdm_voxel_result), voxel_out, 4, n, flags,
                    [m, f](const void *in, void *o, void *o2, uint32_t c, hipStream_t s) {
@@ -357,8 +394,7 @@ sdm_status sdm_query_points(sdm_map *m, const float *xyz, int64_t n, sdm_voxel_r
 }
 
 sdm_status sdm_query_segments(sdm_map *m, const float *ab, int64_t n, sdm_segment_hit *out, uint32_t flags) {
-  const sdm_status e = query_check(m, ab, n, out, flags, SDM_QUERY_ON_DEVICE | SDM_QUERY_UNKNOWN_BLOCKS, "sdm_query_segments");
-  if (e != SDM_OK) return e;
+  SDM_TRY(query_check(m, ab, n, out, flags, SDM_QUERY_ON_DEVICE | SDM_QUERY_UNKNOWN_BLOCKS, "sdm_query_segments"));
   const Frame f = m->f;
   const int unknown_blocks = (flags & SDM_QUERY_UNKNOWN_BLOCKS) ? 1 : 0;
   return run_query(m, ab, 24, out, sizeof(sdm_segment_hit), nullptr, 0, n, flags,
@@ -369,8 +405,7 @@ sdm_status sdm_query_segments(sdm_map *m, const float *ab, int64_t n, sdm_segmen
 }
 
 sdm_status sdm_query_boxes(sdm_map *m, const float *boxes, int64_t n, sdm_box_result *out, uint32_t flags) {
-  const sdm_status e = query_check(m, boxes, n, out, flags, SDM_QUERY_ON_DEVICE, "sdm_query_boxes");
-  if (e != SDM_OK) return e;
+  SDM_TRY(query_check(m, boxes, n, out, flags, SDM_QUERY_ON_DEVICE, "sdm_query_boxes"));
   const Frame f = m->f;
   return run_query(m, boxes, 24, out, sizeof(sdm_box_result), nullptr, 0, n, flags,
                    [m, f](const void *in, void *o, void *, uint32_t c, hipStream_t s) {

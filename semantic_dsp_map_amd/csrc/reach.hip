@@ -27,6 +27,7 @@
 //               cost, metres and the first descent step.
 //   k_reach_paths     a lane per goal: one descent step per round trip to memory, the loads of a step issued together.
 //               The chain is as long as the path and each step depends on the one before: it is bound by latency.
+#include "sdm_layer.h"
 #include "sdm_map.h"
 
 #pragma clang fp contract(off)
@@ -115,8 +116,7 @@ __global__ __launch_bounds__(RC_TPB) void k_reach_classify(Dims d, Frame f, cons
         s[u] = site[c];
       } else {
         const uint32_t x = c & (d.NX - 1), y = (c >> d.x_n) & (d.NY - 1), z = c >> xy_n;
-        w[u] = res[ring_to_voxel(d, axis_correct((int)x + f.eq[0], d.NX), axis_correct((int)y + f.eq[1], d.NY),
-                                 axis_correct((int)z + f.eq[2], d.NZ))].y;
+        w[u] = res[cell_voxel(d, f, (int)x, (int)y, (int)z)].y;
       }
     }
   }
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(RC_TPB) void k_reach_classify(Dims d, Frame f, cons
     const uint32_t chunk = first + (uint32_t)u;
     if (chunk >= nw) break;  // (wave-uniform)
     const uint32_t c = (chunk << 6) + lane;
-    const int occ = (int8_t)(w[u] >> 24);
+    const int occ = occ_of(w[u]);
     bool ok = occ == 0 || (through_unknown && occ == -1);
     if (FIELD && s[u] != INVALID_INDEX) {  // (no site: no obstacle anywhere, d2 = 0xffffffff passes)
       const int dx = (int)(c & (d.NX - 1)) - (int)(s[u] & (d.NX - 1));
@@ -153,7 +153,7 @@ __device__ __forceinline__ uint32_t entry_cell(const Dims &d, const Frame &f, co
   bool ok = true;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const float u = ((xyz[3 * (size_t)i + a] - f.center[a]) - d.pmin[a]) * d.recip;
+    const float u = map_u(d, f, a, xyz[3 * (size_t)i + a]);
     ok = ok && u >= 0.f && u < (float)N[a];  // (NaN and +-inf fail it)
     cell[a] = (uint32_t)(int)floorf(ok ? u : 0.5f);
   }
@@ -342,8 +342,7 @@ __global__ __launch_bounds__(RC_TPB) void k_reach_reduce(Reach g, uint32_t nw) {
     n_reached += (uint32_t)__popcll(__ballot(v != NO_COST));
     if (v != NO_COST) top = max(top, v);
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) top = max(top, (uint32_t)__shfl_xor((int)top, o, 64));
+  top = wave_max(top);
   if (lane == 0) {
     if (n_trav) atomicAdd(g.meta + M_TRAV, n_trav);
     if (n_reached) atomicAdd(g.meta + M_REACHED, n_reached);
@@ -452,11 +451,11 @@ __global__ __launch_bounds__(RQ_TPB) void k_reach_paths(Dims d, Frame f, Reach g
 Reach reach_of(const sdm_map *m, uint32_t max_cost) {
   const Dims &d = m->d;
   Reach g;
-  g.cost = m->d_reach_cost;
-  g.trav = m->d_reach_trav;
-  g.act = m->d_reach_act;
-  g.list = m->d_reach_list;
-  g.meta = m->d_reach_meta;
+  g.cost = m->reach.cost;
+  g.trav = m->reach.trav;
+  g.act = m->reach.act;
+  g.list = m->reach.list;
+  g.meta = m->reach.meta;
   g.x_n = d.x_n, g.y_n = d.y_n, g.z_n = d.z_n;
   g.tx_n = std::min(d.x_n, 3), g.ty_n = std::min(d.y_n, 3), g.tz_n = std::min(d.z_n, 3);
   g.n_tiles = d.V >> (g.tx_n + g.ty_n + g.tz_n);
@@ -472,28 +471,17 @@ constexpr uint32_t REACH_BATCH = 8;  // rounds issued between two looks at the c
 
 // ---- the host side: the entry points behind include/sdm.h ---------------------------------------------------------
 namespace {
-sdm_status reach_check(sdm_map *m, const char *what, bool need_build) {
-  if (m->cfg.shard_count > 1) {
-    set_error(what, __FILE__, __LINE__, "the travel cost of a Z-slab shard (shard_count > 1) is not supported: build it on a whole map");
-    return SDM_ERR_INVALID_ARGUMENT;
-  }
-  if (need_build && !m->reach_valid) {
-    set_error(what, __FILE__, __LINE__, "no travel-cost field: call sdm_reach_update first");
-    return SDM_ERR_INVALID_ARGUMENT;
-  }
-  return SDM_OK;
-}
+constexpr LayerName REACH = {"the travel cost", "travel-cost field", "sdm_reach_update", false};
 
 // the checks the two goal queries share
-sdm_status reach_query_check(sdm_map *m, const float *xyz, const uint32_t *cells, int64_t n, const void *out, uint32_t flags, const char *what) {
+sdm_status goal_query_check(sdm_map *m, const float *xyz, const uint32_t *cells, int64_t n, const void *out, uint32_t flags, const char *what) {
   if (!m) return SDM_ERR_INVALID_ARGUMENT;
   if ((xyz != nullptr) == (cells != nullptr)) {
     set_error(what, __FILE__, __LINE__, "exactly one of xyz and cells must be given");
     return SDM_ERR_INVALID_ARGUMENT;
   }
-  const sdm_status e = query_check(m, xyz ? (const void *)xyz : (const void *)cells, n, out, flags, SDM_QUERY_ON_DEVICE, what);
-  if (e != SDM_OK) return e;
-  return reach_check(m, what, true);
+  SDM_TRY(query_check(m, xyz ? (const void *)xyz : (const void *)cells, n, out, flags, SDM_QUERY_ON_DEVICE, what));
+  return layer_check(m, what, &m->reach, REACH);
 }
 }  // namespace
 
@@ -510,33 +498,32 @@ sdm_status sdm_reach_update(sdm_map *m, const float *start_xyz, const uint32_t *
     set_error("sdm_reach_update", __FILE__, __LINE__, "n_starts < 0 or >= 2^31, or not exactly one of start_xyz and start_cells");
     return SDM_ERR_INVALID_ARGUMENT;
   }
-  const sdm_status e = reach_check(m, "sdm_reach_update", false);
-  if (e != SDM_OK) return e;
-  if (min_d2 > 0 && !m->esdf_valid) {
+  SDM_TRY(layer_check(m, "sdm_reach_update", nullptr, REACH));
+  if (min_d2 > 0 && !m->esdf.valid) {
     set_error("sdm_reach_update", __FILE__, __LINE__, "min_d2 > 0 needs the distance field: call sdm_esdf_update first");
     return SDM_ERR_INVALID_ARGUMENT;
   }
   HIP_TRY(hipSetDevice(m->device));
   const Dims &d = m->d;
   const uint32_t nw = d.V >> 6;
-  if (!m->d_reach_cost) SDM_TRY(alloc_tracked(m, &m->d_reach_cost, d.V));
-  if (!m->d_reach_trav) SDM_TRY(alloc_tracked(m, &m->d_reach_trav, (size_t)nw * 2));
-  if (!m->d_reach_meta) SDM_TRY(alloc_tracked(m, &m->d_reach_meta, META_WORDS));
-  if (!m->h_reach_meta) SDM_TRY(alloc_tracked(m, &m->h_reach_meta, META_WORDS, true));
+  if (!m->reach.cost) SDM_TRY(alloc_tracked(m, &m->reach.cost, d.V));
+  if (!m->reach.trav) SDM_TRY(alloc_tracked(m, &m->reach.trav, (size_t)nw * 2));
+  if (!m->reach.meta) SDM_TRY(alloc_tracked(m, &m->reach.meta, META_WORDS));
+  if (!m->reach.h_meta) SDM_TRY(alloc_tracked(m, &m->reach.h_meta, META_WORDS, true));
   const uint32_t n_tiles = d.V >> (std::min(d.x_n, 3) + std::min(d.y_n, 3) + std::min(d.z_n, 3)), act_words = (n_tiles + 31u) / 32u;
-  if (!m->d_reach_act) SDM_TRY(alloc_tracked(m, &m->d_reach_act, act_words));
-  if (!m->d_reach_list) SDM_TRY(alloc_tracked(m, &m->d_reach_list, n_tiles));
+  if (!m->reach.act) SDM_TRY(alloc_tracked(m, &m->reach.act, act_words));
+  if (!m->reach.list) SDM_TRY(alloc_tracked(m, &m->reach.list, n_tiles));
   const Reach g = reach_of(m, max_cost);
-  m->reach_valid = false;  // (until this build is complete)
+  m->reach.valid = false;  // (until this build is complete)
   hipStream_t s = m->stream;
   const bool field = min_d2 > 0;
-  const Frame f = field ? m->esdf_f : m->f;
+  const Frame f = field ? m->esdf.f : m->f;
   HIP_TRY(hipMemsetAsync(g.meta, 0, META_WORDS * sizeof(uint32_t), s));
   HIP_TRY(hipMemsetAsync(g.act, 0, (size_t)act_words * sizeof(uint32_t), s));
   const uint32_t by_word = (nw + RC_WAVES * RC_U - 1) / (RC_WAVES * RC_U);
   const uint32_t through = (flags & SDM_REACH_THROUGH_UNKNOWN) ? 1u : 0u;
   if (field)
-    hipLaunchKernelGGL(k_reach_classify<true>, dim3(by_word), dim3(RC_TPB), 0, s, d, f, (const uint2 *)nullptr, m->d_esdf_snap, m->d_esdf_site,
+    hipLaunchKernelGGL(k_reach_classify<true>, dim3(by_word), dim3(RC_TPB), 0, s, d, f, (const uint2 *)nullptr, m->esdf.snap, m->esdf.site,
                        min_d2, through, reinterpret_cast<u64 *>(g.trav), g.cost, nw);
   else
     hipLaunchKernelGGL(k_reach_classify<false>, dim3(by_word), dim3(RC_TPB), 0, s, d, f, reinterpret_cast<const uint2 *>(m->st.res),
@@ -566,9 +553,9 @@ sdm_status sdm_reach_update(sdm_map *m, const float *start_xyz, const uint32_t *
       hipLaunchKernelGGL(relax, dim3(grid), dim3(RT_TPB), 0, s, g, (uint32_t)round);
       HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipMemcpyAsync(m->h_reach_meta, g.meta, META_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(m->reach.h_meta, g.meta, META_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    const uint32_t last = m->h_reach_meta[M_CNT + ((round - 1) & 1u)];
+    const uint32_t last = m->reach.h_meta[M_CNT + ((round - 1) & 1u)];
     if (last == 0u) break;  // an empty round: nothing was lowered in the one before it, nothing ever will be
     if (round >= cap) {
       set_error("sdm_reach_update", __FILE__, __LINE__, "the relaxation has not come to rest after V rounds");
@@ -578,45 +565,40 @@ sdm_status sdm_reach_update(sdm_map *m, const float *start_xyz, const uint32_t *
   }
   hipLaunchKernelGGL(k_reach_reduce, dim3(std::min<uint32_t>(RR_GRID, (nw + RC_WAVES - 1) / RC_WAVES)), dim3(RC_TPB), 0, s, g, nw);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(m->h_reach_meta, g.meta, META_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(m->reach.h_meta, g.meta, META_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  m->reach_f = f;
-  m->reach_flags = flags;
-  m->reach_min_d2 = min_d2;
-  m->reach_max_cost = max_cost;
-  m->reach_valid = true;
+  m->reach.min_d2 = min_d2;
+  m->reach.max_cost = max_cost;
+  m->reach.built(f, flags);
   return SDM_OK;
 }
 
 sdm_status sdm_get_reach(sdm_map *m, uint32_t *cost, sdm_reach_info *info, float origin[3]) {
   if (!m) return SDM_ERR_INVALID_ARGUMENT;
-  const sdm_status e = reach_check(m, "sdm_get_reach", true);
-  if (e != SDM_OK) return e;
+  SDM_TRY(layer_check(m, "sdm_get_reach", &m->reach, REACH));
   HIP_TRY(hipSetDevice(m->device));
-  if (cost) HIP_TRY(hipMemcpyAsync(cost, m->d_reach_cost, (size_t)m->d.V * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
+  if (cost) HIP_TRY(hipMemcpyAsync(cost, m->reach.cost, (size_t)m->d.V * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
   HIP_TRY(hipStreamSynchronize(m->stream));
   if (info) {
-    const uint32_t *h = m->h_reach_meta;  // (the build waited for them)
+    const uint32_t *h = m->reach.h_meta;  // (the build waited for them)
     info->n_starts_used = h[M_STARTS];
     info->n_traversable = h[M_TRAV];
     info->n_reached = h[M_REACHED];
     info->max_cost_reached = h[M_MAXCOST];
     info->rounds = h[M_ROUNDS];
-    info->flags = m->reach_flags;
-    info->min_d2 = m->reach_min_d2;
-    info->max_cost = m->reach_max_cost;
+    info->flags = m->reach.flags;
+    info->min_d2 = m->reach.min_d2;
+    info->max_cost = m->reach.max_cost;
   }
-  if (origin)
-    for (int a = 0; a < 3; ++a) origin[a] = m->reach_f.center[a] + m->d.pmin[a];
+  layer_origin(m, m->reach, origin);
   return SDM_OK;
 }
 
 sdm_status sdm_query_reach(sdm_map *m, const float *xyz, const uint32_t *cells, int64_t n, sdm_reach_result *out, uint32_t flags) {
-  const sdm_status e = reach_query_check(m, xyz, cells, n, out, flags, "sdm_query_reach");
-  if (e != SDM_OK) return e;
-  const Frame f = m->reach_f;
-  const Reach g = reach_of(m, m->reach_max_cost);
-  const bool face = (m->reach_flags & SDM_REACH_FACE_CONNECTED) != 0, points = xyz != nullptr;
+  SDM_TRY(goal_query_check(m, xyz, cells, n, out, flags, "sdm_query_reach"));
+  const Frame f = m->reach.f;
+  const Reach g = reach_of(m, m->reach.max_cost);
+  const bool face = (m->reach.flags & SDM_REACH_FACE_CONNECTED) != 0, points = xyz != nullptr;
   return run_query(m, points ? (const void *)xyz : (const void *)cells, points ? 12 : 4, out, sizeof(sdm_reach_result), nullptr, 0, n, flags,
                    [m, f, g, face, points](const void *in, void *o, void *, uint32_t c, hipStream_t s) {
                      const float *p = points ? static_cast<const float *>(in) : nullptr;
@@ -631,17 +613,16 @@ sdm_status sdm_query_reach(sdm_map *m, const float *xyz, const uint32_t *cells, 
 
 sdm_status sdm_reach_paths(sdm_map *m, const float *xyz, const uint32_t *cells, int64_t n, int32_t max_len, uint32_t *cells_out,
                            int32_t *len_out, uint32_t flags) {
-  const sdm_status e = reach_query_check(m, xyz, cells, n, len_out, flags, "sdm_reach_paths");
-  if (e != SDM_OK) return e;
+  SDM_TRY(goal_query_check(m, xyz, cells, n, len_out, flags, "sdm_reach_paths"));
   if (max_len < 0 || (max_len > 0 && !cells_out)) {
     set_error("sdm_reach_paths", __FILE__, __LINE__, "max_len < 0, or no cells_out for max_len > 0");
     return SDM_ERR_INVALID_ARGUMENT;
   }
   if (n == 0) return SDM_OK;
   HIP_TRY(hipSetDevice(m->device));
-  const Frame f = m->reach_f;
-  const Reach g = reach_of(m, m->reach_max_cost);
-  const bool face = (m->reach_flags & SDM_REACH_FACE_CONNECTED) != 0;
+  const Frame f = m->reach.f;
+  const Reach g = reach_of(m, m->reach.max_cost);
+  const bool face = (m->reach.flags & SDM_REACH_FACE_CONNECTED) != 0;
   const size_t in_elem = xyz ? 12 : 4;
   const unsigned char *in = xyz ? reinterpret_cast<const unsigned char *>(xyz) : reinterpret_cast<const unsigned char *>(cells);
   auto launch = [&](const void *src, uint32_t c, uint32_t len_cap, size_t stride, uint32_t *rows, int32_t *lens) {
@@ -653,51 +634,36 @@ sdm_status sdm_reach_paths(sdm_map *m, const float *xyz, const uint32_t *cells, 
     else
       hipLaunchKernelGGL(k_reach_paths<false>, grid, tpb, 0, m->stream, m->d, f, g, p, w, c, len_cap, stride, rows, lens);
   };
+  if (flags & SDM_QUERY_ON_DEVICE)  // (run_query's chunks: a row of the caller's is max_len cells)
+    return run_query(m, in, in_elem, len_out, 4, cells_out, (size_t)max_len * 4, n, flags, [&](const void *src, void *lens, void *rows, uint32_t c, hipStream_t) {
+      launch(src, c, (uint32_t)max_len, (size_t)max_len, static_cast<uint32_t *>(rows), static_cast<int32_t *>(lens));
+    });
   constexpr size_t CHUNK = (size_t)1 << 20;
-  if (flags & SDM_QUERY_ON_DEVICE) {
-    for (size_t off = 0; off < (size_t)n; off += CHUNK) {
-      const uint32_t c = (uint32_t)std::min(CHUNK, (size_t)n - off);
-      launch(in + off * in_elem, c, (uint32_t)max_len, (size_t)max_len, cells_out + off * (size_t)max_len, len_out + off);
-      HIP_TRY(hipGetLastError());
-    }
-    return SDM_OK;
-  }
   // host mode: through the queries' staging area, in chunks of whole rows; a staged row holds what a path can be long (no
   // path has more cells than the map), and only the cells a path has are copied into the caller's row
   const size_t row = std::min<size_t>((size_t)max_len, m->d.V);
   const size_t chunk = std::min<size_t>((size_t)n, std::max<size_t>(1, std::min(CHUNK, ((size_t)16 << 20) / std::max<size_t>(row * 4, 1))));
-  auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o_len = align(chunk * in_elem), o_rows = o_len + align(chunk * 4), need = o_rows + align(chunk * row * 4);
-  if (need > m->query_bytes) {
-    const size_t grown = std::max(need, (size_t)1 << 20);
-    SDM_TRY(regrow(m, &m->h_query, &m->query_bytes, grown, m->stream, true));
-    SDM_TRY(regrow(m, &m->d_query, &m->query_bytes, grown));
-  }
-  unsigned char *hq = m->h_query, *dq = m->d_query;
-  for (size_t off = 0; off < (size_t)n; off += chunk) {
-    const size_t c = std::min(chunk, (size_t)n - off);
-    memcpy(hq, in + off * in_elem, c * in_elem);
-    HIP_TRY(hipMemcpyAsync(dq, hq, c * in_elem, hipMemcpyHostToDevice, m->stream));
-    launch(dq, (uint32_t)c, (uint32_t)row, row, reinterpret_cast<uint32_t *>(dq + o_rows), reinterpret_cast<int32_t *>(dq + o_len));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(hq + o_len, dq + o_len, c * 4, hipMemcpyDeviceToHost, m->stream));
-    if (row) HIP_TRY(hipMemcpyAsync(hq + o_rows, dq + o_rows, c * row * 4, hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    const int32_t *lens = reinterpret_cast<const int32_t *>(hq + o_len);
-    memcpy(len_out + off, lens, c * 4);
-    for (size_t i = 0; i < c; ++i) {
-      const size_t take = std::min<size_t>((size_t)lens[i], row);
-      if (take) memcpy(cells_out + (off + i) * (size_t)max_len, hq + o_rows + i * row * 4, take * 4);
-    }
-  }
-  return SDM_OK;
+  return run_staged(
+      m, (size_t)n, chunk, nullptr, 0,
+      {{StageCol::IN, const_cast<unsigned char *>(in), in_elem}, {StageCol::OUT, len_out, 4}, {StageCol::OUT_RAW, nullptr, row * 4}},
+      [&](const unsigned char *, unsigned char *const *col, size_t c) -> sdm_status {
+        launch(col[0], (uint32_t)c, (uint32_t)row, row, reinterpret_cast<uint32_t *>(col[2]), reinterpret_cast<int32_t *>(col[1]));
+        HIP_TRY(hipGetLastError());
+        return SDM_OK;
+      },
+      [&](const unsigned char *const *col, size_t off, size_t c) {
+        const int32_t *lens = reinterpret_cast<const int32_t *>(col[1]);
+        for (size_t i = 0; i < c; ++i) {
+          const size_t take = std::min<size_t>((size_t)lens[i], row);
+          if (take) memcpy(cells_out + (off + i) * (size_t)max_len, col[2] + i * row * 4, take * 4);
+        }
+      });
 }
 
 sdm_status sdm_debug_reach_tiles(sdm_map *m, int64_t *tiles_out) {
   if (!m || !tiles_out) return SDM_ERR_INVALID_ARGUMENT;
-  const sdm_status e = reach_check(m, "sdm_debug_reach_tiles", true);
-  if (e != SDM_OK) return e;
-  *tiles_out = (int64_t)m->h_reach_meta[M_TILES];
+  SDM_TRY(layer_check(m, "sdm_debug_reach_tiles", &m->reach, REACH));
+  *tiles_out = (int64_t)m->reach.h_meta[M_TILES];
   return SDM_OK;
 }
 

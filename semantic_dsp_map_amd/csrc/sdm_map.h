@@ -1,5 +1,7 @@
-// sdm_map.h — private to the host units of libsdm_hip (not installed): the map object behind the C ABI (include/sdm.h),
-// the error macros, who owns what a map allocates, and the host helpers that more than one unit uses.
+// sdm_map.h — private to the host units of libsdm_hip (not installed): the map object behind the C ABI (include/sdm.h) -
+// the frame pipeline's state flat in sdm_map, the state of every derived layer in a struct of its own -, the error macros,
+// who owns what a map allocates, and the host helpers that more than one unit uses: the frame's, and the layers' (their
+// one check, their one origin, the one staging path of the host-mode batched calls).
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -37,6 +39,60 @@ void set_error(const char *what, const char *file, int line, const char *detail)
 #define SDM_TRY(expr) do { const sdm_status rc_ = (expr); if (rc_ != SDM_OK) return rc_; } while (0)
 
 using namespace sdm;
+
+// ---- the derived map layers ---------------------------------------------------------------------------------------------
+// Built beside the frame pipeline and touched by their own units only (reach.hip also reads the distance field); no frame
+// reads any of it.  Their buffers are the map's like any other (alloc_tracked / regrow, freed by sdm_destroy), allocated
+// by the first build or call.  What every layer with a build keeps: the Frame it was built from (map center, ring
+// offsets), the build's flags, and whether there is a build at all.
+struct Derived {
+  Frame f{};
+  uint32_t flags = 0;
+  bool valid = false;
+  void built(const Frame &from, uint32_t with) { f = from, flags = with, valid = true; }  // the layer answers for this build from here on
+};
+// host-mode staging of the batched calls (run_staged, queries.hip): the preamble and one chunk's inputs and outputs, on
+// the device and page-locked; grown on demand, both together: `bytes` is non-zero only while both exist
+struct QueryStage {
+  unsigned char *d = nullptr, *h = nullptr;
+  size_t bytes = 0;
+};
+// the distance field (esdf.hip): site and snapshot word per cell in map-index order
+struct EsdfLayer : Derived {
+  uint32_t *site = nullptr, *snap = nullptr;
+};
+// the instance table (instances.hip): the accumulators (empty between builds), the table of the last build, its count
+// ([0]) and label counters ([1..256])
+struct InstLayer : Derived {
+  unsigned char *acc = nullptr;
+  sdm_instance *out = nullptr;
+  uint32_t *meta = nullptr;
+};
+// the frontiers (frontiers.hip): the free / unknown / frontier bitmasks and the words' prefix; the per-cell arrays,
+// accumulators (empty between builds) and cluster table, laid out for `alloc` cells of which `cap` are in use and grown
+// by a build that asks for more; the build's counters; a scan scratch of its own
+struct FrontLayer : Derived {
+  unsigned char *bits = nullptr, *cells = nullptr;
+  uint32_t *meta = nullptr, *scan = nullptr;
+  size_t alloc = 0;
+  int64_t cap = 0;
+};
+// view scoring (views.hip): a pool of `masks` bitmasks of V / 8 bytes, one per view in flight, zero between calls; batch:
+// sdm_debug_view_batch's bound on the views in flight (0: as many as the pool has masks); clear_rewalk: a batch's masks
+// are cleared by walking its rays again instead of zeroing them whole
+struct ViewPool {
+  uint32_t *pool = nullptr;
+  uint32_t masks = 0;
+  int32_t batch = 0;
+  bool clear_rewalk = false;
+};
+// the travel-cost field (reach.hip): the cost per cell and the traversable bitmask in map-index order, the tiles' activity
+// bitmask and the list of a round's active tiles, the build's counters (and their page-locked landing area), its arguments
+struct ReachLayer : Derived {
+  uint32_t *cost = nullptr, *trav = nullptr, *act = nullptr, *list = nullptr;
+  uint32_t *meta = nullptr, *h_meta = nullptr;
+  uint32_t min_d2 = 0, max_cost = 0;
+};
 
 struct sdm_map {
   sdm_config cfg{};
@@ -189,50 +245,13 @@ struct sdm_map {
   size_t emit_guess = 1024;  // points fetched together with the length (the last list's length and a margin)
   sdm_point *d_points = nullptr;
   size_t points_cap = 0;
-  // host-mode staging of the batched queries (sdm_query_*): one chunk's inputs and outputs, on the device and page-locked;
-  // grown on demand, used by nothing else (a query between two frames changes nothing the next frame reads)
-  unsigned char *d_query = nullptr, *h_query = nullptr;
-  size_t query_bytes = 0;
-  // the distance field (sdm_esdf_update, esdf.hip): site and snapshot word per cell in map-index order, allocated by the
-  // first build; the Frame of the frame it was built from (its map center and ring offsets); no frame reads any of it
-  uint32_t *d_esdf_site = nullptr, *d_esdf_snap = nullptr;
-  Frame esdf_f{};
-  bool esdf_valid = false;
-  // the instance table (sdm_instances_update, instances.hip): the accumulators (empty between builds), the table of the
-  // last build, its count and label counters, allocated by the first build; the Frame and flags of that build
-  unsigned char *d_inst_acc = nullptr;
-  sdm_instance *d_inst_out = nullptr;
-  uint32_t *d_inst_meta = nullptr;
-  Frame inst_f{};
-  uint32_t inst_flags = 0;
-  bool inst_valid = false;
-  // the frontiers (sdm_frontiers_update, frontiers.hip): the free / unknown / frontier bitmasks and the words' prefix; the
-  // per-cell arrays, accumulators (empty between builds) and cluster table, laid out for front_alloc cells of which
-  // front_cap are in use; the build's counters; a scan scratch of its own.  Allocated by the first build, the cells
-  // grown by one that asks for more; the Frame and flags of the last build
-  unsigned char *d_front_bits = nullptr, *d_front_cells = nullptr;
-  uint32_t *d_front_meta = nullptr, *d_front_scan = nullptr;
-  size_t front_alloc = 0;
-  int64_t front_cap = 0;
-  Frame front_f{};
-  uint32_t front_flags = 0;
-  bool front_valid = false;
-  // view scoring (sdm_query_views, views.hip): a pool of view_pool_masks bitmasks of V / 8 bytes, one per view in flight,
-  // allocated by the first call and zero between calls; view_batch: sdm_debug_view_batch's bound on the views in flight
-  // (0: as many as the pool has masks); view_clear_rewalk: a batch's masks are cleared by walking its rays again
-  // instead of zeroing them whole
-  uint32_t *d_view_pool = nullptr;
-  uint32_t view_pool_masks = 0;
-  int32_t view_batch = 0;
-  bool view_clear_rewalk = false;
-  // the travel-cost field (sdm_reach_update, reach.hip): the cost per cell and the traversable bitmask in map-index
-  // order, the tiles' activity bitmask and the list of a round's active tiles, the build's counters (and their
-  // page-locked landing area), allocated by the first build; the Frame and arguments of the last build
-  uint32_t *d_reach_cost = nullptr, *d_reach_trav = nullptr, *d_reach_act = nullptr, *d_reach_list = nullptr;
-  uint32_t *d_reach_meta = nullptr, *h_reach_meta = nullptr;
-  Frame reach_f{};
-  uint32_t reach_flags = 0, reach_min_d2 = 0, reach_max_cost = 0;
-  bool reach_valid = false;
+  // the derived layers (Derived and the structs behind it, above): nothing of the frame reads or writes them
+  QueryStage stage;
+  EsdfLayer esdf;
+  InstLayer inst;
+  FrontLayer front;
+  ViewPool views;
+  ReachLayer reach;
   sdm_point_xyzrgb *d_points_rgb = nullptr;
   size_t points_rgb_cap = 0;
   ColourTables *d_colours = nullptr;
@@ -314,9 +333,34 @@ sdm_status exchange_counts(sdm_map *m, hipStream_t s);  // the all-gather of the
 sdm_status exchange_check(sdm_map *m);                  // (m->stream is idle) did an exchange through the arenas time out?
 sdm_status exchange_wait(sdm_map *m);                   // sdm_synchronize with a communicator: a bounded wait for the map's streams
 void exchange_teardown(sdm_map *m);                     // communicator, arena, peer mappings, exchange buffers: back to "none"
-// queries.hip: host mode works through a batch in chunks; launch(in, out, out2, count, stream) enqueues one chunk
-using QueryLaunch = std::function<void(const void *, void *, void *, uint32_t, hipStream_t)>;
+// ---- the derived layers' shared host side (queries.hip) ---------------------------------------------------------------
 sdm_status query_check(sdm_map *m, const void *in, int64_t n, const void *out, uint32_t flags, uint32_t allowed, const char *what);
+// How a layer's two refusals name it: "<the_layer> of a Z-slab shard ... is / are not supported: build it / them on a
+// whole map" and "no <build>: call <update> first".
+struct LayerName {
+  const char *the_layer, *build, *update;
+  bool plural;
+};
+// The check of every entry point of a layer: no Z-slab shards, and - `need` given - that layer must hold a build.
+sdm_status layer_check(sdm_map *m, const char *what, const Derived *need, const LayerName &name);
+// the global position of the min corner of cell (0, 0, 0) of the frame layer `l` was built from (origin may be null)
+void layer_origin(const sdm_map *m, const Derived &l, float origin[3]);
+// Host mode works through `n` items in chunks, through the map's staging area (sdm_map::stage): `pre` goes up once (the
+// views' ray table); per chunk every input column is copied up, launch(pre, col, count) enqueues the items on m->stream
+// (device addresses; col[k] null: no such column), every output column is fetched, and after one wait copied out -
+// then copy_out(col, off, count), if given, sees the fetched columns of items [off, off + count).
+struct StageCol {
+  enum Kind { IN, OUT, OUT_RAW } kind;  // OUT_RAW: fetched like OUT, left to copy_out
+  void *host;                           // the caller's array (IN: only read)
+  size_t elem;                          // bytes per item; 0: the call has no such column
+};
+using StageLaunch = std::function<sdm_status(const unsigned char *pre, unsigned char *const *col, size_t count)>;
+using StageCopyOut = std::function<void(const unsigned char *const *col, size_t off, size_t count)>;
+sdm_status run_staged(sdm_map *m, size_t n, size_t chunk, const void *pre, size_t pre_bytes, const std::vector<StageCol> &cols,
+                      const StageLaunch &launch, const StageCopyOut &copy_out = nullptr);
+// The calls of one input and one or two outputs per item, host or device mode, in chunks of 2^20:
+// launch(in, out, out2, count, stream) enqueues one chunk; out2 (may be null) is a second output array
+using QueryLaunch = std::function<void(const void *, void *, void *, uint32_t, hipStream_t)>;
 sdm_status run_query(sdm_map *m, const void *in_v, size_t in_elem, void *out_v, size_t out_elem, void *out2_v, size_t out2_elem, int64_t n,
                      uint32_t flags, const QueryLaunch &launch);
 

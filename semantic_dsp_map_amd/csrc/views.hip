@@ -12,6 +12,7 @@
 // stay exactly what its tests hold it to, and tests/test_views_gpu.py holds the two walks together ray by ray, bit by bit.
 #include <cstdlib>
 
+#include "sdm_layer.h"
 #include "sdm_map.h"
 
 #pragma clang fp contract(off)
@@ -23,21 +24,9 @@ namespace sdm {
 namespace {
 
 constexpr int VTPB = 256;
-constexpr uint32_t RES_UNKNOWN_W1 = 0xff000000u;  // second word of an "unobserved" result: track 0, label 0, occ -1
 constexpr int SEG_K = 8;
 enum : int { SEG_CELL = 0, SEG_OUT = 1, SEG_END = 2 };
 enum : int { VIEW_MARK = 0, VIEW_CLEAR = 1 };
-
-__device__ __forceinline__ int8_t occ_of(uint32_t w1) { return (int8_t)(w1 >> 24); }
-__device__ __forceinline__ float map_u(const Dims &d, const Frame &f, int a, float p) { return ((p - f.center[a]) - d.pmin[a]) * d.recip; }
-__device__ __forceinline__ uint32_t cell_voxel(const Dims &d, const Frame &f, int ix, int iy, int iz) {
-  return ring_to_voxel(d, axis_correct(ix + f.eq[0], d.NX), axis_correct(iy + f.eq[1], d.NY), axis_correct(iz + f.eq[2], d.NZ));
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += (uint32_t)__shfl_xor((int)v, s, 64);
-  return v;
-}
 
 // One lane per ray, a block row per view (blockIdx.y = the view within the batch = its mask in the pool).
 // VIEW_MARK: a lane sets the bits of the cells of a batch with returned atomics, all issued together; where the bit was
@@ -237,21 +226,20 @@ __global__ __launch_bounds__(VTPB) void k_view_rays(Dims d, Frame f, const sdm_v
 constexpr size_t VIEW_POOL_BYTES = (size_t)64 << 20;  // what the pool may take; at least one mask, at most VIEW_POOL_MASKS
 constexpr uint32_t VIEW_POOL_MASKS = 256;
 constexpr size_t VIEW_CHUNK_RAYS = (size_t)1 << 20;   // host mode: rays per staged chunk (whole views; at least one)
-size_t view_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // `n` views from device memory, in batches of as many as the pool has masks (or the test hook allows)
 sdm_status views_enqueue(sdm_map *m, const Frame &f, const sdm_view *views, const float *dirs, uint32_t n_rays, size_t n, sdm_view_gain *out,
                          sdm_segment_hit *rays_out, int32_t *unk_out) {
   const uint32_t mask_words = m->d.V / 32u;
-  if (!m->d_view_pool) {
+  if (!m->views.pool) {
     const size_t mask_bytes = (size_t)mask_words * 4;
-    m->view_pool_masks = (uint32_t)std::min<size_t>(VIEW_POOL_MASKS, std::max<size_t>(1, VIEW_POOL_BYTES / mask_bytes));
-    SDM_TRY(alloc_tracked(m, &m->d_view_pool, (size_t)m->view_pool_masks * mask_words));
-    HIP_TRY(hipMemsetAsync(m->d_view_pool, 0, (size_t)m->view_pool_masks * mask_bytes, m->stream));  // zero; every call leaves it zero again
+    m->views.masks = (uint32_t)std::min<size_t>(VIEW_POOL_MASKS, std::max<size_t>(1, VIEW_POOL_BYTES / mask_bytes));
+    SDM_TRY(alloc_tracked(m, &m->views.pool, (size_t)m->views.masks * mask_words));
+    HIP_TRY(hipMemsetAsync(m->views.pool, 0, (size_t)m->views.masks * mask_bytes, m->stream));  // zero; every call leaves it zero again
   }
   const char *e = getenv("SDM_VIEW_CLEAR");  // A/B (tools/probes/views_probe.py): "rewalk" or "memset", looked up per call
-  const bool rewalk = e ? strcmp(e, "rewalk") == 0 : m->view_clear_rewalk;
-  const uint32_t B = m->view_batch > 0 ? std::min<uint32_t>(m->view_pool_masks, (uint32_t)m->view_batch) : m->view_pool_masks;
+  const bool rewalk = e ? strcmp(e, "rewalk") == 0 : m->views.clear_rewalk;
+  const uint32_t B = m->views.batch > 0 ? std::min<uint32_t>(m->views.masks, (uint32_t)m->views.batch) : m->views.masks;
   const uint2 *res = reinterpret_cast<const uint2 *>(m->st.res);
   HIP_TRY(hipMemsetAsync(out, 0, n * sizeof(sdm_view_gain), m->stream));
   for (size_t v0 = 0; v0 < n; v0 += B) {
@@ -259,15 +247,15 @@ sdm_status views_enqueue(sdm_map *m, const Frame &f, const sdm_view *views, cons
     const dim3 grid((n_rays + VTPB - 1) / VTPB, nb);
     sdm_segment_hit *ro = rays_out ? rays_out + v0 * n_rays : nullptr;
     int32_t *uo = unk_out ? unk_out + v0 * n_rays : nullptr;
-    hipLaunchKernelGGL(k_view_rays<VIEW_MARK>, grid, dim3(VTPB), 0, m->stream, m->d, f, views + v0, dirs, n_rays, res, m->d_view_pool, mask_words,
+    hipLaunchKernelGGL(k_view_rays<VIEW_MARK>, grid, dim3(VTPB), 0, m->stream, m->d, f, views + v0, dirs, n_rays, res, m->views.pool, mask_words,
                        out + v0, ro, uo);
     HIP_TRY(hipGetLastError());
     if (rewalk) {
-      hipLaunchKernelGGL(k_view_rays<VIEW_CLEAR>, grid, dim3(VTPB), 0, m->stream, m->d, f, views + v0, dirs, n_rays, res, m->d_view_pool,
+      hipLaunchKernelGGL(k_view_rays<VIEW_CLEAR>, grid, dim3(VTPB), 0, m->stream, m->d, f, views + v0, dirs, n_rays, res, m->views.pool,
                          mask_words, (sdm_view_gain *)nullptr, (sdm_segment_hit *)nullptr, (int32_t *)nullptr);
       HIP_TRY(hipGetLastError());
     } else {
-      HIP_TRY(hipMemsetAsync(m->d_view_pool, 0, (size_t)nb * mask_words * 4, m->stream));
+      HIP_TRY(hipMemsetAsync(m->views.pool, 0, (size_t)nb * mask_words * 4, m->stream));
     }
   }
   return SDM_OK;
@@ -281,8 +269,7 @@ extern "C" {
 
 sdm_status sdm_query_views(sdm_map *m, const sdm_view *views, int64_t n_views, const float *dirs, int32_t n_rays, sdm_view_gain *out,
                            sdm_segment_hit *rays_out, int32_t *ray_unknown_out, uint32_t flags) {
-  const sdm_status e = query_check(m, views, n_views, out, flags, SDM_QUERY_ON_DEVICE, "sdm_query_views");
-  if (e != SDM_OK) return e;
+  SDM_TRY(query_check(m, views, n_views, out, flags, SDM_QUERY_ON_DEVICE, "sdm_query_views"));
   if (!dirs || n_rays < 1 || n_rays > SDM_VIEW_MAX_RAYS || n_views > (((int64_t)1 << 31) - 1) / n_rays) {
     set_error("sdm_query_views", __FILE__, __LINE__, "null ray table, n_rays outside 1 .. 65536, or n_views * n_rays >= 2^31");
     return SDM_ERR_INVALID_ARGUMENT;
@@ -293,40 +280,21 @@ sdm_status sdm_query_views(sdm_map *m, const sdm_view *views, int64_t n_views, c
   const size_t n = (size_t)n_views, nr = (size_t)n_rays;
   if (flags & SDM_QUERY_ON_DEVICE) return views_enqueue(m, f, views, dirs, (uint32_t)n_rays, n, out, rays_out, ray_unknown_out);
   // host mode: the ray table goes up once, the views in chunks of whole views through the queries' staging area
-  const size_t chunk = std::min(n, std::max<size_t>(1, VIEW_CHUNK_RAYS / nr));
-  const size_t o_views = view_align(nr * 12), o_out = o_views + view_align(chunk * sizeof(sdm_view));
-  const size_t o_rays = o_out + view_align(chunk * sizeof(sdm_view_gain));
-  const size_t o_unk = o_rays + (rays_out ? view_align(chunk * nr * sizeof(sdm_segment_hit)) : 0);
-  const size_t need = o_unk + (ray_unknown_out ? view_align(chunk * nr * 4) : 0);
-  if (need > m->query_bytes) {
-    const size_t grown = std::max(need, (size_t)1 << 20);
-    SDM_TRY(regrow(m, &m->h_query, &m->query_bytes, grown, m->stream, true));
-    SDM_TRY(regrow(m, &m->d_query, &m->query_bytes, grown));
-  }
-  unsigned char *hq = m->h_query, *dq = m->d_query;
-  memcpy(hq, dirs, nr * 12);
-  HIP_TRY(hipMemcpyAsync(dq, hq, nr * 12, hipMemcpyHostToDevice, m->stream));
-  for (size_t off = 0; off < n; off += chunk) {
-    const size_t c = std::min(chunk, n - off);
-    memcpy(hq + o_views, views + off, c * sizeof(sdm_view));
-    HIP_TRY(hipMemcpyAsync(dq + o_views, hq + o_views, c * sizeof(sdm_view), hipMemcpyHostToDevice, m->stream));
-    SDM_TRY(views_enqueue(m, f, reinterpret_cast<const sdm_view *>(dq + o_views), reinterpret_cast<const float *>(dq), (uint32_t)n_rays, c,
-                          reinterpret_cast<sdm_view_gain *>(dq + o_out), rays_out ? reinterpret_cast<sdm_segment_hit *>(dq + o_rays) : nullptr,
-                          ray_unknown_out ? reinterpret_cast<int32_t *>(dq + o_unk) : nullptr));
-    HIP_TRY(hipMemcpyAsync(hq + o_out, dq + o_out, c * sizeof(sdm_view_gain), hipMemcpyDeviceToHost, m->stream));
-    if (rays_out) HIP_TRY(hipMemcpyAsync(hq + o_rays, dq + o_rays, c * nr * sizeof(sdm_segment_hit), hipMemcpyDeviceToHost, m->stream));
-    if (ray_unknown_out) HIP_TRY(hipMemcpyAsync(hq + o_unk, dq + o_unk, c * nr * 4, hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    memcpy(out + off, hq + o_out, c * sizeof(sdm_view_gain));
-    if (rays_out) memcpy(rays_out + off * nr, hq + o_rays, c * nr * sizeof(sdm_segment_hit));
-    if (ray_unknown_out) memcpy(ray_unknown_out + off * nr, hq + o_unk, c * nr * 4);
-  }
-  return SDM_OK;
+  return run_staged(m, n, std::min(n, std::max<size_t>(1, VIEW_CHUNK_RAYS / nr)), dirs, nr * 12,
+                    {{StageCol::IN, const_cast<sdm_view *>(views), sizeof(sdm_view)},
+                     {StageCol::OUT, out, sizeof(sdm_view_gain)},
+                     {StageCol::OUT, rays_out, rays_out ? nr * sizeof(sdm_segment_hit) : 0},
+                     {StageCol::OUT, ray_unknown_out, ray_unknown_out ? nr * 4 : 0}},
+                    [&](const unsigned char *pre, unsigned char *const *col, size_t c) {
+                      return views_enqueue(m, f, reinterpret_cast<const sdm_view *>(col[0]), reinterpret_cast<const float *>(pre), (uint32_t)n_rays,
+                                           c, reinterpret_cast<sdm_view_gain *>(col[1]), reinterpret_cast<sdm_segment_hit *>(col[2]),
+                                           reinterpret_cast<int32_t *>(col[3]));
+                    });
 }
 
 sdm_status sdm_debug_view_batch(sdm_map *m, int32_t max_views_in_flight) {
   if (!m) return SDM_ERR_INVALID_ARGUMENT;
-  m->view_batch = max_views_in_flight > 0 ? max_views_in_flight : 0;
+  m->views.batch = max_views_in_flight > 0 ? max_views_in_flight : 0;
   return SDM_OK;
 }
 
