@@ -756,6 +756,117 @@ sdm_status sdm_query_reach(sdm_map *m, const float *xyz, const uint32_t *cells, 
 sdm_status sdm_reach_paths(sdm_map *m, const float *xyz, const uint32_t *cells, int64_t n, int32_t max_len,
                            uint32_t *cells_out, int32_t *len_out, uint32_t flags);
 
+/* ---- forecast: where will the moving objects be while the robot drives the path it planned? ----
+ * sdm_forecast_update enqueues, on the map's stream, the future occupancy of the moving objects of the last frame enqueued
+ * before the call, and returns without waiting.  Like the other layers the result is a snapshot: it keeps that frame's
+ * map center and ring offsets and answers for it until the next sdm_forecast_update, whatever frames, sdm_clear or
+ * sdm_load_state come in between; nothing of the map's state is modified and no scratch of the frames' or of another
+ * layer is used.  Cells are map-index cells, cell word i | j << x_n | k << (x_n + y_n).  The map is a block, no torus:
+ * what moves out of the block is dropped and counted.  Only integer OR / MIN / ADD atomics build the field: it is
+ * bitwise the same from run to run.
+ * Motions: per moving track one velocity in metres per second in the global frame, translation only (what the object
+ * layer estimates: sdm_object_info.translation_velocity).  n_motions == 0 is allowed: the field then holds only the
+ * classes.  Horizons: n_horizons times t[0] < t[1] < ... in seconds, all finite and > 0, 1 <= n_horizons <=
+ * SDM_FORECAST_MAX_HORIZONS.  The caller chooses horizons that cover the times it will ask about: a time past the last
+ * horizon is answered with the last one.
+ * Shift: all cells of a track move by one integer cell vector per horizon,
+ *   s[k][a] = clamp(nearbyint(((double)v[a] * (double)t[k]) / (double)voxel_size), -1024, 1024)
+ * - two IEEE double operations, ties to even, voxel_size the float32 of the configuration.  Cell centres all shift by the
+ * same vector, so this is the translation rounded to cells: it leaves no holes.
+ * Stamps: motions x horizons are expanded into a list of (track, horizon k, dx, dy, dz), ascending track, then horizon,
+ * then j.  Without flags one stamp s[k] per track and horizon.  With SDM_FORECAST_SWEPT horizon k covers the whole interval
+ * (t[k-1], t[k]]: with p = s[k-1] (s[-1] = 0), q = s[k], D = q - p, J = max_a |D_a| the stamps are
+ *   p_a + sgn(D_a) * ((2 * j * |D_a| + J) / (2 * J))   (integer division),  j = 1 .. J;   J == 0: the single stamp q.
+ * More than SDM_FORECAST_MAX_STAMPS stamps in one build: SDM_ERR_CAPACITY, decided on the host before anything is enqueued
+ * (a limit on the input, not a capacity to guess).  sdm_forecast_stamps is that expansion on its own: host code, no map,
+ * no device; *n_out is the true number of stamps and may exceed cap (nothing is written beyond cap); it checks what the
+ * build checks except the track's upper bound, and answers SDM_ERR_CAPACITY above SDM_FORECAST_MAX_STAMPS.
+ * Field, per map-index cell (x fastest), two uint32:
+ *   mask   bits 0..15: bit k is set when some source cell plus a horizon-k stamp of its track lands here;
+ *          bits 16..17: the class now - 0 unknown (occ == -1), 1 free (occ == 0), 2 an obstacle that stays (occ >= 1, winning
+ *          track not among the motions), 3 source (occ >= 1, winning track among the motions; guessed-occupied cells, occ == 2,
+ *          count like occ == 1, as for segments and the distance field); all other bits 0.
+ *   first  the minimum over all landings of k << 16 | track: the earliest horizon at which anything arrives and, among
+ *          equals, the smallest track id; 0xffffffff where nothing lands.
+ * State of a cell at horizon k, in this priority: 1 stays (class 2); 2 predicted (bit k set); 3 vacated (class 3, bit k
+ * clear); 0 free (class 1); -1 unknown.  Horizon of a time T: the smallest k with T <= t[k]; the last one beyond.
+ * The build does not wait for the device: its table goes up from one of two page-locked copies that builds use in turn, so
+ * a build waits at most until the upload of the build before the last one has left its copy (stream order: whatever was
+ * enqueued before that upload).
+ * Memory: 8 bytes per voxel of device memory (4 B mask, 4 B first), and less than 1 MB for the motion table and the
+ * stamps (twice that page-locked), allocated at the first sdm_forecast_update and freed by sdm_destroy: 134 MB at 256^3, 1.07 GB at 512^3;
+ * sdm_get_forecast_cells adds V / 16 bytes at its first call.
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map, a Z-slab shard (shard_count > 1), unknown flag bits, n_motions < 0 (or
+ * motions NULL with n_motions > 0), a duplicate track, track 0 or a track above max_movable_track, a non-finite velocity,
+ * pad != 0, n_horizons out of range, horizons not finite, not > 0 or not strictly ascending, and a getter or query
+ * before any sdm_forecast_update. */
+#define SDM_FORECAST_SWEPT 0x1u          /* sdm_forecast_update: horizon k covers (t[k-1], t[k]], not the instant t[k] */
+#define SDM_FORECAST_VACATED_BLOCKS 0x4u /* sdm_query_forecast_segments: source cells block although their object leaves */
+#define SDM_FORECAST_MAX_HORIZONS 16
+#define SDM_FORECAST_MAX_STAMPS 65536
+typedef struct {   /* 16 bytes */
+  uint16_t track;  /* 1 .. max_movable_track */
+  uint16_t pad;    /* 0 */
+  float v[3];      /* metres per second, global frame */
+} sdm_motion;
+typedef struct {   /* 12 bytes */
+  uint16_t track;
+  uint8_t horizon;
+  uint8_t pad;     /* 0 */
+  int16_t d[3];    /* cells */
+  int16_t pad2;    /* 0 */
+} sdm_forecast_stamp;
+typedef struct {   /* 40 bytes */
+  uint32_t n_motions, n_horizons, n_stamps, flags;
+  uint32_t n_sources;   /* cells of class 3 */
+  uint32_t n_marked;    /* cells with any horizon bit */
+  uint64_t n_marks_in;  /* (source cell, stamp) pairs that land inside the block */
+  uint64_t n_marks_out; /* ... and outside: dropped */
+} sdm_forecast_info;
+typedef struct {         /* 8 bytes */
+  int8_t state;          /* at `horizon`: -1 unknown, 0 free, 1 stays, 2 predicted, 3 vacated */
+  uint8_t horizon;       /* of the query's time; 0xff outside the map / non-finite */
+  uint16_t track;        /* of `first`; 0 where nothing lands */
+  uint16_t mask;         /* the cell's horizon bits */
+  uint8_t first_horizon; /* of `first`; 0xff where nothing lands */
+  uint8_t pad;           /* 0 */
+} sdm_forecast_result;
+typedef struct {    /* 16 bytes */
+  float t;          /* where the segment enters its first blocking cell, as a fraction of a->b; -1 = nothing blocks */
+  uint32_t cell;    /* map-index word of that cell; 0xffffffff = none / outside the map */
+  int32_t cells;    /* in-map cells visited up to and including the hit (all of them if no hit) */
+  uint16_t track;   /* state 2: of the cell's `first`; else 0 */
+  int8_t state;     /* of the blocking cell: 1 stays, 2 predicted, 3 vacated, -1 unknown / outside; 0 = nothing blocks */
+  uint8_t horizon;  /* state 2: the lowest horizon bit set within the cell's time range; else 0xff */
+} sdm_forecast_hit;
+sdm_status sdm_forecast_stamps(float voxel_size, const sdm_motion *motions, int32_t n_motions, const float *horizons,
+                               int32_t n_horizons, uint32_t flags, sdm_forecast_stamp *out, int64_t cap, int64_t *n_out);
+sdm_status sdm_forecast_update(sdm_map *m, const sdm_motion *motions, int32_t n_motions, const float *horizons,
+                               int32_t n_horizons, uint32_t flags);
+/* Waits; mask and first in map-index order, x fastest (V words each); any of the four pointers may be NULL (origin: the
+ * global position of the min corner of cell (0,0,0) of the snapshot). */
+sdm_status sdm_get_forecast(sdm_map *m, uint32_t *mask, uint32_t *first, sdm_forecast_info *info, float origin[3]);
+/* Waits; the cells with any horizon bit in ascending cell word, with their two field words, for visualisation.  *n_out is
+ * their number (info.n_marked) and may exceed cap; nothing is written beyond cap; any of the three arrays may be NULL. */
+sdm_status sdm_get_forecast_cells(sdm_map *m, uint32_t *cell, uint32_t *mask, uint32_t *first, int64_t cap, int64_t *n_out);
+/* Points in space and time, xyzt[4i..4i+3] = x y z T (global frame, seconds from the snapshot): the cell is floor(u) per
+ * axis with the snapshot's frame, the state that of the table above at the horizon of T.  A point outside the map or a
+ * non-finite value: state -1, horizon 0xff, track 0, mask 0, first_horizon 0xff.  Flags: SDM_QUERY_ON_DEVICE, as for the
+ * other queries; n == 0 launches nothing.  Device mode: xyzt must be aligned to 16 bytes and out to 8 (the kernel moves
+ * whole items; what sdm_device_alloc returns is, an array that begins at an odd item offset inside it may not be). */
+sdm_status sdm_query_forecast(sdm_map *m, const float *xyzt, int64_t n, sdm_forecast_result *out, uint32_t flags);
+/* Space-time segments seg[8i..8i+7] = ax ay az ta bx by bz tb, ta <= tb: the first blocking cell on the way.  The walk is
+ * sdm_query_segments' (same cells, same order, same t, clipped to the map).  A cell entered at tau_in and left at tau_out
+ * (the next cell's tau_in, 1 for the last cell) is occupied during T(tau_in) .. T(tau_out), T(tau) = (double)ta + tau *
+ * ((double)tb - (double)ta).  It blocks when its class is 2 (state 1); when any horizon bit between the horizons of
+ * those two times, inclusive, is set (state 2); with SDM_QUERY_UNKNOWN_BLOCKS when its class is 0 and none of those bits is
+ * set, or it lies outside the map (state -1); with SDM_FORECAST_VACATED_BLOCKS when its class is 3 (state 3, if none of
+ * those bits is set).  ta > tb or any non-finite value is handled like a non-finite coordinate in sdm_query_segments: no
+ * hit and cells = 0, or with SDM_QUERY_UNKNOWN_BLOCKS a hit at t = 0 on cell 0xffffffff.  With no motions and no flags
+ * t, cells and the hit cell are sdm_query_segments'.  Flags: SDM_QUERY_ON_DEVICE, SDM_QUERY_UNKNOWN_BLOCKS,
+ * SDM_FORECAST_VACATED_BLOCKS.  Device mode: out must be aligned to 16 bytes (an item is stored whole), seg to 4. */
+sdm_status sdm_query_forecast_segments(sdm_map *m, const float *seg, int64_t n, sdm_forecast_hit *out, uint32_t flags);
+
 /* ---- owner sets of the object layer: ObjectParticleHashMap (object_layer.h:20-52) */
 sdm_status sdm_object_particle_count(sdm_map *m, int32_t track_id, int64_t *count);
 /* The keys of ObjectParticleHashMap::indices_map whose sets are not empty: every track id that owns at least one slot of

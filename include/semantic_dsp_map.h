@@ -170,6 +170,9 @@ struct SdmObjectLayer {
   /// reference's obj_ptc_hash_map.indices_map, which its floating-object check walks, semantic_dsp_map.h:712-736), told
   /// before collect()
   virtual void setTracksWithParticles(const int32_t *, int32_t) {}
+  /// the velocities the layer predicts the moving objects with, for SemanticDSPMap::forecast (sdm.h, "forecast"); a layer
+  /// that estimates none reports none
+  virtual void motions(std::vector<sdm_motion> &out) { out.clear(); }
 };
 
 /// The library's own object layer (sdm_objects.h): objectLevelUpdate and the object loop of the
@@ -241,6 +244,7 @@ class SdmBuiltinObjectLayer : public SdmObjectLayer {
   void setTracksWithParticles(const int32_t *ids, int32_t n) override {
     owner_tracks_.assign(ids, ids + (n > 0 ? n : 0));
     have_owner_tracks_ = true;
+    told_owner_tracks_ = true;
   }
   /// the frame these removals belonged to was not applied: offer them again
   void requeue(const std::vector<int32_t> &remove_tracks) {
@@ -252,8 +256,28 @@ class SdmBuiltinObjectLayer : public SdmObjectLayer {
   void clear() override {
     sdm_objects_clear(h_);
     maybe_present_.clear();
+    owner_tracks_.clear();
+    have_owner_tracks_ = told_owner_tracks_ = false;
   }
   sdm_objects *handle() { return h_; }
+  /// Of the tracks that own particles (as last told by the map - also when it told of none -, which collect() leaves in
+  /// place; a layer nobody ever told falls back on its own bookkeeping): those the layer tracks,
+  /// has seen move and can predict, with the translation velocity it predicts them with (MotionEstimation: identity
+  /// rotation, v * dt), ascending track id.
+  void motions(std::vector<sdm_motion> &out) override {
+    out.clear();
+    const std::set<int32_t> present = told_owner_tracks_ ? std::set<int32_t>(owner_tracks_.begin(), owner_tracks_.end()) : maybe_present_;
+    for (int32_t id : present) {
+      sdm_object_info info;
+      if (id < 1 || id > max_movable_ || id > 65535 || sdm_objects_query(h_, id, &info) != SDM_OK) continue;
+      if (!info.exists || !info.moving || !info.prediction_available) continue;
+      sdm_motion mo;
+      mo.track = (uint16_t)id;
+      mo.pad = 0;
+      for (int a = 0; a < 3; ++a) mo.v[a] = (float)info.translation_velocity[a];
+      if (std::isfinite(mo.v[0]) && std::isfinite(mo.v[1]) && std::isfinite(mo.v[2])) out.push_back(mo);
+    }
+  }
 
  private:
   sdm_objects *h_;
@@ -262,7 +286,8 @@ class SdmBuiltinObjectLayer : public SdmObjectLayer {
   int max_movable_;
   std::set<int32_t> maybe_present_, seen_this_frame_;
   std::vector<int32_t> owner_tracks_;
-  bool have_owner_tracks_ = false;
+  bool have_owner_tracks_ = false;    // told since the last collect()
+  bool told_owner_tracks_ = false;    // told ever (since the last clear()): owner_tracks_ is the map's last word
 };
 
 /// Where the last update() call spent its wall-clock time (milliseconds); see SemanticDSPMap::lastUpdateTimes().
@@ -357,6 +382,9 @@ class SemanticDSPMap {
   /// test - hands it over before the first update().
   void setNoiseTable(const float *table, size_t n) { noise_table_.assign(table, table + n); }
   void setObjectLayer(SdmObjectLayer *layer) { object_layer_ = layer; }
+  /// the built-in object layer, once useBuiltinObjectLayer() or the first update() has made it (else null): its handle
+  /// answers sdm_objects_query
+  SdmBuiltinObjectLayer *builtinObjectLayer() { return builtin_layer_.get(); }
   /// Use the library's object layer (sdm_objects.h).  mode = the reference's SETTING (settings.h:22); call after
   /// setGridPreset / setLabelTables / setBeyesianMovementParameters.
   void useBuiltinObjectLayer(int mode, uint64_t seed = 20250217ull) {
@@ -510,6 +538,51 @@ class SemanticDSPMap {
       for (size_t i = 0; i < goals.size(); ++i) (*paths)[i].assign(rows.begin() + i * longest, rows.begin() + i * longest + lens[i]);
     }
     return costs_out.size();
+  }
+  /// Where will the moving objects be (sdm.h, "forecast")?  Builds the forecast over the results of the last update() from
+  /// the velocities the object layer predicts its moving objects with (SdmObjectLayer::motions) at the given horizons -
+  /// ascending times in seconds from now, at most SDM_FORECAST_MAX_HORIZONS; swept: a horizon covers the whole interval
+  /// since the one before it.  The build is enqueued, the call does not wait.  used (may be null): the motions it was
+  /// built from.  Returns 1 when the build is enqueued; 0 before the first update(), without horizons or when the call fails.
+  size_t forecast(const std::vector<float> &horizons, bool swept = false, std::vector<sdm_motion> *used = nullptr) {
+    std::vector<sdm_motion> mo;
+    if (object_layer_) object_layer_->motions(mo);
+    if (used) *used = mo;
+    return forecast(mo, horizons, swept);
+  }
+  /// the same from motions of the caller's (one per track id, 1 .. the largest movable id)
+  size_t forecast(const std::vector<sdm_motion> &motions, const std::vector<float> &horizons, bool swept = false) {
+    if (!map_ || horizons.empty()) return 0;
+    return check(sdm_forecast_update(map_, motions.empty() ? nullptr : motions.data(), (int32_t)motions.size(), horizons.data(),
+                                     (int32_t)horizons.size(), swept ? SDM_FORECAST_SWEPT : 0u),
+                 "sdm_forecast_update")
+               ? 1
+               : 0;
+  }
+  /// Is the path still free when the robot gets there?  waypoints: positions (global frame); times: per waypoint when
+  /// the robot passes it, in seconds from the forecast's frame and ascending; out[i] answers for the leg from waypoint i
+  /// to i + 1: the first cell on it that is occupied while the robot is inside it - by an obstacle that stays or by a
+  /// predicted object - or t = -1.  unknown_blocks / vacated_blocks: as the flags of sdm_query_forecast_segments.  Waits.
+  /// Returns the number of legs answered; 0 (and an empty vector) before the first update() and forecast(), with fewer
+  /// than two waypoints, with not one time per waypoint, or when the call fails.
+  size_t checkTrajectory(const std::vector<Eigen::Vector3d> &waypoints, const std::vector<double> &times, std::vector<sdm_forecast_hit> &out,
+                         bool unknown_blocks = false, bool vacated_blocks = false) {
+    out.clear();
+    if (!map_ || waypoints.size() < 2 || times.size() != waypoints.size()) return 0;
+    const size_t n = waypoints.size() - 1;
+    std::vector<float> seg(8 * n);
+    for (size_t i = 0; i < n; ++i)
+      for (size_t e = 0; e < 2; ++e) {
+        const Eigen::Vector3d &w = waypoints[i + e];
+        seg[8 * i + 4 * e] = (float)w.x();
+        seg[8 * i + 4 * e + 1] = (float)w.y();
+        seg[8 * i + 4 * e + 2] = (float)w.z();
+        seg[8 * i + 4 * e + 3] = (float)times[i + e];
+      }
+    out.resize(n);
+    const uint32_t flags = (unknown_blocks ? SDM_QUERY_UNKNOWN_BLOCKS : 0u) | (vacated_blocks ? SDM_FORECAST_VACATED_BLOCKS : 0u);
+    if (!check(sdm_query_forecast_segments(map_, seg.data(), (int64_t)n, out.data(), flags), "sdm_query_forecast_segments")) out.clear();
+    return out.size();
   }
   /// the ray table scoreViews uses at `stride`: three floats per ray
   const std::vector<float> &viewRays(int stride) {

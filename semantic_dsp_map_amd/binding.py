@@ -64,6 +64,18 @@ REACH_FACE_CONNECTED = 0x1
 REACH_THROUGH_UNKNOWN = 0x2
 REACH_COST_PER_CELL = 10
 REACH_NO_COST = 0xFFFFFFFF
+# the forecast (sdm.h: sdm_motion, sdm_forecast_stamp / _info / _result / _hit)
+MOTION = np.dtype([("track", "<u2"), ("pad", "<u2"), ("v", "<f4", (3,))])
+FORECAST_STAMP = np.dtype([("track", "<u2"), ("horizon", "u1"), ("pad", "u1"), ("d", "<i2", (3,)), ("pad2", "<i2")])
+FORECAST_INFO = np.dtype([("n_motions", "<u4"), ("n_horizons", "<u4"), ("n_stamps", "<u4"), ("flags", "<u4"), ("n_sources", "<u4"),
+                          ("n_marked", "<u4"), ("n_marks_in", "<u8"), ("n_marks_out", "<u8")])
+FORECAST_RESULT = np.dtype([("state", "i1"), ("horizon", "u1"), ("track", "<u2"), ("mask", "<u2"), ("first_horizon", "u1"), ("pad", "u1")])
+FORECAST_HIT = np.dtype([("t", "<f4"), ("cell", "<u4"), ("cells", "<i4"), ("track", "<u2"), ("state", "i1"), ("horizon", "u1")])
+FORECAST_SWEPT = 0x1
+FORECAST_VACATED_BLOCKS = 0x4
+FORECAST_MAX_HORIZONS = 16
+FORECAST_MAX_STAMPS = 65536
+FORECAST_NOTHING = 0xFFFFFFFF
 
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
@@ -217,6 +229,12 @@ def load_library():
         "sdm_query_reach": [vp, vp, vp, i64, vp, u32],
         "sdm_reach_paths": [vp, vp, vp, i64, i32, vp, vp, u32],
         "sdm_debug_reach_tiles": [vp, C.POINTER(i64)],
+        "sdm_forecast_stamps": [C.c_float, vp, i32, vp, i32, u32, vp, i64, C.POINTER(i64)],
+        "sdm_forecast_update": [vp, vp, i32, vp, i32, u32],
+        "sdm_get_forecast": [vp, vp, vp, vp, vp],
+        "sdm_get_forecast_cells": [vp, vp, vp, vp, i64, C.POINTER(i64)],
+        "sdm_query_forecast": [vp, vp, i64, vp, u32],
+        "sdm_query_forecast_segments": [vp, vp, i64, vp, u32],
         "sdm_object_particle_count": [vp, i32, C.POINTER(i64)],
         "sdm_tracks_with_particles": [vp, vp, i32, C.POINTER(i32)],
         "sdm_comm_set_options": [vp, i32, i32],
@@ -726,6 +744,58 @@ class SdmMap:
         _check(self.L, self.L.sdm_debug_reach_tiles(self.h, C.byref(n)), "sdm_debug_reach_tiles")
         return n.value
 
+    # ---- the forecast (sdm.h).  forecast_update enqueues a build on the map's stream from the last frame's results and the
+    # motions given; forecast(), forecast_cells() and the two queries answer for that frame until the next build.
+    def forecast_update(self, motions, horizons, swept=False):
+        """motions: MOTION records (or None: none), horizons: ascending times in seconds"""
+        mo = np.zeros(0, MOTION) if motions is None else np.ascontiguousarray(motions, dtype=MOTION).reshape(-1)
+        t = np.ascontiguousarray(horizons, dtype=np.float32).reshape(-1)
+        _check(self.L, self.L.sdm_forecast_update(self.h, _ptr(mo), len(mo), _ptr(t), len(t), FORECAST_SWEPT if swept else 0), "sdm_forecast_update")
+
+    def forecast(self):
+        """-> (mask, first, info, origin): uint32 arrays shaped [NZ, NY, NX] in map-index order, a FORECAST_INFO record,
+        origin the global position of the min corner of cell (0, 0, 0) of the snapshot (float32[3])"""
+        c = self.cfg
+        shape = (1 << c.z_n, 1 << c.y_n, 1 << c.x_n)
+        mask, first = np.empty(shape, np.uint32), np.empty(shape, np.uint32)
+        info, origin = np.zeros(1, FORECAST_INFO), np.empty(3, np.float32)
+        _check(self.L, self.L.sdm_get_forecast(self.h, _ptr(mask), _ptr(first), _ptr(info), _ptr(origin)), "sdm_get_forecast")
+        return mask, first, info[0], origin
+
+    def forecast_cells(self, cap=None):
+        """-> (cell, mask, first): the cells with any horizon bit in ascending map-index cell word and their field words;
+        cap: at most so many of them (-> also the true count, as a fourth value)"""
+        n = C.c_int64(0)
+        _check(self.L, self.L.sdm_get_forecast_cells(self.h, None, None, None, 0, C.byref(n)), "sdm_get_forecast_cells")
+        k = n.value if cap is None else min(int(cap), n.value)
+        cell, mask, first = np.empty(k, np.uint32), np.empty(k, np.uint32), np.empty(k, np.uint32)
+        _check(self.L, self.L.sdm_get_forecast_cells(self.h, _ptr(cell), _ptr(mask), _ptr(first), k, C.byref(n)), "sdm_get_forecast_cells")
+        return (cell, mask, first) if cap is None else (cell, mask, first, n.value)
+
+    def query_forecast(self, xyzt, on_device=False, n=None, out=None):
+        """xyzt: (n, 4) global positions and times -> FORECAST_RESULT per point.  on_device: xyzt and out (n FORECAST_RESULT)
+        are device pointers."""
+        if on_device:
+            _check(self.L, self.L.sdm_query_forecast(self.h, _ptr(int(xyzt)), int(n), _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_forecast")
+            return None
+        p = np.ascontiguousarray(xyzt, dtype=np.float32).reshape(-1, 4)
+        res = np.empty(len(p), FORECAST_RESULT)
+        _check(self.L, self.L.sdm_query_forecast(self.h, _ptr(p), len(p), _ptr(res), 0), "sdm_query_forecast")
+        return res
+
+    def query_forecast_segments(self, seg, unknown_blocks=False, vacated_blocks=False, on_device=False, n=None, out=None):
+        """seg: (n, 8) rows ax ay az ta bx by bz tb -> FORECAST_HIT per segment.  on_device: seg and out (n FORECAST_HIT)
+        are device pointers."""
+        fl = (QUERY_UNKNOWN_BLOCKS if unknown_blocks else 0) | (FORECAST_VACATED_BLOCKS if vacated_blocks else 0)
+        if on_device:
+            _check(self.L, self.L.sdm_query_forecast_segments(self.h, _ptr(int(seg)), int(n), _ptr(int(out)), fl | QUERY_ON_DEVICE),
+                   "sdm_query_forecast_segments")
+            return None
+        sg = np.ascontiguousarray(seg, dtype=np.float32).reshape(-1, 8)
+        res = np.empty(len(sg), FORECAST_HIT)
+        _check(self.L, self.L.sdm_query_forecast_segments(self.h, _ptr(sg), len(sg), _ptr(res), fl), "sdm_query_forecast_segments")
+        return res
+
     def occupied(self, cap=None, zero_center=False, free=False, mark_fov=False):
         cap = cap or self.v_count
         out = np.empty(cap, POINT)
@@ -882,6 +952,21 @@ class SdmMap:
         ms = C.c_float()
         _check(self.L, self.L.sdm_time_occupancy_sweep(self.h, iters, C.byref(ms)), "sdm_time_occupancy_sweep")
         return ms.value
+
+
+def forecast_stamps(voxel_size, motions, horizons, swept=False, cap=None):
+    """The stamps a forecast build makes of these motions and horizons (sdm_forecast_stamps: host code, no map, no device)
+    -> FORECAST_STAMP records (with cap: at most so many, and the true count as a second value)"""
+    L = load_library()
+    mo = np.zeros(0, MOTION) if motions is None else np.ascontiguousarray(motions, dtype=MOTION).reshape(-1)
+    t = np.ascontiguousarray(horizons, dtype=np.float32).reshape(-1)
+    fl, n = FORECAST_SWEPT if swept else 0, C.c_int64(0)
+    if cap is None:
+        _check(L, L.sdm_forecast_stamps(float(voxel_size), _ptr(mo), len(mo), _ptr(t), len(t), fl, None, 0, C.byref(n)), "sdm_forecast_stamps")
+    k = n.value if cap is None else int(cap)
+    out = np.zeros(k, FORECAST_STAMP)
+    _check(L, L.sdm_forecast_stamps(float(voxel_size), _ptr(mo), len(mo), _ptr(t), len(t), fl, _ptr(out), k, C.byref(n)), "sdm_forecast_stamps")
+    return out if cap is None else (out[:min(k, n.value)], n.value)
 
 
 def pinhole_rays(cfg, stride=1):

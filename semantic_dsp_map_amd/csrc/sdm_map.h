@@ -93,6 +93,20 @@ struct ReachLayer : Derived {
   uint32_t *meta = nullptr, *h_meta = nullptr;
   uint32_t min_d2 = 0, max_cost = 0;
 };
+// the forecast (forecast.hip): the two field words per cell in map-index order; the build's table - the motions' track
+// set, the per-track stamp offsets, the stamps - on the device and in two page-locked copies that builds fill in turn, each
+// with the event that says its last upload has left it; the build's counters (and their page-locked landing area); the cell list's word
+// popcounts and scan scratch; what the last build was given
+struct ForecastLayer : Derived {
+  uint32_t *mask = nullptr, *first = nullptr;
+  uint32_t *table = nullptr, *h_table[2] = {nullptr, nullptr};
+  hipEvent_t ev_table[2] = {nullptr, nullptr};
+  int table_next = 0;
+  unsigned long long *meta = nullptr, *h_meta = nullptr;
+  uint32_t *pre = nullptr, *scan = nullptr;
+  float t[16] = {};
+  uint32_t n_motions = 0, n_horizons = 0, n_stamps = 0;
+};
 
 struct sdm_map {
   sdm_config cfg{};
@@ -252,6 +266,7 @@ struct sdm_map {
   FrontLayer front;
   ViewPool views;
   ReachLayer reach;
+  ForecastLayer forecast;
   sdm_point_xyzrgb *d_points_rgb = nullptr;
   size_t points_rgb_cap = 0;
   ColourTables *d_colours = nullptr;
