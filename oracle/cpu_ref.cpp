@@ -2,11 +2,15 @@
  * oracle/cpu_ref.cpp — CPU oracle for the particle-grid update hot path of
  * tud-amr/semantic_dsp_map.
  *
- * TEST INFRASTRUCTURE ONLY (see cpu_ref.h).  PARITY UNPINNED: the reference
- * has no tests/golden vectors and cannot be built here; this file restates
- * its loops literally, single-threaded, with run-time grid dimensions and
- * without Eigen/OpenCV/PCL.  Every function cites the reference lines it
- * follows (paths relative to /root/reference/include).
+ * TEST INFRASTRUCTURE ONLY (see cpu_ref.h).  This file restates the
+ * reference's loops literally, single-threaded, with run-time grid dimensions
+ * and without Eigen/OpenCV/PCL.  The ring layer and the tables (everything
+ * that follows the mc_ring headers and utils/basic_algorithms.h) are pinned to the
+ * reference's own code by tests/test_oracle_vs_reference.py; the frame
+ * stages that follow semantic_dsp_map.h (weights, births, resampling) and the
+ * point-cloud generator are PARITY UNPINNED: the reference has no tests or
+ * golden vectors for them.  Every function cites the reference lines it
+ * follows (paths relative to the reference's include/).
  *
  * Where the reference relies on implementation-defined / undefined behaviour
  * or on un-vendored third-party arithmetic (Eigen, libstdc++), the choice made
@@ -900,6 +904,96 @@ struct oracle_map {
     }
   }
 
+  // operations.h:457-600 (calculateWeightAndSemanticsInVoxelConsiderNeighbors).  The frame does not call it
+  // (semantic_dsp_map.h:1244-1255 sweeps with determineIfVoxelOccupied); it is restated for the reference-harness
+  // comparison only.  The x and y neighbours are taken on RING indices and not wrapped, as there: indices 0 and 1
+  // have no smaller neighbour (0 - 1 wraps to 2^32 - 1, which passes `>= 1` and is then dropped by the voxel-count
+  // test of :488, and 1 - 1 = 0 fails `>= 1`), and N - 3 is the last index with a bigger neighbour (`< N - 1`, :494).
+  // PINNED: label / track are uninitialised locals of the caller when no contributor wins; (0, 0) here.
+  // The reference freezes threshold + 0.1f in a function-static at the first call (:580); one threshold per map here.
+  void fusionConsiderNeighbors(uint32_t voxel_index, float occ_threshold, float &weight_sum, float &guessed_weight,
+                               uint8_t &label_id, uint16_t &track_id) {
+    uint32_t rx, ry, rz;
+    voxelToRing(voxel_index, rx, ry, rz);
+    label_id = 0;
+    track_id = 0;
+    if (!isVoxelValid(voxel_index, rx, ry, rz)) {
+      weight_sum = -1.f;
+      guessed_weight = 0.f;
+      return;
+    }
+    std::map<uint16_t, float> track_id_weight_map;
+    std::map<uint16_t, uint8_t> track_id_label_map;
+    struct Nb { uint32_t v, x, y, z; };
+    std::vector<Nb> nb;
+    nb.push_back({voxel_index, rx, ry, rz});
+    auto consider = [&](uint32_t x, uint32_t y) {
+      uint32_t v = ringToVoxel(x, y, rz);
+      if (v < V && isVoxelValid(v, x, y, rz)) nb.push_back({v, x, y, rz});
+    };
+    const uint32_t xs = rx - 1, ys = ry - 1, xb = rx + 1, yb = ry + 1;
+    if (xs >= 1) consider(xs, ry);
+    if (xb < NX - 1) consider(xb, ry);
+    if (ys >= 1) consider(rx, ys);
+    if (yb < NY - 1) consider(rx, yb);
+    weight_sum = 0.f;
+    guessed_weight = 0.f;
+    std::vector<float> weight_sum_vec(nb.size(), 0.f);
+    for (size_t j = 0; j < nb.size(); ++j) {
+      uint32_t start = nb[j].v << cfg.p_n;
+      for (uint32_t i = 1; i < S; ++i) {
+        Particle &p = P[start + i];
+        if (isParticleVacant(p, nb[j].x, nb[j].y, nb[j].z)) continue;
+        if (p.status == GUESSED_BORN) {
+          guessed_weight += p.weight;
+        } else if (p.status == UPDATED && p.weight < C_PARTICLE_OCC_INIT_WEIGHT) {
+          p.status = INVALID;
+          continue;
+        } else {
+          if (p.weight > 1.f) p.weight = 1.f;
+          weight_sum_vec[j] += p.weight;
+        }
+        if (track_id_weight_map.find(p.track_id) == track_id_weight_map.end()) track_id_weight_map[p.track_id] = 0.f;
+        track_id_weight_map[p.track_id] += p.weight;
+        track_id_label_map[p.track_id] = (uint8_t)p.label_id;
+      }
+    }
+    int big_count = 0;
+    for (size_t j = 1; j < weight_sum_vec.size(); ++j)
+      if (weight_sum_vec[j] > occ_threshold) ++big_count;
+    if (weight_sum_vec[0] > occ_threshold) {
+      weight_sum = big_count == 0 ? 0.f : weight_sum_vec[0];
+    } else {
+      const float infered_voxel_weight = occ_threshold + 0.1f;
+      weight_sum = big_count >= 2 ? infered_voxel_weight : weight_sum_vec[0];
+    }
+    float max_weight = 0.f;
+    for (auto it = track_id_weight_map.begin(); it != track_id_weight_map.end(); ++it) {
+      if (it->second > max_weight) {
+        max_weight = it->second;
+        track_id = it->first;
+        label_id = track_id_label_map[it->first];
+      }
+    }
+  }
+
+  // operations.h:192-205
+  inline void addGuessedParticles(float x, float y, float z, uint8_t label, uint16_t track, uint32_t &voxel_index,
+                                  uint32_t &particle_index) {
+    Particle particle;
+    particle.status = GUESSED_BORN;
+    particle.time_stamp = (uint16_t)global_time_stamp;
+    particle.forget_count = 0;
+    particle.x = x;
+    particle.y = y;
+    particle.z = z;
+    particle.weight = C_PARTICLE_OCC_INIT_WEIGHT;
+    particle.label_id = label;
+    particle.track_id = track;
+    particle_index = addParticleByGlobalPos(particle, voxel_index);
+  }
+
+
   // ------------------------------------------------------------- frame
   float cam_R[9]{}, cam_p[3]{};
 
@@ -1275,6 +1369,22 @@ uint32_t oracle_add_particle(oracle_map *m, float x, float y, float z, uint8_t l
   uint32_t v, p;
   m->addNewParticleWithSemantics(x, y, z, label, track, v, p);
   return p;
+}
+uint32_t oracle_add_guessed_particle(oracle_map *m, float x, float y, float z, uint8_t label, uint16_t track) {
+  uint32_t v, p;
+  m->addGuessedParticles(x, y, z, label, track, v, p);
+  return p;
+}
+void oracle_fusion_neighbors(oracle_map *m, uint32_t voxel, float threshold, oracle_voxel_result *out, float *guessed) {
+  uint8_t label;
+  uint16_t track;
+  float wsum, g;
+  m->fusionConsiderNeighbors(voxel, threshold, wsum, g, label, track);
+  out->wsum = wsum;
+  out->track = track;
+  out->label = label;
+  out->occ = 0;
+  if (guessed) *guessed = g;
 }
 int32_t oracle_resample_voxel(oracle_map *m, uint32_t voxel) { return m->resampleParticlesInVoxel(voxel) ? 1 : 0; }
 void oracle_set_global_time_stamp(oracle_map *m, uint32_t t) { m->global_time_stamp = t; }

@@ -5,12 +5,17 @@
  * only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may
  * load this library, and only as the checker / the timed CPU baseline.
  *
- * PARITY UNPINNED: the reference ships no tests and no golden vectors for
- * this path and cannot be compiled in this image (needs
- * Eigen, OpenCV, PCL, ROS).  The oracle is a literal single-threaded
- * restatement of the reference's loops; it is pinned only by the analytic
- * known-answer tests in tests/test_oracle_kat.py that are derived from the
- * reference code (file:line cited on each function in cpu_ref.cpp).
+ * PARITY: the oracle is a literal single-threaded restatement of the
+ * reference's loops.  Its ring layer (ego shift, index math, slot choice,
+ * moves, removal, visibility BFS, frustum test, occupancy fusion) and its
+ * tables are pinned to the reference's own mc_ring headers, compiled over
+ * oracle/ref_shims/ and driven by oracle/ref_harness.cpp
+ * (tests/test_oracle_vs_reference.py).  What restates
+ * SemanticDSPMap::subObjectLevelUpdate itself (weights, births, resampling),
+ * generateLabeledPointCloud and object_layer.h is UNPINNED - the reference
+ * ships no tests for it and it does not compile without PCL / OpenCV - and
+ * rests on the analytic known-answer tests in tests/test_oracle_kat.py
+ * (file:line cited on each function in cpu_ref.cpp).
  */
 #pragma once
 #include <stdint.h>
@@ -177,6 +182,10 @@ int32_t oracle_point_in_frustum(oracle_map *m, float x, float y, float z); /* op
 float oracle_query_pdf(oracle_map *m, float x, float mu, float sigma);
 float oracle_forgetting_factor(oracle_map *m, int32_t forget_count);
 uint32_t oracle_add_particle(oracle_map *m, float x, float y, float z, uint8_t label, uint16_t track);
+uint32_t oracle_add_guessed_particle(oracle_map *m, float x, float y, float z, uint8_t label, uint16_t track); /* operations.h:192-205 */
+/* calculateWeightAndSemanticsInVoxelConsiderNeighbors (operations.h:457-600), which the frame does not call: wsum, label
+ * and track of `out` (occ is left 0) and the guessed weight. */
+void oracle_fusion_neighbors(oracle_map *m, uint32_t voxel, float threshold, oracle_voxel_result *out, float *guessed);
 int32_t oracle_resample_voxel(oracle_map *m, uint32_t voxel);
 void oracle_set_global_time_stamp(oracle_map *m, uint32_t t);
 

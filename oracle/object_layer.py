@@ -10,8 +10,8 @@ Follows the reference class by class with numpy standing in for Eigen (np.linalg
   ObjectLayer.update               include/semantic_dsp_map.h:304-566  (objectLevelUpdate)
   ObjectLayer.collect              include/semantic_dsp_map.h:588-736  (object loop of the prediction step)
 
-Parity unpinned: the reference cannot be built here (Eigen/OpenCV/PCL are not in the image) and ships no tests or golden
-vectors for this code; its RANSAC draws from an unseeded std::mt19937, so it has no reproducible output to pin against
+Parity unpinned: object_layer.h needs more of Eigen than the stand-in headers of oracle/ref_shims/ give (they cover the
+ring buffer, which tests/test_oracle_vs_reference.py pins) and the reference ships no tests or golden vectors for this code; its RANSAC draws from an unseeded std::mt19937, so it has no reproducible output to pin against
 either.  The sampler below (splitmix64) is this project's and is the one the product (csrc/objects.cpp) uses.
 """
 import math

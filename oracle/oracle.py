@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY: importable from tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg — never from the product package.
-PARITY UNPINNED (see cpu_ref.h).
+What is pinned to the reference's own code and what is not: see cpu_ref.h.
 
 The shared library is compiled on demand with -march=native; one build per
 host CPU (keyed by the cpuinfo flags) so that a library built in the CPU
@@ -129,6 +129,9 @@ def lib():
         L.oracle_forgetting_factor.argtypes = [vp, C.c_int32]
         L.oracle_add_particle.restype = C.c_uint32
         L.oracle_add_particle.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_uint8, C.c_uint16]
+        L.oracle_add_guessed_particle.restype = C.c_uint32
+        L.oracle_add_guessed_particle.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_uint8, C.c_uint16]
+        L.oracle_fusion_neighbors.argtypes = [vp, C.c_uint32, C.c_float, vp, vp]
         L.oracle_resample_voxel.restype = C.c_int32
         L.oracle_resample_voxel.argtypes = [vp, C.c_uint32]
         L.oracle_set_global_time_stamp.argtypes = [vp, C.c_uint32]
@@ -343,6 +346,16 @@ class OracleMap:
 
     def add_particle(self, x, y, z, label=0, track=65535):
         return int(self.L.oracle_add_particle(self.h, x, y, z, label, track))
+
+    def add_guessed_particle(self, x, y, z, label=0, track=65535):
+        return int(self.L.oracle_add_guessed_particle(self.h, x, y, z, label, track))
+
+    def fusion_neighbors(self, v, threshold):
+        """(wsum, guessed weight, label, track) of calculateWeightAndSemanticsInVoxelConsiderNeighbors"""
+        out = np.zeros(1, VOXEL_RESULT)
+        g = np.zeros(1, np.float32)
+        self.L.oracle_fusion_neighbors(self.h, int(v), float(threshold), _ptr(out), _ptr(g))
+        return np.float32(out["wsum"][0]), np.float32(g[0]), int(out["label"][0]), int(out["track"][0])
 
     def resample_voxel(self, v):
         return int(self.L.oracle_resample_voxel(self.h, v))

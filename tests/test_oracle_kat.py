@@ -1,5 +1,7 @@
-"""Known-answer tests of the CPU oracle (SURVEY.md §8c list), CPU only.  The oracle is "parity unpinned" by the
-reference (it ships no tests); these analytic cases, each derived from the cited reference lines, are what pins it."""
+"""Known-answer tests of the CPU oracle (SURVEY.md §8c list), CPU only.  The reference ships no tests.  The oracle's ring
+layer and tables are held to the reference's own compiled code by tests/test_oracle_vs_reference.py; for what restates
+SemanticDSPMap::subObjectLevelUpdate itself (weights, births, resampling) these analytic cases, each derived from the
+cited reference lines, are what pins it."""
 import numpy as np
 import pytest
 
