@@ -867,6 +867,100 @@ sdm_status sdm_query_forecast(sdm_map *m, const float *xyzt, int64_t n, sdm_fore
  * SDM_FORECAST_VACATED_BLOCKS.  Device mode: out must be aligned to 16 bytes (an item is stored whole), seg to 4. */
 sdm_status sdm_query_forecast_segments(sdm_map *m, const float *seg, int64_t n, sdm_forecast_hit *out, uint32_t flags);
 
+/* ---- ground layer: where is the surface I stand on, which columns can I not enter, does my body fit here? ----
+ * sdm_ground_update enqueues, on the map's stream, a 2-D view of the last frame enqueued before the call - a height map, a
+ * costmap and its distance transform - and returns without waiting.  Like the other layers the result is a snapshot: it
+ * keeps that frame's map center and ring offsets and answers for it until the next sdm_ground_update, whatever frames,
+ * sdm_clear, sdm_load_state or sdm_set_ring_state come in between; nothing of the map's state is modified and no scratch
+ * of the frames' or of another layer is used.  Everything is integer and bitwise reproducible; all options are in cells.
+ * Up axis: up_axis a in {0, 1, 2}, up_sign +1 or -1 (a camera-style frame with the ground at +y is (1, -1); z-up poses are
+ * (2, +1)).  The height of map-index cell idx_a is h = idx_a for sign +1 and N_a - 1 - idx_a for sign -1.
+ * Columns: the other two axes in ascending order are u and v; the grid is N_u x N_v, column word col = i_u + j_v * N_u.
+ * A column is the N_a cells over one grid cell.  The ring's wrap point is no neighbour relation; the grid is a block.
+ * Cell classes, from the second word of the result (track, label, occ):
+ *   solid     occ >= 1 (guessed-occupied counts); with SDM_GROUND_IGNORE_MOVABLE an occ >= 1 cell whose track is movable
+ *             (1 <= track <= max_movable_track) is not solid and is passable instead.
+ *   passable  occ == 0; with SDM_GROUND_UNKNOWN_PASSABLE also occ == -1.  A height outside the map (h >= N_a) is passable.
+ *   support at h: the cell is solid, its track is not movable, bit `label` of support_labels is set (bit l of word l / 32),
+ *             and the cells h + 1 .. h + clearance of the column are all passable.  Those are read as they are, also
+ *             above h_hi: the band limits where supports are looked for, not the headroom test.
+ * Per column (sdm_ground_cell): level = the highest support h in [h_lo, h_hi], 0xffff if none; top = the highest solid h
+ * in the band, 0xffff if none; label = the level cell's label, 0 if none; headroom = the consecutive passable cells
+ * directly above level up to the map's top, saturating at 255, 0 if no level; n_unknown = the occ == -1 cells in the band,
+ * saturating at 255.
+ * Class byte cls = class | step << 2 | lethal << 3.  class: 1 ground (a level), 2 obstacle (no level, a top), 0 none.
+ * step: the column P has a level and some 4-neighbour Q inside the grid has one with level(P) > level(Q) + max_step - only
+ * the higher side is marked: one can drive up to a kerb.  lethal: class 2, or step, or with SDM_GROUND_NONE_IS_LETHAL class 0.
+ * Distance: d2[col], uint32, the exact squared Euclidean distance in columns to the nearest lethal column; 0 on one,
+ * 0xffffffff everywhere when there is none.
+ * sdm_query_ground: the point's cell is floor(u) per axis, as for the distance query.  Outside the map or non-finite:
+ * col 0xffffffff, d2 0xffffffff, surface 0, above INT32_MIN, cell {0xffff, 0xffff, 0, 0, 0, 0}, dist -1, status 3.
+ * sdm_query_footprints: a footprint is a rectangle on the grid's plane: its centre in global metres along u and v, its
+ * heading as a unit vector (dir_u, dir_v) the caller supplies - neither side takes a sine -, half its length along the
+ * heading and half its width.  Column (i, j) is covered when, in float32 without contraction,
+ *   pu = origin[u] + ((float)i + 0.5f) * voxel_size, pv likewise; du = pu - center_u, dv = pv - center_v;
+ *   |du * dir_u + dv * dir_v| <= half_len  and  |dv * dir_u - du * dir_v| <= half_wid.
+ * The answer is as if every column of the grid were tested; nothing outside the grid is counted.  A non-finite field, or
+ * half_len + half_wid > 64 * voxel_size (float32), gives the answer of a footprint that covers nothing: the counts 0,
+ * level_min = level_max = 0xffff, min_d2 = first_lethal = 0xffffffff.
+ * Both queries answer for the last build and take SDM_QUERY_ON_DEVICE as the other queries do (device pointers, enqueued,
+ * no wait; items are 4-byte aligned); host mode goes through the queries' staging area.
+ * Memory: 14 B per column (8 B cell, 4 B d2, 2 B of the distance transform's row pass) for the largest of the three
+ * grids, 917 KB at 256^2, and 32 B of counters per row of the grid; allocated at the first sdm_ground_update, freed by
+ * sdm_destroy.
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map or NULL options, unknown flag bits, up_axis not in 0..2, up_sign not
+ * +1 / -1, a band that is not 0 <= h_lo <= h_hi < N_a, clearance > 255, max_step > 65535, a Z-slab shard (shard_count > 1),
+ * a NULL input or output or a negative count of a query, and the getter or a query before any sdm_ground_update. */
+#define SDM_GROUND_UNKNOWN_PASSABLE 0x1u /* occ == -1 cells are passable */
+#define SDM_GROUND_IGNORE_MOVABLE   0x2u /* occ >= 1 cells of a movable track are passable, not solid */
+#define SDM_GROUND_NONE_IS_LETHAL   0x4u /* columns of class 0 are lethal */
+typedef struct {              /* 60 bytes */
+  int32_t up_axis, up_sign;
+  int32_t h_lo, h_hi;         /* the band, heights in cells */
+  uint32_t clearance;         /* 0..255 cells */
+  uint32_t max_step;          /* 0..65535 cells */
+  uint32_t support_labels[8]; /* bit l of the 256: label l may carry the robot */
+  uint32_t flags;
+} sdm_ground_options;
+typedef struct {       /* 8 bytes */
+  uint16_t level, top; /* heights; 0xffff = none */
+  uint8_t label;
+  uint8_t cls;         /* class | step << 2 | lethal << 3 */
+  uint8_t headroom, n_unknown;
+} sdm_ground_cell;
+typedef struct {       /* 104 bytes */
+  uint32_t n_u, n_v, axis_u, axis_v;
+  uint32_t n_ground, n_obstacle, n_none, n_step, n_lethal; /* columns */
+  uint32_t level_min, level_max;                           /* over the ground columns; 0xffff if there is none */
+  sdm_ground_options options;                              /* the build's, echoed */
+} sdm_ground_info;
+typedef struct {        /* 32 bytes */
+  uint32_t col;         /* the point's column word; 0xffffffff outside the map / non-finite */
+  uint32_t d2;
+  float surface;        /* global coordinate along the up axis of the level cell's upper face: origin[a] + (float)k * voxel_size,
+                           k = idx_a + 1 for sign +1, idx_a for sign -1; float32, no contraction; 0 where there is no level */
+  int32_t above;        /* h(point) - level; INT32_MIN where there is no level */
+  sdm_ground_cell cell;
+  float dist;           /* sqrtf((float)d2) * voxel_size, as the distance field's D; -1 when d2 is 0xffffffff */
+  uint32_t status;      /* 0 inside, 3 outside / non-finite */
+} sdm_ground_result;
+typedef struct {        /* 24 bytes */
+  float center_u, center_v, dir_u, dir_v, half_len, half_wid;
+} sdm_footprint;
+typedef struct {        /* 32 bytes */
+  uint32_t n_cols, n_lethal, n_none, n_ground; /* covered columns: all, lethal, of class 0, of class 1 */
+  uint16_t level_min, level_max;               /* over the covered ground columns; 0xffff if none */
+  uint32_t min_d2;                             /* over the covered columns; 0xffffffff if none (or no lethal column at all) */
+  uint32_t first_lethal;                       /* the smallest covered lethal column word; 0xffffffff if none */
+  uint32_t pad;                                /* 0 */
+} sdm_footprint_result;
+sdm_status sdm_ground_update(sdm_map *m, const sdm_ground_options *options);
+/* Waits; cells and d2 in column-word order (N_u * N_v items each); any of the four pointers may be NULL (origin: the
+ * global position of the min corner of cell (0,0,0) of the snapshot). */
+sdm_status sdm_get_ground(sdm_map *m, sdm_ground_cell *cells, uint32_t *d2, sdm_ground_info *info, float origin[3]);
+sdm_status sdm_query_ground(sdm_map *m, const float *xyz, int64_t n, sdm_ground_result *out, uint32_t flags);
+sdm_status sdm_query_footprints(sdm_map *m, const sdm_footprint *fp, int64_t n, sdm_footprint_result *out, uint32_t flags);
+
 /* ---- owner sets of the object layer: ObjectParticleHashMap (object_layer.h:20-52) */
 sdm_status sdm_object_particle_count(sdm_map *m, int32_t track_id, int64_t *count);
 /* The keys of ObjectParticleHashMap::indices_map whose sets are not empty: every track id that owns at least one slot of

@@ -584,6 +584,41 @@ class SemanticDSPMap {
     if (!check(sdm_query_forecast_segments(map_, seg.data(), (int64_t)n, out.data(), flags), "sdm_query_forecast_segments")) out.clear();
     return out.size();
   }
+  /// Where can a ground robot stand (sdm.h, "ground layer")?  Builds the height map, the costmap and its distance
+  /// transform over the results of the last update() under `options` (all in cells: the up axis and its sign, the band,
+  /// the clearance, the largest step, the labels that carry the robot, flags) and copies them out: one cell and one
+  /// squared distance per column, column word i_u + j_v * n_u.  info (may be null): the grid, the counts and the options
+  /// echoed.  The call waits.  Returns the number of columns; 0 (and empty vectors) before the first update() or when a
+  /// call fails.
+  size_t ground(const sdm_ground_options &options, std::vector<sdm_ground_cell> &cells_out, std::vector<uint32_t> &d2_out,
+                sdm_ground_info *info = nullptr) {
+    cells_out.clear();
+    d2_out.clear();
+    if (!map_) return 0;
+    sdm_ground_info gi;
+    if (!check(sdm_ground_update(map_, &options), "sdm_ground_update")) return 0;
+    if (!check(sdm_get_ground(map_, nullptr, nullptr, &gi, nullptr), "sdm_get_ground")) return 0;
+    cells_out.resize((size_t)gi.n_u * gi.n_v);
+    d2_out.resize(cells_out.size());
+    if (!check(sdm_get_ground(map_, cells_out.data(), d2_out.data(), nullptr, nullptr), "sdm_get_ground")) {
+      cells_out.clear();
+      d2_out.clear();
+      return 0;
+    }
+    if (info) *info = gi;
+    return cells_out.size();
+  }
+  /// Does the robot's body fit there?  Every footprint - a rectangle on the ground layer's plane: centre, heading as a unit
+  /// vector, half length, half width - against the layer ground() built last: the columns it covers, how many of them are
+  /// lethal, unknown ground or ground, the levels under it and the distance to the nearest lethal column.  Waits.  Returns
+  /// the number of footprints answered; 0 (and an empty vector) before the first ground() or when the call fails.
+  size_t checkFootprints(const std::vector<sdm_footprint> &footprints, std::vector<sdm_footprint_result> &out) {
+    out.clear();
+    if (!map_ || footprints.empty()) return 0;
+    out.resize(footprints.size());
+    if (!check(sdm_query_footprints(map_, footprints.data(), (int64_t)footprints.size(), out.data(), 0u), "sdm_query_footprints")) out.clear();
+    return out.size();
+  }
   /// the ray table scoreViews uses at `stride`: three floats per ray
   const std::vector<float> &viewRays(int stride) {
     if (stride != view_rays_stride_ || view_rays_.empty()) {

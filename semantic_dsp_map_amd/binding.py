@@ -76,6 +76,25 @@ FORECAST_VACATED_BLOCKS = 0x4
 FORECAST_MAX_HORIZONS = 16
 FORECAST_MAX_STAMPS = 65536
 FORECAST_NOTHING = 0xFFFFFFFF
+# the ground layer (sdm.h: sdm_ground_update / sdm_get_ground / sdm_query_ground / sdm_query_footprints)
+GROUND_OPTIONS = np.dtype([("up_axis", "<i4"), ("up_sign", "<i4"), ("h_lo", "<i4"), ("h_hi", "<i4"), ("clearance", "<u4"),
+                           ("max_step", "<u4"), ("support_labels", "<u4", (8,)), ("flags", "<u4")])
+GROUND_CELL = np.dtype([("level", "<u2"), ("top", "<u2"), ("label", "u1"), ("cls", "u1"), ("headroom", "u1"), ("n_unknown", "u1")])
+GROUND_INFO = np.dtype([("n_u", "<u4"), ("n_v", "<u4"), ("axis_u", "<u4"), ("axis_v", "<u4"), ("n_ground", "<u4"), ("n_obstacle", "<u4"),
+                        ("n_none", "<u4"), ("n_step", "<u4"), ("n_lethal", "<u4"), ("level_min", "<u4"), ("level_max", "<u4"),
+                        ("options", GROUND_OPTIONS)])
+GROUND_RESULT = np.dtype([("col", "<u4"), ("d2", "<u4"), ("surface", "<f4"), ("above", "<i4"), ("cell", GROUND_CELL), ("dist", "<f4"),
+                          ("status", "<u4")])
+FOOTPRINT = np.dtype([("center_u", "<f4"), ("center_v", "<f4"), ("dir_u", "<f4"), ("dir_v", "<f4"), ("half_len", "<f4"), ("half_wid", "<f4")])
+FOOTPRINT_RESULT = np.dtype([("n_cols", "<u4"), ("n_lethal", "<u4"), ("n_none", "<u4"), ("n_ground", "<u4"), ("level_min", "<u2"),
+                             ("level_max", "<u2"), ("min_d2", "<u4"), ("first_lethal", "<u4"), ("pad", "<u4")])
+assert GROUND_OPTIONS.itemsize == 60 and GROUND_CELL.itemsize == 8 and GROUND_INFO.itemsize == 104 and GROUND_RESULT.itemsize == 32
+assert FOOTPRINT.itemsize == 24 and FOOTPRINT_RESULT.itemsize == 32
+GROUND_UNKNOWN_PASSABLE = 0x1
+GROUND_IGNORE_MOVABLE = 0x2
+GROUND_NONE_IS_LETHAL = 0x4
+GROUND_NO_LEVEL = 0xFFFF
+GROUND_MAX_FOOTPRINT_CELLS = 64   # half_len + half_wid of a footprint, in voxels
 
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
@@ -88,6 +107,29 @@ NO_INSTANCES = 0x4     # sdm_update_raw: ignore the object masks (g_consider_ins
 
 STATUS_NAMES = {0: "SDM_OK", 1: "SDM_ERR_INVALID_ARGUMENT", 2: "SDM_ERR_NO_DEVICE", 3: "SDM_ERR_HIP",
                 4: "SDM_ERR_CAPACITY", 5: "SDM_ERR_NOT_CONVERGED", 6: "SDM_ERR_COMM"}
+
+
+def label_mask(labels):
+    """the 256-bit label mask of sdm_ground_options::support_labels: bit l of word l // 32 for every label id given"""
+    m = np.zeros(8, np.uint32)
+    for l in ([] if labels is None else labels):
+        if not 0 <= int(l) <= 255:
+            raise ValueError("label %r is not in 0..255" % (l,))
+        m[int(l) >> 5] |= np.uint32(1 << (int(l) & 31))
+    return m
+
+
+def ground_band(cfg, origin, up, lo_m, hi_m):
+    """the ground layer's band from metres: global coordinates lo_m <= hi_m along the up axis -> (h_lo, h_hi), the heights
+    of the cells that hold them, clamped to the map.  cfg: the map's configuration (dict); origin: the global position of
+    the min corner of cell (0, 0, 0) (ground()'s, or map centre + pmin); up: (axis, sign).  Host arithmetic in float64."""
+    axis, sign = int(up[0]), int(up[1])
+    if axis not in (0, 1, 2) or sign not in (1, -1) or not lo_m <= hi_m:
+        raise ValueError("up must be (0..2, +1 / -1) and lo_m <= hi_m")
+    n = 1 << int(cfg[("x_n", "y_n", "z_n")[axis]])
+    idx = [int(np.clip(np.floor((float(m) - float(origin[axis])) / float(cfg["voxel_size"])), 0, n - 1)) for m in (lo_m, hi_m)]
+    h = idx if sign > 0 else [n - 1 - i for i in idx]
+    return min(h), max(h)
 
 
 class Config(C.Structure):
@@ -229,6 +271,10 @@ def load_library():
         "sdm_query_reach": [vp, vp, vp, i64, vp, u32],
         "sdm_reach_paths": [vp, vp, vp, i64, i32, vp, vp, u32],
         "sdm_debug_reach_tiles": [vp, C.POINTER(i64)],
+        "sdm_ground_update": [vp, vp],
+        "sdm_get_ground": [vp, vp, vp, vp, vp],
+        "sdm_query_ground": [vp, vp, i64, vp, u32],
+        "sdm_query_footprints": [vp, vp, i64, vp, u32],
         "sdm_forecast_stamps": [C.c_float, vp, i32, vp, i32, u32, vp, i64, C.POINTER(i64)],
         "sdm_forecast_update": [vp, vp, i32, vp, i32, u32],
         "sdm_get_forecast": [vp, vp, vp, vp, vp],
@@ -794,6 +840,52 @@ class SdmMap:
         sg = np.ascontiguousarray(seg, dtype=np.float32).reshape(-1, 8)
         res = np.empty(len(sg), FORECAST_HIT)
         _check(self.L, self.L.sdm_query_forecast_segments(self.h, _ptr(sg), len(sg), _ptr(res), fl), "sdm_query_forecast_segments")
+        return res
+
+    # ---- the ground layer (sdm.h).  ground_update enqueues a build on the map's stream from the last frame's results;
+    # ground(), query_ground() and query_footprints() answer for that frame until the next build.
+    def ground_update(self, up=(1, -1), h_lo=0, h_hi=0, clearance=0, max_step=0, support_labels=None, unknown_passable=False,
+                      ignore_movable=False, none_is_lethal=False):
+        """up: (axis, sign); h_lo, h_hi, clearance, max_step in cells (ground_band gives a band from metres);
+        support_labels: the label ids that may carry the robot (None: none)"""
+        o = np.zeros(1, GROUND_OPTIONS)
+        o["up_axis"], o["up_sign"], o["h_lo"], o["h_hi"], o["clearance"], o["max_step"] = up[0], up[1], h_lo, h_hi, clearance, max_step
+        o["support_labels"] = label_mask(support_labels)
+        o["flags"] = ((GROUND_UNKNOWN_PASSABLE if unknown_passable else 0) | (GROUND_IGNORE_MOVABLE if ignore_movable else 0) |
+                      (GROUND_NONE_IS_LETHAL if none_is_lethal else 0))
+        _check(self.L, self.L.sdm_ground_update(self.h, _ptr(o)), "sdm_ground_update")
+
+    def ground(self):
+        """-> (cells, d2, info, origin): GROUND_CELL and uint32 arrays shaped [N_v, N_u] (column word = i_u + j_v * N_u), a
+        GROUND_INFO record, origin the global position of the min corner of cell (0, 0, 0) of the snapshot (float32[3])"""
+        info, origin = np.zeros(1, GROUND_INFO), np.empty(3, np.float32)
+        _check(self.L, self.L.sdm_get_ground(self.h, None, None, _ptr(info), _ptr(origin)), "sdm_get_ground")
+        shape = (int(info["n_v"][0]), int(info["n_u"][0]))
+        cells, d2 = np.empty(shape, GROUND_CELL), np.empty(shape, np.uint32)
+        _check(self.L, self.L.sdm_get_ground(self.h, _ptr(cells), _ptr(d2), None, None), "sdm_get_ground")
+        return cells, d2, info[0], origin
+
+    def query_ground(self, xyz, on_device=False, n=None, out=None):
+        """xyz: (n, 3) global positions -> GROUND_RESULT per point.  on_device: xyz and out (n GROUND_RESULT) are device
+        pointers, as for query_points."""
+        if on_device:
+            _check(self.L, self.L.sdm_query_ground(self.h, _ptr(int(xyz)), int(n), _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_ground")
+            return None
+        p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        res = np.empty(len(p), GROUND_RESULT)
+        _check(self.L, self.L.sdm_query_ground(self.h, _ptr(p), len(p), _ptr(res), 0), "sdm_query_ground")
+        return res
+
+    def query_footprints(self, footprints, on_device=False, n=None, out=None):
+        """footprints: FOOTPRINT records -> FOOTPRINT_RESULT per footprint.  on_device: footprints and out (n
+        FOOTPRINT_RESULT) are device pointers."""
+        if on_device:
+            _check(self.L, self.L.sdm_query_footprints(self.h, _ptr(int(footprints)), int(n), _ptr(int(out)), QUERY_ON_DEVICE),
+                   "sdm_query_footprints")
+            return None
+        fp = np.ascontiguousarray(footprints, dtype=FOOTPRINT).reshape(-1)
+        res = np.empty(len(fp), FOOTPRINT_RESULT)
+        _check(self.L, self.L.sdm_query_footprints(self.h, _ptr(fp), len(fp), _ptr(res), 0), "sdm_query_footprints")
         return res
 
     def occupied(self, cap=None, zero_center=False, free=False, mark_fov=False):

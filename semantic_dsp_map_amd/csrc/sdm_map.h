@@ -108,6 +108,16 @@ struct ForecastLayer : Derived {
   uint32_t n_motions = 0, n_horizons = 0, n_stamps = 0;
 };
 
+// the ground layer (ground.hip): a cell, a squared distance and the distance transform's row distance per column of the
+// grid, laid out for the largest of the three grids; the build's counters, eight words per row of the grid; the build's
+// options (its flags are Derived's)
+struct GroundLayer : Derived {
+  sdm_ground_cell *cells = nullptr;
+  uint32_t *d2 = nullptr, *meta = nullptr;
+  uint16_t *rowd = nullptr;
+  sdm_ground_options opt{};
+};
+
 struct sdm_map {
   sdm_config cfg{};
   sdm_params prm{};
@@ -267,6 +277,7 @@ struct sdm_map {
   ViewPool views;
   ReachLayer reach;
   ForecastLayer forecast;
+  GroundLayer ground;
   sdm_point_xyzrgb *d_points_rgb = nullptr;
   size_t points_rgb_cap = 0;
   ColourTables *d_colours = nullptr;
