@@ -262,7 +262,12 @@ sdm_status sdm_update_raw(sdm_map *m, const float *depth, const uint8_t *static_
  *  - ZED2 (SETTING 3): pixels whose track id is sky_instance are invalid (:236-242); object_bbox (n_objects x 6
  *    doubles: min x, max x, min y, max y, min z, max z of the object's current key points +- 1 m, global frame,
  *    :174-196) turns points of a movable instance that lie outside their object's box into Background (:254-272).
- *    sky_instance < 0 / object_bbox NULL: off. */
+ *    An id below max_movable_track that no object carries - it can only come out of label_to_static_instance - has
+ *    the all-zero box, as in the reference, also in a frame without objects: hand a non-NULL object_bbox with
+ *    n_objects == 0 to keep the filter on there (it is not read).
+ *    sky_instance < 0 / object_bbox NULL: off.
+ * The label of a pixel with a movable id (<= max_movable_track) is the label_id of the LAST object with that track_id,
+ * whether or not that object's mask covers the pixel (track_to_label_id_map, :168, :281); 0 if no object has the id. */
 typedef struct {
   int32_t src_width, src_height;
   float rescale;

@@ -757,7 +757,8 @@ class SemanticDSPMap {
       const int sky_label = label_id_["Sky"];
       if (sky_label >= 0 && sky_label < 256) opt.sky_instance = label_to_inst_[sky_label];
     }
-    opt.object_bbox = preset_.zed2_filters && !boxes_.empty() ? boxes_.data() : nullptr;
+    static const double no_boxes[6] = {0, 0, 0, 0, 0, 0};  // (a frame without objects keeps the filter on, :254-272)
+    opt.object_bbox = preset_.zed2_filters ? (boxes_.empty() ? no_boxes : boxes_.data()) : nullptr;
     if (!check(sdm_update_raw_ex(map_, depth_.data(), have_static_ ? static_mask_.data() : nullptr, label_to_inst_,
                                  objects_.empty() ? nullptr : objects_.data(), (int32_t)objects_.size(), cam_pos_d, cam_q_d,
                                  moves.empty() ? nullptr : moves.data(), (int32_t)moves.size(),

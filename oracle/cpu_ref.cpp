@@ -1286,18 +1286,13 @@ void oracle_generate_cloud_ex(oracle_map *m, const float *depth_in, const uint8_
       }
       uint32_t inst = 65535u;
       int label = 0;
-      bool from_object = false;
       if (static_mask) {
         uint32_t pixel_label = (uint32_t)static_mask[p] + 1u;  // :137-138
         inst = label_to_inst[pixel_label > 255u ? 255u : pixel_label];
       }
       if (consider_instance)
         for (int k = 0; k < n_objects; ++k)
-          if (obj_masks[(size_t)k * hw + p] > 0) {  // :196-207
-            inst = (uint32_t)obj_track[k];
-            label = obj_label[k];
-            from_object = true;
-          }
+          if (obj_masks[(size_t)k * hw + p] > 0) inst = (uint32_t)obj_track[k];  // :196-207
       if (sky_instance >= 0 && inst == (uint32_t)sky_instance) {  // :236-242
         out[p] = invalid;
         continue;
@@ -1334,8 +1329,12 @@ void oracle_generate_cloud_ex(oracle_map *m, const float *depth_in, const uint8_
               label = l;
               break;
             }
-      } else if (!from_object) {
-        label = 0;
+      } else if (consider_instance) {
+        // :168, :281 track_to_label_id_map[instance]: the label of the LAST entry with that track id, whether or not its
+        // mask covers this pixel or anything at all; 0 (the map's default) for an id no entry has - also for a movable
+        // id that came out of the static mask's table
+        for (int k = 0; k < n_objects; ++k)
+          if ((uint32_t)obj_track[k] == inst) label = obj_label[k];
       }
       o.x = (float)gx;  // :298-300
       o.y = (float)gy;

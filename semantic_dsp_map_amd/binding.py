@@ -428,16 +428,24 @@ class SdmMap:
             self.synchronize()
 
     def update_raw(self, depth, static_mask, label_to_inst, objects, cam_pos, cam_q, moves=None, remove_tracks=None,
-                   stop_after="all", flags=0, sync=False, src_size=None, rescale=1.0, sky_instance=-1, object_bbox=None):
-        """SURVEY row N1 on the device.  objects: list of (track_id, label_id, mask HxW uint8); pose in double."""
-        depth = np.ascontiguousarray(depth, dtype=np.float32)
-        sm = None if static_mask is None else np.ascontiguousarray(static_mask, dtype=np.uint8)
+                   stop_after="all", flags=0, sync=False, src_size=None, rescale=1.0, sky_instance=-1, object_bbox=None,
+                   on_device=False):
+        """SURVEY row N1 on the device.  objects: list of (track_id, label_id, mask HxW uint8); pose in double.
+        on_device: depth, static_mask and every object's mask are device pointers (device_put) instead of arrays."""
         tab = np.ascontiguousarray(label_to_inst, dtype=np.uint16)
         assert tab.size == 256
-        masks = [np.ascontiguousarray(o[2], dtype=np.uint8) for o in objects]
         arr = (InstanceMask * max(len(objects), 1))()
+        if on_device:
+            flags |= INPUT_ON_DEVICE
+            depth = int(depth)
+            sm = None if static_mask is None else int(static_mask)
+            masks = [int(o[2]) for o in objects]
+        else:
+            depth = np.ascontiguousarray(depth, dtype=np.float32)
+            sm = None if static_mask is None else np.ascontiguousarray(static_mask, dtype=np.uint8)
+            masks = [np.ascontiguousarray(o[2], dtype=np.uint8) for o in objects]
         for k, o in enumerate(objects):
-            arr[k].track_id, arr[k].label_id, arr[k].mask = int(o[0]), int(o[1]), masks[k].ctypes.data
+            arr[k].track_id, arr[k].label_id, arr[k].mask = int(o[0]), int(o[1]), masks[k] if on_device else masks[k].ctypes.data
         pos = np.ascontiguousarray(cam_pos, dtype=np.float64)
         q = np.ascontiguousarray(cam_q, dtype=np.float64)
         mv = np.ascontiguousarray(moves if moves is not None else np.zeros(0, OBJECT_MOVE), dtype=OBJECT_MOVE)

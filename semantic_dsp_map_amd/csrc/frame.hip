@@ -774,8 +774,10 @@ sdm_status sdm_update_raw_ex(sdm_map *m, const float *depth, const uint8_t *stat
       if ((rc = stage_in(objects[k].mask, in.obj_masks + hw * k, 1)) != SDM_OK) return rc;
   }
   a.sky_instance = opt ? opt->sky_instance : -1;
-  a.has_bbox = opt && opt->object_bbox && n_objects > 0 ? 1 : 0;
-  if (a.has_bbox) HIP_TRY(hipMemcpyAsync(in.bbox, opt->object_bbox, sizeof(double) * 6 * n_objects, hipMemcpyHostToDevice, sc_));
+  // (a frame without objects keeps the filter: a movable id out of the static table has the all-zero box there too)
+  a.has_bbox = opt && opt->object_bbox ? 1 : 0;
+  if (a.has_bbox && n_objects > 0)
+    HIP_TRY(hipMemcpyAsync(in.bbox, opt->object_bbox, sizeof(double) * 6 * n_objects, hipMemcpyHostToDevice, sc_));
   HIP_TRY(hipEventRecord(m->ev_copy, sc_));
   HIP_TRY(hipStreamWaitEvent(s, m->ev_copy, 0));
   // Eigen's Quaternion::toRotationMatrix in double (pointcloud_tools.h:107-110)

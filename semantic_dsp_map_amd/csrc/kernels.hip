@@ -3365,15 +3365,10 @@ __global__ __launch_bounds__(TPB) void k_labeled_cloud(Dims d, CloudArgs a, cons
   // track id image: static mask first (:121-156), then every movable object's mask in order (:163-213)
   uint32_t inst = 65535u;
   int label = 0;
-  bool from_object = false;
   if (a.has_static) inst = label_to_inst[(uint32_t)static_mask[p] + 1u > 255u ? 255u : (uint32_t)static_mask[p] + 1u];
   if (a.consider_instance)
     for (int k = 0; k < a.n_objects; ++k)
-      if (obj_masks[(size_t)k * hw + p] > 0) {
-        inst = (uint32_t)a.track[k];
-        label = a.label[k];
-        from_object = true;
-      }
+      if (obj_masks[(size_t)k * hw + p] > 0) inst = (uint32_t)a.track[k];
   if (a.sky_instance >= 0 && inst == (uint32_t)a.sky_instance) {  // ZED2: sky pixels are invalid (:236-242)
     o.x = o.y = o.z = 0.f;
     o.sigma = a.consider_depth_noise ? a.sigma0 : 0.1f;
@@ -3415,8 +3410,11 @@ __global__ __launch_bounds__(TPB) void k_labeled_cloud(Dims d, CloudArgs a, cons
           label = l;
           break;
         }
-  } else if (!from_object) {
-    label = 0;  // movable id that came out of the static mask table: track_to_label_id_map default (:282)
+  } else if (a.consider_instance) {
+    // track_to_label_id_map[instance] (:168, :281): the label of the LAST object with that track id, whether or not
+    // its mask covers this pixel; 0, the map's default, for an id no object has (a movable id out of the static table)
+    for (int k = 0; k < a.n_objects; ++k)
+      if ((uint32_t)a.track[k] == inst) label = a.label[k];
   }
   o.x = (float)gx;
   o.y = (float)gy;

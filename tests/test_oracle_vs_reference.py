@@ -6,8 +6,8 @@ text it answered.  Here the oracle runs the same scenarios through update(stop_a
 set_stamps and its known-answer helpers, with bin_order=0 (the literal BFS order), and is compared with those answers:
 integers exactly, the floats of exact scenarios bit for bit, the floats of random ones within ref_ring_cases.FLOAT_TOL.
 This pins the ring layer (ego shift, index math, slot choice, moves, removal, visibility BFS, frustum, occupancy
-fusion) and the tables; SemanticDSPMap::subObjectLevelUpdate itself, generateLabeledPointCloud and object_layer.h stay
-unpinned.
+fusion) and the tables; generateLabeledPointCloud is held the same way by tests/test_oracle_cloud_vs_reference.py;
+SemanticDSPMap::subObjectLevelUpdate itself and object_layer.h stay unpinned (DESIGN.md 5).
 
 Where oracle/_ref/ holds the harness executables (`make -C oracle ref`, which needs the reference), every scenario is
 run again and must reproduce the fixture byte for byte; only that leg may skip.
