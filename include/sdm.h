@@ -966,6 +966,90 @@ sdm_status sdm_get_ground(sdm_map *m, sdm_ground_cell *cells, uint32_t *d2, sdm_
 sdm_status sdm_query_ground(sdm_map *m, const float *xyz, int64_t n, sdm_ground_result *out, uint32_t flags);
 sdm_status sdm_query_footprints(sdm_map *m, const sdm_footprint *fp, int64_t n, sdm_footprint_result *out, uint32_t flags);
 
+/* ---- surface mesh: what does the map look like - to a person, a simulator, a renderer? ----
+ * sdm_mesh_update enqueues, on the map's stream, a face mesh of the last frame enqueued before the call and returns
+ * without waiting.  Like the other layers the result is a snapshot: it keeps that frame's map center and ring offsets
+ * until the next sdm_mesh_update, whatever frames, sdm_clear, sdm_load_state or sdm_set_ring_state come in between;
+ * nothing of the map's state is modified and no scratch of the frames' or of another layer is used.  Everything is
+ * integer and bitwise reproducible.
+ * Cells are map-index cells (i, j, k), cell word i | j << x_n | k << (x_n + y_n).  The map is a block, not a torus: the
+ * ring's wrap point is no neighbour relation.
+ * Solid cell, from the second word of its result (track, label, occ): occ >= 1 (occ == 1 with SDM_MESH_OBSERVED_ONLY), bit
+ * `label` of `labels` set (bit l of word l / 32), track == options.track unless that is -1, and the static / movable flag
+ * admits the track (movable: 1 <= track <= max_movable_track).
+ * Face: a solid cell and a direction whose face neighbour is not solid or lies outside the map.  kind: what is behind it -
+ * 0 a free cell (occ == 0), 1 an unknown cell (occ == -1), 2 nothing, the map ends there, 3 a cell with occ >= 1 that is
+ * not solid under these options.  SDM_MESH_SKIP_UNKNOWN_FACES and SDM_MESH_SKIP_BORDER_FACES leave kinds 1 and 2 out.
+ * Faces ascend in (cell word, dir).
+ * Vertices: the lattice corners (i, j, k) in 0..NX, 0..NY, 0..NZ used by at least one emitted face, each once, ascending in
+ * corner word i + (NX + 1) * (j + (NY + 1) * k).
+ * Quads: quads[4f .. 4f+3] are the indices into the vertex list of face f's corners q0..q3, counter-clockwise seen from
+ * outside; as offsets from the cell's (i, j, k):
+ *   dir 0 (-x): 0,0,0  0,0,1  0,1,1  0,1,0      dir 1 (+x): 1,0,0  1,1,0  1,1,1  1,0,1
+ *   dir 2 (-y): 0,0,0  1,0,0  1,0,1  0,0,1      dir 3 (+y): 0,1,0  0,1,1  1,1,1  1,1,0
+ *   dir 4 (-z): 0,0,0  0,1,0  1,1,0  1,0,0      dir 5 (+z): 0,0,1  1,0,1  1,1,1  0,1,1
+ * (q1 - q0) x (q3 - q0) is the outward unit normal, q0 is the quad's smallest corner word, the triangles are (q0, q1, q2)
+ * and (q0, q2, q3).  With no skip flag the mesh is closed: every lattice edge carries 2 or 4 faces.
+ * Positions: xyz[3v + a] = origin[a] + (float)corner_a * voxel_size in float32, one IEEE operation at a time; origin is
+ * the global position of the min corner of cell (0,0,0) of the snapshot.
+ * Capacity: max_faces 0 = max(V / 8, 1) faces (V = NX*NY*NZ; at most 6 V), max_vertices 0 = one and a half times the face
+ * capacity, rounded down (at most the number of corners; a cell that stands alone has 8 vertices to its 6 faces).  The counts are known on the device only and the update does not wait: a build with more faces
+ * or more vertices than either list holds writes no list entry; sdm_get_mesh_faces and sdm_get_mesh_vertices then return
+ * SDM_ERR_CAPACITY and still set *n_out to the true count, sdm_get_mesh_info returns SDM_OK with the true n_faces,
+ * n_vertices and n_solid (faces_by_dir and faces_by_kind count the faces emitted: zeros); nothing is written out of bounds
+ * and nothing is truncated; an update that asks for enough then succeeds.
+ * Memory: SDM_MESH_BYTES_PER_WORD = 28 bytes per 64 cells (three bitmasks and the faces' prefix: V * 7 / 16 bytes),
+ * SDM_MESH_BYTES_PER_CORNER_WORD = 12 bytes per 64 lattice corners (the corner mask and its prefix),
+ * SDM_MESH_BYTES_PER_FACE = 28 bytes per face of capacity (12 B record, 16 B vertex ids), SDM_MESH_BYTES_PER_VERTEX = 8
+ * bytes per vertex of capacity, and 44 bytes of counters per 4096 cells: 10.7 MB + 83.9 MB at 256^3 with the default
+ * capacities.  Allocated at the first sdm_mesh_update, grown by one that asks for more, freed by sdm_destroy.
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map or NULL options, unknown flag bits, both SDM_MESH_STATIC_ONLY and
+ * SDM_MESH_MOVABLE_ONLY, track < -1 or > 65535, a negative capacity, cap < 0, a NULL n_out, a Z-slab shard (shard_count >
+ * 1), and a getter or sdm_mesh_device before any sdm_mesh_update. */
+#define SDM_MESH_STATIC_ONLY        0x01u  /* a cell whose winning track is movable (1 <= track <= max_movable_track) is not solid */
+#define SDM_MESH_MOVABLE_ONLY       0x02u  /* only such cells are solid (both bits: SDM_ERR_INVALID_ARGUMENT) */
+#define SDM_MESH_OBSERVED_ONLY      0x04u  /* occ == 2 (guessed occupied) is not solid */
+#define SDM_MESH_SKIP_UNKNOWN_FACES 0x08u  /* faces of kind 1 are left out: only surfaces seen from known space */
+#define SDM_MESH_SKIP_BORDER_FACES  0x10u  /* faces of kind 2 are left out: the mesh is open where the map ends */
+#define SDM_MESH_BYTES_PER_WORD 28
+#define SDM_MESH_BYTES_PER_CORNER_WORD 12
+#define SDM_MESH_BYTES_PER_FACE 28
+#define SDM_MESH_BYTES_PER_VERTEX 8
+typedef struct {          /* 56 bytes, every field naturally aligned */
+  uint32_t flags;
+  int32_t  track;         /* -1: any; 0..65535: only cells whose winning track is this one (one object's surface) */
+  uint32_t labels[8];     /* bit l of the 256 (binding.label_mask): cells of label l may be solid */
+  int64_t  max_faces;     /* capacity of the face list; 0 = max(V / 8, 1); at most 6 V */
+  int64_t  max_vertices;  /* capacity of the vertex list; 0 = 3 / 2 of the face capacity; at most the number of corners */
+} sdm_mesh_options;
+typedef struct {          /* 12 bytes */
+  uint32_t cell;          /* the solid cell's word */
+  uint16_t track; uint8_t label; int8_t occ;   /* its result, as sdm_get_voxels holds it */
+  uint8_t  dir;           /* 0 -x, 1 +x, 2 -y, 3 +y, 4 -z, 5 +z: the outward normal */
+  uint8_t  kind;          /* the neighbour behind the face: 0 free (occ == 0), 1 unknown (occ == -1), 2 outside the map,
+                             3 an occ >= 1 cell that is not solid under these options */
+  uint16_t pad;           /* 0 */
+} sdm_mesh_face;
+typedef struct {          /* 8 bytes */
+  uint16_t i, j, k, pad;  /* a lattice corner, 0..NX, 0..NY, 0..NZ; pad 0 */
+} sdm_mesh_vertex;
+typedef struct {          /* 112 bytes, every field naturally aligned */
+  uint32_t n_faces, n_vertices, n_solid;       /* true counts, also when over capacity */
+  uint32_t faces_by_dir[6], faces_by_kind[4];  /* of the faces emitted */
+  uint32_t pad;                                /* 0: the options begin at a multiple of 8 bytes */
+  sdm_mesh_options options;                    /* echoed, capacities resolved */
+} sdm_mesh_info;
+sdm_status sdm_mesh_update(sdm_map *m, const sdm_mesh_options *options);
+/* Waits.  info and origin may each be NULL. */
+sdm_status sdm_get_mesh_info(sdm_map *m, sdm_mesh_info *info, float origin[3]);
+/* Wait; write at most cap entries and set *n_out to the true count.  faces, quads (4 per face), corners and xyz (3 per
+ * vertex) may each be NULL. */
+sdm_status sdm_get_mesh_faces(sdm_map *m, sdm_mesh_face *faces, uint32_t *quads, int64_t cap, int64_t *n_out);
+sdm_status sdm_get_mesh_vertices(sdm_map *m, sdm_mesh_vertex *corners, float *xyz, int64_t cap, int64_t *n_out);
+/* Device pointers to the three lists of the last build, for a renderer: valid until the next sdm_mesh_update or
+ * sdm_destroy, to be read in stream order on sdm_stream (the counts: sdm_get_mesh_info).  Each may be NULL. */
+sdm_status sdm_mesh_device(sdm_map *m, const sdm_mesh_face **faces, const uint32_t **quads, const sdm_mesh_vertex **corners);
+
 /* ---- owner sets of the object layer: ObjectParticleHashMap (object_layer.h:20-52) */
 sdm_status sdm_object_particle_count(sdm_map *m, int32_t track_id, int64_t *count);
 /* The keys of ObjectParticleHashMap::indices_map whose sets are not empty: every track id that owns at least one slot of

@@ -619,6 +619,51 @@ class SemanticDSPMap {
     if (!check(sdm_query_footprints(map_, footprints.data(), (int64_t)footprints.size(), out.data(), 0u), "sdm_query_footprints")) out.clear();
     return out.size();
   }
+  /// What does the map look like (sdm.h, "surface mesh")?  Builds the face mesh of the results of the last update() under
+  /// `options` - one unit quad per face between a solid cell and a neighbour that is not, the lattice corners as welded
+  /// vertices - and copies it out: xyz holds three floats per vertex, triangles three vertex indices per triangle, two
+  /// triangles per face in the faces' order ((q0, q1, q2) and (q0, q2, q3), counter-clockwise seen from outside).  faces
+  /// (may be null): per face the cell, its track, label and occ, the direction and what lies behind it, for colouring.
+  /// info (may be null): the counts and the options echoed, capacities resolved.  A build that needs longer lists than
+  /// `options` asks for (0: the library's defaults) is repeated once with the true counts.  The call waits.  Returns the
+  /// number of triangles; 0 (and empty vectors) before the first update() or when a call fails.
+  size_t mesh(const sdm_mesh_options &options, std::vector<float> &xyz, std::vector<uint32_t> &triangles,
+              std::vector<sdm_mesh_face> *faces = nullptr, sdm_mesh_info *info = nullptr) {
+    xyz.clear();
+    triangles.clear();
+    if (faces) faces->clear();
+    if (!map_) return 0;
+    sdm_mesh_options opt = options;
+    sdm_mesh_info mi;
+    for (int attempt = 0;; ++attempt) {
+      if (!check(sdm_mesh_update(map_, &opt), "sdm_mesh_update")) return 0;
+      if (!check(sdm_get_mesh_info(map_, &mi, nullptr), "sdm_get_mesh_info")) return 0;
+      if ((int64_t)mi.n_faces <= mi.options.max_faces && (int64_t)mi.n_vertices <= mi.options.max_vertices) break;
+      if (attempt == 1) return 0;  // (the counts of one frame do not change between two builds)
+      opt.max_faces = std::max<int64_t>(mi.n_faces, 1);
+      opt.max_vertices = std::max<int64_t>(mi.n_vertices, 1);
+    }
+    std::vector<uint32_t> quads(4 * (size_t)mi.n_faces);
+    std::vector<sdm_mesh_face> own;
+    std::vector<sdm_mesh_face> &fc = faces ? *faces : own;
+    if (faces) fc.resize(mi.n_faces);
+    xyz.resize(3 * (size_t)mi.n_vertices);
+    int64_t n = 0;
+    if (!check(sdm_get_mesh_faces(map_, faces ? fc.data() : nullptr, quads.data(), (int64_t)mi.n_faces, &n), "sdm_get_mesh_faces") ||
+        !check(sdm_get_mesh_vertices(map_, nullptr, xyz.data(), (int64_t)mi.n_vertices, &n), "sdm_get_mesh_vertices")) {
+      xyz.clear();
+      if (faces) faces->clear();
+      return 0;
+    }
+    triangles.resize(6 * (size_t)mi.n_faces);
+    for (size_t f = 0; f < mi.n_faces; ++f) {
+      const uint32_t *q = &quads[4 * f];
+      uint32_t *t = &triangles[6 * f];
+      t[0] = q[0], t[1] = q[1], t[2] = q[2], t[3] = q[0], t[4] = q[2], t[5] = q[3];
+    }
+    if (info) *info = mi;
+    return 2 * (size_t)mi.n_faces;
+  }
   /// the ray table scoreViews uses at `stride`: three floats per ray
   const std::vector<float> &viewRays(int stride) {
     if (stride != view_rays_stride_ || view_rays_.empty()) {

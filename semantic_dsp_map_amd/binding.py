@@ -95,6 +95,18 @@ GROUND_IGNORE_MOVABLE = 0x2
 GROUND_NONE_IS_LETHAL = 0x4
 GROUND_NO_LEVEL = 0xFFFF
 GROUND_MAX_FOOTPRINT_CELLS = 64   # half_len + half_wid of a footprint, in voxels
+# the surface mesh (sdm.h: sdm_mesh_update / sdm_get_mesh_info / sdm_get_mesh_faces / sdm_get_mesh_vertices / sdm_mesh_device)
+MESH_OPTIONS = np.dtype([("flags", "<u4"), ("track", "<i4"), ("labels", "<u4", (8,)), ("max_faces", "<i8"), ("max_vertices", "<i8")])
+MESH_FACE = np.dtype([("cell", "<u4"), ("track", "<u2"), ("label", "u1"), ("occ", "i1"), ("dir", "u1"), ("kind", "u1"), ("pad", "<u2")])
+MESH_VERTEX = np.dtype([("i", "<u2"), ("j", "<u2"), ("k", "<u2"), ("pad", "<u2")])
+MESH_INFO = np.dtype([("n_faces", "<u4"), ("n_vertices", "<u4"), ("n_solid", "<u4"), ("faces_by_dir", "<u4", (6,)),
+                      ("faces_by_kind", "<u4", (4,)), ("pad", "<u4"), ("options", MESH_OPTIONS)])
+assert MESH_OPTIONS.itemsize == 56 and MESH_FACE.itemsize == 12 and MESH_VERTEX.itemsize == 8 and MESH_INFO.itemsize == 112
+MESH_STATIC_ONLY = 0x01
+MESH_MOVABLE_ONLY = 0x02
+MESH_OBSERVED_ONLY = 0x04
+MESH_SKIP_UNKNOWN_FACES = 0x08
+MESH_SKIP_BORDER_FACES = 0x10
 
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
@@ -117,6 +129,36 @@ def label_mask(labels):
             raise ValueError("label %r is not in 0..255" % (l,))
         m[int(l) >> 5] |= np.uint32(1 << (int(l) & 31))
     return m
+
+
+def mesh_triangles(quads):
+    """[n, 4] vertex ids of quads (q0, q1, q2, q3) -> [2n, 3]: the triangles (q0, q1, q2) and (q0, q2, q3) of each, in
+    the quads' order and with their winding"""
+    q = np.asarray(quads).reshape(-1, 4)
+    return q[:, [0, 1, 2, 0, 2, 3]].reshape(-1, 3)
+
+
+def write_ply(path, xyz, quads, face_rgb=None):
+    """ASCII PLY of a mesh: vertices xyz [m, 3], two triangles per quad (mesh_triangles), optionally one colour per quad
+    (face_rgb [n, 3], 0..255) written to both of its triangles.  Plain host code."""
+    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
+    tri = mesh_triangles(quads)
+    rgb = None
+    if face_rgb is not None:
+        rgb = np.repeat(np.asarray(face_rgb).reshape(-1, 3).astype(np.uint8), 2, axis=0)
+        if len(rgb) != len(tri):
+            raise ValueError("face_rgb needs one colour per quad")
+    with open(path, "w") as f:
+        f.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % len(xyz))
+        f.write("element face %d\nproperty list uchar int vertex_indices\n" % len(tri))
+        if rgb is not None:
+            f.write("property uchar red\nproperty uchar green\nproperty uchar blue\n")
+        f.write("end_header\n")
+        for p in xyz:
+            f.write("%.9g %.9g %.9g\n" % (p[0], p[1], p[2]))   # (9 digits: float32 round-trips)
+        for k, t in enumerate(tri):
+            f.write("3 %d %d %d" % (t[0], t[1], t[2]))
+            f.write(" %d %d %d\n" % tuple(rgb[k]) if rgb is not None else "\n")
 
 
 def ground_band(cfg, origin, up, lo_m, hi_m):
@@ -275,6 +317,11 @@ def load_library():
         "sdm_get_ground": [vp, vp, vp, vp, vp],
         "sdm_query_ground": [vp, vp, i64, vp, u32],
         "sdm_query_footprints": [vp, vp, i64, vp, u32],
+        "sdm_mesh_update": [vp, vp],
+        "sdm_get_mesh_info": [vp, vp, vp],
+        "sdm_get_mesh_faces": [vp, vp, vp, i64, C.POINTER(i64)],
+        "sdm_get_mesh_vertices": [vp, vp, vp, i64, C.POINTER(i64)],
+        "sdm_mesh_device": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
         "sdm_forecast_stamps": [C.c_float, vp, i32, vp, i32, u32, vp, i64, C.POINTER(i64)],
         "sdm_forecast_update": [vp, vp, i32, vp, i32, u32],
         "sdm_get_forecast": [vp, vp, vp, vp, vp],
@@ -895,6 +942,46 @@ class SdmMap:
         res = np.empty(len(fp), FOOTPRINT_RESULT)
         _check(self.L, self.L.sdm_query_footprints(self.h, _ptr(fp), len(fp), _ptr(res), 0), "sdm_query_footprints")
         return res
+
+    # ---- the surface mesh (sdm.h).  mesh_update enqueues a build on the map's stream from the last frame's results;
+    # mesh() and mesh_device() answer for that frame until the next build.
+    def mesh_update(self, labels=None, track=-1, static_only=False, movable_only=False, observed_only=False, skip_unknown_faces=False,
+                    skip_border_faces=False, max_faces=0, max_vertices=0):
+        """labels: the label ids whose cells may be solid (None: all 256); track: -1 any, else that track's cells only;
+        max_faces / max_vertices: the lists' capacities (0: the defaults, V / 8 faces and 3 / 2 as many vertices)"""
+        o = np.zeros(1, MESH_OPTIONS)
+        o["labels"] = np.full(8, 0xFFFFFFFF, np.uint32) if labels is None else label_mask(labels)
+        o["track"], o["max_faces"], o["max_vertices"] = track, max_faces, max_vertices
+        o["flags"] = ((MESH_STATIC_ONLY if static_only else 0) | (MESH_MOVABLE_ONLY if movable_only else 0) |
+                      (MESH_OBSERVED_ONLY if observed_only else 0) | (MESH_SKIP_UNKNOWN_FACES if skip_unknown_faces else 0) |
+                      (MESH_SKIP_BORDER_FACES if skip_border_faces else 0))
+        _check(self.L, self.L.sdm_mesh_update(self.h, _ptr(o)), "sdm_mesh_update")
+
+    def mesh_info(self):
+        """-> (info, origin): a MESH_INFO record (true counts, also of a build over capacity) and the global position of the
+        min corner of cell (0, 0, 0) of the snapshot (float32[3])"""
+        info, origin = np.zeros(1, MESH_INFO), np.empty(3, np.float32)
+        _check(self.L, self.L.sdm_get_mesh_info(self.h, _ptr(info), _ptr(origin)), "sdm_get_mesh_info")
+        return info[0], origin
+
+    def mesh(self):
+        """-> dict(faces MESH_FACE[n], quads uint32[n, 4], corners MESH_VERTEX[m], xyz float32[m, 3], info, origin).  A build
+        over capacity raises SdmError (SDM_ERR_CAPACITY): mesh_info() has the counts to ask for."""
+        info, origin = self.mesh_info()
+        n, k = int(info["n_faces"]), int(info["n_vertices"])
+        faces, quads = np.empty(n, MESH_FACE), np.empty((n, 4), np.uint32)
+        corners, xyz = np.empty(k, MESH_VERTEX), np.empty((k, 3), np.float32)
+        got = C.c_int64(0)
+        _check(self.L, self.L.sdm_get_mesh_faces(self.h, _ptr(faces), _ptr(quads), n, C.byref(got)), "sdm_get_mesh_faces")
+        _check(self.L, self.L.sdm_get_mesh_vertices(self.h, _ptr(corners), _ptr(xyz), k, C.byref(got)), "sdm_get_mesh_vertices")
+        return dict(faces=faces, quads=quads, corners=corners, xyz=xyz, info=info, origin=origin)
+
+    def mesh_device(self):
+        """-> (faces, quads, corners): device addresses of the last build's lists (MESH_FACE, 4 uint32 per face, MESH_VERTEX),
+        valid until the next mesh_update, to be read in stream order on the map's stream"""
+        p = [C.c_void_p() for _ in range(3)]
+        _check(self.L, self.L.sdm_mesh_device(self.h, *(C.byref(x) for x in p)), "sdm_mesh_device")
+        return tuple(x.value for x in p)
 
     def occupied(self, cap=None, zero_center=False, free=False, mark_fov=False):
         cap = cap or self.v_count

@@ -1,6 +1,6 @@
 // sdm_layer.h — device helpers of the derived map layers (queries.hip, esdf.hip, instances.hip, frontiers.hip, views.hip,
-// reach.hip, forecast.hip, ground.hip): how they read a result word, go from a global position to a map-index coordinate and from a map-index cell
-// to its storage index, and reduce a value over the 64 lanes of a wave.  Only those eight units include it: the frame
+// reach.hip, forecast.hip, ground.hip, mesh.hip): how they read a result word, go from a global position to a map-index coordinate and from a map-index cell
+// to its storage index, and reduce a value over the 64 lanes of a wave.  Only those nine units include it: the frame
 // pipeline's units see sdm_internal.h alone.
 #pragma once
 #include "sdm_internal.h"

@@ -118,6 +118,20 @@ struct GroundLayer : Derived {
   sdm_ground_options opt{};
 };
 
+// the surface mesh (mesh.hip): the solid / unknown / occupied masks, the corner mask and the two prefixes in one block; the
+// face records, their vertex ids and the vertex list, laid out for alloc_f faces and alloc_v vertices and grown by a build
+// that asks for more; the build's counters and rows of counts, the rows every wave of the emitting kernel leaves; a scan
+// scratch of its own; the build's options with the capacities resolved (its flags are Derived's)
+struct MeshLayer : Derived {
+  unsigned char *bits = nullptr;
+  sdm_mesh_face *faces = nullptr;
+  uint32_t *quads = nullptr;
+  sdm_mesh_vertex *verts = nullptr;
+  uint32_t *meta = nullptr, *stats = nullptr, *scan = nullptr;
+  size_t alloc_f = 0, alloc_v = 0;
+  sdm_mesh_options opt{};
+};
+
 struct sdm_map {
   sdm_config cfg{};
   sdm_params prm{};
@@ -278,6 +292,7 @@ struct sdm_map {
   ReachLayer reach;
   ForecastLayer forecast;
   GroundLayer ground;
+  MeshLayer mesh;
   sdm_point_xyzrgb *d_points_rgb = nullptr;
   size_t points_rgb_cap = 0;
   ColourTables *d_colours = nullptr;
