@@ -168,7 +168,9 @@ __global__ __launch_bounds__(64) void k_esdf_env(Dims d, uint32_t *__restrict__ 
 
 // ---- the distance query: one lane per point ------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t cell_d2(const Dims &d, int cx, int cy, int cz, uint32_t s) {
-  const int dx = cx - (int)(s & (d.NX - 1)), dy = cy - (int)((s >> d.x_n) & (d.NY - 1)), dz = cz - (int)(s >> (d.x_n + d.y_n));
+  int sx, sy, sz;
+  cell_xyz(d, s, sx, sy, sz);
+  const int dx = cx - sx, dy = cy - sy, dz = cz - sz;
   return (uint32_t)(dx * dx + dy * dy + dz * dz);
 }
 
@@ -178,21 +180,18 @@ __global__ __launch_bounds__(QTPB) void k_query_distance(Dims d, Frame f, const 
   const uint32_t i = blockIdx.x * QTPB + threadIdx.x;
   if (i >= n) return;
   const int N[3] = {(int)d.NX, (int)d.NY, (int)d.NZ};
-  float t[3];
+  const float p[3] = {xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]};
+  float uu[3], t[3];
   int cell[3], c0[3], c1[3];
-  bool ok = true;
+  const bool ok = point_coords(d, f, p, cell, uu);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const float u = map_u(d, f, a, xyz[3 * (size_t)i + a]);
-    ok = ok && u >= 0.f && u < (float)N[a];  // (NaN and +-inf fail it)
-    const float uu = ok ? u : 0.5f;           // (no cast of a value outside the map)
-    cell[a] = (int)floorf(uu);
-    const float s = uu - 0.5f, i0 = floorf(s);
+    const float s = uu[a] - 0.5f, i0 = floorf(s);
     t[a] = s - i0;
     c0[a] = min(max((int)i0, 0), N[a] - 1);
     c1[a] = min(max((int)i0 + 1, 0), N[a] - 1);
   }
-  auto lin = [&](int x, int y, int z) { return (uint32_t)x | ((uint32_t)y << d.x_n) | ((uint32_t)z << (d.x_n + d.y_n)); };
+  auto lin = [&](int x, int y, int z) { return cell_word(d, x, y, z); };
   // the point's cell and the eight corners: nine independent loads (corners differing in x are mostly adjacent words)
   uint32_t sc = INVALID_INDEX, sk[8];
   if (ok) {
@@ -228,7 +227,8 @@ __global__ __launch_bounds__(QTPB) void k_query_distance(Dims d, Frame f, const 
     r.gradient[0] = gx * d.recip;
     r.gradient[1] = gy * d.recip;
     r.gradient[2] = gz * d.recip;
-    const uint32_t s3[3] = {sc & (d.NX - 1), (sc >> d.x_n) & (d.NY - 1), sc >> (d.x_n + d.y_n)};
+    uint32_t s3[3];
+    cell_xyz(d, sc, s3[0], s3[1], s3[2]);
 #pragma unroll
     for (int a = 0; a < 3; ++a) r.nearest[a] = (f.center[a] + d.pmin[a]) + ((float)s3[a] + 0.5f) * d.voxel_size;
     r.d2 = cell_d2(d, cell[0], cell[1], cell[2], sc);

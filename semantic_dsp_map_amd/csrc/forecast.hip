@@ -17,17 +17,16 @@
 //               sources times their stamps, which under SWEPT is uneven for a fast object.
 //   k_forecast_reduce    counts the cells with any horizon bit.
 //   k_query_forecast     a lane per point and time.
-//   k_query_forecast_segments   a lane per segment: k_query_segments' walk restated statement for statement (float32
-//               map_u, the DDA in double, SEG_K cells a round with their loads issued together, x before y before z at
-//               equal t, clipped to the map), reading mask words in map-index order instead of results, plus per cell the
-//               times at which it is entered and left and the horizon bits between them.
+//   k_query_forecast_segments   a lane per segment: k_query_segments' walk (sdm_walk.h), reading mask words in map-index
+//               order instead of results, plus per cell the times at which it is entered and left and the horizon bits
+//               between them.
 //   k_forecast_cells_count / exclusive_scan_u32 / k_forecast_cells_write   the list of marked cells in ascending cell
 //               word: word popcounts, their scan, a write pass (as the frontiers compact theirs).
 // Only integer OR / MIN / ADD atomics: the field is bitwise the same from run to run.
 #include <cmath>
 
-#include "sdm_layer.h"
 #include "sdm_map.h"
+#include "sdm_walk.h"
 
 #pragma clang fp contract(off)
 
@@ -38,8 +37,6 @@ static_assert(SDM_FORECAST_MAX_HORIZONS == 16, "the horizon bits are the low hal
 namespace sdm {
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int FC_TPB = 256, FC_WAVES = FC_TPB / 64;
 constexpr int FC_U = 8;             // chunks of 64 cells a wave takes
@@ -69,18 +66,8 @@ __global__ __launch_bounds__(FC_TPB) void k_forecast_classify(Dims d, Frame f, c
                                                               uint32_t nw) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t chunk0 = (blockIdx.x * FC_WAVES + (threadIdx.x >> 6)) * FC_U;
-  const uint32_t xy_n = (uint32_t)(d.x_n + d.y_n);
   uint32_t w[FC_U];
-#pragma unroll
-  for (int u = 0; u < FC_U; ++u) {  // every load first (V is a multiple of 64: a chunk inside the map is whole)
-    const uint32_t chunk = chunk0 + (uint32_t)u;
-    w[u] = RES_UNKNOWN_W1;
-    if (chunk < nw) {
-      const uint32_t c = (chunk << 6) + lane;
-      const uint32_t x = c & (d.NX - 1), y = (c >> d.x_n) & (d.NY - 1), z = c >> xy_n;
-      w[u] = res[cell_voxel(d, f, (int)x, (int)y, (int)z)].y;
-    }
-  }
+  load_w1(d, f, res, chunk0, nw, lane, w);
   uint32_t in_set[FC_U];
 #pragma unroll
   for (int u = 0; u < FC_U; ++u) in_set[u] = set[(w[u] & 0xffffu) >> 5];  // (any track has a word: the set holds all 65536)
@@ -101,20 +88,10 @@ __global__ __launch_bounds__(FC_TPB) void k_forecast_classify(Dims d, Frame f, c
 }
 
 // ---- scatter ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 wave_sum64(u64 v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, s, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), s, 64);
-    v += ((u64)hi << 32) | lo;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(FC_TPB) void k_forecast_scatter(Dims d, Frame f, const uint2 *__restrict__ res, Table tb, uint32_t *mask,
                                                              uint32_t *first, u64 *__restrict__ meta, uint32_t nw) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t chunk0 = (blockIdx.x * FC_WAVES + (threadIdx.x >> 6)) * FC_U;
-  const uint32_t xy_n = (uint32_t)(d.x_n + d.y_n);
   uint32_t mw[FC_U];
 #pragma unroll
   for (int u = 0; u < FC_U; ++u) {
@@ -127,7 +104,8 @@ __global__ __launch_bounds__(FC_TPB) void k_forecast_scatter(Dims d, Frame f, co
     const bool src = ((mw[u] >> 16) & 3u) == 3u;
     if (!__ballot(src)) continue;  // (wave-uniform; chunks beyond the map read 0)
     const uint32_t c = ((chunk0 + (uint32_t)u) << 6) + lane;
-    const int x = (int)(c & (d.NX - 1)), y = (int)((c >> d.x_n) & (d.NY - 1)), z = (int)(c >> xy_n);
+    int x, y, z;
+    cell_xyz(d, c, x, y, z);
     uint32_t track = 0, beg = 0, cnt = 0;
     if (src) {
       track = res[cell_voxel(d, f, x, y, z)].y & 0xffffu;  // (in the set, so 1 <= track <= max_track: off[track + 1] exists)
@@ -142,7 +120,7 @@ __global__ __launch_bounds__(FC_TPB) void k_forecast_scatter(Dims d, Frame f, co
       const int tx = x + (int)(st.x & 0xfffu) - SHIFT_MAX, ty = y + (int)((st.x >> 12) & 0xfffu) - SHIFT_MAX, tz = z + (int)st.y - SHIFT_MAX;
       const uint32_t k = st.x >> 24;
       if ((uint32_t)tx < d.NX && (uint32_t)ty < d.NY && (uint32_t)tz < d.NZ) {
-        const uint32_t t = (uint32_t)tx | ((uint32_t)ty << d.x_n) | ((uint32_t)tz << xy_n);  // < V
+        const uint32_t t = cell_word(d, tx, ty, tz);  // < V
         atomicOr(mask + t, 1u << k);
         atomicMin(first + t, (k << 16) | track);
         ++n_in;
@@ -187,7 +165,7 @@ __global__ __launch_bounds__(FC_TPB) void k_forecast_cells_write(const uint32_t 
   const bool marked = (mw & 0xffffu) != 0u;
   const u64 m = __ballot(marked);
   if (!marked) return;
-  const uint32_t r = pre[chunk] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+  const uint32_t r = pre[chunk] + lane_rank(m, lane);
   if (r >= take) return;  // nothing is written beyond the caller's capacity
   if (cell_out) cell_out[r] = c;
   if (mask_out) mask_out[r] = mw;
@@ -209,18 +187,9 @@ __global__ __launch_bounds__(FQ_TPB) void k_query_forecast(Dims d, Frame f, Fiel
   if (i >= n) return;
   const float4 p = reinterpret_cast<const float4 *>(xyzt)[i];
   const float pos[3] = {p.x, p.y, p.z};
-  const int N[3] = {(int)d.NX, (int)d.NY, (int)d.NZ};
-  uint32_t cell[3];
-  bool ok = isfinite(p.w);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float u = map_u(d, f, a, pos[a]);
-    ok = ok && u >= 0.f && u < (float)N[a];  // (NaN and +-inf fail it)
-    cell[a] = (uint32_t)(int)floorf(ok ? u : 0.5f);
-  }
+  const uint32_t c = point_cell(d, f, pos);
   uint2 o = make_uint2(0xff00u | 0xffu, 0x00ff0000u);  // state -1, horizon 0xff; track 0; mask 0, first_horizon 0xff, pad 0
-  if (ok) {
-    const uint32_t c = cell[0] | (cell[1] << d.x_n) | (cell[2] << (d.x_n + d.y_n));
+  if (isfinite(p.w) && c != INVALID_INDEX) {
     const uint32_t mw = g.mask[c], fw = g.first[c];
     const uint32_t k = horizon_of(g, (double)p.w);
     const uint32_t cls = (mw >> 16) & 3u;
@@ -232,15 +201,10 @@ __global__ __launch_bounds__(FQ_TPB) void k_query_forecast(Dims d, Frame f, Fiel
   out[i] = o;
 }
 
-constexpr int SEG_K = 8;
-enum : int { SEG_CELL = 0, SEG_OUT = 1, SEG_END = 2 };
-
 __global__ __launch_bounds__(FQ_TPB) void k_query_forecast_segments(Dims d, Frame f, Field g, const float *__restrict__ seg, uint32_t n,
                                                                     sdm_forecast_hit *__restrict__ out, int unknown_blocks, int vacated_blocks) {
   const uint32_t i = blockIdx.x * FQ_TPB + threadIdx.x;
   if (i >= n) return;
-  const int N[3] = {(int)d.NX, (int)d.NY, (int)d.NZ};
-  const int xy_n = d.x_n + d.y_n;
   float ua[3], ub[3];
   const float ta = seg[8 * (size_t)i + 3], tb = seg[8 * (size_t)i + 7];
   bool finite = isfinite(ta) && isfinite(tb) && ta <= tb;
@@ -255,82 +219,31 @@ __global__ __launch_bounds__(FQ_TPB) void k_query_forecast_segments(Dims d, Fram
   uint32_t hit_c = NOTHING, hit_track = 0u, hit_h = 0xffu;
   int hit_state = 0;
   int cells = 0;
-  // the state of the walk: current cell c, the t at which it was entered, per axis the t of the next plane
-  int c[3] = {0, 0, 0}, step[3] = {0, 0, 0};
-  double A[3], inv[3], tn[3];
-  double t_cur = 0.0;
-  int kind = SEG_END;  // of the current cell
+  SegWalk sw;
+  sw.kind = SEG_END;
   if (!finite) {
     if (unknown_blocks) hit_t = 0.f, hit_state = -1;
   } else {
-    bool inside = true, empty = false;
-    double t_in = -INFINITY, t_out = INFINITY;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      A[a] = (double)ua[a];
-      const double D = (double)ub[a] - A[a];
-      inside = inside && ua[a] >= 0.f && ua[a] < (float)N[a];
-      if (D == 0.0) {
-        empty = empty || !(ua[a] >= 0.f && ua[a] < (float)N[a]);
-        inv[a] = 0.0;
-      } else {
-        inv[a] = 1.0 / D;
-        const double t0 = (0.0 - A[a]) * inv[a], t1 = ((double)N[a] - A[a]) * inv[a];
-        t_in = fmax(t_in, fmin(t0, t1));
-        t_out = fmin(t_out, fmax(t0, t1));
-      }
-      step[a] = D > 0.0 ? 1 : (D < 0.0 ? -1 : 0);
-    }
-    if (inside) {
-      kind = SEG_CELL;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) c[a] = (int)floorf(ua[a]);
+    const SegClip cl = seg_begin(sw, d, ua, ub);
+    if (cl.inside) {
+      seg_enter_inside(sw, ua);
     } else if (unknown_blocks) {
       hit_t = 0.f, hit_state = -1;  // a lies outside the map, which blocks
-    } else if (!empty && t_in <= 1.0 && t_out > 0.0 && t_in < t_out) {
-      // clipped: the walk starts where the segment enters the map (rounding at the face is clamped back into the map)
-      kind = SEG_CELL;
-      t_cur = fmax(t_in, 0.0);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) c[a] = min(max((int)floor(A[a] + t_cur * ((double)ub[a] - A[a])), 0), N[a] - 1);
+    } else if (cl.enters()) {
+      seg_enter_clipped(sw, cl, ub);
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) tn[a] = step[a] == 0 ? INFINITY : ((double)(c[a] + (step[a] > 0)) - A[a]) * inv[a];
+    seg_planes(sw);
   }
-  while (kind != SEG_END) {
+  while (sw.kind != SEG_END) {
     uint32_t word[SEG_K], w[SEG_K], range[SEG_K];
     float tin[SEG_K];
     int kd[SEG_K];
 #pragma unroll
     for (int k = 0; k < SEG_K; ++k) {  // the next SEG_K cells: arithmetic only
-      kd[k] = kind;
-      tin[k] = (float)t_cur;
-      word[k] = kind == SEG_CELL ? ((uint32_t)c[0] | ((uint32_t)c[1] << d.x_n) | ((uint32_t)c[2] << xy_n)) : NOTHING;
-      const double tau_in = t_cur;
-      double tau_out = 1.0;
-      if (kind == SEG_CELL) {
-        int ax = 0;  // the plane crossed next: x before y before z at equal t
-        double tm = tn[0];
-        if (tn[1] < tm) { ax = 1; tm = tn[1]; }
-        if (tn[2] < tm) { ax = 2; tm = tn[2]; }
-        if (tm > 1.0) {
-          kind = SEG_END;
-        } else {
-          const int cn = (ax == 0 ? c[0] : ax == 1 ? c[1] : c[2]) + (ax == 0 ? step[0] : ax == 1 ? step[1] : step[2]);
-          const int na = ax == 0 ? N[0] : ax == 1 ? N[1] : N[2];
-#pragma unroll
-          for (int a = 0; a < 3; ++a)
-            if (a == ax) {
-              c[a] = cn;
-              tn[a] = ((double)(cn + (step[a] > 0)) - A[a]) * inv[a];
-            }
-          t_cur = tm;
-          tau_out = tm;
-          if (cn < 0 || cn >= na) kind = SEG_OUT;
-        }
-      } else {
-        kind = SEG_END;  // (after the cell outside the map there is nothing: the map is convex)
-      }
+      kd[k] = sw.kind;
+      tin[k] = (float)sw.t_cur;
+      const double tau_in = sw.t_cur;
+      const double tau_out = seg_advance(sw, word[k], [&](int x, int y, int z) { return cell_word(d, x, y, z); });
       // the horizon bits of the time the cell is occupied (lo <= hi: T is monotonic in tau)
       const uint32_t lo = horizon_of(g, T0 + tau_in * dT), hi = horizon_of(g, T0 + tau_out * dT);
       range[k] = (2u << hi) - (1u << lo);
@@ -393,35 +306,30 @@ __global__ __launch_bounds__(FQ_TPB) void k_query_forecast_segments(Dims d, Fram
 namespace {
 constexpr LayerName FORECAST = {"the forecast", "forecast", "sdm_forecast_update", false};
 
-sdm_status refuse(const char *what, int line, const char *why) {
-  set_error(what, __FILE__, line, why);
-  return SDM_ERR_INVALID_ARGUMENT;
-}
-
 // The checks of the motions and horizons and their expansion into stamps (sdm.h): emit(track, horizon, d) sees the first
 // `limit` stamps in order, *n_out is how many there are.  max_track < 0: no upper bound on the tracks (no map to ask).
 template <typename Emit>
 sdm_status expand(const char *what, float voxel_size, const sdm_motion *motions, int32_t n_motions, const float *horizons, int32_t n_horizons,
                   uint32_t flags, int max_track, int64_t limit, int64_t *n_out, const Emit &emit) {
-  if (flags & ~SDM_FORECAST_SWEPT) return refuse(what, __LINE__, "unknown flag bits");
-  if (!(voxel_size > 0.f) || !std::isfinite(voxel_size)) return refuse(what, __LINE__, "voxel_size is not a positive number");
-  if (n_motions < 0 || (n_motions > 0 && !motions)) return refuse(what, __LINE__, "n_motions < 0, or no motions");
+  if (flags & ~SDM_FORECAST_SWEPT) return LAYER_REFUSE(what, "unknown flag bits");
+  if (!(voxel_size > 0.f) || !std::isfinite(voxel_size)) return LAYER_REFUSE(what, "voxel_size is not a positive number");
+  if (n_motions < 0 || (n_motions > 0 && !motions)) return LAYER_REFUSE(what, "n_motions < 0, or no motions");
   if (n_horizons < 1 || n_horizons > SDM_FORECAST_MAX_HORIZONS || !horizons)
-    return refuse(what, __LINE__, "n_horizons outside 1 .. SDM_FORECAST_MAX_HORIZONS, or no horizons");
+    return LAYER_REFUSE(what, "n_horizons outside 1 .. SDM_FORECAST_MAX_HORIZONS, or no horizons");
   for (int k = 0; k < n_horizons; ++k)
     if (!std::isfinite(horizons[k]) || !(horizons[k] > 0.f) || (k > 0 && !(horizons[k] > horizons[k - 1])))
-      return refuse(what, __LINE__, "horizons must be finite, > 0 and strictly ascending");
+      return LAYER_REFUSE(what, "horizons must be finite, > 0 and strictly ascending");
   std::vector<int32_t> order((size_t)n_motions);
   for (int32_t i = 0; i < n_motions; ++i) {
     const sdm_motion &mo = motions[i];
-    if (mo.track == 0 || (max_track >= 0 && (int)mo.track > max_track)) return refuse(what, __LINE__, "track 0 or a track above max_movable_track");
-    if (mo.pad != 0) return refuse(what, __LINE__, "sdm_motion.pad != 0");
-    if (!std::isfinite(mo.v[0]) || !std::isfinite(mo.v[1]) || !std::isfinite(mo.v[2])) return refuse(what, __LINE__, "a velocity is not finite");
+    if (mo.track == 0 || (max_track >= 0 && (int)mo.track > max_track)) return LAYER_REFUSE(what, "track 0 or a track above max_movable_track");
+    if (mo.pad != 0) return LAYER_REFUSE(what, "sdm_motion.pad != 0");
+    if (!std::isfinite(mo.v[0]) || !std::isfinite(mo.v[1]) || !std::isfinite(mo.v[2])) return LAYER_REFUSE(what, "a velocity is not finite");
     order[(size_t)i] = i;
   }
   std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return motions[a].track < motions[b].track; });
   for (int32_t i = 1; i < n_motions; ++i)
-    if (motions[order[(size_t)i]].track == motions[order[(size_t)i - 1]].track) return refuse(what, __LINE__, "a track appears twice");
+    if (motions[order[(size_t)i]].track == motions[order[(size_t)i - 1]].track) return LAYER_REFUSE(what, "a track appears twice");
   const bool swept = (flags & SDM_FORECAST_SWEPT) != 0;
   int64_t n = 0;
   for (int32_t i = 0; i < n_motions; ++i) {
@@ -489,7 +397,7 @@ extern "C" {
 
 sdm_status sdm_forecast_stamps(float voxel_size, const sdm_motion *motions, int32_t n_motions, const float *horizons, int32_t n_horizons,
                                uint32_t flags, sdm_forecast_stamp *out, int64_t cap, int64_t *n_out) {
-  if (!n_out || cap < 0 || (cap > 0 && !out)) return refuse("sdm_forecast_stamps", __LINE__, "no n_out, cap < 0, or no out for cap > 0");
+  if (!n_out || cap < 0 || (cap > 0 && !out)) return LAYER_REFUSE("sdm_forecast_stamps", "no n_out, cap < 0, or no out for cap > 0");
   int64_t at = 0;
   return expand("sdm_forecast_stamps", voxel_size, motions, n_motions, horizons, n_horizons, flags, -1, cap, n_out,
                 [&](uint16_t track, int k, const int (&e)[3]) {
@@ -601,7 +509,7 @@ sdm_status sdm_get_forecast(sdm_map *m, uint32_t *mask, uint32_t *first, sdm_for
 
 sdm_status sdm_get_forecast_cells(sdm_map *m, uint32_t *cell, uint32_t *mask, uint32_t *first, int64_t cap, int64_t *n_out) {
   if (!m) return SDM_ERR_INVALID_ARGUMENT;
-  if (cap < 0 || !n_out) return refuse("sdm_get_forecast_cells", __LINE__, "cap < 0 or no n_out");
+  if (cap < 0 || !n_out) return LAYER_REFUSE("sdm_get_forecast_cells", "cap < 0 or no n_out");
   SDM_TRY(layer_check(m, "sdm_get_forecast_cells", &m->forecast, FORECAST));
   HIP_TRY(hipSetDevice(m->device));
   ForecastLayer &L = m->forecast;

@@ -51,8 +51,6 @@ namespace sdm {
 
 namespace {
 
-typedef unsigned long long u64;
-
 constexpr int FC_TPB = 256, FC_WAVES = FC_TPB / 64;
 constexpr int FC_U = 8;            // chunks (words) a wave takes
 constexpr int FR_TPB = 256;        // the kernels over ranks
@@ -87,18 +85,8 @@ __global__ __launch_bounds__(FC_TPB) void k_frontier_classify(Dims d, Frame f, c
                                                               u64 *__restrict__ unk_m, uint32_t nw) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t first = (blockIdx.x * FC_WAVES + (threadIdx.x >> 6)) * FC_U;
-  const uint32_t xy_n = (uint32_t)(d.x_n + d.y_n);
   uint32_t w[FC_U];
-#pragma unroll
-  for (int u = 0; u < FC_U; ++u) {  // every load first (V is a multiple of 64: a chunk inside the map is whole)
-    const uint32_t chunk = first + (uint32_t)u;
-    w[u] = 0x01000000u;
-    if (chunk < nw) {
-      const uint32_t c = (chunk << 6) + lane;
-      const uint32_t x = c & (d.NX - 1), y = (c >> d.x_n) & (d.NY - 1), z = c >> xy_n;
-      w[u] = res[cell_voxel(d, f, (int)x, (int)y, (int)z)].y;
-    }
-  }
+  load_w1(d, f, res, first, nw, lane, w);
 #pragma unroll
   for (int u = 0; u < FC_U; ++u) {
     const uint32_t chunk = first + (uint32_t)u;
@@ -113,49 +101,14 @@ __global__ __launch_bounds__(FC_TPB) void k_frontier_classify(Dims d, Frame f, c
 }
 
 // ---- the frontier mask ---------------------------------------------------------------------------------------------
-// the low `width` bits of every `period` bits (powers of two, width <= period <= 64)
-__device__ __forceinline__ u64 rep_mask(uint32_t period, uint32_t width) {
-  u64 m = width >= 64u ? ~0ull : (1ull << width) - 1ull;
-  for (uint32_t p = period; p < 64u; p <<= 1) m |= m << p;
-  return m;
-}
-
-// the bits b of the word that begins at cell c0 (a multiple of 64) whose coordinate ((c0 + b) >> s) & (2^nb - 1) is t
-__device__ __forceinline__ u64 coord_is(uint32_t c0, int s, int nb, uint32_t t) {
-  const uint32_t N = 1u << nb;
-  if (s >= 6) return ((c0 >> s) & (N - 1u)) == t ? ~0ull : 0ull;              // the whole word has one coordinate
-  if (s + nb <= 6) return rep_mask(1u << (s + nb), 1u << s) << (t << s);      // the word holds every coordinate, 64 >> (s + nb) times
-  const uint32_t k = t - ((c0 >> s) & (N - 1u));                              // the word holds 64 >> s coordinates from its first
-  if (k >= (64u >> s)) return 0ull;
-  return ((1ull << (1u << s)) - 1ull) << (k << s);
-}
-
-// bit b: is cell c0 + b - 2^s (down) / c0 + b + 2^s (up) unknown; cells beyond the ends of the mask read 0
-__device__ __forceinline__ u64 unknown_down(const u64 *__restrict__ unk, uint32_t wi, int s) {
-  if (s >= 6) {
-    const uint32_t k = 1u << (s - 6);
-    return wi >= k ? unk[wi - k] : 0ull;
-  }
-  const uint32_t D = 1u << s;
-  return (unk[wi] << D) | (wi > 0u ? unk[wi - 1u] >> (64u - D) : 0ull);
-}
-__device__ __forceinline__ u64 unknown_up(const u64 *__restrict__ unk, uint32_t wi, uint32_t nw, int s) {
-  if (s >= 6) {
-    const uint32_t k = 1u << (s - 6);
-    return wi + k < nw ? unk[wi + k] : 0ull;
-  }
-  const uint32_t D = 1u << s;
-  return (unk[wi] >> D) | (wi + 1u < nw ? unk[wi + 1u] << (64u - D) : 0ull);
-}
-
 // per face (x-, x+, y-, y+, z-, z+): the cells of word wi whose neighbour across it lies inside the map and is unknown
 __device__ __forceinline__ void unknown_faces(const Front &g, uint32_t wi, u64 (&m)[6]) {
   const uint32_t c0 = wi << 6;
   const int s[3] = {0, g.x_n, g.x_n + g.y_n}, nb[3] = {g.x_n, g.y_n, g.z_n};
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    m[2 * a] = unknown_down(g.unk_m, wi, s[a]) & ~coord_is(c0, s[a], nb[a], 0u);
-    m[2 * a + 1] = unknown_up(g.unk_m, wi, g.nw, s[a]) & ~coord_is(c0, s[a], nb[a], (1u << nb[a]) - 1u);
+    m[2 * a] = bits_down(g.unk_m, wi, s[a]) & ~coord_is(c0, s[a], nb[a], 0u);
+    m[2 * a + 1] = bits_up(g.unk_m, wi, g.nw, s[a]) & ~coord_is(c0, s[a], nb[a], (1u << nb[a]) - 1u);
   }
 }
 
@@ -192,13 +145,13 @@ __global__ __launch_bounds__(FC_TPB) void k_frontier_compact(Front g) {
     const u64 begins = fr & (~(fr << 1) | coord_is(wi << 6, 0, g.x_n, 0u));
     if ((fr >> lane) & 1ull) {
       const uint32_t base = g.pre[wi];
-      const uint32_t r = base + (uint32_t)__popcll(fr & ((1ull << lane) - 1ull));  // < total <= cap
+      const uint32_t r = base + lane_rank(fr, lane);  // < total <= cap
       const uint32_t first = 63u - (uint32_t)__builtin_clzll(begins & ((2ull << lane) - 1ull));  // of this cell's run (<= lane)
       uint32_t n = 0;
 #pragma unroll
       for (int i = 0; i < 6; ++i) n += (uint32_t)((m[i] >> lane) & 1ull);
       g.cell[r] = (wi << 6) | lane;
-      g.parent[r] = base + (uint32_t)__popcll(fr & ((1ull << first) - 1ull));  // the run is one tree already, its first cell the root
+      g.parent[r] = base + lane_rank(fr, first);  // the run is one tree already, its first cell the root
       g.faces[r] = (uint8_t)n;
     }
   }
@@ -244,7 +197,8 @@ __global__ __launch_bounds__(FR_TPB) void k_frontier_label(Front g) {
   const int xy_n = g.x_n + g.y_n;
   for (uint32_t r = blockIdx.x * FR_TPB + threadIdx.x; r < n; r += gridDim.x * FR_TPB) {
     const uint32_t c = g.cell[r];
-    const int x = (int)(c & (N[0] - 1u)), y = (int)((c >> g.x_n) & (N[1] - 1u)), z = (int)(c >> xy_n);
+    int x, y, z;
+    cell_xyz(g.x_n, g.y_n, c, x, y, z);
 #pragma unroll
     for (int k = 0; k < 13; ++k) {  // the neighbours before the cell in cell order: (dz, dy, dx) < (0, 0, 0)
       const int dx = k % 3 - 1, dy = (k / 3) % 3 - 1, dz = k / 9 - 1;
@@ -255,7 +209,7 @@ __global__ __launch_bounds__(FR_TPB) void k_frontier_label(Front g) {
       const uint32_t cn = nx | (ny << g.x_n) | (nz << xy_n), wi = cn >> 6, b = cn & 63u;
       const u64 fw = g.front_m[wi];
       if (!((fw >> b) & 1ull)) continue;
-      unite(g.parent, r, g.pre[wi] + (uint32_t)__popcll(fw & ((1ull << b) - 1ull)));
+      unite(g.parent, r, g.pre[wi] + lane_rank(fw, b));
     }
   }
 }
@@ -282,7 +236,6 @@ __device__ __forceinline__ void send_root(FAcc *a, const uint32_t (&v)[FA_VALUES
 __global__ __launch_bounds__(FR_TPB) void k_frontier_accumulate(Front g) {
   const uint32_t n = g.meta[META_N_USED];
   const uint32_t lane = threadIdx.x & 63u;
-  const int xy_n = g.x_n + g.y_n;
   // a wave takes FA_RUN consecutive chunks of 64 ranks and carries the totals of the root it reduced last (wave-uniform
   // values) from chunk to chunk: a large cluster's cells are long runs of ranks, and its accumulator sees one set of
   // atomics per change of root instead of one per chunk
@@ -299,7 +252,8 @@ __global__ __launch_bounds__(FR_TPB) void k_frontier_accumulate(Front g) {
         rt = a;
         g.root[r] = rt;
         const uint32_t c = g.cell[r];
-        const uint32_t x = c & ((1u << g.x_n) - 1u), y = (c >> g.x_n) & ((1u << g.y_n) - 1u), z = c >> xy_n;
+        uint32_t x, y, z;
+        cell_xyz(g.x_n, g.y_n, c, x, y, z);
         own[0] = x, own[1] = y, own[2] = z, own[3] = 1u, own[4] = g.faces[r];
         own[5] = ~x, own[6] = ~y, own[7] = x, own[8] = y, own[9] = z;
       }
@@ -439,27 +393,23 @@ hipError_t launch_frontiers_build(const Dims &d, const Frame &f, const State &st
   const uint32_t by_word = (g.nw + FC_WAVES * FC_U - 1) / (FC_WAVES * FC_U);
   const uint32_t by_rank = std::min<uint32_t>((g.cap + FR_TPB) / FR_TPB, FR_GRID);  // (>= 1: rank n of k_frontier_flags too)
   hipError_t e;
-#define FRONT_LAUNCH(kernel, grid, tpb, ...)                         \
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(tpb), 0, s, __VA_ARGS__); \
-  if ((e = hipGetLastError()) != hipSuccess) return e
-  FRONT_LAUNCH(k_frontier_classify, by_word, FC_TPB, d, f, reinterpret_cast<const uint2 *>(st.res), g.free_m, g.unk_m, g.nw);
-  FRONT_LAUNCH(k_frontier_mask, (g.nw + FR_TPB - 1) / FR_TPB, FR_TPB, g);
+  LAYER_LAUNCH(k_frontier_classify, by_word, FC_TPB, s, d, f, reinterpret_cast<const uint2 *>(st.res), g.free_m, g.unk_m, g.nw);
+  LAYER_LAUNCH(k_frontier_mask, (g.nw + FR_TPB - 1) / FR_TPB, FR_TPB, s, g);
   const ScanScratch l = front_scan_layout(d);
   exclusive_scan_u32(g.pre, g.pre, g.nw, scan_scratch + l.words, s);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  FRONT_LAUNCH(k_frontier_compact, by_word, FC_TPB, g);
+  LAYER_LAUNCH(k_frontier_compact, by_word, FC_TPB, s, g);
   if (flags & SDM_FRONTIERS_FACE_CONNECTED) {
-    FRONT_LAUNCH(k_frontier_label<true>, by_rank, FR_TPB, g);
+    LAYER_LAUNCH(k_frontier_label<true>, by_rank, FR_TPB, s, g);
   } else {
-    FRONT_LAUNCH(k_frontier_label<false>, by_rank, FR_TPB, g);
+    LAYER_LAUNCH(k_frontier_label<false>, by_rank, FR_TPB, s, g);
   }
-  FRONT_LAUNCH(k_frontier_accumulate, by_rank, FR_TPB, g);
-  FRONT_LAUNCH(k_frontier_flags, by_rank, FR_TPB, g, min_cells);
+  LAYER_LAUNCH(k_frontier_accumulate, by_rank, FR_TPB, s, g);
+  LAYER_LAUNCH(k_frontier_flags, by_rank, FR_TPB, s, g, min_cells);
   exclusive_scan_u32(g.idx, g.idx, (size_t)g.cap + 1, scan_scratch + (scan_is_one_launch((size_t)g.cap + 1) ? l.flags_one : l.flags_two), s,
                      g.meta + META_N_SCAN);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  FRONT_LAUNCH(k_frontier_table, by_rank, FR_TPB, d, f, g);
-#undef FRONT_LAUNCH
+  LAYER_LAUNCH(k_frontier_table, by_rank, FR_TPB, s, d, f, g);
   return hipSuccess;
 }
 

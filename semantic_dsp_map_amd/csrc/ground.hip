@@ -326,15 +326,10 @@ __global__ __launch_bounds__(GQ_TPB) void k_query_ground(Dims d, Frame f, Grid g
                                                          sdm_ground_result *__restrict__ out) {
   const uint32_t p = blockIdx.x * GQ_TPB + threadIdx.x;
   if (p >= n) return;
-  const int N[3] = {(int)d.NX, (int)d.NY, (int)d.NZ};
+  const float pos[3] = {xyz[3 * (size_t)p], xyz[3 * (size_t)p + 1], xyz[3 * (size_t)p + 2]};
   int cell[3];
-  bool ok = true;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float u = map_u(d, f, a, xyz[3 * (size_t)p + a]);
-    ok = ok && u >= 0.f && u < (float)N[a];          // (NaN and +-inf fail it)
-    cell[a] = (int)floorf(ok ? u : 0.5f);            // (no cast of a value outside the map)
-  }
+  float u[3];
+  const bool ok = point_coords(d, f, pos, cell, u);
   sdm_ground_result r;
   r.col = INVALID_INDEX;
   r.d2 = INVALID_INDEX;
@@ -479,10 +474,6 @@ hipError_t launch_ground_build(const Dims &d, const Frame &f, const Grid &g, con
   return hipGetLastError();
 }
 
-sdm_status refuse(const char *what, int line, const char *why) {
-  set_error(what, __FILE__, line, why);
-  return SDM_ERR_INVALID_ARGUMENT;
-}
 
 }  // namespace
 
@@ -496,12 +487,12 @@ extern "C" {
 sdm_status sdm_ground_update(sdm_map *m, const sdm_ground_options *o) {
   const char *what = "sdm_ground_update";
   if (!m) return SDM_ERR_INVALID_ARGUMENT;
-  if (!o) return refuse(what, __LINE__, "no options");
-  if (o->flags & ~ALL_FLAGS) return refuse(what, __LINE__, "unknown flag bits");
-  if (o->up_axis < 0 || o->up_axis > 2 || (o->up_sign != 1 && o->up_sign != -1)) return refuse(what, __LINE__, "up_axis not in 0..2 or up_sign not +1 / -1");
+  if (!o) return LAYER_REFUSE(what, "no options");
+  if (o->flags & ~ALL_FLAGS) return LAYER_REFUSE(what, "unknown flag bits");
+  if (o->up_axis < 0 || o->up_axis > 2 || (o->up_sign != 1 && o->up_sign != -1)) return LAYER_REFUSE(what, "up_axis not in 0..2 or up_sign not +1 / -1");
   const int32_t NA = (int32_t)(o->up_axis == 0 ? m->d.NX : (o->up_axis == 1 ? m->d.NY : m->d.NZ));
-  if (o->h_lo < 0 || o->h_lo > o->h_hi || o->h_hi >= NA) return refuse(what, __LINE__, "the band needs 0 <= h_lo <= h_hi < N along the up axis");
-  if (o->clearance > 255u || o->max_step > 65535u) return refuse(what, __LINE__, "clearance > 255 or max_step > 65535");
+  if (o->h_lo < 0 || o->h_lo > o->h_hi || o->h_hi >= NA) return LAYER_REFUSE(what, "the band needs 0 <= h_lo <= h_hi < N along the up axis");
+  if (o->clearance > 255u || o->max_step > 65535u) return LAYER_REFUSE(what, "clearance > 255 or max_step > 65535");
   SDM_TRY(layer_check(m, what, nullptr, GROUND));
   HIP_TRY(hipSetDevice(m->device));
   GroundLayer &L = m->ground;

@@ -202,8 +202,7 @@ __global__ __launch_bounds__(IA_TPB) void k_instances_accumulate(Dims d, Frame f
       } else {
         const uint32_t c = c0 + lane;
         if (c < d.V) {
-          const uint32_t x = c & (d.NX - 1), y = (c >> d.x_n) & (d.NY - 1), z = c >> xy_n;
-          w[u] = res[cell_voxel(d, f, (int)x, (int)y, (int)z)];
+          w[u] = res[word_voxel(d, f, c)];
         }
       }
     }
@@ -247,7 +246,8 @@ __global__ __launch_bounds__(IA_TPB) void k_instances_accumulate(Dims d, Frame f
       s.wmax = max(s.wmax, wim);
     } else {
       const uint32_t c = c0 + lane;
-      const unsigned long long x = c & (d.NX - 1), y = (c >> d.x_n) & (d.NY - 1), z = c >> xy_n;
+      unsigned long long x, y, z;
+      cell_xyz(d, c, x, y, z);
       const unsigned long long a[A64] = {x, y, z, x * x, y * y, z * z, x * y, x * z, y * z, ~(((unsigned long long)c << 8) | label)};
       const uint32_t b[A32] = {1u, guessed, ~(uint32_t)x, ~(uint32_t)y, ~(uint32_t)z, (uint32_t)x, (uint32_t)y, (uint32_t)z, ~label, label, wim};
       send_track(tab, keys, g, track, a, b);

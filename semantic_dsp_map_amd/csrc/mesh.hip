@@ -35,7 +35,7 @@
 //               atomics on shared counters.  The faces of a build over capacity count as not emitted.
 // The corner mask is zeroed at the start of every build.  The counts are only known on the device and sdm_mesh_update
 // does not wait: every kernel runs on a grid fixed by the map, and the two over the lists read the totals behind the
-// scans.  (coord_is and the neighbour shifts restate frontiers.hip's: the units of the layers share headers, not code.)
+// scans.
 #include "sdm_layer.h"
 #include "sdm_map.h"
 
@@ -51,8 +51,6 @@ static_assert(sizeof(sdm_mesh_vertex) == SDM_MESH_BYTES_PER_VERTEX, "sdm.h state
 namespace sdm {
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int MC_TPB = 256, MC_WAVES = MC_TPB / 64;
 constexpr int MC_U = 8;        // chunks (words) a wave of k_mesh_classify takes
@@ -102,18 +100,8 @@ __device__ __forceinline__ bool is_solid(const Mesh &g, uint32_t w1) {
 __global__ __launch_bounds__(MC_TPB) void k_mesh_classify(Dims d, Frame f, const uint2 *__restrict__ res, Mesh g) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t first = (blockIdx.x * MC_WAVES + (threadIdx.x >> 6)) * MC_U;
-  const uint32_t xy_n = (uint32_t)(d.x_n + d.y_n);
   uint32_t w[MC_U];
-#pragma unroll
-  for (int u = 0; u < MC_U; ++u) {  // every load first (V is a multiple of 64: a chunk inside the map is whole)
-    const uint32_t chunk = first + (uint32_t)u;
-    w[u] = RES_UNKNOWN_W1;
-    if (chunk < g.nw) {
-      const uint32_t c = (chunk << 6) + lane;
-      const uint32_t x = c & (d.NX - 1), y = (c >> d.x_n) & (d.NY - 1), z = c >> xy_n;
-      w[u] = res[cell_voxel(d, f, (int)x, (int)y, (int)z)].y;
-    }
-  }
+  load_w1(d, f, res, first, g.nw, lane, w);
 #pragma unroll
   for (int u = 0; u < MC_U; ++u) {
     const uint32_t chunk = first + (uint32_t)u;
@@ -130,41 +118,6 @@ __global__ __launch_bounds__(MC_TPB) void k_mesh_classify(Dims d, Frame f, const
 }
 
 // ---- the face masks ------------------------------------------------------------------------------------------------
-// the low `width` bits of every `period` bits (powers of two, width <= period <= 64)
-__device__ __forceinline__ u64 rep_mask(uint32_t period, uint32_t width) {
-  u64 m = width >= 64u ? ~0ull : (1ull << width) - 1ull;
-  for (uint32_t p = period; p < 64u; p <<= 1) m |= m << p;
-  return m;
-}
-
-// the bits b of the word that begins at cell c0 (a multiple of 64) whose coordinate ((c0 + b) >> s) & (2^nb - 1) is t
-__device__ __forceinline__ u64 coord_is(uint32_t c0, int s, int nb, uint32_t t) {
-  const uint32_t N = 1u << nb;
-  if (s >= 6) return ((c0 >> s) & (N - 1u)) == t ? ~0ull : 0ull;          // the whole word has one coordinate
-  if (s + nb <= 6) return rep_mask(1u << (s + nb), 1u << s) << (t << s);  // the word holds every coordinate, 64 >> (s + nb) times
-  const uint32_t k = t - ((c0 >> s) & (N - 1u));                          // the word holds 64 >> s coordinates from its first
-  if (k >= (64u >> s)) return 0ull;
-  return ((1ull << (1u << s)) - 1ull) << (k << s);
-}
-
-// bit b: the bit of cell c0 + b - 2^s (down) / c0 + b + 2^s (up) in mask; cells beyond the ends of the mask read 0
-__device__ __forceinline__ u64 bits_down(const u64 *__restrict__ mask, uint32_t wi, int s) {
-  if (s >= 6) {
-    const uint32_t k = 1u << (s - 6);
-    return wi >= k ? mask[wi - k] : 0ull;
-  }
-  const uint32_t D = 1u << s;
-  return (mask[wi] << D) | (wi > 0u ? mask[wi - 1u] >> (64u - D) : 0ull);
-}
-__device__ __forceinline__ u64 bits_up(const u64 *__restrict__ mask, uint32_t wi, uint32_t nw, int s) {
-  if (s >= 6) {
-    const uint32_t k = 1u << (s - 6);
-    return wi + k < nw ? mask[wi + k] : 0ull;
-  }
-  const uint32_t D = 1u << s;
-  return (mask[wi] >> D) | (wi + 1u < nw ? mask[wi + 1u] << (64u - D) : 0ull);
-}
-
 // Per direction (x-, x+, y-, y+, z-, z+) of word wi, whose solid cells are `solid`: f = the cells that have a face there
 // under the skip flags, and of those k1 / k2 / k3 the faces of kind 1, 2, 3 (the rest are of kind 0).
 __device__ __forceinline__ void face_masks(const Mesh &g, uint32_t wi, u64 solid, u64 (&f)[6], u64 (&k1)[6], u64 (&k2)[6], u64 (&k3)[6]) {
@@ -243,7 +196,8 @@ __global__ __launch_bounds__(MF_TPB) void k_mesh_faces(Mesh g) {
       const u64 r0 = (u0 >> r) & row_mask, r1 = (u1 >> r) & row_mask;
       if (!(r0 | r1)) continue;
       const uint32_t c = c0 + r;
-      const uint32_t x = c & (NX - 1u), y = (c >> g.x_n) & (NY - 1u), z = c >> (g.x_n + g.y_n);
+      uint32_t x, y, z;
+      cell_xyz(g.x_n, g.y_n, c, x, y, z);
       const uint32_t o = x + (NX + 1u) * ((y + dy) + (NY + 1u) * (z + dz));  // the corner word of the row's first corner
       const u64 lo = r0 | (r1 << 1), hi = r1 >> 63;                          // L + 1 <= 65 bits from corner o on
       const uint32_t sh = o & 63u, w = o >> 6;
@@ -293,7 +247,8 @@ __global__ __launch_bounds__(MF_TPB) void k_mesh_emit(Dims d, Frame fr, const ui
     const uint32_t b = (uint32_t)__builtin_ctzll(todo);
     todo &= todo - 1ull;
     const uint32_t c = (wi << 6) | b;
-    const uint32_t x = c & (NX - 1u), y = (c >> g.x_n) & (NY - 1u), z = c >> (g.x_n + g.y_n);
+    uint32_t x, y, z;
+    cell_xyz(g.x_n, g.y_n, c, x, y, z);
     const uint32_t w1 = res[cell_voxel(d, fr, (int)x, (int)y, (int)z)].y;  // track | label << 16 | occ << 24: the record's second word
     // the ranks of the cell's eight corners, every load issued before the first is used; a corner no face of the build
     // uses gets a number nobody reads
@@ -309,7 +264,7 @@ __global__ __launch_bounds__(MF_TPB) void k_mesh_emit(Dims d, Frame fr, const ui
         bit[o] = cw & 63u;
       }
 #pragma unroll
-      for (int o = 0; o < 8; ++o) id[o] = pre[o] + (uint32_t)__popcll(cm[o] & ((1ull << bit[o]) - 1ull));
+      for (int o = 0; o < 8; ++o) id[o] = pre[o] + lane_rank(cm[o], bit[o]);
     }
 #pragma unroll
     for (int dir = 0; dir < 6; ++dir) {
@@ -343,7 +298,7 @@ __global__ __launch_bounds__(MC_TPB) void k_mesh_vertices(Mesh g) {
 #pragma unroll
   for (int u = 0; u < MV_U; ++u) {
     if (!((cm[u] >> lane) & 1ull)) continue;
-    const uint32_t r = pre[u] + (uint32_t)__popcll(cm[u] & ((1ull << lane) - 1ull));  // < n_verts <= cap_v
+    const uint32_t r = pre[u] + lane_rank(cm[u], lane);  // < n_verts <= cap_v
     const uint32_t cw = ((first + (uint32_t)u) << 6) | lane, t = cw / RX;
     sdm_mesh_vertex v;
     v.i = (uint16_t)(cw - t * RX);
@@ -428,28 +383,19 @@ hipError_t launch_mesh_build(const Dims &d, const Frame &f, const State &st, con
   const uint2 *res = reinterpret_cast<const uint2 *>(st.res);
   const uint32_t classify_waves = (g.nw + MC_U - 1) / MC_U, corner_waves = (g.ncw + MV_U - 1) / MV_U;
   hipError_t e;
-#define MESH_LAUNCH(kernel, grid, tpb, ...)                             \
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(tpb), 0, s, __VA_ARGS__); \
-  if ((e = hipGetLastError()) != hipSuccess) return e
   if ((e = hipMemsetAsync(g.corner_m, 0, (size_t)g.ncw * sizeof(u64), s)) != hipSuccess) return e;  // no corner of the build before
-  MESH_LAUNCH(k_mesh_classify, (classify_waves + MC_WAVES - 1) / MC_WAVES, MC_TPB, d, f, res, g);
-  MESH_LAUNCH(k_mesh_faces, (g.nw + MF_TPB - 1) / MF_TPB, MF_TPB, g);
-  MESH_LAUNCH(k_mesh_corner_count, (g.ncw + MF_TPB - 1) / MF_TPB, MF_TPB, g);
+  LAYER_LAUNCH(k_mesh_classify, (classify_waves + MC_WAVES - 1) / MC_WAVES, MC_TPB, s, d, f, res, g);
+  LAYER_LAUNCH(k_mesh_faces, (g.nw + MF_TPB - 1) / MF_TPB, MF_TPB, s, g);
+  LAYER_LAUNCH(k_mesh_corner_count, (g.ncw + MF_TPB - 1) / MF_TPB, MF_TPB, s, g);
   const ScanScratch l = mesh_scan_layout(d);
   exclusive_scan_u32(g.pre_f, g.pre_f, (size_t)g.nw + 1, scan_scratch + l.faces, s);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   exclusive_scan_u32(g.pre_c, g.pre_c, (size_t)g.ncw + 1, scan_scratch + l.corners, s);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  MESH_LAUNCH(k_mesh_emit, (g.nw + MF_TPB - 1) / MF_TPB, MF_TPB, d, f, res, g);
-  MESH_LAUNCH(k_mesh_vertices, (corner_waves + MC_WAVES - 1) / MC_WAVES, MC_TPB, g);
-  MESH_LAUNCH(k_mesh_stats, MS_ROWS, 64, g);
-#undef MESH_LAUNCH
+  LAYER_LAUNCH(k_mesh_emit, (g.nw + MF_TPB - 1) / MF_TPB, MF_TPB, s, d, f, res, g);
+  LAYER_LAUNCH(k_mesh_vertices, (corner_waves + MC_WAVES - 1) / MC_WAVES, MC_TPB, s, g);
+  LAYER_LAUNCH(k_mesh_stats, MS_ROWS, 64, s, g);
   return hipSuccess;
-}
-
-sdm_status refuse(const char *what, int line, const char *why) {
-  set_error(what, __FILE__, line, why);
-  return SDM_ERR_INVALID_ARGUMENT;
 }
 
 constexpr LayerName MESH = {"the mesh", "mesh", "sdm_mesh_update", false};
@@ -485,11 +431,11 @@ extern "C" {
 sdm_status sdm_mesh_update(sdm_map *m, const sdm_mesh_options *o) {
   const char *what = "sdm_mesh_update";
   if (!m) return SDM_ERR_INVALID_ARGUMENT;
-  if (!o) return refuse(what, __LINE__, "no options");
-  if (o->flags & ~ALL_FLAGS) return refuse(what, __LINE__, "unknown flag bits");
-  if ((o->flags & SDM_MESH_STATIC_ONLY) && (o->flags & SDM_MESH_MOVABLE_ONLY)) return refuse(what, __LINE__, "both STATIC_ONLY and MOVABLE_ONLY");
-  if (o->track < -1 || o->track > 65535) return refuse(what, __LINE__, "track not in -1..65535");
-  if (o->max_faces < 0 || o->max_vertices < 0) return refuse(what, __LINE__, "a negative capacity");
+  if (!o) return LAYER_REFUSE(what, "no options");
+  if (o->flags & ~ALL_FLAGS) return LAYER_REFUSE(what, "unknown flag bits");
+  if ((o->flags & SDM_MESH_STATIC_ONLY) && (o->flags & SDM_MESH_MOVABLE_ONLY)) return LAYER_REFUSE(what, "both STATIC_ONLY and MOVABLE_ONLY");
+  if (o->track < -1 || o->track > 65535) return LAYER_REFUSE(what, "track not in -1..65535");
+  if (o->max_faces < 0 || o->max_vertices < 0) return LAYER_REFUSE(what, "a negative capacity");
   SDM_TRY(layer_check(m, what, nullptr, MESH));
   HIP_TRY(hipSetDevice(m->device));
   const Dims &d = m->d;
@@ -548,7 +494,7 @@ sdm_status sdm_get_mesh_info(sdm_map *m, sdm_mesh_info *info, float origin[3]) {
 sdm_status sdm_get_mesh_faces(sdm_map *m, sdm_mesh_face *faces, uint32_t *quads, int64_t cap, int64_t *n_out) {
   const char *what = "sdm_get_mesh_faces";
   if (!m) return SDM_ERR_INVALID_ARGUMENT;
-  if (cap < 0 || !n_out) return refuse(what, __LINE__, "cap < 0 or no n_out");
+  if (cap < 0 || !n_out) return LAYER_REFUSE(what, "cap < 0 or no n_out");
   SDM_TRY(layer_check(m, what, &m->mesh, MESH));
   uint32_t meta[META_WORDS], st[ST_WORDS];
   SDM_TRY(mesh_meta(m, what, meta, st, true));
@@ -566,7 +512,7 @@ sdm_status sdm_get_mesh_faces(sdm_map *m, sdm_mesh_face *faces, uint32_t *quads,
 sdm_status sdm_get_mesh_vertices(sdm_map *m, sdm_mesh_vertex *corners, float *xyz, int64_t cap, int64_t *n_out) {
   const char *what = "sdm_get_mesh_vertices";
   if (!m) return SDM_ERR_INVALID_ARGUMENT;
-  if (cap < 0 || !n_out) return refuse(what, __LINE__, "cap < 0 or no n_out");
+  if (cap < 0 || !n_out) return LAYER_REFUSE(what, "cap < 0 or no n_out");
   SDM_TRY(layer_check(m, what, &m->mesh, MESH));
   uint32_t meta[META_WORDS], st[ST_WORDS];
   SDM_TRY(mesh_meta(m, what, meta, st, true));

@@ -5,8 +5,8 @@
 // last issued frame (Frame: map center, ring offsets) come by value, so a query enqueued between two frames answers for
 // the frame before it whatever the host does next.  Segments and boxes only need the second word of a result (track,
 // label, occ): they gather 4 bytes per cell.
-#include "sdm_layer.h"
 #include "sdm_map.h"
+#include "sdm_walk.h"
 
 #pragma clang fp contract(off)
 
@@ -31,23 +31,12 @@ __global__ __launch_bounds__(QTPB) void k_query_points(Dims d, Frame f, const fl
   if (voxel_out) voxel_out[i] = v;
 }
 
-// ---- segments: one lane per segment, a 3-D DDA in batches of SEG_K cells -------------------------------------------
-// The cells a segment visits follow from its end points alone; only "stop here" depends on the map.  So the DDA walks
-// SEG_K cells ahead, the SEG_K loads are issued together, and then their results are tested: one memory round trip per
-// SEG_K cells instead of one per cell (a 100-cell segment taken cell by cell would wait ~100 x 900 cycles).  Every load
-// of a batch feeds the stop mask below unconditionally, so none of them can be sunk behind an earlier cell's test.
-// The DDA runs in double: crossing parameters t = (plane - u_a) * (1 / (u_b - u_a)) are computed fresh from the end
-// points for every plane (no accumulated increments), so a cell sequence differs from the exact one only where two crossings lie
-// within rounding of each other.
-constexpr int SEG_K = 8;
-enum : int { SEG_CELL = 0, SEG_OUT = 1, SEG_END = 2 };
-
+// ---- segments: one lane per segment, the walk of sdm_walk.h ---------------------------------------------------------
 __global__ __launch_bounds__(QTPB) void k_query_segments(Dims d, Frame f, const float *__restrict__ ab, uint32_t n,
                                                          const uint2 *__restrict__ res, sdm_segment_hit *__restrict__ out,
                                                          int unknown_blocks) {
   const uint32_t i = blockIdx.x * QTPB + threadIdx.x;
   if (i >= n) return;
-  const int N[3] = {(int)d.NX, (int)d.NY, (int)d.NZ};
   float ua[3], ub[3];
   bool finite = true;
 #pragma unroll
@@ -59,79 +48,30 @@ __global__ __launch_bounds__(QTPB) void k_query_segments(Dims d, Frame f, const 
   float hit_t = -1.f;
   uint32_t hit_v = INVALID_INDEX, hit_w = RES_UNKNOWN_W1;
   int cells = 0;
-  // the state of the walk: current cell c, the t at which it was entered, per axis the t of the next plane
-  int c[3] = {0, 0, 0}, step[3] = {0, 0, 0};
-  double A[3], inv[3], tn[3];
-  double t_cur = 0.0;
-  int kind = SEG_END;  // of the current cell
+  SegWalk sw;
+  sw.kind = SEG_END;
   if (!finite) {
     if (unknown_blocks) hit_t = 0.f;
   } else {
-    bool inside = true, empty = false;
-    double t_in = -INFINITY, t_out = INFINITY;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      A[a] = (double)ua[a];
-      const double D = (double)ub[a] - A[a];
-      inside = inside && ua[a] >= 0.f && ua[a] < (float)N[a];
-      if (D == 0.0) {
-        empty = empty || !(ua[a] >= 0.f && ua[a] < (float)N[a]);
-        inv[a] = 0.0;
-      } else {
-        inv[a] = 1.0 / D;
-        const double t0 = (0.0 - A[a]) * inv[a], t1 = ((double)N[a] - A[a]) * inv[a];
-        t_in = fmax(t_in, fmin(t0, t1));
-        t_out = fmin(t_out, fmax(t0, t1));
-      }
-      step[a] = D > 0.0 ? 1 : (D < 0.0 ? -1 : 0);
-    }
-    if (inside) {
-      kind = SEG_CELL;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) c[a] = (int)floorf(ua[a]);
+    const SegClip cl = seg_begin(sw, d, ua, ub);
+    if (cl.inside) {
+      seg_enter_inside(sw, ua);
     } else if (unknown_blocks) {
       hit_t = 0.f;  // a lies outside the map, which blocks
-    } else if (!empty && t_in <= 1.0 && t_out > 0.0 && t_in < t_out) {
-      // clipped: the walk starts where the segment enters the map (rounding at the face is clamped back into the map)
-      kind = SEG_CELL;
-      t_cur = fmax(t_in, 0.0);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) c[a] = min(max((int)floor(A[a] + t_cur * ((double)ub[a] - A[a])), 0), N[a] - 1);
+    } else if (cl.enters()) {
+      seg_enter_clipped(sw, cl, ub);
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) tn[a] = step[a] == 0 ? INFINITY : ((double)(c[a] + (step[a] > 0)) - A[a]) * inv[a];
+    seg_planes(sw);
   }
-  while (kind != SEG_END) {
+  while (sw.kind != SEG_END) {
     uint32_t vox[SEG_K], w[SEG_K];
     float tin[SEG_K];
     int kd[SEG_K];
 #pragma unroll
     for (int k = 0; k < SEG_K; ++k) {  // the next SEG_K cells: arithmetic only
-      kd[k] = kind;
-      tin[k] = (float)t_cur;
-      vox[k] = kind == SEG_CELL ? cell_voxel(d, f, c[0], c[1], c[2]) : INVALID_INDEX;
-      if (kind == SEG_CELL) {
-        int ax = 0;  // the plane crossed next: x before y before z at equal t
-        double tm = tn[0];
-        if (tn[1] < tm) { ax = 1; tm = tn[1]; }
-        if (tn[2] < tm) { ax = 2; tm = tn[2]; }
-        if (tm > 1.0) {
-          kind = SEG_END;
-        } else {
-          const int cn = (ax == 0 ? c[0] : ax == 1 ? c[1] : c[2]) + (ax == 0 ? step[0] : ax == 1 ? step[1] : step[2]);
-          const int na = ax == 0 ? N[0] : ax == 1 ? N[1] : N[2];
-#pragma unroll
-          for (int a = 0; a < 3; ++a)
-            if (a == ax) {
-              c[a] = cn;
-              tn[a] = ((double)(cn + (step[a] > 0)) - A[a]) * inv[a];
-            }
-          t_cur = tm;
-          if (cn < 0 || cn >= na) kind = SEG_OUT;
-        }
-      } else {
-        kind = SEG_END;  // (after the cell outside the map there is nothing: the map is convex)
-      }
+      kd[k] = sw.kind;
+      tin[k] = (float)sw.t_cur;
+      seg_advance(sw, vox[k], [&](int x, int y, int z) { return cell_voxel(d, f, x, y, z); });
     }
 #pragma unroll
     for (int k = 0; k < SEG_K; ++k) w[k] = res[kd[k] == SEG_CELL ? vox[k] : 0u].y;  // SEG_K independent loads

@@ -39,8 +39,6 @@ namespace sdm {
 
 namespace {
 
-typedef unsigned long long u64;
-
 constexpr int RC_TPB = 256, RC_WAVES = RC_TPB / 64;
 constexpr int RC_U = 8;             // chunks (mask words) a wave takes
 constexpr int RT_TPB = 256;         // k_reach_relax: up to two cells of the tile and four of the halo region a thread
@@ -102,23 +100,20 @@ __global__ __launch_bounds__(RC_TPB) void k_reach_classify(Dims d, Frame f, cons
                                                            u64 *__restrict__ trav, uint32_t *__restrict__ cost, uint32_t nw) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t first = (blockIdx.x * RC_WAVES + (threadIdx.x >> 6)) * RC_U;
-  const uint32_t xy_n = (uint32_t)(d.x_n + d.y_n);
   uint32_t w[RC_U], s[RC_U];
+  if (FIELD) {
 #pragma unroll
-  for (int u = 0; u < RC_U; ++u) {  // every load first (V is a multiple of 64: a chunk inside the map is whole)
-    const uint32_t chunk = first + (uint32_t)u;
-    w[u] = 0x01000000u;
-    s[u] = INVALID_INDEX;
-    if (chunk < nw) {
-      const uint32_t c = (chunk << 6) + lane;
-      if (FIELD) {
-        w[u] = snap[c];
-        s[u] = site[c];
-      } else {
-        const uint32_t x = c & (d.NX - 1), y = (c >> d.x_n) & (d.NY - 1), z = c >> xy_n;
-        w[u] = res[cell_voxel(d, f, (int)x, (int)y, (int)z)].y;
+    for (int u = 0; u < RC_U; ++u) {  // every load first, like load_w1's: the field's words are in map-index order already
+      const uint32_t chunk = first + (uint32_t)u;
+      w[u] = RES_UNKNOWN_W1;
+      s[u] = INVALID_INDEX;
+      if (chunk < nw) {
+        w[u] = snap[(chunk << 6) + lane];
+        s[u] = site[(chunk << 6) + lane];
       }
     }
+  } else {
+    load_w1(d, f, res, first, nw, lane, w);
   }
 #pragma unroll
   for (int u = 0; u < RC_U; ++u) {
@@ -128,9 +123,10 @@ __global__ __launch_bounds__(RC_TPB) void k_reach_classify(Dims d, Frame f, cons
     const int occ = occ_of(w[u]);
     bool ok = occ == 0 || (through_unknown && occ == -1);
     if (FIELD && s[u] != INVALID_INDEX) {  // (no site: no obstacle anywhere, d2 = 0xffffffff passes)
-      const int dx = (int)(c & (d.NX - 1)) - (int)(s[u] & (d.NX - 1));
-      const int dy = (int)((c >> d.x_n) & (d.NY - 1)) - (int)((s[u] >> d.x_n) & (d.NY - 1));
-      const int dz = (int)(c >> xy_n) - (int)(s[u] >> xy_n);
+      int x, y, z, sx, sy, sz;
+      cell_xyz(d, c, x, y, z);
+      cell_xyz(d, s[u], sx, sy, sz);
+      const int dx = x - sx, dy = y - sy, dz = z - sz;
       ok = ok && (uint32_t)(dx * dx + dy * dy + dz * dz) >= min_d2;
     }
     const u64 tm = __ballot(ok);
@@ -140,24 +136,16 @@ __global__ __launch_bounds__(RC_TPB) void k_reach_classify(Dims d, Frame f, cons
 }
 
 // ---- goals and starts ------------------------------------------------------------------------------------------------
-// entry i as a cell word: a cell word itself, or the cell of a point (k_query_distance's rule); INVALID_INDEX outside the
-// map and for non-finite points
+// entry i as a cell word: a cell word itself, or the cell of a point (point_cell); INVALID_INDEX outside the map and for
+// non-finite points
 __device__ __forceinline__ uint32_t entry_cell(const Dims &d, const Frame &f, const float *__restrict__ xyz, const uint32_t *__restrict__ cells,
                                                uint32_t i) {
   if (cells) {
     const uint32_t c = cells[i];
     return c < d.V ? c : INVALID_INDEX;
   }
-  const int N[3] = {(int)d.NX, (int)d.NY, (int)d.NZ};
-  uint32_t cell[3];
-  bool ok = true;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float u = map_u(d, f, a, xyz[3 * (size_t)i + a]);
-    ok = ok && u >= 0.f && u < (float)N[a];  // (NaN and +-inf fail it)
-    cell[a] = (uint32_t)(int)floorf(ok ? u : 0.5f);
-  }
-  return ok ? (cell[0] | (cell[1] << d.x_n) | (cell[2] << (d.x_n + d.y_n))) : INVALID_INDEX;
+  const float p[3] = {xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]};
+  return point_cell(d, f, p);
 }
 
 __device__ __forceinline__ bool is_traversable(const Reach &g, uint32_t c) { return (g.trav[c >> 5] >> (c & 31u)) & 1u; }
@@ -169,8 +157,9 @@ __global__ __launch_bounds__(RQ_TPB) void k_reach_seed(Dims d, Frame f, Reach g,
   const uint32_t c = entry_cell(d, f, xyz, cells, i);
   if (c == INVALID_INDEX || !is_traversable(g, c)) return;
   if (atomicMin(g.cost + c, 0u) != 0u) atomicAdd(g.meta + M_STARTS, 1u);
-  const int xy_n = g.x_n + g.y_n;
-  const int t[3] = {(int)(c & (d.NX - 1)) >> g.tx_n, (int)((c >> g.x_n) & (d.NY - 1)) >> g.ty_n, (int)(c >> xy_n) >> g.tz_n};
+  int x, y, z;
+  cell_xyz(d, c, x, y, z);
+  const int t[3] = {x >> g.tx_n, y >> g.ty_n, z >> g.tz_n};
   const int nt[3] = {1 << (g.x_n - g.tx_n), 1 << (g.y_n - g.ty_n), 1 << (g.z_n - g.tz_n)};
   for (int k = 0; k < 27; ++k) {  // the tile and its neighbours: a start on a tile's border is news for their halos
     const int a = t[0] + move_d(k, 0), b = t[1] + move_d(k, 1), e = t[2] + move_d(k, 2);
@@ -407,7 +396,9 @@ __global__ __launch_bounds__(RQ_TPB) void k_query_reach(Dims d, Frame f, Reach g
       next = 13u;
       if (v != 0u) {
         uint32_t nc, nv;
-        descent_step<FACE>(g, (int)(c & (d.NX - 1)), (int)((c >> d.x_n) & (d.NY - 1)), (int)(c >> (d.x_n + d.y_n)), v, next, nc, nv);
+        int x, y, z;
+        cell_xyz(d, c, x, y, z);
+        descent_step<FACE>(g, x, y, z, v, next, nc, nv);
       }
     }
   }
@@ -438,7 +429,9 @@ __global__ __launch_bounds__(RQ_TPB) void k_reach_paths(Dims d, Frame f, Reach g
         ++len;
         if (v == 0u || len >= longest) break;
         uint32_t next, nc, nv;
-        descent_step<FACE>(g, (int)(c & (d.NX - 1)), (int)((c >> d.x_n) & (d.NY - 1)), (int)(c >> (d.x_n + d.y_n)), v, next, nc, nv);
+        int x, y, z;
+        cell_xyz(d, c, x, y, z);
+        descent_step<FACE>(g, x, y, z, v, next, nc, nv);
         if (next == 255u) break;
         c = nc;
         v = nv;

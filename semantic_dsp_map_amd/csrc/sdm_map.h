@@ -1,7 +1,8 @@
 // sdm_map.h — private to the host units of libsdm_hip (not installed): the map object behind the C ABI (include/sdm.h) -
 // the frame pipeline's state flat in sdm_map, the state of every derived layer in a struct of its own -, the error macros,
 // who owns what a map allocates, and the host helpers that more than one unit uses: the frame's, and the layers' (their
-// one check, their one origin, the one staging path of the host-mode batched calls).
+// one check, their one refusal, their one origin, their one checked launch, the one staging path of the host-mode batched
+// calls).
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -37,6 +38,15 @@ void set_error(const char *what, const char *file, int line, const char *detail)
     }                                                                        \
   } while (0)
 #define SDM_TRY(expr) do { const sdm_status rc_ = (expr); if (rc_ != SDM_OK) return rc_; } while (0)
+// the layers' refusal of an argument: the thread's error names the place, the value is the status to return
+#define LAYER_REFUSE(what, why) (sdm::set_error(what, __FILE__, __LINE__, why), SDM_ERR_INVALID_ARGUMENT)
+// a launch of a layer's build, inside a function that returns hipError_t: returns the launch's error, if any
+#define LAYER_LAUNCH(kernel, grid, tpb, stream, ...)                             \
+  do {                                                                           \
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(tpb), 0, stream, __VA_ARGS__);   \
+    const hipError_t e_ = hipGetLastError();                                     \
+    if (e_ != hipSuccess) return e_;                                             \
+  } while (0)
 
 using namespace sdm;
 

@@ -7,13 +7,12 @@
 // caller's outputs - and a pool of bitmasks of its own, one bit per voxel and view in flight, which every call leaves
 // zeroed.
 //
-// The walk restates k_query_segments' (queries.hip) statement for statement - the DDA in double, SEG_K cells computed
-// ahead, their SEG_K loads issued together - rather than sharing it through a header: that kernel's registers and ISA
-// stay exactly what its tests hold it to, and tests/test_views_gpu.py holds the two walks together ray by ray, bit by bit.
+// The walk is k_query_segments' (sdm_walk.h has it and says why it goes SEG_K cells ahead); tests/test_views_gpu.py holds
+// the two kernels together ray by ray, bit by bit.
 #include <cstdlib>
 
-#include "sdm_layer.h"
 #include "sdm_map.h"
+#include "sdm_walk.h"
 
 #pragma clang fp contract(off)
 
@@ -24,8 +23,6 @@ namespace sdm {
 namespace {
 
 constexpr int VTPB = 256;
-constexpr int SEG_K = 8;
-enum : int { SEG_CELL = 0, SEG_OUT = 1, SEG_END = 2 };
 enum : int { VIEW_MARK = 0, VIEW_CLEAR = 1 };
 
 // One lane per ray, a block row per view (blockIdx.y = the view within the batch = its mask in the pool).
@@ -45,7 +42,6 @@ __global__ __launch_bounds__(VTPB) void k_view_rays(Dims d, Frame f, const sdm_v
   const uint32_t v = blockIdx.y;
   const bool live = r < n_rays;
   uint32_t *__restrict__ mask = pool + (size_t)v * mask_words;
-  const int N[3] = {(int)d.NX, (int)d.NY, (int)d.NZ};
   // the ray: a = pos, b = pos + range * (R(q) d), float32, one operation at a time (sdm.h pins the order)
   const float px = views[v].pos[0], py = views[v].pos[1], pz = views[v].pos[2];
   const float qw = views[v].q[0], qx = views[v].q[1], qy = views[v].q[2], qz = views[v].q[3];
@@ -76,75 +72,26 @@ __global__ __launch_bounds__(VTPB) void k_view_rays(Dims d, Frame f, const sdm_v
   uint32_t hit_v = INVALID_INDEX, hit_w = RES_UNKNOWN_W1;
   int cells = 0;
   uint32_t n_unk = 0, n_free = 0, n_occ = 0, r_unk = 0;
-  // the state of the walk: current cell c, the t at which it was entered, per axis the t of the next plane
-  int c[3] = {0, 0, 0}, step[3] = {0, 0, 0};
-  double A[3], inv[3], tn[3];
-  double t_cur = 0.0;
-  int kind = SEG_END;  // of the current cell
+  SegWalk sw;
+  sw.kind = SEG_END;
   if (finite) {
-    bool inside = true, empty = false;
-    double t_in = -INFINITY, t_out = INFINITY;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      A[a] = (double)ua[a];
-      const double D = (double)ub[a] - A[a];
-      inside = inside && ua[a] >= 0.f && ua[a] < (float)N[a];
-      if (D == 0.0) {
-        empty = empty || !(ua[a] >= 0.f && ua[a] < (float)N[a]);
-        inv[a] = 0.0;
-      } else {
-        inv[a] = 1.0 / D;
-        const double t0 = (0.0 - A[a]) * inv[a], t1 = ((double)N[a] - A[a]) * inv[a];
-        t_in = fmax(t_in, fmin(t0, t1));
-        t_out = fmin(t_out, fmax(t0, t1));
-      }
-      step[a] = D > 0.0 ? 1 : (D < 0.0 ? -1 : 0);
+    const SegClip cl = seg_begin(sw, d, ua, ub);
+    if (cl.inside) {
+      seg_enter_inside(sw, ua);
+    } else if (cl.enters()) {
+      seg_enter_clipped(sw, cl, ub);
     }
-    if (inside) {
-      kind = SEG_CELL;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) c[a] = (int)floorf(ua[a]);
-    } else if (!empty && t_in <= 1.0 && t_out > 0.0 && t_in < t_out) {
-      // clipped: the walk starts where the segment enters the map (rounding at the face is clamped back into the map)
-      kind = SEG_CELL;
-      t_cur = fmax(t_in, 0.0);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) c[a] = min(max((int)floor(A[a] + t_cur * ((double)ub[a] - A[a])), 0), N[a] - 1);
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) tn[a] = step[a] == 0 ? INFINITY : ((double)(c[a] + (step[a] > 0)) - A[a]) * inv[a];
+    seg_planes(sw);
   }
-  while (kind != SEG_END) {
+  while (sw.kind != SEG_END) {
     uint32_t vox[SEG_K], w[SEG_K];
     float tin[SEG_K];
     int kd[SEG_K];
 #pragma unroll
     for (int k = 0; k < SEG_K; ++k) {  // the next SEG_K cells: arithmetic only
-      kd[k] = kind;
-      tin[k] = (float)t_cur;
-      vox[k] = kind == SEG_CELL ? cell_voxel(d, f, c[0], c[1], c[2]) : INVALID_INDEX;
-      if (kind == SEG_CELL) {
-        int ax = 0;  // the plane crossed next: x before y before z at equal t
-        double tm = tn[0];
-        if (tn[1] < tm) { ax = 1; tm = tn[1]; }
-        if (tn[2] < tm) { ax = 2; tm = tn[2]; }
-        if (tm > 1.0) {
-          kind = SEG_END;
-        } else {
-          const int cn = (ax == 0 ? c[0] : ax == 1 ? c[1] : c[2]) + (ax == 0 ? step[0] : ax == 1 ? step[1] : step[2]);
-          const int na = ax == 0 ? N[0] : ax == 1 ? N[1] : N[2];
-#pragma unroll
-          for (int a = 0; a < 3; ++a)
-            if (a == ax) {
-              c[a] = cn;
-              tn[a] = ((double)(cn + (step[a] > 0)) - A[a]) * inv[a];
-            }
-          t_cur = tm;
-          if (cn < 0 || cn >= na) kind = SEG_OUT;
-        }
-      } else {
-        kind = SEG_END;  // (after the cell outside the map there is nothing: the map is convex)
-      }
+      kd[k] = sw.kind;
+      tin[k] = (float)sw.t_cur;
+      seg_advance(sw, vox[k], [&](int x, int y, int z) { return cell_voxel(d, f, x, y, z); });
     }
 #pragma unroll
     for (int k = 0; k < SEG_K; ++k) w[k] = res[kd[k] == SEG_CELL ? vox[k] : 0u].y;  // SEG_K independent loads

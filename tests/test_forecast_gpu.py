@@ -348,6 +348,52 @@ def test_segments(name):
     assert np.array_equal(geo.voxel(cells), plain["voxel"][hit]) and (got["state"][hit] == 1).all()
 
 
+def face_segments(geo, size):
+    """axis-parallel segments that lie in the plane of a cell face: inside the map, along its min face, and leaving it"""
+    lo, N = geo.center + geo.pmin, geo.N
+    rows = []
+    for ax in range(3):
+        for along in ((ax + 1) % 3, (ax + 2) % 3):
+            for plane in (0, 1, int(N[ax]) // 2, int(N[ax]) - 1, int(N[ax])):
+                a = (N // 2).astype(np.float32) + np.array([0.5, 0.25, 0.75], np.float32)
+                a[ax] = plane
+                for start, end in ((0.5, N[along] - 0.5), (N[along] - 1.5, -3.0), (-2.0, N[along] + 2.0)):
+                    p, q = a.copy(), a.copy()
+                    p[along], q[along] = start, end
+                    rows.append(list(lo + p * size) + [0.0] + list(lo + q * size) + [0.0])
+    return np.array(rows, np.float32)
+
+
+@pytest.mark.parametrize("name", ["A", "B", "driven-T0"])
+def test_a_forecast_without_motions_walks_like_the_segment_query(name):
+    """k_query_forecast_segments and k_query_segments share one walk (sdm_walk.h): with no motions and ta = tb = 0 the two
+    answer alike on every segment, ambiguous ones included - t and cells byte for byte, the hit cell through the ring."""
+    if name in sc.ALL_CASES:
+        cfg, g, geo, vox, _ = scene(name)
+    else:
+        cfg, g, geo, vox = get_map(*name.split("-"))
+    size = np.float32(cfg["voxel_size"])
+    seg = np.concatenate([random_segments(geo, size, n=3000, seed=11), hand_segments(geo, size), face_segments(geo, size)])
+    seg[:, 3] = seg[:, 7] = 0.0
+    a, b = seg[:, 0:3], seg[:, 4:7]
+    inside = lambda p: ((geo.u(p) >= 0) & (geo.u(p) < geo.N)).all(axis=1)
+    assert (~inside(a)).sum() > 100 and (a == b).all(axis=1).any() and not np.isfinite(seg).all()
+    g.forecast_update(None, HORIZONS)
+    for ub in (False, True):
+        plain = g.query_segments(a, b, unknown_blocks=ub)
+        got = g.query_forecast_segments(seg, unknown_blocks=ub)
+        print(name, "unknown_blocks", ub, "hits", int((plain["t"] >= 0).sum()), "misses", int((plain["cells"] == 0).sum()))
+        assert got["t"].tobytes() == plain["t"].tobytes() and got["cells"].tobytes() == plain["cells"].tobytes()
+        hit = got["cell"] != fc.NOTHING
+        assert np.array_equal(hit, plain["voxel"] != qr.INVALID) and hit.any() and (plain["cells"] == 0).any()
+        c = got["cell"][hit].astype(np.int64)
+        cells = np.stack([c % geo.N[0], (c // geo.N[0]) % geo.N[1], c // (geo.N[0] * geo.N[1])], 1)
+        assert np.array_equal(geo.voxel(cells), plain["voxel"][hit])
+        occupied = (plain["voxel"] != qr.INVALID) & (plain["occ"] >= 1)
+        assert occupied.any() and (got["state"][occupied] == 1).all()
+        assert ((got["state"][hit & ~occupied] == -1) & (plain["occ"][hit & ~occupied] == -1)).all() and (ub or not (hit & ~occupied).any())
+
+
 # ---- the rules --------------------------------------------------------------------------------------------------------------
 def _moving_tracks(g, vox, cfg):
     t = np.unique(vox["track"][(vox["occ"] >= 1) & (vox["track"] >= 1) & (vox["track"] <= cfg["max_movable_track"])])
