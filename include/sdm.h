@@ -1050,6 +1050,96 @@ sdm_status sdm_get_mesh_vertices(sdm_map *m, sdm_mesh_vertex *corners, float *xy
  * sdm_destroy, to be read in stream order on sdm_stream (the counts: sdm_get_mesh_info).  Each may be NULL. */
 sdm_status sdm_mesh_device(sdm_map *m, const sdm_mesh_face **faces, const uint32_t **quads, const sdm_mesh_vertex **corners);
 
+/* ---- world archive: what did the map know about a place the block has left? ----
+ * Every layer above answers for the block the ring buffer covers; a slab that leaves it is re-stamped and reads unknown
+ * from then on.  The world archive is a world-fixed, sparse store of result words that outlives the ring's shifts.
+ * sdm_world_update enqueues, on the map's stream, the merge of the result array of the last frame enqueued before the
+ * call into the archive and returns without waiting; nothing of the map's state is modified and no scratch of the frames'
+ * or of another layer is used.  Everything is integer and bitwise reproducible, including which bricks get room.
+ * Geometry.  World cell of map-index cell i on axis a, in the frame the update reads: g = moved_steps[a] + i - (N[a] >> 1)
+ * (exact: map_center = moved_steps * voxel_size, pmin = -(N >> 1) * voxel_size).  Brick: 8 x 8 x 8 world cells, b = g >> 3
+ * as an arithmetic shift (floor); the cell inside it c = g & 7, cell word cx | cy << 3 | cz << 6.  Brick coordinates are
+ * int16 per axis (+-26 km at 0.1 m voxels); a brick outside that range is never created: per update such candidate
+ * bricks with a writing cell are counted in out_of_range_last.  Brick order: ascending in (bz, by, bx), signed.
+ * World cell of a global position: floorf(p * recip) per axis, one float32 multiply by the map's own recip (1 /
+ * voxel_size in float32).  This rule and the map's own cell rule ((p - center) - pmin) * recip can differ inside a rounding
+ * sliver at a cell's faces (as a point of sdm_query_points and a segment through it can): query cell centres where that
+ * matters.  Global position of a world cell's min corner: (float)g * voxel_size, one float32 multiply per axis.
+ * The store holds at most max_bricks bricks, fixed by the first update after creation or after sdm_world_clear: 0 means
+ * max(2 * (NX / 8 + 1) * (NY / 8 + 1) * (NZ / 8 + 1), 4096) rounded up to a power of two; at most 2^21.  A later update
+ * that asks for a different non-zero capacity while the archive holds bricks is refused (that update waits for the
+ * stream; while the archive holds none the buffers are exchanged).  Per brick: 512 words, unknown (0xff000000) until
+ * written, and the header below.
+ * Which cells write: a block cell writes iff its occ >= 0, except that with SDM_WORLD_STATIC_ONLY a cell with occ >= 1
+ * whose track is movable (1 <= track <= max_movable_track) and with SDM_WORLD_OBSERVED_ONLY a cell with occ == 2 write
+ * nothing.  A writing cell stores its result word (track | label << 16 | occ << 24) verbatim into its world cell: the
+ * latest observation wins.  A cell that does not write leaves the archive as it was: an unknown slab that has just
+ * entered the block erases nothing.
+ * A brick is created iff it is not in the archive and at least one of its cells writes in this update.  The candidate
+ * bricks the block overlaps are taken in brick order and those to create ranked: a new brick of rank r gets room iff
+ * n_bricks + r < max_bricks.  The others are not created; their writing cells are dropped for this update and counted
+ * (cells) in dropped_last and dropped_total, and a later update may create them once there is room.  n_occupied and n_free
+ * of every brick with a writing cell are counted again, last_stamp is set there.
+ * sdm_world_clear empties the archive and keeps the buffers; the calls that need an update are refused again until the
+ * next one.  sdm_clear, sdm_load_state and sdm_set_ring_state leave the archive alone: later updates trust moved_steps
+ * as it then stands, so a caller that sets another ring state and means another world clears the archive itself.
+ * Memory: SDM_WORLD_BYTES_PER_BRICK = 2112 bytes per brick of capacity (2048 B of words, 20 B header, 24 B for its two
+ * hash slots, 20 B of the brick order's sort buffers and counts), 16 bytes per candidate brick ((ceil(N / 8) + 1) per
+ * axis) and the scratch of one scan and one sort: 277 MB at 256^3 with the default capacity of 131072 bricks.
+ * Allocated at the first sdm_world_update, freed by sdm_destroy.
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map, options, info or other required pointer, unknown flag bits, a
+ * negative capacity, count, first or cap, max_bricks above 2^21, a NULL n_out, a Z-slab shard (shard_count > 1), and -
+ * sdm_get_world_info and sdm_world_clear apart - a call before any sdm_world_update. */
+#define SDM_WORLD_STATIC_ONLY   0x01u  /* a cell with occ >= 1 whose winning track is movable writes nothing */
+#define SDM_WORLD_OBSERVED_ONLY 0x02u  /* a cell with occ == 2 (guessed occupied) writes nothing */
+#define SDM_WORLD_BYTES_PER_BRICK 2112
+typedef struct {          /* 16 bytes, every field naturally aligned */
+  uint32_t flags;
+  uint32_t pad;           /* 0 */
+  int64_t  max_bricks;    /* capacity of the store; 0: the default, or what it already is */
+} sdm_world_options;
+typedef struct {          /* 20 bytes */
+  int16_t  bx, by, bz;    /* world brick coordinate */
+  uint16_t n_occupied;    /* cells with occ >= 1 now */
+  uint16_t n_free;        /* cells with occ == 0 now (unknown: 512 - both) */
+  uint16_t pad;           /* 0 */
+  uint32_t first_stamp;   /* global_time_stamp of the update that created it */
+  uint32_t last_stamp;    /* ... of the last update in which one of its cells was written */
+} sdm_world_brick;
+typedef struct {          /* 8 bytes */
+  uint16_t track; uint8_t label; int8_t occ;   /* the world cell's word; 0, 0, -1 where the archive has no brick */
+  uint32_t stamp;         /* its brick's last_stamp; 0 where there is none */
+} sdm_world_cell;
+typedef struct {          /* 80 bytes, every field naturally aligned */
+  uint32_t n_bricks, max_bricks, n_updates;    /* n_updates: since creation or sdm_world_clear */
+  uint32_t created_last;                       /* bricks the last update created */
+  uint32_t dropped_last;                       /* writing cells of bricks the last update had no room for */
+  uint32_t out_of_range_last;                  /* candidate bricks of the last update beyond the int16 range */
+  uint64_t dropped_total, n_occupied, n_free;  /* dropped_last summed over the updates; the headers' counts summed */
+  int32_t  bmin[3], bmax[3];                   /* inclusive brick bounds; 0 and -1 when empty */
+  uint32_t flags, stamp;                       /* of the last update */
+} sdm_world_info;
+sdm_status sdm_world_update(sdm_map *m, const sdm_world_options *options);
+sdm_status sdm_world_clear(sdm_map *m);
+/* Waits.  SDM_OK with zeros (bmax -1) before any update and after sdm_world_clear. */
+sdm_status sdm_get_world_info(sdm_map *m, sdm_world_info *info);
+/* Waits.  Headers and - cells not NULL - 512 words per brick, in brick order from the first-th brick on, at most cap of
+ * them; *n_out = the archive's brick count.  bricks and cells may each be NULL.  The pool is kept in creation order: the
+ * first call of this or of sdm_get_world_occupied after an update sorts it (two passes of the radix sort). */
+sdm_status sdm_get_world_bricks(sdm_map *m, sdm_world_brick *bricks, uint32_t *cells, int64_t first, int64_t cap, int64_t *n_out);
+/* Every archived cell with occ >= 1 as sdm_point (the min corner as above, track, label, occ), ascending in (brick order,
+ * cell word): the world-wide counterpart of sdm_get_occupied.  *n_out is the true count, nothing is written beyond cap.
+ * Waits for the count also with SDM_QUERY_ON_DEVICE, with which out is a device pointer filled in stream order. */
+sdm_status sdm_get_world_occupied(sdm_map *m, sdm_point *out, int64_t cap, int64_t *n_out, uint32_t flags);
+/* Per point the world cell's word and its brick's last_stamp; {0, 0, -1, 0} for a cell of no brick, a non-finite
+ * coordinate or a brick out of range.  SDM_QUERY_ON_DEVICE as for sdm_query_points; host mode through the queries'
+ * staging area.  n == 0 launches nothing. */
+sdm_status sdm_query_world_points(sdm_map *m, const float *xyz, int64_t n, sdm_world_cell *out, uint32_t flags);
+/* The dense word grid of the box of world cells cell_min .. cell_min + size - 1, x fastest; cells of no brick hold the
+ * unknown word 0xff000000.  Sizes > 0 with a product of at most 2^28.  With SDM_QUERY_ON_DEVICE words is a device pointer
+ * and the call does not wait; without it, it goes through the queries' staging area and waits. */
+sdm_status sdm_get_world_region(sdm_map *m, const int32_t cell_min[3], const int32_t size[3], uint32_t *words, uint32_t flags);
+
 /* ---- owner sets of the object layer: ObjectParticleHashMap (object_layer.h:20-52) */
 sdm_status sdm_object_particle_count(sdm_map *m, int32_t track_id, int64_t *count);
 /* The keys of ObjectParticleHashMap::indices_map whose sets are not empty: every track id that owns at least one slot of

@@ -664,6 +664,51 @@ class SemanticDSPMap {
     if (info) *info = mi;
     return 2 * (size_t)mi.n_faces;
   }
+  /// What did the map know about a place the block has left (sdm.h, "world archive")?  worldUpdate merges the results of
+  /// the last update() into the world-fixed archive (flags: SDM_WORLD_STATIC_ONLY, SDM_WORLD_OBSERVED_ONLY; the
+  /// library's default capacity); it does not wait.  Call it after every update() whose results are to be remembered.
+  /// Returns false before the first update() or when the call fails.
+  bool worldUpdate(uint32_t flags = 0) {
+    if (!map_) return false;
+    sdm_world_options o;
+    std::memset(&o, 0, sizeof(o));
+    o.flags = flags;
+    return check(sdm_world_update(map_, &o), "sdm_world_update");
+  }
+  /// The archive's counts and brick bounds; zeros before the first worldUpdate().  Waits.
+  bool worldInfo(sdm_world_info &info) {
+    std::memset(&info, 0, sizeof(info));
+    if (!map_) return false;
+    return check(sdm_get_world_info(map_, &info), "sdm_get_world_info");
+  }
+  /// Every archived cell with occ >= 1, the world-wide counterpart of the occupied cloud: min corner, track, label, occ,
+  /// ascending in (brick order, cell word).  Waits.  Returns the number of points; 0 (and an empty vector) before the
+  /// first worldUpdate() or when a call fails.
+  size_t worldOccupied(std::vector<sdm_point> &out) {
+    out.clear();
+    if (!map_) return 0;
+    int64_t n = 0;
+    if (!check(sdm_get_world_occupied(map_, nullptr, 0, &n, 0u), "sdm_get_world_occupied")) return 0;
+    out.resize((size_t)n);
+    if (n && !check(sdm_get_world_occupied(map_, out.data(), n, &n, 0u), "sdm_get_world_occupied")) out.clear();
+    return out.size();
+  }
+  /// What the archive holds at each position (global frame): the cell's track, label and occ and the stamp of the last
+  /// update that wrote into its brick; occ -1 where nothing is archived.  Waits.  Returns the number of points answered;
+  /// 0 (and an empty vector) before the first worldUpdate() or when the call fails.
+  size_t queryWorld(const std::vector<Eigen::Vector3d> &points, std::vector<sdm_world_cell> &out) {
+    out.clear();
+    if (!map_ || points.empty()) return 0;
+    std::vector<float> xyz(3 * points.size());
+    for (size_t i = 0; i < points.size(); ++i) {
+      xyz[3 * i] = (float)points[i].x();
+      xyz[3 * i + 1] = (float)points[i].y();
+      xyz[3 * i + 2] = (float)points[i].z();
+    }
+    out.resize(points.size());
+    if (!check(sdm_query_world_points(map_, xyz.data(), (int64_t)points.size(), out.data(), 0u), "sdm_query_world_points")) out.clear();
+    return out.size();
+  }
   /// the ray table scoreViews uses at `stride`: three floats per ray
   const std::vector<float> &viewRays(int stride) {
     if (stride != view_rays_stride_ || view_rays_.empty()) {

@@ -107,6 +107,19 @@ MESH_MOVABLE_ONLY = 0x02
 MESH_OBSERVED_ONLY = 0x04
 MESH_SKIP_UNKNOWN_FACES = 0x08
 MESH_SKIP_BORDER_FACES = 0x10
+# the world archive (sdm.h: sdm_world_update / sdm_get_world_info / sdm_get_world_bricks / sdm_get_world_occupied /
+# sdm_query_world_points / sdm_get_world_region / sdm_world_clear)
+WORLD_OPTIONS = np.dtype([("flags", "<u4"), ("pad", "<u4"), ("max_bricks", "<i8")])
+WORLD_BRICK = np.dtype([("bx", "<i2"), ("by", "<i2"), ("bz", "<i2"), ("n_occupied", "<u2"), ("n_free", "<u2"), ("pad", "<u2"),
+                        ("first_stamp", "<u4"), ("last_stamp", "<u4")])
+WORLD_CELL = np.dtype([("track", "<u2"), ("label", "u1"), ("occ", "i1"), ("stamp", "<u4")])
+WORLD_INFO = np.dtype([("n_bricks", "<u4"), ("max_bricks", "<u4"), ("n_updates", "<u4"), ("created_last", "<u4"), ("dropped_last", "<u4"),
+                       ("out_of_range_last", "<u4"), ("dropped_total", "<u8"), ("n_occupied", "<u8"), ("n_free", "<u8"),
+                       ("bmin", "<i4", (3,)), ("bmax", "<i4", (3,)), ("flags", "<u4"), ("stamp", "<u4")])
+assert WORLD_OPTIONS.itemsize == 16 and WORLD_BRICK.itemsize == 20 and WORLD_CELL.itemsize == 8 and WORLD_INFO.itemsize == 80
+WORLD_STATIC_ONLY = 0x01
+WORLD_OBSERVED_ONLY = 0x02
+WORLD_UNKNOWN_WORD = 0xFF000000
 
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
@@ -322,6 +335,13 @@ def load_library():
         "sdm_get_mesh_faces": [vp, vp, vp, i64, C.POINTER(i64)],
         "sdm_get_mesh_vertices": [vp, vp, vp, i64, C.POINTER(i64)],
         "sdm_mesh_device": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
+        "sdm_world_update": [vp, vp],
+        "sdm_world_clear": [vp],
+        "sdm_get_world_info": [vp, vp],
+        "sdm_get_world_bricks": [vp, vp, vp, i64, i64, C.POINTER(i64)],
+        "sdm_get_world_occupied": [vp, vp, i64, C.POINTER(i64), u32],
+        "sdm_query_world_points": [vp, vp, i64, vp, u32],
+        "sdm_get_world_region": [vp, vp, vp, vp, u32],
         "sdm_forecast_stamps": [C.c_float, vp, i32, vp, i32, u32, vp, i64, C.POINTER(i64)],
         "sdm_forecast_update": [vp, vp, i32, vp, i32, u32],
         "sdm_get_forecast": [vp, vp, vp, vp, vp],
@@ -982,6 +1002,67 @@ class SdmMap:
         p = [C.c_void_p() for _ in range(3)]
         _check(self.L, self.L.sdm_mesh_device(self.h, *(C.byref(x) for x in p)), "sdm_mesh_device")
         return tuple(x.value for x in p)
+
+    # ---- the world archive (sdm.h).  world_update enqueues the merge of the last frame's results into the archive on the
+    # map's stream; the getters and queries answer for everything archived so far, wherever the block is now.
+    def world_update(self, static_only=False, observed_only=False, max_bricks=0):
+        o = np.zeros(1, WORLD_OPTIONS)
+        o["flags"] = (WORLD_STATIC_ONLY if static_only else 0) | (WORLD_OBSERVED_ONLY if observed_only else 0)
+        o["max_bricks"] = int(max_bricks)
+        _check(self.L, self.L.sdm_world_update(self.h, _ptr(o)), "sdm_world_update")
+
+    def world_clear(self):
+        _check(self.L, self.L.sdm_world_clear(self.h), "sdm_world_clear")
+
+    def world_info(self):
+        """-> a WORLD_INFO record; zeros (bmax -1) before any update and after world_clear"""
+        info = np.zeros(1, WORLD_INFO)
+        _check(self.L, self.L.sdm_get_world_info(self.h, _ptr(info)), "sdm_get_world_info")
+        return info[0]
+
+    def world_bricks(self, with_cells=True, first=0, cap=None):
+        """-> (bricks WORLD_BRICK[n], cells uint32[n, 512] or None) in brick order: ascending in (bz, by, bx)"""
+        got = C.c_int64()
+        if cap is None:
+            _check(self.L, self.L.sdm_get_world_bricks(self.h, None, None, 0, 0, C.byref(got)), "sdm_get_world_bricks")
+            cap = max(got.value - int(first), 0)
+        bricks = np.empty(cap, WORLD_BRICK)
+        cells = np.empty((cap, 512), np.uint32) if with_cells else None
+        _check(self.L, self.L.sdm_get_world_bricks(self.h, _ptr(bricks), _ptr(cells), int(first), cap, C.byref(got)), "sdm_get_world_bricks")
+        n = max(min(got.value - int(first), cap), 0)
+        return bricks[:n], (cells[:n] if with_cells else None)
+
+    def world_occupied(self, cap=None):
+        """-> (points POINT[min(n, cap)], n): every archived cell with occ >= 1, ascending in (brick order, cell word)"""
+        got = C.c_int64()
+        if cap is None:
+            _check(self.L, self.L.sdm_get_world_occupied(self.h, None, 0, C.byref(got), 0), "sdm_get_world_occupied")
+            cap = got.value
+        out = np.empty(cap, POINT)
+        _check(self.L, self.L.sdm_get_world_occupied(self.h, _ptr(out), cap, C.byref(got), 0), "sdm_get_world_occupied")
+        return out[:min(got.value, cap)], got.value
+
+    def query_world(self, xyz, on_device=False, n=None, out=None):
+        """xyz: (n, 3) global positions -> WORLD_CELL per point.  on_device: xyz and out (n WORLD_CELL) are device pointers,
+        as for query_points."""
+        if on_device:
+            _check(self.L, self.L.sdm_query_world_points(self.h, _ptr(int(xyz)), int(n), _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_world_points")
+            return None
+        p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        res = np.empty(len(p), WORLD_CELL)
+        _check(self.L, self.L.sdm_query_world_points(self.h, _ptr(p), len(p), _ptr(res), 0), "sdm_query_world_points")
+        return res
+
+    def world_region(self, cell_min, size, on_device=False, out=None):
+        """-> uint32 [size z, size y, size x]: the words of the box of world cells from cell_min (x, y, z) on; on_device: out is
+        a device pointer to size x * y * z words, filled in stream order"""
+        lo, sz = np.ascontiguousarray(cell_min, np.int32).reshape(3), np.ascontiguousarray(size, np.int32).reshape(3)
+        if on_device:
+            _check(self.L, self.L.sdm_get_world_region(self.h, _ptr(lo), _ptr(sz), _ptr(int(out)), QUERY_ON_DEVICE), "sdm_get_world_region")
+            return None
+        words = np.empty((max(int(sz[2]), 0), max(int(sz[1]), 0), max(int(sz[0]), 0)), np.uint32)
+        _check(self.L, self.L.sdm_get_world_region(self.h, _ptr(lo), _ptr(sz), _ptr(words), 0), "sdm_get_world_region")
+        return words
 
     def occupied(self, cap=None, zero_center=False, free=False, mark_fov=False):
         cap = cap or self.v_count

@@ -142,6 +142,23 @@ struct MeshLayer : Derived {
   sdm_mesh_options opt{};
 };
 
+// the world archive (world.hip): the hash table (64-bit keys, the pool slot beside each), the pool of bricks - 512 words
+// and a header of five words each, in creation order -, the candidates' arrays of an update (flag, rank, slot, writing
+// cells), the counters, a scan scratch (scan_off: where the getters' region begins) and a sort scratch of its own, the
+// sort's four buffers and the per-brick counts of the occupied list; order: the pool slots in brick order (inside
+// sortbuf) while `sorted`.  Derived's frame and flags are the last update's, steps the moved_steps it was built from;
+// capacity_set: an update since creation or sdm_world_clear has fixed max_bricks.
+struct WorldLayer : Derived {
+  int steps[3] = {0, 0, 0};
+  unsigned long long *keys = nullptr;
+  uint32_t *vals = nullptr, *cells = nullptr, *hdr = nullptr, *cand = nullptr, *meta = nullptr;
+  uint32_t *scan = nullptr, *sort = nullptr, *sortbuf = nullptr, *cnt = nullptr;
+  const uint32_t *order = nullptr;
+  size_t scan_off = 0;
+  uint32_t max_bricks = 0, hmask = 0, n_updates = 0;
+  bool capacity_set = false, sorted = false;
+};
+
 struct sdm_map {
   sdm_config cfg{};
   sdm_params prm{};
@@ -303,6 +320,7 @@ struct sdm_map {
   ForecastLayer forecast;
   GroundLayer ground;
   MeshLayer mesh;
+  WorldLayer world;
   sdm_point_xyzrgb *d_points_rgb = nullptr;
   size_t points_rgb_cap = 0;
   ColourTables *d_colours = nullptr;
