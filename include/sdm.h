@@ -1217,8 +1217,6 @@ sdm_status sdm_test_sort_pairs(const uint32_t *keys_in, const uint32_t *vals_in,
  *
  * sdm_test_scan_seq: `out` is uploaded before the calls and downloaded after them, so the caller sees what the scan left
  * alone.  With SDM_TEST_IN_PLACE the scan runs with out == in on a copy of `in`, and `out` receives that buffer.
- * Sequences whose calls would not all take the same form of the scan (one launch / two launches) are refused: a scratch
- * region may only ever see one of them.
  *
  * sdm_test_sort_pairs_seq: keys_in / vals_in are uploaded as the first pair of buffers, keys_out / vals_out as the
  * second; which[i] is what radix_sort_pairs returned for call i (0 = first pair, 1 = second), and slice i of keys_out /

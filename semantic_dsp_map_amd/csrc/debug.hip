@@ -138,8 +138,8 @@ sdm_status sdm_test_scan(const uint32_t *in, uint32_t *out, int64_t n) {
   DevTemps tmp;
   HIP_TRY(tmp.alloc(&din, (size_t)n));
   HIP_TRY(tmp.alloc(&dout, (size_t)n));
-  HIP_TRY(tmp.alloc(&scr, scan_scratch_elems((size_t)n) + 16));
-  HIP_TRY(hipMemset(scr, 0, (scan_scratch_elems((size_t)n) + 16) * 4));
+  HIP_TRY(tmp.alloc(&scr, scan_scratch_elems((size_t)n)));
+  HIP_TRY(hipMemset(scr, 0, scan_scratch_elems((size_t)n) * 4));
   HIP_TRY(hipMemcpy(din, in, (size_t)n * 4, hipMemcpyHostToDevice));
   exclusive_scan_u32(din, dout, (size_t)n, scr, nullptr);
   HIP_TRY(hipDeviceSynchronize());
@@ -156,8 +156,8 @@ sdm_status sdm_test_sort_pairs(const uint32_t *keys_in, const uint32_t *vals_in,
   HIP_TRY(tmp.alloc(&va, (size_t)n));
   HIP_TRY(tmp.alloc(&kb, (size_t)n));
   HIP_TRY(tmp.alloc(&vb, (size_t)n));
-  HIP_TRY(tmp.alloc(&scr, sort_scratch_elems((size_t)n) + 16));
-  HIP_TRY(hipMemset(scr, 0, (sort_scratch_elems((size_t)n) + 16) * 4));
+  HIP_TRY(tmp.alloc(&scr, sort_scratch_elems((size_t)n)));
+  HIP_TRY(hipMemset(scr, 0, sort_scratch_elems((size_t)n) * 4));
   HIP_TRY(hipMemcpy(ka, keys_in, (size_t)n * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(va, vals_in, (size_t)n * 4, hipMemcpyHostToDevice));
   int which = radix_sort_pairs(ka, va, kb, vb, (size_t)n, nbits, scr, nullptr);
@@ -232,11 +232,6 @@ sdm_status sdm_test_scan_seq(int32_t n_calls, const int64_t *capacity, const int
   std::vector<size_t> first;
   size_t total, longest;
   if (!seq_layout(n_calls, capacity, count, on_device, &first, &total, &longest)) return SDM_ERR_INVALID_ARGUMENT;
-  // one form of the scan per scratch region (sdm_internal.h): the form of the longest capacity, which sizes the scratch
-  for (int32_t i = 0; i < n_calls; ++i) {
-    const size_t n = on_device ? (size_t)capacity[i] : (size_t)count[i];
-    if (n && scan_is_one_launch(n) != scan_is_one_launch(longest)) return SDM_ERR_INVALID_ARGUMENT;
-  }
   const size_t scr_n = scan_scratch_elems(longest);
   uint32_t *din, *dout, *scr, *dcount;
   DevTemps tmp;

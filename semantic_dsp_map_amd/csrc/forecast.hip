@@ -521,11 +521,8 @@ sdm_status sdm_get_forecast_cells(sdm_map *m, uint32_t *cell, uint32_t *mask, ui
   if (!take || !(cell || mask || first)) return SDM_OK;
   const uint32_t nw = m->d.V >> 6;
   if (!L.pre) SDM_TRY(alloc_tracked(m, &L.pre, nw));
-  if (!L.scan) {
-    const size_t elems = scan_scratch_elems(nw);
-    SDM_TRY(alloc_tracked(m, &L.scan, elems));
-    HIP_TRY(hipMemsetAsync(L.scan, 0, elems * sizeof(uint32_t), s));  // (one length, one form of the scan: it leaves what it needs)
-  }
+  uint32_t *scan = nullptr;
+  SDM_TRY(layer_scan_scratch(m, nw, &scan));
   DevTemps tmp;
   uint32_t *d_out[3] = {nullptr, nullptr, nullptr};
   uint32_t *const host[3] = {cell, mask, first};
@@ -534,7 +531,7 @@ sdm_status sdm_get_forecast_cells(sdm_map *m, uint32_t *cell, uint32_t *mask, ui
   const uint32_t by_chunk = (nw + FC_WAVES - 1) / FC_WAVES;
   hipLaunchKernelGGL(k_forecast_cells_count, dim3(by_chunk), dim3(FC_TPB), 0, s, (const uint32_t *)L.mask, L.pre, nw);
   HIP_TRY(hipGetLastError());
-  exclusive_scan_u32(L.pre, L.pre, nw, L.scan, s);
+  exclusive_scan_u32(L.pre, L.pre, nw, scan, s);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_forecast_cells_write, dim3(by_chunk), dim3(FC_TPB), 0, s, (const uint32_t *)L.mask, (const uint32_t *)L.first,
                      (const uint32_t *)L.pre, nw, (uint32_t)take, d_out[0], d_out[1], d_out[2]);

@@ -364,30 +364,6 @@ Front front_of(const sdm_map *m) {
   return g;
 }
 
-// The scratch of the two scans.  exclusive_scan_u32 has a one-launch form, which needs its scratch zero and leaves it
-// zero, and for long inputs a two-launch form, which leaves its tile totals behind: a region must only ever see one of
-// the two.  The words' scan has one length per map and a region of its own; the flags' scan runs over capacity + 1
-// entries, which differs from build to build, and has one region for each form.  (Regions begin at even words: the
-// one-launch form keeps 8-byte words behind its two counters.)
-struct ScanScratch {
-  size_t words, flags_one, flags_two, total;  // offsets in uint32
-};
-ScanScratch front_scan_layout(const Dims &d) {
-  auto even = [](size_t n) { return (n + 1) & ~(size_t)1; };
-  const size_t longest = (size_t)d.V + 1;
-  size_t one = scan_scratch_elems(1);  // the one-launch form's scratch for the longest input it takes (<= longest)
-  for (size_t n = 2048; scan_is_one_launch(std::min(n, longest)); n += 2048) {
-    one = scan_scratch_elems(std::min(n, longest));
-    if (n >= longest) break;
-  }
-  ScanScratch l;
-  l.words = 0;
-  l.flags_one = even(scan_scratch_elems((size_t)d.V >> 6));
-  l.flags_two = l.flags_one + even(one);
-  l.total = l.flags_two + even(scan_scratch_elems(longest));
-  return l;
-}
-
 hipError_t launch_frontiers_build(const Dims &d, const Frame &f, const State &st, const Front &g, uint32_t flags, uint32_t min_cells,
                                   uint32_t *scan_scratch, hipStream_t s) {
   const uint32_t by_word = (g.nw + FC_WAVES * FC_U - 1) / (FC_WAVES * FC_U);
@@ -395,8 +371,7 @@ hipError_t launch_frontiers_build(const Dims &d, const Frame &f, const State &st
   hipError_t e;
   LAYER_LAUNCH(k_frontier_classify, by_word, FC_TPB, s, d, f, reinterpret_cast<const uint2 *>(st.res), g.free_m, g.unk_m, g.nw);
   LAYER_LAUNCH(k_frontier_mask, (g.nw + FR_TPB - 1) / FR_TPB, FR_TPB, s, g);
-  const ScanScratch l = front_scan_layout(d);
-  exclusive_scan_u32(g.pre, g.pre, g.nw, scan_scratch + l.words, s);
+  exclusive_scan_u32(g.pre, g.pre, g.nw, scan_scratch, s);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   LAYER_LAUNCH(k_frontier_compact, by_word, FC_TPB, s, g);
   if (flags & SDM_FRONTIERS_FACE_CONNECTED) {
@@ -406,8 +381,7 @@ hipError_t launch_frontiers_build(const Dims &d, const Frame &f, const State &st
   }
   LAYER_LAUNCH(k_frontier_accumulate, by_rank, FR_TPB, s, g);
   LAYER_LAUNCH(k_frontier_flags, by_rank, FR_TPB, s, g, min_cells);
-  exclusive_scan_u32(g.idx, g.idx, (size_t)g.cap + 1, scan_scratch + (scan_is_one_launch((size_t)g.cap + 1) ? l.flags_one : l.flags_two), s,
-                     g.meta + META_N_SCAN);
+  exclusive_scan_u32(g.idx, g.idx, (size_t)g.cap + 1, scan_scratch, s, g.meta + META_N_SCAN);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   LAYER_LAUNCH(k_frontier_table, by_rank, FR_TPB, s, d, f, g);
   return hipSuccess;
@@ -457,11 +431,8 @@ sdm_status sdm_frontiers_update(sdm_map *m, uint32_t flags, int32_t min_cells, i
   const size_t cap = max_cells == 0 ? std::max<size_t>(d.V / 16, 1) : (size_t)std::min<int64_t>(max_cells, (int64_t)d.V);
   if (!m->front.bits) SDM_TRY(alloc_tracked(m, &m->front.bits, nw * (3 * 8 + 4)));
   if (!m->front.meta) SDM_TRY(alloc_tracked(m, &m->front.meta, META_WORDS));
-  if (!m->front.scan) {
-    const size_t elems = front_scan_layout(d).total;
-    SDM_TRY(alloc_tracked(m, &m->front.scan, elems));
-    HIP_TRY(hipMemsetAsync(m->front.scan, 0, elems * sizeof(uint32_t), m->stream));  // (the scans leave it zeroed)
-  }
+  uint32_t *scan = nullptr;
+  SDM_TRY(layer_scan_scratch(m, (size_t)d.V + 1, &scan));
   if (cap > m->front.alloc) {  // a longer cell list: the old one goes once the builds that use it have run
     size_t bytes = 0;
     m->front.alloc = 0;  // (cells; there is no list while it is replaced)
@@ -471,7 +442,7 @@ sdm_status sdm_frontiers_update(sdm_map *m, uint32_t flags, int32_t min_cells, i
   }
   m->front.cap = (int64_t)cap;
   const Frame f = m->f;
-  HIP_TRY(launch_frontiers_build(d, f, m->st, front_of(m), flags, (uint32_t)std::max<int32_t>(min_cells, 1), m->front.scan, m->stream));
+  HIP_TRY(launch_frontiers_build(d, f, m->st, front_of(m), flags, (uint32_t)std::max<int32_t>(min_cells, 1), scan, m->stream));
   m->front.built(f, flags);
   return SDM_OK;
 }

@@ -596,10 +596,10 @@ static sdm_status map_init(sdm_map *m, const sdm_config *cfg, int shard_count) {
   HIP_TRY(hipMemsetAsync(sc.track_to_obj, 0xFF, 65536, m->stream));
   // one scratch buffer per scan call site: the one-launch scan keeps its (self-clearing) words there, which start at zero
   size_t scan_need = scan_scratch_elems(hw + 1);
-  A(sc.scan_scratch, scan_need + 16);
-  A(sc.scan_scratch_b, scan_scratch_elems(hw + 1) + 16);
-  HIP_TRY(hipMemsetAsync(sc.scan_scratch, 0, (scan_need + 16) * 4, m->stream));
-  HIP_TRY(hipMemsetAsync(sc.scan_scratch_b, 0, (scan_scratch_elems(hw + 1) + 16) * 4, m->stream));
+  A(sc.scan_scratch, scan_need);
+  A(sc.scan_scratch_b, scan_need);
+  HIP_TRY(hipMemsetAsync(sc.scan_scratch, 0, scan_need * 4, m->stream));
+  HIP_TRY(hipMemsetAsync(sc.scan_scratch_b, 0, scan_need * 4, m->stream));
   A(sc.mv_row, (size_t)d.v_count * MV_ROW);  // (64 bytes per voxel: 1.07 GB at 256^3 - the part has 288 GB)
   HIP_TRY(hipMemsetAsync(sc.mv_row, 0xff, (size_t)d.v_count * MV_ROW * sizeof(uint32_t), m->stream));  // idle: counters and chain heads all ones; the replay leaves them that way
   A(sc.mv_next, sc.cap_move);

@@ -336,21 +336,6 @@ __global__ __launch_bounds__(64) void k_mesh_stats(Mesh g) {
 
 size_t corner_count(const Dims &d) { return (size_t)(d.NX + 1) * (d.NY + 1) * (d.NZ + 1); }
 
-// The two scans have one length each per map, so each has a region of its own that only ever sees one form of the scan
-// (sdm_internal.h: the one-launch form needs its scratch zero and leaves it zero, the two-launch form leaves its tile
-// totals behind).  Regions begin at even words.
-struct ScanScratch {
-  size_t faces, corners, total;  // offsets in uint32
-};
-ScanScratch mesh_scan_layout(const Dims &d) {
-  auto even = [](size_t n) { return (n + 1) & ~(size_t)1; };
-  ScanScratch l;
-  l.faces = 0;
-  l.corners = even(scan_scratch_elems(((size_t)d.V >> 6) + 1));
-  l.total = l.corners + even(scan_scratch_elems((corner_count(d) + 63) / 64 + 1));
-  return l;
-}
-
 Mesh mesh_of(const sdm_map *m, const sdm_mesh_options &o) {
   const Dims &d = m->d;
   const MeshLayer &L = m->mesh;
@@ -387,10 +372,9 @@ hipError_t launch_mesh_build(const Dims &d, const Frame &f, const State &st, con
   LAYER_LAUNCH(k_mesh_classify, (classify_waves + MC_WAVES - 1) / MC_WAVES, MC_TPB, s, d, f, res, g);
   LAYER_LAUNCH(k_mesh_faces, (g.nw + MF_TPB - 1) / MF_TPB, MF_TPB, s, g);
   LAYER_LAUNCH(k_mesh_corner_count, (g.ncw + MF_TPB - 1) / MF_TPB, MF_TPB, s, g);
-  const ScanScratch l = mesh_scan_layout(d);
-  exclusive_scan_u32(g.pre_f, g.pre_f, (size_t)g.nw + 1, scan_scratch + l.faces, s);
+  exclusive_scan_u32(g.pre_f, g.pre_f, (size_t)g.nw + 1, scan_scratch, s);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  exclusive_scan_u32(g.pre_c, g.pre_c, (size_t)g.ncw + 1, scan_scratch + l.corners, s);
+  exclusive_scan_u32(g.pre_c, g.pre_c, (size_t)g.ncw + 1, scan_scratch, s);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   LAYER_LAUNCH(k_mesh_emit, (g.nw + MF_TPB - 1) / MF_TPB, MF_TPB, s, d, f, res, g);
   LAYER_LAUNCH(k_mesh_vertices, (corner_waves + MC_WAVES - 1) / MC_WAVES, MC_TPB, s, g);
@@ -450,11 +434,8 @@ sdm_status sdm_mesh_update(sdm_map *m, const sdm_mesh_options *o) {
     SDM_TRY(alloc_tracked(m, &L.meta, (size_t)META_WORDS + MS_ROWS * ST_WORDS));
     SDM_TRY(alloc_tracked(m, &L.stats, n_rows * ST_WORDS));
   }
-  if (!L.scan) {
-    const size_t elems = mesh_scan_layout(d).total;
-    SDM_TRY(alloc_tracked(m, &L.scan, elems));
-    HIP_TRY(hipMemsetAsync(L.scan, 0, elems * sizeof(uint32_t), m->stream));  // (the one-launch scans leave it zeroed)
-  }
+  uint32_t *scan = nullptr;
+  SDM_TRY(layer_scan_scratch(m, std::max(nw, ncw) + 1, &scan));
   if ((size_t)opt.max_faces > L.alloc_f) {  // longer lists: the old ones go once the builds that use them have run
     size_t n = 0;
     L.alloc_f = 0;
@@ -467,7 +448,7 @@ sdm_status sdm_mesh_update(sdm_map *m, const sdm_mesh_options *o) {
     SDM_TRY(regrow(m, &L.verts, &L.alloc_v, (size_t)opt.max_vertices, L.verts ? m->stream : nullptr));
   }
   const Frame f = m->f;
-  HIP_TRY(launch_mesh_build(d, f, m->st, mesh_of(m, opt), L.scan, m->stream));
+  HIP_TRY(launch_mesh_build(d, f, m->st, mesh_of(m, opt), scan, m->stream));
   L.opt = opt;
   L.built(f, opt.flags);
   return SDM_OK;

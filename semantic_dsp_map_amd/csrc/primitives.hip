@@ -252,38 +252,33 @@ __global__ __launch_bounds__(RS_THREADS) void rs_scatter(const uint32_t *__restr
 
 }  // namespace
 
-// the scratch holds either the tile totals of the two-launch scan or, for at most SCAN_ONEPASS_MAX_TILES tiles, the
-// 8-byte words + two counters of the one-launch scan, which must be ZERO before the first use (they clean up after
-// themselves)
+// scan scratch, whatever n is: [fixed region: two counters + SCAN_ONEPASS_MAX_TILES 8-byte words of the one-launch scan,
+// ZERO before the first use (they clean up after themselves) | tile totals of a two-launch scan, never read before written]
+constexpr size_t SCAN_FIXED_REGION = 2 * (size_t)SCAN_ONEPASS_MAX_TILES + 8;
 size_t scan_scratch_elems(size_t n) {
   const size_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-  return tiles <= (size_t)SCAN_ONEPASS_MAX_TILES ? 2 * tiles + 8 : tiles + 1;
+  return SCAN_FIXED_REGION + (tiles > (size_t)SCAN_ONEPASS_MAX_TILES ? tiles : 0);
 }
-bool scan_is_one_launch(size_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE <= (size_t)SCAN_ONEPASS_MAX_TILES; }
 
 void exclusive_scan_u32(const uint32_t *in, uint32_t *out, size_t n, uint32_t *scratch, hipStream_t s, const uint32_t *n_dev) {
   if (n == 0) return;
   size_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
   if (tiles <= (size_t)SCAN_ONEPASS_MAX_TILES) {
-    // two counters first, the words behind them (8-byte aligned): the layout does not depend on n, so scans of different
-    // sizes may share a scratch buffer - each leaves the part it used zeroed
+    // two counters first, the words behind them (8-byte aligned)
     uint32_t *counters = scratch;
     unsigned long long *desc = reinterpret_cast<unsigned long long *>(scratch + 2);
     hipLaunchKernelGGL(scan_onepass, dim3((unsigned)tiles), dim3(SCAN_THREADS), 0, s, in, out, n, n_dev, desc, counters);
     return;
   }
-  hipLaunchKernelGGL(scan_tile_sums, dim3((unsigned)tiles), dim3(SCAN_THREADS), 0, s, in, scratch, n, n_dev);
-  hipLaunchKernelGGL(scan_tiles, dim3((unsigned)tiles), dim3(SCAN_THREADS), 0, s, in, out, scratch, n, n_dev);
+  uint32_t *sums = scratch + SCAN_FIXED_REGION;
+  hipLaunchKernelGGL(scan_tile_sums, dim3((unsigned)tiles), dim3(SCAN_THREADS), 0, s, in, sums, n, n_dev);
+  hipLaunchKernelGGL(scan_tiles, dim3((unsigned)tiles), dim3(SCAN_THREADS), 0, s, in, out, sums, n, n_dev);
 }
 
-// sort scratch: [one-launch scan region, fixed size | digit histogram | tile totals of a two-launch scan, if the
-// histogram is that long].  The scan region sits at a fixed place so that it stays zero whatever n is sorted next.
-constexpr size_t RS_SCAN_REGION = 2 * (size_t)SCAN_ONEPASS_MAX_TILES + 8;
+// sort scratch: [scan scratch of the digit histogram | digit histogram]
 size_t sort_scratch_elems(size_t n) {
-  size_t tiles = (n + RS_TILE - 1) / RS_TILE;
-  size_t hist = (size_t)RS_RADIX * tiles;
-  size_t scan_tiles = (hist + SCAN_TILE - 1) / SCAN_TILE;
-  return RS_SCAN_REGION + hist + (scan_tiles > (size_t)SCAN_ONEPASS_MAX_TILES ? scan_tiles + 1 : 0);
+  const size_t hist_n = (size_t)RS_RADIX * ((n + RS_TILE - 1) / RS_TILE);
+  return scan_scratch_elems(hist_n) + hist_n;
 }
 
 int radix_sort_pairs(uint32_t *keys_a, uint32_t *vals_a, uint32_t *keys_b, uint32_t *vals_b, size_t n, int nbits,
@@ -291,15 +286,13 @@ int radix_sort_pairs(uint32_t *keys_a, uint32_t *vals_a, uint32_t *keys_b, uint3
   if (n == 0) return 0;
   size_t tiles = (n + RS_TILE - 1) / RS_TILE;
   size_t hist_n = (size_t)RS_RADIX * tiles;
-  uint32_t *hist = scratch + RS_SCAN_REGION;
-  const size_t scan_tiles = (hist_n + SCAN_TILE - 1) / SCAN_TILE;
-  uint32_t *scan_scratch = scan_tiles > (size_t)SCAN_ONEPASS_MAX_TILES ? hist + hist_n : scratch;
+  uint32_t *hist = scratch + scan_scratch_elems(hist_n);
   int which = 0;
   for (int shift = 0; shift < nbits; shift += RS_BITS) {
     uint32_t *kin = which ? keys_b : keys_a, *vin = which ? vals_b : vals_a;
     uint32_t *kout = which ? keys_a : keys_b, *vout = which ? vals_a : vals_b;
     hipLaunchKernelGGL(rs_histogram, dim3((unsigned)tiles), dim3(RS_THREADS), 0, s, kin, hist, n, shift, (uint32_t)tiles, n_dev);
-    exclusive_scan_u32(hist, hist, hist_n, scan_scratch, s, nullptr);
+    exclusive_scan_u32(hist, hist, hist_n, scratch, s, nullptr);
     hipLaunchKernelGGL(rs_scatter, dim3((unsigned)tiles), dim3(RS_THREADS), 0, s, kin, vin, kout, vout, hist, n, shift,
                        (uint32_t)tiles, n_dev);
     which ^= 1;

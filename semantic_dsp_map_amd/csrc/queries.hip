@@ -243,6 +243,16 @@ sdm_status layer_check(sdm_map *m, const char *what, const Derived *need, const 
   return SDM_ERR_INVALID_ARGUMENT;
 }
 
+sdm_status layer_scan_scratch(sdm_map *m, size_t longest, uint32_t **scratch) {
+  const size_t elems = scan_scratch_elems(longest);
+  if (elems > m->layer_scan_elems) {  // (the old one goes once the scans that use it have run)
+    SDM_TRY(regrow(m, &m->layer_scan, &m->layer_scan_elems, elems, m->layer_scan ? m->stream : nullptr));
+    HIP_TRY(hipMemsetAsync(m->layer_scan, 0, elems * sizeof(uint32_t), m->stream));  // (the scans leave its fixed region zeroed)
+  }
+  *scratch = m->layer_scan;
+  return SDM_OK;
+}
+
 void layer_origin(const sdm_map *m, const Derived &l, float origin[3]) {
   if (origin)
     for (int a = 0; a < 3; ++a) origin[a] = l.f.center[a] + m->d.pmin[a];

@@ -643,12 +643,11 @@ __device__ __forceinline__ void mark_slab_voxel_dirty(const Dims &d, const State
 // exclusive prefix sum of n uint32, exact modulo 2^32; in == out allowed. scratch must hold scan_scratch_elems(n) uint32.
 // If n_dev is not null the element count is min(*n_dev, n) read on the device (n is then the capacity the launch is
 // sized for): elements beyond the count are not summed, and nothing beyond it is written.
-// The scan has two forms (scan_is_one_launch(n)).  The one-launch form needs its scratch ZERO before the first use and
-// leaves all of it zero, so scans of any lengths of that form may follow each other on one scratch that was zeroed
-// once.  The two-launch form needs nothing of its scratch and leaves the totals of its tiles of 2048 elements there
-// (tiles beyond the count: zero), so a scratch region must only ever see one of the two forms.
+// A scratch of scan_scratch_elems(longest) words, zeroed once, serves any sequence of scans of any lengths up to
+// longest, of either form (one launch up to 512 tiles of 2048 elements, two beyond), in stream order.  Its first 1032
+// words are zero after every scan; a two-launch scan leaves the totals of its tiles from word 1032 on (tiles beyond the
+// count: zero), and nothing behind word 1032 needs initialising.
 size_t scan_scratch_elems(size_t n);
-bool scan_is_one_launch(size_t n);
 void exclusive_scan_u32(const uint32_t *in, uint32_t *out, size_t n, uint32_t *scratch, hipStream_t s, const uint32_t *n_dev = nullptr);
 // stable LSD radix sort of (key,val) pairs on key bits [0,nbits). Result ends in (keys_a, vals_a) if the returned
 // value is 0, in (keys_b, vals_b) if 1. scratch must hold sort_scratch_elems(n) uint32.  If n_dev is not null the
@@ -656,9 +655,9 @@ void exclusive_scan_u32(const uint32_t *in, uint32_t *out, size_t n, uint32_t *s
 // the count are not counted or moved, and nothing beyond it is written in any of the four buffers.
 // Precondition: keys < 2^nbits.  The sort works on whole 9-bit digits, so a key bit at or above nbits that lies inside
 // the top digit would take part in the order (the map's keys never have one: their sentinel is V = 2^(nbits - 1)).
-// The scratch begins with a region for one-launch scans, scan_scratch_elems of the longest of them, which must be ZERO
-// before the first sort and is zero after every sort; the rest needs no initialisation.  Sorts of any lengths, with
-// either form of the scan inside, may therefore follow each other on one scratch that was zeroed once.
+// The scratch begins with the scan's scratch (see its contract above): 1032 words that must be ZERO before the first
+// sort and are zero after every sort; the rest needs no initialisation.  Sorts of any lengths may therefore follow each
+// other on one scratch that was zeroed once.
 size_t sort_scratch_elems(size_t n);
 int radix_sort_pairs(uint32_t *keys_a, uint32_t *vals_a, uint32_t *keys_b, uint32_t *vals_b, size_t n, int nbits,
                      uint32_t *scratch, hipStream_t s, const uint32_t *n_dev = nullptr);

@@ -80,10 +80,10 @@ struct InstLayer : Derived {
 };
 // the frontiers (frontiers.hip): the free / unknown / frontier bitmasks and the words' prefix; the per-cell arrays,
 // accumulators (empty between builds) and cluster table, laid out for `alloc` cells of which `cap` are in use and grown
-// by a build that asks for more; the build's counters; a scan scratch of its own
+// by a build that asks for more; the build's counters (its scans use the layers' shared scratch, layer_scan_scratch)
 struct FrontLayer : Derived {
   unsigned char *bits = nullptr, *cells = nullptr;
-  uint32_t *meta = nullptr, *scan = nullptr;
+  uint32_t *meta = nullptr;
   size_t alloc = 0;
   int64_t cap = 0;
 };
@@ -106,14 +106,14 @@ struct ReachLayer : Derived {
 // the forecast (forecast.hip): the two field words per cell in map-index order; the build's table - the motions' track
 // set, the per-track stamp offsets, the stamps - on the device and in two page-locked copies that builds fill in turn, each
 // with the event that says its last upload has left it; the build's counters (and their page-locked landing area); the cell list's word
-// popcounts and scan scratch; what the last build was given
+// popcounts (their scan uses the layers' shared scratch); what the last build was given
 struct ForecastLayer : Derived {
   uint32_t *mask = nullptr, *first = nullptr;
   uint32_t *table = nullptr, *h_table[2] = {nullptr, nullptr};
   hipEvent_t ev_table[2] = {nullptr, nullptr};
   int table_next = 0;
   unsigned long long *meta = nullptr, *h_meta = nullptr;
-  uint32_t *pre = nullptr, *scan = nullptr;
+  uint32_t *pre = nullptr;
   float t[16] = {};
   uint32_t n_motions = 0, n_horizons = 0, n_stamps = 0;
 };
@@ -130,21 +130,21 @@ struct GroundLayer : Derived {
 
 // the surface mesh (mesh.hip): the solid / unknown / occupied masks, the corner mask and the two prefixes in one block; the
 // face records, their vertex ids and the vertex list, laid out for alloc_f faces and alloc_v vertices and grown by a build
-// that asks for more; the build's counters and rows of counts, the rows every wave of the emitting kernel leaves; a scan
-// scratch of its own; the build's options with the capacities resolved (its flags are Derived's)
+// that asks for more; the build's counters and rows of counts, the rows every wave of the emitting kernel leaves; the
+// build's options with the capacities resolved (its flags are Derived's).  Its scans use the layers' shared scratch.
 struct MeshLayer : Derived {
   unsigned char *bits = nullptr;
   sdm_mesh_face *faces = nullptr;
   uint32_t *quads = nullptr;
   sdm_mesh_vertex *verts = nullptr;
-  uint32_t *meta = nullptr, *stats = nullptr, *scan = nullptr;
+  uint32_t *meta = nullptr, *stats = nullptr;
   size_t alloc_f = 0, alloc_v = 0;
   sdm_mesh_options opt{};
 };
 
 // the world archive (world.hip): the hash table (64-bit keys, the pool slot beside each), the pool of bricks - 512 words
 // and a header of five words each, in creation order -, the candidates' arrays of an update (flag, rank, slot, writing
-// cells), the counters, a scan scratch (scan_off: where the getters' region begins) and a sort scratch of its own, the
+// cells), the counters, a sort scratch of its own (its scans use the layers' shared scratch), the
 // sort's four buffers and the per-brick counts of the occupied list; order: the pool slots in brick order (inside
 // sortbuf) while `sorted`.  Derived's frame and flags are the last update's, steps the moved_steps it was built from;
 // capacity_set: an update since creation or sdm_world_clear has fixed max_bricks.
@@ -152,9 +152,8 @@ struct WorldLayer : Derived {
   int steps[3] = {0, 0, 0};
   unsigned long long *keys = nullptr;
   uint32_t *vals = nullptr, *cells = nullptr, *hdr = nullptr, *cand = nullptr, *meta = nullptr;
-  uint32_t *scan = nullptr, *sort = nullptr, *sortbuf = nullptr, *cnt = nullptr;
+  uint32_t *sort = nullptr, *sortbuf = nullptr, *cnt = nullptr;
   const uint32_t *order = nullptr;
-  size_t scan_off = 0;
   uint32_t max_bricks = 0, hmask = 0, n_updates = 0;
   bool capacity_set = false, sorted = false;
 };
@@ -321,6 +320,9 @@ struct sdm_map {
   GroundLayer ground;
   MeshLayer mesh;
   WorldLayer world;
+  // the scan scratch the layers share (layer_scan_scratch): they all enqueue on `stream` only, so their scans are ordered
+  uint32_t *layer_scan = nullptr;
+  size_t layer_scan_elems = 0;  // its capacity in uint32
   sdm_point_xyzrgb *d_points_rgb = nullptr;
   size_t points_rgb_cap = 0;
   ColourTables *d_colours = nullptr;
@@ -410,6 +412,10 @@ struct LayerName {
   const char *the_layer, *build, *update;
   bool plural;
 };
+// The scratch of every scan a layer runs on m->stream: at least scan_scratch_elems(longest) words that honour the scan's
+// contract (sdm_internal.h).  Allocated and zeroed at first use; regrown, once the stream has drained, and zeroed again
+// only when a caller asks for a longer one - so a layer passes the longest scan it can ever run on this map.
+sdm_status layer_scan_scratch(sdm_map *m, size_t longest, uint32_t **scratch);
 // The check of every entry point of a layer: no Z-slab shards, and - `need` given - that layer must hold a build.
 sdm_status layer_check(sdm_map *m, const char *what, const Derived *need, const LayerName &name);
 // the global position of the min corner of cell (0, 0, 0) of the frame layer `l` was built from (origin may be null)

@@ -329,7 +329,6 @@ __global__ __launch_bounds__(WTPB) void k_world_region(WBox b, uint32_t off, uin
 // ---- host ------------------------------------------------------------------------------------------------------------
 constexpr LayerName WORLD = {"the world archive", "archive", "sdm_world_update", false};
 
-size_t even(size_t n) { return (n + 1) & ~(size_t)1; }
 uint32_t candidates_max(const Dims &d) { return (((d.NX + 7) >> 3) + 1) * (((d.NY + 7) >> 3) + 1) * (((d.NZ + 7) >> 3) + 1); }
 int64_t default_bricks(const Dims &d) {
   int64_t want = std::max<int64_t>(2 * (int64_t)(d.NX / 8 + 1) * (d.NY / 8 + 1) * (d.NZ / 8 + 1), 4096), p = 1;
@@ -340,7 +339,7 @@ int64_t default_bricks(const Dims &d) {
 void world_release(sdm_map *m) {
   WorldLayer &L = m->world;
   release(m, &L.keys), release(m, &L.vals), release(m, &L.cells), release(m, &L.hdr), release(m, &L.cand), release(m, &L.meta);
-  release(m, &L.scan), release(m, &L.sort), release(m, &L.sortbuf), release(m, &L.cnt);
+  release(m, &L.sort), release(m, &L.sortbuf), release(m, &L.cnt);
   L.max_bricks = 0;
 }
 
@@ -351,24 +350,20 @@ sdm_status world_alloc(sdm_map *m, uint32_t bricks) {
   uint32_t slots = 2;
   while (slots < 2 * bricks) slots <<= 1;
   const size_t nc_max = candidates_max(m->d);
-  const size_t scan_elems = even(scan_scratch_elems(nc_max + 1)) + even(scan_scratch_elems((size_t)bricks + 1));
   SDM_TRY(alloc_tracked(m, &L.keys, slots));
   SDM_TRY(alloc_tracked(m, &L.vals, slots));
   SDM_TRY(alloc_tracked(m, &L.cells, (size_t)bricks * 512));
   SDM_TRY(alloc_tracked(m, &L.hdr, (size_t)bricks * HDR_WORDS));
   SDM_TRY(alloc_tracked(m, &L.cand, 4 * nc_max + 2));
   SDM_TRY(alloc_tracked(m, &L.meta, (size_t)M_WORDS));
-  SDM_TRY(alloc_tracked(m, &L.scan, scan_elems));
   SDM_TRY(alloc_tracked(m, &L.sort, sort_scratch_elems(bricks)));
   SDM_TRY(alloc_tracked(m, &L.sortbuf, 4 * (size_t)bricks));
   SDM_TRY(alloc_tracked(m, &L.cnt, (size_t)bricks + 1));
   HIP_TRY(hipMemsetAsync(L.keys, 0xff, (size_t)slots * sizeof(u64), m->stream));
   HIP_TRY(hipMemsetAsync(L.meta, 0, M_WORDS * sizeof(uint32_t), m->stream));
-  HIP_TRY(hipMemsetAsync(L.scan, 0, scan_elems * sizeof(uint32_t), m->stream));  // (the one-launch scans leave it zeroed)
   HIP_TRY(hipMemsetAsync(L.sort, 0, sort_scratch_elems(bricks) * sizeof(uint32_t), m->stream));
   L.max_bricks = bricks;
   L.hmask = slots - 1;
-  L.scan_off = even(scan_scratch_elems(nc_max + 1));
   return SDM_OK;
 }
 
@@ -392,13 +387,14 @@ WGeo geo_of(const sdm_map *m, uint32_t flags) {
   return g;
 }
 
-hipError_t launch_world_update(const Dims &d, const Frame &f, const State &st, const WGeo &g, const WorldLayer &L, hipStream_t s) {
+hipError_t launch_world_update(const Dims &d, const Frame &f, const State &st, const WGeo &g, const WorldLayer &L, uint32_t *scan_scratch,
+                               hipStream_t s) {
   const uint2 *res = reinterpret_cast<const uint2 *>(st.res);
   uint32_t *need = L.cand, *rank = need + g.nc_max + 1, *cslot = rank + g.nc_max + 1, *cnw = cslot + g.nc_max;
   hipError_t e;
   if ((e = hipMemsetAsync(L.meta + M_CREATED, 0, 3 * sizeof(uint32_t), s)) != hipSuccess) return e;  // created, dropped, out of range: of this update
   LAYER_LAUNCH(k_world_mark, (g.nc_max + WWAVES - 1) / WWAVES, WTPB, s, d, f, res, g, L.keys, L.vals, need, cslot, cnw, L.meta);
-  exclusive_scan_u32(need, rank, (size_t)g.nc_max + 1, L.scan, s);
+  exclusive_scan_u32(need, rank, (size_t)g.nc_max + 1, scan_scratch, s);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   LAYER_LAUNCH(k_world_merge, (g.nc + WWAVES - 1) / WWAVES, WTPB, s, d, f, res, g, L.keys, L.vals, need, rank, cslot, cnw, L.cells, L.hdr, L.meta);
   LAYER_LAUNCH(k_world_finish, 1, 64, s, g, rank, L.meta);
@@ -420,6 +416,11 @@ hipError_t launch_world_sort(WorldLayer &L, hipStream_t s) {
   L.order = w2 ? vb : va;
   L.sorted = true;
   return hipSuccess;
+}
+
+// the layers' shared scratch, for the longer of the update's scan and the getter's
+sdm_status world_scan_scratch(sdm_map *m, uint32_t **scratch) {
+  return layer_scan_scratch(m, std::max<size_t>(candidates_max(m->d), m->world.max_bricks) + 1, scratch);
 }
 
 // waits; the archive's counters
@@ -464,8 +465,10 @@ sdm_status sdm_world_update(sdm_map *m, const sdm_world_options *o) {
     if (meta[M_N_BRICKS]) return LAYER_REFUSE(what, "another max_bricks while the archive holds bricks: call sdm_world_clear first");
     SDM_TRY(world_alloc(m, (uint32_t)o->max_bricks));
   }
+  uint32_t *scan = nullptr;
+  SDM_TRY(world_scan_scratch(m, &scan));
   const Frame f = m->f;
-  HIP_TRY(launch_world_update(m->d, f, m->st, geo_of(m, o->flags), L, m->stream));
+  HIP_TRY(launch_world_update(m->d, f, m->st, geo_of(m, o->flags), L, scan, m->stream));
   for (int a = 0; a < 3; ++a) L.steps[a] = m->moved_steps[a];
   L.n_updates++;
   L.sorted = false;
@@ -566,9 +569,11 @@ sdm_status sdm_get_world_occupied(sdm_map *m, sdm_point *out, int64_t cap, int64
   WorldLayer &L = m->world;
   SDM_TRY(world_sorted(m));
   const uint32_t bricks = L.max_bricks;
+  uint32_t *scan = nullptr;
+  SDM_TRY(world_scan_scratch(m, &scan));
   hipLaunchKernelGGL(k_world_occ_count, dim3(bricks / WTPB + 1), dim3(WTPB), 0, m->stream, L.order, L.hdr, L.meta, bricks, L.cnt);
   HIP_TRY(hipGetLastError());
-  exclusive_scan_u32(L.cnt, L.cnt, (size_t)bricks + 1, L.scan + L.scan_off, m->stream);
+  exclusive_scan_u32(L.cnt, L.cnt, (size_t)bricks + 1, scan, m->stream);
   HIP_TRY(hipGetLastError());
   uint32_t total = 0;
   HIP_TRY(hipMemcpyAsync(&total, L.cnt + bricks, sizeof(total), hipMemcpyDeviceToHost, m->stream));

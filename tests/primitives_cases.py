@@ -47,9 +47,10 @@ SCAN_SIZES = [
     4194304 + 17,
 ]
 SCAN_VALUES = ["small", "uniform32", "all_ones", "zero", "flags"]
-# one scratch, zeroed once, for each form
+# one scratch, zeroed once: for each form, and for the two in turn
 SCAN_REUSE_ONE_LAUNCH = [TILE + 1, 1, ONEPASS_MAX, LANES + 1, ONEPASS_MAX, 2 * TILE + 1]
 SCAN_REUSE_TWO_LAUNCH = [ONEPASS_MAX + 1, 4194304 + 17, ONEPASS_MAX + 1]
+SCAN_REUSE_MIXED = [ONEPASS_MAX + 1, TILE + 1, 4194304 + 17, ONEPASS_MAX, 1, ONEPASS_MAX + 1]
 
 
 def _frozen(a):
@@ -88,7 +89,7 @@ def scan_ref(a, count=None):
 
 
 def tile_totals_ref(a, count, capacity):
-    """what a two-launch scan leaves in its scratch (sdm_internal.h): the totals mod 2^32 of the tiles of TILE elements of
+    """what a two-launch scan leaves behind its scratch's fixed region (sdm_internal.h): the totals mod 2^32 of the tiles of TILE elements of
     the launch, counting only the first `count` elements"""
     padded = np.zeros(tiles(capacity) * TILE, np.uint64)
     m = min(count, capacity)

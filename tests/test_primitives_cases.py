@@ -105,6 +105,9 @@ def test_size_tables_straddle_every_edge():
     assert not any(pc.one_launch(n) for n in pc.SCAN_REUSE_TWO_LAUNCH)
     assert pc.SCAN_REUSE_ONE_LAUNCH == [2049, 1, 512 * 2048, 65, 512 * 2048, 4097]
     assert pc.SCAN_REUSE_TWO_LAUNCH == [512 * 2048 + 1, 4194321, 512 * 2048 + 1]
+    assert pc.SCAN_REUSE_MIXED == [512 * 2048 + 1, 2049, 4194321, 512 * 2048, 1, 512 * 2048 + 1]
+    forms = [pc.one_launch(n) for n in pc.SCAN_REUSE_MIXED]
+    assert sum(a != b for a, b in zip(forms, forms[1:])) >= 3 and not forms[0] and not forms[-1]
     t = set(pc.SORT_SIZES)
     for edge in (pc.LANES, 256, pc.TILE):
         assert {edge - 1, edge, edge + 1} <= t
@@ -122,14 +125,10 @@ def test_size_tables_straddle_every_edge():
 
 
 def test_hooks_refuse_bad_sequences_before_touching_a_gpu():
-    """the argument checks of the sequence hooks come before their first HIP call: a scratch region sees one form of the scan
-    only, a host-side count fits its capacity, nbits is 1..32"""
+    """the argument checks of the sequence hooks come before their first HIP call: a host-side count fits its capacity,
+    nbits is 1..32.  (Sequences that mix the two forms of the scan are no longer refused: they work,
+    tests/test_primitives_gpu.py::test_scan_reuses_its_scratch and ::test_scan_counted_short_of_a_two_launch_scratch.)"""
     z = lambda n: np.zeros(n, np.uint32)
-    mixed = [pc.ONEPASS_MAX, pc.ONEPASS_MAX + 1]
-    with pytest.raises(binding.SdmError, match="SDM_ERR_INVALID_ARGUMENT"):
-        binding.test_scan_seq(mixed, z(sum(mixed)), z(sum(mixed)))
-    with pytest.raises(binding.SdmError, match="SDM_ERR_INVALID_ARGUMENT"):   # launched at the capacity, but counted short
-        binding.test_scan_seq([pc.ONEPASS_MAX + 1], z(pc.ONEPASS_MAX + 1), z(pc.ONEPASS_MAX + 1), count=[pc.TILE])
     with pytest.raises(binding.SdmError, match="SDM_ERR_INVALID_ARGUMENT"):
         binding.test_scan_seq([8], z(8), z(8), count=[9])
     for nbits in (0, 33):

@@ -55,7 +55,8 @@ def first_words(n):
 def run_scans(capacity, arrays, count=None, in_place=False, count_on_device=False):
     """One sequence of scans, checked in full: slice i of the output holds the reference of its first min(count, capacity)
     elements and, beyond them, what the buffer held before the call (the sentinel; in place, the input).  The guard words
-    behind the scratch are intact; a one-launch sequence leaves the scratch zero, a two-launch scan its tiles' totals."""
+    behind the scratch are intact; every sequence leaves the scratch's fixed region zero, a two-launch scan its tiles'
+    totals behind it."""
     capacity = list(capacity)
     count = capacity if count is None else list(count)
     a = np.concatenate(arrays)
@@ -68,13 +69,14 @@ def run_scans(capacity, arrays, count=None, in_place=False, count_on_device=Fals
         what = "scan %d of %d, capacity %d, count %d" % (i, len(capacity), capacity[i], count[i])
         same(out[lo:lo + m], pc.scan_ref(arrays[i], m), what)
         same(out[lo + m:hi], before[lo + m:hi], what + ", beyond the count")
-    launched = [c for c, k in zip(capacity, count) if count_on_device or k]
-    if launched and pc.one_launch(max(capacity)):
-        assert not scratch.any(), "a one-launch scan left %d words of its scratch set" % np.count_nonzero(scratch)
-    elif launched:
-        i = len(capacity) - 1
+    launched = [i for i, k in enumerate(count) if count_on_device or k]
+    if launched:
+        fixed = binding.test_scratch_elems(False, 1)
+        assert not scratch[:fixed].any(), "the scans left %d words of the scratch's fixed region set" % np.count_nonzero(scratch[:fixed])
+        i = launched[-1]
         n = capacity[i] if count_on_device else count[i]
-        same(scratch[:pc.tiles(n)], pc.tile_totals_ref(arrays[i], count[i], n), "tile totals left by the last scan")
+        if not pc.one_launch(n):
+            same(scratch[fixed:fixed + pc.tiles(n)], pc.tile_totals_ref(arrays[i], count[i], n), "tile totals left by the last scan")
     return out
 
 
@@ -135,11 +137,18 @@ def test_scan_device_count(capacity, which, in_place):
     run_scans([capacity], [a], count=[count], in_place=in_place, count_on_device=True)
 
 
-# (g) one scratch, zeroed once, scan after scan (the frame's and the frontiers' use)
-@pytest.mark.parametrize("sizes", [pc.SCAN_REUSE_ONE_LAUNCH, pc.SCAN_REUSE_TWO_LAUNCH], ids=["one_launch", "two_launch"])
+# (g) one scratch, zeroed once, scan after scan of either form (the frame's use, and the derived layers' on their shared one)
+@pytest.mark.parametrize("sizes", [pc.SCAN_REUSE_ONE_LAUNCH, pc.SCAN_REUSE_TWO_LAUNCH, pc.SCAN_REUSE_MIXED],
+                         ids=["one_launch", "two_launch", "mixed"])
 @pytest.mark.parametrize("in_place", [False, True], ids=["two_buffers", "in_place"])
 def test_scan_reuses_its_scratch(sizes, in_place):
     run_scans(sizes, [pc.scan_values("uniform32", n) for n in sizes], in_place=in_place)
+
+
+def test_scan_counted_short_of_a_two_launch_scratch():
+    """a scratch sized for a two-launch scan, a host-side count that takes the one-launch form (the hooks used to refuse it)"""
+    cap = pc.ONEPASS_MAX + 1
+    run_scans([cap], [pc.scan_values("uniform32", cap)], count=[pc.TILE])
 
 
 def test_scan_reuses_its_scratch_with_device_counts():
