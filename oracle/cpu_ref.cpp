@@ -1374,6 +1374,16 @@ uint32_t oracle_add_guessed_particle(oracle_map *m, float x, float y, float z, u
   m->addGuessedParticles(x, y, z, label, track, v, p);
   return p;
 }
+// SemanticDSPMap::addGuessedParticle, semantic_dsp_map.h:1126-1142: the ring's insertion, then the owner set of a movable track
+uint32_t oracle_add_guessed_point(oracle_map *m, float x, float y, float z, uint8_t label, uint16_t track) {
+  uint32_t v, p;
+  m->addGuessedParticles(x, y, z, label, track, v, p);
+  if (p != INVALID_PARTICLE_INDEX) {
+    int t = track;
+    if (t <= m->cfg.max_movable_track) m->ownerInsert(t, p);
+  }
+  return p;
+}
 void oracle_fusion_neighbors(oracle_map *m, uint32_t voxel, float threshold, oracle_voxel_result *out, float *guessed) {
   uint8_t label;
   uint16_t track;

@@ -183,6 +183,8 @@ float oracle_query_pdf(oracle_map *m, float x, float mu, float sigma);
 float oracle_forgetting_factor(oracle_map *m, int32_t forget_count);
 uint32_t oracle_add_particle(oracle_map *m, float x, float y, float z, uint8_t label, uint16_t track);
 uint32_t oracle_add_guessed_particle(oracle_map *m, float x, float y, float z, uint8_t label, uint16_t track); /* operations.h:192-205 */
+/* SemanticDSPMap::addGuessedParticle (semantic_dsp_map.h:1126-1142): the same, then the owner set of a movable track */
+uint32_t oracle_add_guessed_point(oracle_map *m, float x, float y, float z, uint8_t label, uint16_t track);
 /* calculateWeightAndSemanticsInVoxelConsiderNeighbors (operations.h:457-600), which the frame does not call: wsum, label
  * and track of `out` (occ is left 0) and the guessed weight. */
 void oracle_fusion_neighbors(oracle_map *m, uint32_t voxel, float threshold, oracle_voxel_result *out, float *guessed);

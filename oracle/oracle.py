@@ -131,6 +131,8 @@ def lib():
         L.oracle_add_particle.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_uint8, C.c_uint16]
         L.oracle_add_guessed_particle.restype = C.c_uint32
         L.oracle_add_guessed_particle.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_uint8, C.c_uint16]
+        L.oracle_add_guessed_point.restype = C.c_uint32
+        L.oracle_add_guessed_point.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_uint8, C.c_uint16]
         L.oracle_fusion_neighbors.argtypes = [vp, C.c_uint32, C.c_float, vp, vp]
         L.oracle_resample_voxel.restype = C.c_int32
         L.oracle_resample_voxel.argtypes = [vp, C.c_uint32]
@@ -349,6 +351,10 @@ class OracleMap:
 
     def add_guessed_particle(self, x, y, z, label=0, track=65535):
         return int(self.L.oracle_add_guessed_particle(self.h, x, y, z, label, track))
+
+    def add_guessed_point(self, x, y, z, label=0, track=65535):
+        """SemanticDSPMap::addGuessedParticle: add_guessed_particle and the owner set of a movable track"""
+        return int(self.L.oracle_add_guessed_point(self.h, x, y, z, label, track))
 
     def fusion_neighbors(self, v, threshold):
         """(wsum, guessed weight, label, track) of calculateWeightAndSemanticsInVoxelConsiderNeighbors"""

@@ -110,9 +110,9 @@ class Script:
             self.lines.append("dump_" + w)
 
 
-def run(variant, text, flavour=None):
+def run(variant, text, flavour=None, path=None):
     """run one scenario in a process of its own (the reference's map is global state) and return the result text"""
-    path = exe(variant, flavour)
+    path = path or exe(variant, flavour)
     if not os.path.exists(path):
         raise FileNotFoundError(path)
     with tempfile.TemporaryDirectory() as d:
@@ -192,7 +192,7 @@ def parse(text):
         elif name == "stamps":
             n = tk.ints(3)
             out.append((name, tuple(tk.ints(int(k), np.uint32) for k in n)))
-        elif name == "state":
+        elif name in ("state", "particles"):      # particles: the same rows without the time slots (ref_filter_harness.cpp)
             n = tk.int()
             sp = {"idx": np.empty(n, np.int64), "px": np.empty(n, np.float32), "py": np.empty(n, np.float32), "pz": np.empty(n, np.float32),
                   "w": np.empty(n, np.float32), "ts": np.empty(n, np.int64), "track": np.empty(n, np.int64), "label": np.empty(n, np.int64),
@@ -202,6 +202,19 @@ def parse(text):
                 sp["px"][k], sp["py"][k], sp["pz"][k], sp["w"][k] = tk.floats(4)
                 sp["ts"][k], sp["track"][k], sp["label"][k], sp["status"][k], sp["forget"][k] = tk.ints(5)
             out.append((name, sp))
+        elif name == "births":        # oracle/ref_filter_harness.cpp: added_particle_num, the resampled voxels in ascending order
+            added, n = tk.int(), tk.int()
+            out.append((name, {"added": added, "resampled": tk.ints(n, np.uint32)}))
+        elif name == "resample":
+            out.append((name, tk.ints(tk.int(), np.uint8)))
+        elif name == "cursor":
+            out.append((name, tk.int()))
+        elif name == "owners":
+            owners = {}
+            for _ in range(tk.int()):
+                track, n = tk.int(), tk.int()
+                owners[track] = tk.ints(n, np.uint32)
+            out.append((name, owners))
         elif name == "bins":
             bins = {}
             for _ in range(tk.int()):
