@@ -1139,6 +1139,63 @@ sdm_status sdm_query_world_points(sdm_map *m, const float *xyz, int64_t n, sdm_w
  * unknown word 0xff000000.  Sizes > 0 with a product of at most 2^28.  With SDM_QUERY_ON_DEVICE words is a device pointer
  * and the call does not wait; without it, it goes through the queries' staging area and waits. */
 sdm_status sdm_get_world_region(sdm_map *m, const int32_t cell_min[3], const int32_t size[3], uint32_t *words, uint32_t flags);
+/* ---- world archive, the way back in: sdm_world_import merges n foreign bricks - what sdm_get_world_bricks of this or of
+ * another map returned, kept in a file or not - into the archive under a whole-cell offset; sdm_world_retain trims it.
+ * Both are integer and bitwise reproducible like the update, and leave the map's own state alone.
+ * Source.  n bricks in any order, cells 512 words per brick in cell-word order.  Of a source header bx, by, bz, first_stamp
+ * and last_stamp are read; n_occupied, n_free and pad are ignored, counts are always taken again.  Of several source
+ * bricks with the same coordinates the one with the lowest array index is used and the others are ignored entirely; in no
+ * other way does the result depend on the order of the array.
+ * Geometry.  Source world cell g = 8 * b + c per axis, destination world cell g + cell_offset, destination brick >> 3
+ * (arithmetic).  An offset that is no multiple of 8 spreads one source brick over up to 8 destination bricks, and lets one
+ * destination brick receive from up to 8 sources.  |cell_offset[a]| <= 2^19.  A destination brick outside the int16 range
+ * is never created; such bricks with a writing cell are counted in out_of_range_last.
+ * Which cells write: an incoming word writes iff its occ >= 0 and it passes SDM_WORLD_STATIC_ONLY / SDM_WORLD_OBSERVED_ONLY
+ * exactly as a block cell does (movable: 1 <= track <= the map's max_movable_track); with SDM_WORLD_IMPORT_FILL the
+ * destination cell must also read unknown (no brick there, or occ < 0).  A writing cell stores the word verbatim, a cell
+ * that does not write leaves the archive as it is.
+ * Creation and capacity: the update's rule.  The distinct destination bricks with at least one writing cell that are not
+ * archived are taken in brick order and ranked; one of rank r is created iff n_bricks + r < max_bricks; the writing cells
+ * of the others are counted in dropped_last and dropped_total.  created_last, dropped_last and out_of_range_last of
+ * sdm_world_info are those of the last update or import; n_updates, flags and stamp keep describing the last
+ * sdm_world_update (0 if there was none).
+ * Stamps.  The contributors of a destination brick are the source bricks with at least one writing cell in it.  A created
+ * brick gets first_stamp = min and last_stamp = max over its contributors' (unsigned), so a round trip into an empty
+ * archive reproduces every header byte; an archived brick with a written cell gets min(its own, theirs) and max(its own,
+ * theirs); a brick with no written cell is not touched at all.
+ * Lifecycle.  Like an update, the first import after creation or sdm_world_clear fixes the capacity (the same default, the
+ * same refusal of another non-zero capacity while bricks are held, the same 2^21), and after an import the calls that need
+ * an update are served.  n == 0 returns SDM_OK and changes nothing.  Without SDM_WORLD_IMPORT_ON_DEVICE (the import's own
+ * bit: SDM_QUERY_ON_DEVICE has the value of SDM_WORLD_STATIC_ONLY and cannot share a word with it) bricks and cells are host
+ * pointers, uploaded whole (one import is one ranking), the call waits and frees its device temporaries - the sources'
+ * copies, 2068 bytes per brick, and the work arrays - before it returns.  With it they are device pointers read in
+ * stream order on the map's stream and the call does not wait; the work arrays (up to 48 bytes per source brick and 40 per
+ * destination it can touch: 1, 2, 4 or 8 by the offset's residues) then stay with the map, and a call that needs larger
+ * ones than the last waits for the stream once.
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map or options, NULL bricks or cells with n > 0, n < 0 or n > 2^21, unknown
+ * flag bits, an offset beyond +-2^19, a capacity as refused by sdm_world_update, a Z-slab shard. */
+#define SDM_WORLD_IMPORT_FILL 0x10u   /* an incoming cell writes only where the archive's cell reads unknown */
+#define SDM_WORLD_IMPORT_ON_DEVICE 0x20u   /* bricks and cells are device pointers; enqueued on the map's stream, no host wait */
+typedef struct {            /* 24 bytes, every field naturally aligned */
+  uint32_t flags;           /* SDM_WORLD_STATIC_ONLY | SDM_WORLD_OBSERVED_ONLY | SDM_WORLD_IMPORT_FILL | SDM_WORLD_IMPORT_ON_DEVICE */
+  int32_t  cell_offset[3];  /* destination world cell = source world cell + cell_offset */
+  int64_t  max_bricks;      /* as in sdm_world_options */
+} sdm_world_import_options;
+sdm_status sdm_world_import(sdm_map *m, const sdm_world_import_options *o, const sdm_world_brick *bricks, const uint32_t *cells, int64_t n);
+/* Keeps exactly the bricks inside the inclusive brick box whose last_stamp >= min_last_stamp (a plain unsigned compare)
+ * and removes the others; bmax < bmin on an axis is an empty box, which removes everything.  Waits; *n_removed (may be
+ * NULL) = the bricks removed.  Kept bricks keep every header and cell byte; afterwards the archive behaves in every
+ * observable way like one that only ever held them: lookups, getters, and the capacity rule of later updates and imports
+ * with the new n_bricks.  The pool stays dense and in its previous relative order (through a transient copy of the bricks
+ * held, freed before the call returns); the hash table is rebuilt.  Unlike sdm_world_clear an empty box keeps capacity,
+ * n_updates and the archive itself; dropped_total and the *_last counters are unchanged.  Errors:
+ * SDM_ERR_INVALID_ARGUMENT for a NULL map or options, flags != 0, a Z-slab shard, a call before any update or import. */
+typedef struct {            /* 32 bytes, every field naturally aligned */
+  int32_t  bmin[3], bmax[3];   /* inclusive brick box; bmax < bmin on an axis: an empty box */
+  uint32_t min_last_stamp;     /* plain unsigned compare */
+  uint32_t flags;              /* 0 */
+} sdm_world_retain_options;
+sdm_status sdm_world_retain(sdm_map *m, const sdm_world_retain_options *o, int64_t *n_removed);
 
 /* ---- owner sets of the object layer: ObjectParticleHashMap (object_layer.h:20-52) */
 sdm_status sdm_object_particle_count(sdm_map *m, int32_t track_id, int64_t *count);

@@ -709,6 +709,46 @@ class SemanticDSPMap {
     if (!check(sdm_query_world_points(map_, xyz.data(), (int64_t)points.size(), out.data(), 0u), "sdm_query_world_points")) out.clear();
     return out.size();
   }
+  /// The archive as sdm_get_world_bricks gives it: headers and 512 words per brick, in brick order - what worldImport of this
+  /// or of another map takes.  Waits.  Returns the number of bricks; 0 (and empty vectors) before the first worldUpdate() or
+  /// worldImport() or when a call fails.
+  size_t worldBricks(std::vector<sdm_world_brick> &bricks, std::vector<uint32_t> &cells) {
+    bricks.clear();
+    cells.clear();
+    if (!map_) return 0;
+    int64_t n = 0;
+    if (!check(sdm_get_world_bricks(map_, nullptr, nullptr, 0, 0, &n), "sdm_get_world_bricks") || !n) return 0;
+    bricks.resize((size_t)n);
+    cells.resize(512 * (size_t)n);
+    if (!check(sdm_get_world_bricks(map_, bricks.data(), cells.data(), 0, n, &n), "sdm_get_world_bricks")) bricks.clear(), cells.clear();
+    return bricks.size();
+  }
+  /// Merges foreign bricks (headers and 512 words each, e.g. another map's worldBricks) into the archive, their world cells
+  /// moved by `offset` cells (flags: SDM_WORLD_STATIC_ONLY, SDM_WORLD_OBSERVED_ONLY, SDM_WORLD_IMPORT_FILL; the library's
+  /// default capacity).  Waits.  Returns false without a map, when cells does not hold 512 words per brick or when the call
+  /// fails.
+  bool worldImport(const std::vector<sdm_world_brick> &bricks, const std::vector<uint32_t> &cells, const Eigen::Vector3i &offset = Eigen::Vector3i(0, 0, 0),
+                   uint32_t flags = 0) {
+    if (!map_ || cells.size() != 512 * bricks.size()) return false;
+    sdm_world_import_options o;
+    std::memset(&o, 0, sizeof(o));
+    o.flags = flags & ~(uint32_t)SDM_WORLD_IMPORT_ON_DEVICE;
+    o.cell_offset[0] = offset.x(), o.cell_offset[1] = offset.y(), o.cell_offset[2] = offset.z();
+    return check(sdm_world_import(map_, &o, bricks.data(), cells.data(), (int64_t)bricks.size()), "sdm_world_import");
+  }
+  /// Keeps the archived bricks inside the inclusive brick box bmin .. bmax whose last_stamp >= min_last_stamp and removes
+  /// the others.  Waits.  Returns the number of bricks removed; -1 before the first worldUpdate() or worldImport() or when
+  /// the call fails.
+  int64_t worldRetain(const Eigen::Vector3i &bmin, const Eigen::Vector3i &bmax, uint32_t min_last_stamp = 0) {
+    if (!map_) return -1;
+    sdm_world_retain_options o;
+    std::memset(&o, 0, sizeof(o));
+    o.bmin[0] = bmin.x(), o.bmin[1] = bmin.y(), o.bmin[2] = bmin.z();
+    o.bmax[0] = bmax.x(), o.bmax[1] = bmax.y(), o.bmax[2] = bmax.z();
+    o.min_last_stamp = min_last_stamp;
+    int64_t removed = 0;
+    return check(sdm_world_retain(map_, &o, &removed), "sdm_world_retain") ? removed : -1;
+  }
   /// the ray table scoreViews uses at `stride`: three floats per ray
   const std::vector<float> &viewRays(int stride) {
     if (stride != view_rays_stride_ || view_rays_.empty()) {

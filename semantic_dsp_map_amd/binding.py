@@ -120,6 +120,12 @@ assert WORLD_OPTIONS.itemsize == 16 and WORLD_BRICK.itemsize == 20 and WORLD_CEL
 WORLD_STATIC_ONLY = 0x01
 WORLD_OBSERVED_ONLY = 0x02
 WORLD_UNKNOWN_WORD = 0xFF000000
+# ... its way back in and its trim (sdm.h: sdm_world_import / sdm_world_retain)
+WORLD_IMPORT_OPTIONS = np.dtype([("flags", "<u4"), ("cell_offset", "<i4", (3,)), ("max_bricks", "<i8")])
+WORLD_RETAIN_OPTIONS = np.dtype([("bmin", "<i4", (3,)), ("bmax", "<i4", (3,)), ("min_last_stamp", "<u4"), ("flags", "<u4")])
+assert WORLD_IMPORT_OPTIONS.itemsize == 24 and WORLD_RETAIN_OPTIONS.itemsize == 32
+WORLD_IMPORT_FILL = 0x10
+WORLD_IMPORT_ON_DEVICE = 0x20
 
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
@@ -342,6 +348,8 @@ def load_library():
         "sdm_get_world_occupied": [vp, vp, i64, C.POINTER(i64), u32],
         "sdm_query_world_points": [vp, vp, i64, vp, u32],
         "sdm_get_world_region": [vp, vp, vp, vp, u32],
+        "sdm_world_import": [vp, vp, vp, vp, i64],
+        "sdm_world_retain": [vp, vp, C.POINTER(i64)],
         "sdm_forecast_stamps": [C.c_float, vp, i32, vp, i32, u32, vp, i64, C.POINTER(i64)],
         "sdm_forecast_update": [vp, vp, i32, vp, i32, u32],
         "sdm_get_forecast": [vp, vp, vp, vp, vp],
@@ -1063,6 +1071,52 @@ class SdmMap:
         words = np.empty((max(int(sz[2]), 0), max(int(sz[1]), 0), max(int(sz[0]), 0)), np.uint32)
         _check(self.L, self.L.sdm_get_world_region(self.h, _ptr(lo), _ptr(sz), _ptr(words), 0), "sdm_get_world_region")
         return words
+
+    def world_import(self, bricks, cells, offset=(0, 0, 0), fill=False, static_only=False, observed_only=False, max_bricks=0, on_device=False,
+                     n=None):
+        """Merges foreign bricks - WORLD_BRICK[n] and uint32 [n, 512], as world_bricks returns them - into the archive, the
+        source's world cells moved by `offset` cells; fill: only where the archive reads unknown.  on_device: bricks and
+        cells are device pointers to n bricks, read in stream order on the map's stream; the call does not wait."""
+        o = np.zeros(1, WORLD_IMPORT_OPTIONS)
+        o["flags"] = ((WORLD_STATIC_ONLY if static_only else 0) | (WORLD_OBSERVED_ONLY if observed_only else 0) | (WORLD_IMPORT_FILL if fill else 0) |
+                      (WORLD_IMPORT_ON_DEVICE if on_device else 0))
+        o["cell_offset"][0] = np.asarray(offset, np.int64).reshape(3)
+        o["max_bricks"] = int(max_bricks)
+        if on_device:
+            _check(self.L, self.L.sdm_world_import(self.h, _ptr(o), _ptr(int(bricks)), _ptr(int(cells)), int(n)), "sdm_world_import")
+            return
+        b = np.ascontiguousarray(bricks, WORLD_BRICK).reshape(-1)
+        c = np.ascontiguousarray(cells, np.uint32).reshape(-1, 512)
+        if len(b) != len(c):
+            raise ValueError("world_import: %d headers and %d bricks of cells" % (len(b), len(c)))
+        _check(self.L, self.L.sdm_world_import(self.h, _ptr(o), _ptr(b), _ptr(c), len(b) if n is None else int(n)), "sdm_world_import")
+
+    def world_retain(self, bmin=None, bmax=None, min_last_stamp=0):
+        """Keeps the bricks inside the inclusive brick box bmin .. bmax (None: no bound) whose last_stamp >= min_last_stamp,
+        removes the others -> how many were removed"""
+        o = np.zeros(1, WORLD_RETAIN_OPTIONS)
+        o["bmin"][0] = np.asarray((-32768,) * 3 if bmin is None else bmin, np.int64).reshape(3)
+        o["bmax"][0] = np.asarray((32767,) * 3 if bmax is None else bmax, np.int64).reshape(3)
+        o["min_last_stamp"] = int(min_last_stamp)
+        got = C.c_int64()
+        _check(self.L, self.L.sdm_world_retain(self.h, _ptr(o), C.byref(got)), "sdm_world_retain")
+        return got.value
+
+    def save_world(self, path):
+        """the archive as a NumPy .npz: bricks (WORLD_BRICK), cells (uint32 [n, 512]) and the map's voxel_size (float32)"""
+        bricks, cells = self.world_bricks()
+        with open(path, "wb") as f:
+            np.savez(f, bricks=bricks, cells=cells, voxel_size=np.float32(self.cfg.voxel_size))
+
+    def load_world(self, path, **import_kwargs):
+        """world_import of a file save_world wrote -> the number of bricks in it; ValueError if the file's voxel_size is not,
+        bit for bit, this map's"""
+        with np.load(path) as z:
+            bricks, cells, size = z["bricks"], z["cells"], z["voxel_size"]
+        if size.dtype != np.float32 or size.tobytes() != np.float32(self.cfg.voxel_size).tobytes():
+            raise ValueError("load_world: the file's voxel_size %r is not the map's %r" % (size, np.float32(self.cfg.voxel_size)))
+        self.world_import(bricks.astype(WORLD_BRICK, copy=False), cells, **import_kwargs)
+        return len(bricks)
 
     def occupied(self, cap=None, zero_center=False, free=False, mark_fov=False):
         cap = cap or self.v_count

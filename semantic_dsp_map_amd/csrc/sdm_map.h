@@ -147,8 +147,11 @@ struct MeshLayer : Derived {
 // cells), the counters, a sort scratch of its own (its scans use the layers' shared scratch), the
 // sort's four buffers and the per-brick counts of the occupied list; order: the pool slots in brick order (inside
 // sortbuf) while `sorted`.  Derived's frame and flags are the last update's, steps the moved_steps it was built from;
-// capacity_set: an update since creation or sdm_world_clear has fixed max_bricks.
+// capacity_set: an update or import since creation or sdm_world_clear has fixed max_bricks.  io: the work arrays of an
+// import (world_io.hip), io_elems words: grown on demand, kept by an import in device mode, released by one in host mode.
 struct WorldLayer : Derived {
+  uint32_t *io = nullptr;
+  size_t io_elems = 0;
   int steps[3] = {0, 0, 0};
   unsigned long long *keys = nullptr;
   uint32_t *vals = nullptr, *cells = nullptr, *hdr = nullptr, *cand = nullptr, *meta = nullptr;

@@ -19,8 +19,9 @@
 // Which bricks get room depends on the scan alone, so everything is reproducible bit for bit.  The pool is in creation
 // order; the getters that promise brick order sort the pool slots by two passes of the stable radix sort (low word
 // (bx, by), then bz), lazily at the first such getter after an update.
-#include "sdm_layer.h"
-#include "sdm_map.h"
+// The table's key, hash, lookup and insertion, cell_writes, the header words, the counters' indices and k_world_finish
+// are in sdm_world.h, shared with world_io.hip (import and retain).
+#include "sdm_world.h"
 
 #pragma clang fp contract(off)
 
@@ -34,66 +35,6 @@ static_assert(SDM_WORLD_BYTES_PER_BRICK == 512 * 4 + 20 + 2 * (8 + 4) + 4 * 4 + 
 namespace sdm {
 
 namespace {
-
-constexpr int WTPB = 256, WWAVES = WTPB / 64;
-constexpr uint32_t NONE = 0xffffffffu;
-constexpr u64 EMPTY_KEY = ~0ull;
-constexpr uint32_t HDR_WORDS = 5;  // sdm_world_brick as words: bx | by << 16, bz | n_occupied << 16, n_free | pad << 16, first_stamp, last_stamp
-constexpr uint32_t ALL_FLAGS = SDM_WORLD_STATIC_ONLY | SDM_WORLD_OBSERVED_ONLY;
-constexpr int64_t MAX_BRICKS_LIMIT = (int64_t)1 << 21;  // 512 words each: the pool's word index stays in 32 bits
-enum { M_N_BRICKS = 0, M_CREATED, M_DROPPED, M_OOR, M_DROPPED_TOTAL /* u64: two words */, M_WORDS = 8 };
-
-struct WGeo {       // an update's geometry, by value
-  int g0[3];        // world cell of map-index cell (0, 0, 0)
-  int b0[3], nb[3]; // the candidates: bricks b0 .. b0 + nb - 1 per axis
-  uint32_t nc;      // nb[0] * nb[1] * nb[2]
-  uint32_t nc_max;  // what the candidate arrays and the scan are sized for
-  uint32_t flags, gts, max_bricks, hmask;
-  int max_movable;
-};
-
-__device__ __forceinline__ bool brick_in_range(int bx, int by, int bz) {
-  return bx >= -32768 && bx <= 32767 && by >= -32768 && by <= 32767 && bz >= -32768 && bz <= 32767;
-}
-__device__ __forceinline__ u64 brick_key(int bx, int by, int bz) {
-  return (u64)(uint32_t)(bx + 32768) | ((u64)(uint32_t)(by + 32768) << 16) | ((u64)(uint32_t)(bz + 32768) << 32);
-}
-__device__ __forceinline__ uint32_t key_hash(u64 k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return (uint32_t)k;
-}
-// the pool slot of a key, NONE if the archive has no such brick (the table is never more than half full)
-__device__ __forceinline__ uint32_t world_find(const u64 *__restrict__ keys, const uint32_t *__restrict__ vals, uint32_t hmask, u64 key) {
-  uint32_t h = key_hash(key) & hmask;
-  for (uint32_t i = 0; i <= hmask; ++i) {
-    const u64 k = keys[h];
-    if (k == key) return vals[h];
-    if (k == EMPTY_KEY) return NONE;
-    h = (h + 1u) & hmask;
-  }
-  return NONE;
-}
-__device__ __forceinline__ void world_insert(u64 *__restrict__ keys, uint32_t *__restrict__ vals, uint32_t hmask, u64 key, uint32_t slot) {
-  uint32_t h = key_hash(key) & hmask;
-  for (uint32_t i = 0; i <= hmask; ++i) {
-    if (atomicCAS(keys + h, EMPTY_KEY, key) == EMPTY_KEY) {
-      vals[h] = slot;  // (read by later launches only)
-      return;
-    }
-    h = (h + 1u) & hmask;
-  }
-}
-
-__device__ __forceinline__ bool cell_writes(uint32_t w1, uint32_t flags, int max_movable) {
-  const int occ = occ_of(w1);
-  const uint32_t track = w1 & 0xffffu;
-  const bool movable = track >= 1u && (int)track <= max_movable;
-  return occ >= 0 && !((flags & SDM_WORLD_STATIC_ONLY) && occ >= 1 && movable) && !((flags & SDM_WORLD_OBSERVED_ONLY) && occ == 2);
-}
 
 __device__ __forceinline__ void candidate_brick(const WGeo &g, uint32_t c, int &bx, int &by, int &bz) {
   const uint32_t nx = (uint32_t)g.nb[0], ny = (uint32_t)g.nb[1];
@@ -192,16 +133,6 @@ __global__ __launch_bounds__(WTPB) void k_world_merge(Dims d, Frame f, const uin
   h[2] = n_free;
   if (fresh) h[3] = g.gts;
   h[4] = g.gts;
-}
-
-__global__ __launch_bounds__(64) void k_world_finish(WGeo g, const uint32_t *__restrict__ rank, uint32_t *__restrict__ meta) {
-  if (threadIdx.x != 0u) return;
-  const uint32_t n = meta[M_N_BRICKS], wanted = rank[g.nc_max], room = g.max_bricks - n;
-  const uint32_t created = wanted < room ? wanted : room;
-  meta[M_N_BRICKS] = n + created;
-  meta[M_CREATED] = created;
-  u64 *total = reinterpret_cast<u64 *>(meta + M_DROPPED_TOTAL);
-  *total += meta[M_DROPPED];
 }
 
 // ---- brick order ----------------------------------------------------------------------------------------------------
@@ -327,8 +258,6 @@ __global__ __launch_bounds__(WTPB) void k_world_region(WBox b, uint32_t off, uin
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-constexpr LayerName WORLD = {"the world archive", "archive", "sdm_world_update", false};
-
 uint32_t candidates_max(const Dims &d) { return (((d.NX + 7) >> 3) + 1) * (((d.NY + 7) >> 3) + 1) * (((d.NZ + 7) >> 3) + 1); }
 int64_t default_bricks(const Dims &d) {
   int64_t want = std::max<int64_t>(2 * (int64_t)(d.NX / 8 + 1) * (d.NY / 8 + 1) * (d.NZ / 8 + 1), 4096), p = 1;
@@ -438,6 +367,31 @@ sdm_status world_sorted(sdm_map *m) {
 
 }  // namespace
 
+sdm_status world_counters(sdm_map *m, uint32_t *meta) {
+  uint32_t got[M_WORDS];
+  SDM_TRY(world_meta(m, got));
+  std::memcpy(meta, got, sizeof(got));
+  return SDM_OK;
+}
+
+sdm_status world_capacity(sdm_map *m, const char *what, int64_t max_bricks) {
+  WorldLayer &L = m->world;
+  if (!L.capacity_set) {  // the first update after creation or sdm_world_clear sets the capacity
+    const uint32_t want = (uint32_t)(max_bricks ? max_bricks : default_bricks(m->d));
+    if (want != L.max_bricks) {
+      if (L.max_bricks) HIP_TRY(hipStreamSynchronize(m->stream));
+      SDM_TRY(world_alloc(m, want));
+    }
+    L.capacity_set = true;
+  } else if (max_bricks && (uint32_t)max_bricks != L.max_bricks) {
+    uint32_t meta[M_WORDS];
+    SDM_TRY(world_meta(m, meta));
+    if (meta[M_N_BRICKS]) return LAYER_REFUSE(what, "another max_bricks while the archive holds bricks: call sdm_world_clear first");
+    SDM_TRY(world_alloc(m, (uint32_t)max_bricks));
+  }
+  return SDM_OK;
+}
+
 }  // namespace sdm
 
 // ---- the host side: the entry points behind include/sdm.h ---------------------------------------------------------
@@ -452,19 +406,7 @@ sdm_status sdm_world_update(sdm_map *m, const sdm_world_options *o) {
   SDM_TRY(layer_check(m, what, nullptr, WORLD));
   HIP_TRY(hipSetDevice(m->device));
   WorldLayer &L = m->world;
-  if (!L.capacity_set) {  // the first update after creation or sdm_world_clear sets the capacity
-    const uint32_t want = (uint32_t)(o->max_bricks ? o->max_bricks : default_bricks(m->d));
-    if (want != L.max_bricks) {
-      if (L.max_bricks) HIP_TRY(hipStreamSynchronize(m->stream));
-      SDM_TRY(world_alloc(m, want));
-    }
-    L.capacity_set = true;
-  } else if (o->max_bricks && (uint32_t)o->max_bricks != L.max_bricks) {
-    uint32_t meta[M_WORDS];
-    SDM_TRY(world_meta(m, meta));
-    if (meta[M_N_BRICKS]) return LAYER_REFUSE(what, "another max_bricks while the archive holds bricks: call sdm_world_clear first");
-    SDM_TRY(world_alloc(m, (uint32_t)o->max_bricks));
-  }
+  SDM_TRY(world_capacity(m, what, o->max_bricks));
   uint32_t *scan = nullptr;
   SDM_TRY(world_scan_scratch(m, &scan));
   const Frame f = m->f;

@@ -1,0 +1,32 @@
+"""SemanticDSPMap::worldBricks / worldImport / worldRetain (include/semantic_dsp_map.h): tests/cpp/adapter_world_io.cpp
+compiled against the stand-in Eigen/OpenCV/PCL headers and linked with libsdm_hip.so; constructed here, and on the GPU one
+map's archive of a wall scene is handed to a second map - at offset 0, with FILL, moved by an offset - and trimmed, the
+trim compared with the C ABI called directly."""
+import os
+import subprocess
+
+import pytest
+
+from semantic_dsp_map_amd import binding
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def build_exe(tmp_path):
+    csrc = os.path.dirname(binding.LIB_PATH)
+    exe = str(tmp_path / "adapter_world_io")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "tests", "mock_includes"), "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "adapter_world_io.cpp"), "-o", exe, "-L", csrc, "-lsdm_hip",
+                           "-Wl,-rpath," + csrc, "-Wl,-rpath,/opt/rocm/lib"])
+    return exe
+
+
+def test_adapter_world_io_compiles_and_links(tmp_path):
+    out = subprocess.run([build_exe(tmp_path)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "adapter constructed" in out.stdout, out.stdout + out.stderr
+
+
+@pytest.mark.gpu
+def test_adapter_world_io_hands_an_archive_to_a_second_map(tmp_path):
+    out = subprocess.run([build_exe(tmp_path), "run"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "world io ok" in out.stdout, out.stdout + out.stderr
