@@ -1197,6 +1197,89 @@ typedef struct {            /* 32 bytes, every field naturally aligned */
 } sdm_world_retain_options;
 sdm_status sdm_world_retain(sdm_map *m, const sdm_world_retain_options *o, int64_t *n_removed);
 
+/* ---- world reach: how far is it, through everything the map remembers, to a place the block has left? ----
+ * sdm_world_reach_update builds, on the map's stream, the travel-cost field of sdm_reach_update over the bricks of the
+ * world archive instead of the map block, from a set of start cells.  Like sdm_reach_update IT WAITS: the host decides
+ * when the relaxation is at rest, and no kernel ever waits for another workgroup.  Cells are world cells (int32 per
+ * axis): world cell of a point = floorf(p * recip) per axis, the archive's rule; brick = cell >> 3 (arithmetic).
+ * The field is the set of archived bricks at the time of the build; with SDM_WORLD_REACH_BOX those inside the inclusive
+ * brick box bmin .. bmax, and a brick outside it is as if absent.  Bricks are ranked in brick order - ascending in
+ * (bz, by, bx), signed, the order of sdm_get_world_bricks: without a box row r of sdm_get_world_reach belongs to row r of
+ * sdm_get_world_bricks taken at the same moment.  A cell of no brick of the field is never traversable under any flag:
+ * that bounds the search.  A neighbour brick whose coordinate would leave the int16 range is absent.
+ * The build is a SNAPSHOT: it owns its copy of the bricks' coordinates, a hash table of its own from brick to rank, the
+ * neighbour ranks, the masks and the costs, and answers the same bytes after any later sdm_world_update,
+ * sdm_world_import, sdm_world_retain or sdm_world_clear, until the next sdm_world_reach_update.  Nothing of the archive
+ * or of the map's state is modified.
+ * Cell class, from the archived word: traversable iff occ == 0; with SDM_WORLD_REACH_THROUGH_UNKNOWN also occ == -1 inside
+ * a brick of the field; with SDM_WORLD_REACH_IGNORE_MOVABLE a cell with occ >= 1 and 1 <= track <= max_movable_track counts
+ * as occ == 0 and is no obstacle.  An obstacle is a cell with occ >= 1 after that rule.
+ * Inflation: with inflate = r (1 or 2) a cell is traversable only if no obstacle cell lies within Chebyshev distance r of
+ * it.  Cells of no brick and unknown cells are no obstacles; the obstacles of absent bricks - with a box, of bricks outside
+ * it - do not exist.
+ * Moves, weights, field and descent are word for word those of sdm_reach_update: the 26 offsets numbered
+ * (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1), six with SDM_WORLD_REACH_FACE_CONNECTED; a move c -> c + o is allowed iff all 2,
+ * 4 or 8 cells c + s, s_a in {0, o_a}, are traversable cells of the field; weights 10 / 14 / 17; the descent takes the
+ * smallest allowed move number with cost(c + o) + w(o) == cost(c).  Everything is integer and bitwise reproducible.
+ * Budget: 17 x 512 x 2^21 does not fit 32 bits, so the effective budget is max_cost if that is non-zero and 0xfffffffe
+ * otherwise; a cell whose true cost exceeds it reads 0xffffffff, additions saturate, and the truncated field is still
+ * exact because every prefix of a cheapest path lies within the budget.
+ * Starts and goals: points (three floats each) or world cells (three int32 each); exactly one of the two pointers is
+ * non-NULL, also with a count of 0.  A start on a cell that is not traversable, in no brick of the field, non-finite or
+ * beyond the brick range is ignored; duplicates are fine; no usable start is no error: every cell then reads unreachable.
+ * sdm_get_world_reach waits: coords takes three int16 (bx, by, bz) and cost 512 words (cell word cx | cy << 3 | cz << 6;
+ * 0xffffffff: unreachable or not traversable) per brick of rows first .. first + cap - 1 of the field; *n_out = the bricks
+ * of the field; coords, cost and info may each be NULL.
+ * sdm_query_world_reach / sdm_world_reach_paths answer for the last build; SDM_QUERY_ON_DEVICE as for the other queries
+ * (device pointers, enqueued, no wait; out 8-byte aligned), host mode through the queries' staging area.  Row g of
+ * cells_out (n rows of max_len * 3 int32) takes the world cells of goal g's path from the goal to a start, both included;
+ * len_out[g] is its true length, 0 where there is none, and may exceed max_len: only the first min(len, max_len) cells
+ * are written, the rest of the row is left untouched, in host mode too.
+ * Memory, per brick of the field (in steps of 256 bricks): 2048 B of cost, 64 B of traversable and 64 B of obstacle mask,
+ * 108 B of neighbour ranks, 8 B of coordinates, its two hash slots (24 B), 4 B of list and a bit of activity: about 2320 B.
+ * Allocated at the first build, grown by a build of more bricks, freed by sdm_destroy.  A build also holds 12 B per
+ * archived brick (flags, ranks, pool slots) until it returns.
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map, options or output (n_out, out, len_out; cells_out with max_len > 0),
+ * none or both start / goal pointers, unknown flag bits, inflate > 2, a non-zero pad, bmax < bmin with the box flag,
+ * negative counts, first, cap or max_len, a Z-slab shard (shard_count > 1), a build before the archive has had an update
+ * or import, and the getter or a query before any build.  SDM_ERR_NOT_CONVERGED if the relaxation has not come to rest
+ * after 512 x n_bricks rounds: a defect, never a result. */
+#define SDM_WORLD_REACH_FACE_CONNECTED  0x01u  /* the six face moves only */
+#define SDM_WORLD_REACH_THROUGH_UNKNOWN 0x02u  /* cells with occ == -1 inside a brick of the field are traversable too */
+#define SDM_WORLD_REACH_IGNORE_MOVABLE  0x04u  /* occupied cells on movable tracks count as free */
+#define SDM_WORLD_REACH_BOX             0x08u  /* the field is the bricks inside bmin .. bmax */
+typedef struct {            /* 40 bytes, every field naturally aligned */
+  uint32_t flags;
+  uint32_t inflate;         /* 0, 1 or 2 cells */
+  uint32_t max_cost;        /* 0: no budget */
+  uint32_t pad;             /* 0 */
+  int32_t  bmin[3], bmax[3];/* inclusive brick box, read only with SDM_WORLD_REACH_BOX */
+} sdm_world_reach_options;
+typedef struct {            /* 40 bytes */
+  uint32_t n_bricks;        /* bricks in the field */
+  uint32_t n_starts_used;   /* distinct start cells that were traversable */
+  uint32_t n_traversable, n_reached, max_cost_reached;
+  uint32_t rounds;          /* relaxation rounds the build took (diagnostic; not part of the bitwise contract) */
+  uint32_t flags, inflate, max_cost;
+  uint32_t stamp;           /* the archive's stamp at the build: sdm_world_info.stamp */
+} sdm_world_reach_info;
+typedef struct {            /* 24 bytes */
+  uint32_t cost;            /* 0xffffffff: no path */
+  float    metres;          /* (float)cost * (voxel_size * 0.1f), float32, no contraction; -1 where no path */
+  int32_t  cell[3];         /* the goal's world cell; (0, 0, 0) for a point that is non-finite or beyond the brick range */
+  uint8_t  next;            /* move number of the first descent step; 13 at a start; 255 where no path */
+  uint8_t  status;          /* 0 reached, 1 traversable but unreachable (or beyond the budget), 2 in a brick of the field but
+                               not traversable, 3 in no brick of the field / non-finite / out of range */
+  uint16_t pad;             /* 0 */
+} sdm_world_reach_result;
+sdm_status sdm_world_reach_update(sdm_map *m, const sdm_world_reach_options *o, const float *start_xyz, const int32_t *start_cells,
+                                  int64_t n_starts);
+sdm_status sdm_get_world_reach(sdm_map *m, int16_t *coords, uint32_t *cost, int64_t first, int64_t cap, int64_t *n_out,
+                               sdm_world_reach_info *info);
+sdm_status sdm_query_world_reach(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n, sdm_world_reach_result *out, uint32_t flags);
+sdm_status sdm_world_reach_paths(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n, int32_t max_len, int32_t *cells_out,
+                                 int32_t *len_out, uint32_t flags);
+
 /* ---- owner sets of the object layer: ObjectParticleHashMap (object_layer.h:20-52) */
 sdm_status sdm_object_particle_count(sdm_map *m, int32_t track_id, int64_t *count);
 /* The keys of ObjectParticleHashMap::indices_map whose sets are not empty: every track id that owns at least one slot of
@@ -1256,6 +1339,8 @@ sdm_status sdm_debug_sweep_mode(sdm_map *m, int32_t *mode_out);
 sdm_status sdm_debug_alias_cap(sdm_map *m, int32_t cap);
 /* Diagnostic (tools/probes/reach_probe.py): the tiles relaxed by the last sdm_reach_update, summed over its rounds. */
 sdm_status sdm_debug_reach_tiles(sdm_map *m, int64_t *tiles_out);
+/* Diagnostic (tools/probes/world_reach_probe.py): the bricks relaxed by the last sdm_world_reach_update, summed over its rounds. */
+sdm_status sdm_debug_world_reach_bricks(sdm_map *m, int64_t *bricks_out);
 /* Test hook.  sdm_query_views keeps at most max_views_in_flight views in flight (never more than its pool has masks);
  * <= 0: the library's choice.  A test on a small map can so force a call to take several batches. */
 sdm_status sdm_debug_view_batch(sdm_map *m, int32_t max_views_in_flight);

@@ -749,6 +749,71 @@ class SemanticDSPMap {
     int64_t removed = 0;
     return check(sdm_world_retain(map_, &o, &removed), "sdm_world_retain") ? removed : -1;
   }
+  /// positions as the batched calls take them: three floats each
+  static std::vector<float> flat_points(const std::vector<Eigen::Vector3d> &points) {
+    std::vector<float> xyz(3 * points.size());
+    for (size_t i = 0; i < points.size(); ++i) {
+      xyz[3 * i] = (float)points[i].x();
+      xyz[3 * i + 1] = (float)points[i].y();
+      xyz[3 * i + 2] = (float)points[i].z();
+    }
+    return xyz;
+  }
+  /// How far is it, through everything the map remembers (sdm.h, "world reach")?  Builds the travel-cost field over the
+  /// bricks of the world archive from `start` (a global position, the robot's): the moves and weights of reach(), in world
+  /// cells, so it reaches what has left the block.  through_unknown: archived cells that were never observed can be crossed
+  /// as well as free ones (a cell of no brick never).  max_metres > 0 bounds the search.  inflate_cells (0, 1 or 2) keeps
+  /// the path that many cells away from every archived obstacle.  ignore_movable: obstacles on movable tracks count as
+  /// free.  The build is a snapshot: queryWorldReach() and worldReachPaths() answer for it until the next worldReach(),
+  /// whatever happens to the archive.  The call waits for the build.  info (may be null): the build's counts.  Returns
+  /// false before the first worldUpdate() or worldImport() or when the call fails.
+  bool worldReach(const Eigen::Vector3d &start, bool through_unknown = false, float max_metres = 0.f, int inflate_cells = 0,
+                  bool ignore_movable = false, sdm_world_reach_info *info = nullptr) {
+    if (!map_ || inflate_cells < 0) return false;
+    const float s[3] = {(float)start.x(), (float)start.y(), (float)start.z()};
+    sdm_world_reach_options o;
+    std::memset(&o, 0, sizeof(o));
+    o.flags = (through_unknown ? SDM_WORLD_REACH_THROUGH_UNKNOWN : 0u) | (ignore_movable ? SDM_WORLD_REACH_IGNORE_MOVABLE : 0u);
+    o.inflate = (uint32_t)inflate_cells;
+    // (0 would mean "no budget": a positive max_metres below a cost unit asks for one; 4294967040 is the largest float below 2^32)
+    o.max_cost = max_metres > 0.f ? (uint32_t)std::min(std::max(max_metres / (preset_.voxel_size * 0.1f), 1.f), 4294967040.f) : 0u;
+    if (!check(sdm_world_reach_update(map_, &o, s, nullptr, 1), "sdm_world_reach_update")) return false;
+    int64_t n = 0;
+    return !info || check(sdm_get_world_reach(map_, nullptr, nullptr, 0, 0, &n, info), "sdm_get_world_reach");
+  }
+  /// Per goal position (global frame) of the last worldReach(): cost, the same in metres, the goal's world cell, the first
+  /// step of the way back and a status.  Waits.  Returns the number of goals answered; 0 (and an empty vector) before the
+  /// first worldReach() or when the call fails.
+  size_t queryWorldReach(const std::vector<Eigen::Vector3d> &goals, std::vector<sdm_world_reach_result> &out) {
+    out.clear();
+    if (!map_ || goals.empty()) return 0;
+    const std::vector<float> xyz = flat_points(goals);
+    out.resize(goals.size());
+    if (!check(sdm_query_world_reach(map_, xyz.data(), nullptr, (int64_t)goals.size(), out.data(), 0u), "sdm_query_world_reach")) out.clear();
+    return out.size();
+  }
+  /// Per goal position of the last worldReach() the world cells from the goal to the start, both included; empty where
+  /// there is no path.  Waits.  Returns the number of goals answered; 0 (and an empty vector) before the first worldReach()
+  /// or when a call fails.
+  size_t worldReachPaths(const std::vector<Eigen::Vector3d> &goals, std::vector<std::vector<Eigen::Vector3i>> &paths) {
+    paths.clear();
+    if (!map_ || goals.empty()) return 0;
+    const std::vector<float> xyz = flat_points(goals);
+    std::vector<int32_t> lens(goals.size());
+    if (!check(sdm_world_reach_paths(map_, xyz.data(), nullptr, (int64_t)goals.size(), 0, nullptr, lens.data(), 0u), "sdm_world_reach_paths")) return 0;
+    const int32_t longest = *std::max_element(lens.begin(), lens.end());  // (the true lengths, whatever max_len)
+    std::vector<int32_t> rows(goals.size() * (size_t)longest * 3);
+    if (longest && !check(sdm_world_reach_paths(map_, xyz.data(), nullptr, (int64_t)goals.size(), longest, rows.data(), lens.data(), 0u),
+                          "sdm_world_reach_paths"))
+      return 0;
+    paths.resize(goals.size());
+    for (size_t i = 0; i < goals.size(); ++i)
+      for (int32_t k = 0; k < lens[i]; ++k) {
+        const int32_t *c = rows.data() + (i * (size_t)longest + (size_t)k) * 3;
+        paths[i].push_back(Eigen::Vector3i(c[0], c[1], c[2]));
+      }
+    return paths.size();
+  }
   /// the ray table scoreViews uses at `stride`: three floats per ray
   const std::vector<float> &viewRays(int stride) {
     if (stride != view_rays_stride_ || view_rays_.empty()) {

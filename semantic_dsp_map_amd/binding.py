@@ -126,6 +126,19 @@ WORLD_RETAIN_OPTIONS = np.dtype([("bmin", "<i4", (3,)), ("bmax", "<i4", (3,)), (
 assert WORLD_IMPORT_OPTIONS.itemsize == 24 and WORLD_RETAIN_OPTIONS.itemsize == 32
 WORLD_IMPORT_FILL = 0x10
 WORLD_IMPORT_ON_DEVICE = 0x20
+# world reach (sdm.h: sdm_world_reach_update / sdm_get_world_reach / sdm_query_world_reach / sdm_world_reach_paths)
+WORLD_REACH_OPTIONS = np.dtype([("flags", "<u4"), ("inflate", "<u4"), ("max_cost", "<u4"), ("pad", "<u4"), ("bmin", "<i4", (3,)),
+                                ("bmax", "<i4", (3,))])
+WORLD_REACH_INFO = np.dtype([("n_bricks", "<u4"), ("n_starts_used", "<u4"), ("n_traversable", "<u4"), ("n_reached", "<u4"),
+                             ("max_cost_reached", "<u4"), ("rounds", "<u4"), ("flags", "<u4"), ("inflate", "<u4"), ("max_cost", "<u4"),
+                             ("stamp", "<u4")])
+WORLD_REACH_RESULT = np.dtype([("cost", "<u4"), ("metres", "<f4"), ("cell", "<i4", (3,)), ("next", "u1"), ("status", "u1"), ("pad", "<u2")])
+assert WORLD_REACH_OPTIONS.itemsize == 40 and WORLD_REACH_INFO.itemsize == 40 and WORLD_REACH_RESULT.itemsize == 24
+WORLD_REACH_FACE_CONNECTED = 0x01
+WORLD_REACH_THROUGH_UNKNOWN = 0x02
+WORLD_REACH_IGNORE_MOVABLE = 0x04
+WORLD_REACH_BOX = 0x08
+WORLD_REACH_NO_CELL = -0x80000000   # what world_reach_paths fills its rows with behind a path
 
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
@@ -350,6 +363,11 @@ def load_library():
         "sdm_get_world_region": [vp, vp, vp, vp, u32],
         "sdm_world_import": [vp, vp, vp, vp, i64],
         "sdm_world_retain": [vp, vp, C.POINTER(i64)],
+        "sdm_world_reach_update": [vp, vp, vp, vp, i64],
+        "sdm_get_world_reach": [vp, vp, vp, i64, i64, C.POINTER(i64), vp],
+        "sdm_query_world_reach": [vp, vp, vp, i64, vp, u32],
+        "sdm_world_reach_paths": [vp, vp, vp, i64, i32, vp, vp, u32],
+        "sdm_debug_world_reach_bricks": [vp, C.POINTER(i64)],
         "sdm_forecast_stamps": [C.c_float, vp, i32, vp, i32, u32, vp, i64, C.POINTER(i64)],
         "sdm_forecast_update": [vp, vp, i32, vp, i32, u32],
         "sdm_get_forecast": [vp, vp, vp, vp, vp],
@@ -1101,6 +1119,73 @@ class SdmMap:
         got = C.c_int64()
         _check(self.L, self.L.sdm_world_retain(self.h, _ptr(o), C.byref(got)), "sdm_world_retain")
         return got.value
+
+    # ---- world reach (sdm.h).  world_reach_update builds the travel-cost field over the archive's bricks and WAITS until it
+    # is complete; world_reach(), query_world_reach() and world_reach_paths() answer for that build - a snapshot that later
+    # updates, imports, retains and clears of the archive do not touch - until the next one.
+    def world_reach_update(self, starts=None, start_cells=None, inflate=0, max_cost=0, face_connected=False, through_unknown=False,
+                           ignore_movable=False, box=None):
+        """starts: (n, 3) global positions, or start_cells: (n, 3) world cells (exactly one of the two); box: (bmin, bmax),
+        an inclusive box of brick coordinates the field is cut to"""
+        o = np.zeros(1, WORLD_REACH_OPTIONS)
+        o["flags"] = ((WORLD_REACH_FACE_CONNECTED if face_connected else 0) | (WORLD_REACH_THROUGH_UNKNOWN if through_unknown else 0) |
+                      (WORLD_REACH_IGNORE_MOVABLE if ignore_movable else 0) | (WORLD_REACH_BOX if box is not None else 0))
+        o["inflate"], o["max_cost"] = int(inflate), int(max_cost)
+        if box is not None:
+            o["bmin"], o["bmax"] = box[0], box[1]
+        p = None if starts is None else np.ascontiguousarray(starts, dtype=np.float32).reshape(-1, 3)
+        w = None if start_cells is None else np.ascontiguousarray(start_cells, dtype=np.int32).reshape(-1, 3)
+        n = len(p) if p is not None else len(w) if w is not None else 0
+        _check(self.L, self.L.sdm_world_reach_update(self.h, _ptr(o), _ptr(p), _ptr(w), n), "sdm_world_reach_update")
+
+    def world_reach(self, with_cost=True, first=0, cap=None):
+        """-> (coords int16 [n, 3] (bx, by, bz), cost uint32 [n, 512] or None, info a WORLD_REACH_INFO record): the bricks of
+        the field in brick order, rows first .. first + cap - 1"""
+        got = C.c_int64(0)
+        info = np.zeros(1, WORLD_REACH_INFO)
+        _check(self.L, self.L.sdm_get_world_reach(self.h, None, None, 0, 0, C.byref(got), _ptr(info)), "sdm_get_world_reach")
+        take = max(min(got.value - int(first), got.value if cap is None else int(cap)), 0)
+        coords = np.empty((take, 3), np.int16)
+        cost = np.empty((take, 512), np.uint32) if with_cost else None
+        _check(self.L, self.L.sdm_get_world_reach(self.h, _ptr(coords), _ptr(cost), int(first), take, C.byref(got), None), "sdm_get_world_reach")
+        return coords, cost, info[0]
+
+    def query_world_reach(self, xyz=None, cells=None, on_device=False, n=None, out=None):
+        """goals as (n, 3) global positions or as (n, 3) world cells -> WORLD_REACH_RESULT per goal.  on_device: the one
+        given of xyz / cells and out (n WORLD_REACH_RESULT) are device pointers."""
+        if on_device:
+            _check(self.L, self.L.sdm_query_world_reach(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
+                                                        _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_world_reach")
+            return None
+        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+        n = len(p) if p is not None else len(w) if w is not None else 0
+        res = np.empty(n, WORLD_REACH_RESULT)
+        _check(self.L, self.L.sdm_query_world_reach(self.h, _ptr(p), _ptr(w), n, _ptr(res), 0), "sdm_query_world_reach")
+        return res
+
+    def world_reach_paths(self, xyz=None, cells=None, max_len=0, on_device=False, n=None, cells_out=None, len_out=None,
+                          fill=WORLD_REACH_NO_CELL):
+        """-> (cells_out int32 [n, max_len, 3], len_out): row g holds the first min(len, max_len) world cells of goal g's
+        path, goal first, and `fill` behind them; len_out the true lengths (int32, 0: no path).  on_device: the pointers are
+        device pointers (cells_out n * max_len * 3 int32, len_out n int32) and nothing is returned."""
+        if on_device:
+            _check(self.L, self.L.sdm_world_reach_paths(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
+                                                        int(max_len), _ptr(int(cells_out)) if cells_out else None, _ptr(int(len_out)),
+                                                        QUERY_ON_DEVICE), "sdm_world_reach_paths")
+            return None
+        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+        n = len(p) if p is not None else len(w) if w is not None else 0
+        rows, lens = np.full((n, int(max_len), 3), fill, np.int32), np.zeros(n, np.int32)
+        _check(self.L, self.L.sdm_world_reach_paths(self.h, _ptr(p), _ptr(w), n, int(max_len), _ptr(rows), _ptr(lens), 0), "sdm_world_reach_paths")
+        return rows, lens
+
+    def world_reach_bricks_relaxed(self):
+        """Diagnostic: the bricks the last world_reach_update relaxed, summed over its rounds (sdm_debug_world_reach_bricks)."""
+        n = C.c_int64(0)
+        _check(self.L, self.L.sdm_debug_world_reach_bricks(self.h, C.byref(n)), "sdm_debug_world_reach_bricks")
+        return n.value
 
     def save_world(self, path):
         """the archive as a NumPy .npz: bricks (WORLD_BRICK), cells (uint32 [n, 512]) and the map's voxel_size (float32)"""

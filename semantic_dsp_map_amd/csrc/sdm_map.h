@@ -161,6 +161,19 @@ struct WorldLayer : Derived {
   bool capacity_set = false, sorted = false;
 };
 
+// world reach (world_reach.hip): a snapshot of the archive's bricks as a travel-cost field, laid out for `cap` bricks of
+// which n are in use and grown by a build that needs more: per brick of rank r its coordinates (two words), the ranks of
+// the 27 bricks round it, the traversable and the obstacle mask (8 x 64 bits each) and 512 costs; the hash table from
+// brick key to rank (hmask + 1 slots in use); the bricks' activity bitmask and the list of a round's active bricks; the
+// build's counters (and their page-locked landing area), its arguments and the archive's stamp.  No pool slot is kept.
+struct WorldReachLayer : Derived {
+  uint32_t *cost = nullptr, *nbr = nullptr, *coord = nullptr, *vals = nullptr, *act = nullptr, *list = nullptr;
+  unsigned long long *trav = nullptr, *obst = nullptr, *keys = nullptr;
+  uint32_t *meta = nullptr, *h_meta = nullptr;
+  size_t cap = 0;
+  uint32_t n = 0, hmask = 0, inflate = 0, max_cost = 0, stamp = 0;
+};
+
 struct sdm_map {
   sdm_config cfg{};
   sdm_params prm{};
@@ -323,6 +336,7 @@ struct sdm_map {
   GroundLayer ground;
   MeshLayer mesh;
   WorldLayer world;
+  WorldReachLayer wreach;
   // the scan scratch the layers share (layer_scan_scratch): they all enqueue on `stream` only, so their scans are ordered
   uint32_t *layer_scan = nullptr;
   size_t layer_scan_elems = 0;  // its capacity in uint32

@@ -1,7 +1,8 @@
-// sdm_world.h — what the two units of the world archive share (world.hip: the update, the getters and the queries;
-// world_io.hip: import and retain): the hash table's key, hash, lookup and insertion, which cells write, the header-word
-// layout, the indices of the counters, an update's geometry and its closing kernel, and the two host helpers of world.hip
-// that world_io.hip calls.  Everything but those two helpers has internal linkage: each unit compiles its own copy.
+// sdm_world.h — what the units of the world archive share (world.hip: the update, the getters and the queries;
+// world_io.hip: import and retain; world_reach.hip: the travel-cost field over the bricks): the hash table's key, hash,
+// lookup and insertion, which cells write, the header-word layout, the indices of the counters, an update's geometry and
+// its closing kernel, and the three host helpers of world.hip that the other two units call.  Everything but those three
+// helpers has internal linkage: each unit compiles its own copy.
 #pragma once
 #include "sdm_layer.h"
 #include "sdm_map.h"
@@ -13,6 +14,9 @@ namespace sdm {
 sdm_status world_capacity(sdm_map *m, const char *what, int64_t max_bricks);
 // world.hip: waits; the archive's counters (M_WORDS words)
 sdm_status world_counters(sdm_map *m, uint32_t *meta);
+// world.hip: the pool slots in brick order, n_bricks of them (device memory, good until the archive next changes); sorted
+// at the first call after a change, like sdm_get_world_bricks, which shares the order
+sdm_status world_order(sdm_map *m, const uint32_t **order);
 
 namespace {
 

@@ -374,6 +374,12 @@ sdm_status world_counters(sdm_map *m, uint32_t *meta) {
   return SDM_OK;
 }
 
+sdm_status world_order(sdm_map *m, const uint32_t **order) {
+  SDM_TRY(world_sorted(m));
+  *order = m->world.order;
+  return SDM_OK;
+}
+
 sdm_status world_capacity(sdm_map *m, const char *what, int64_t max_bricks) {
   WorldLayer &L = m->world;
   if (!L.capacity_set) {  // the first update after creation or sdm_world_clear sets the capacity
