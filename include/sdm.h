@@ -1280,6 +1280,88 @@ sdm_status sdm_query_world_reach(sdm_map *m, const float *xyz, const int32_t *ce
 sdm_status sdm_world_reach_paths(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n, int32_t max_len, int32_t *cells_out,
                                  int32_t *len_out, uint32_t flags);
 
+/* ---- world frontiers: where, beyond the block, is it worth going? ----
+ * sdm_world_frontiers_update builds, on the map's stream, the frontiers of sdm_frontiers_update over the bricks of the
+ * world archive instead of the map block: the free cells that border never-observed space, their connected clusters
+ * across brick borders and a table of them.  Like sdm_world_reach_update IT WAITS: it reads the number of bricks of the
+ * field and then the number of frontier cells, and sizes its buffers from them.  Cells are world cells (int32 per axis,
+ * brick = cell >> 3), the archive's origin is the world's, as in sdm_query_world_points.  The archive is what the layer
+ * reads: frontiers that mix the live block and the archive do not exist - call sdm_world_update first.
+ * Field: the archived bricks at the time of the build; with SDM_WORLD_FRONTIERS_BOX those inside the inclusive brick box
+ * bmin .. bmax (bmax < bmin on an axis: no brick, which is no error).  Bricks are ranked in brick order - ascending in
+ * (bz, by, bx), signed, the order of sdm_get_world_bricks.
+ * Frontier cell: a cell of a field brick whose archived word has occ == 0 and at least one of whose six face neighbours
+ * reads unknown; unknown_faces counts those neighbours (1 .. 6).  A neighbour reads unknown if its archived word has
+ * occ == -1, and also if it lies in no archived brick - the world is unbounded, an absent brick was never observed -
+ * unless SDM_WORLD_FRONTIERS_INSIDE_BRICKS is given.  The neighbour's word is read from the whole archive, not only from
+ * the field: a box makes no false frontier along its sides.  A neighbour brick beyond the int16 range is absent.
+ * Cell order: the cell list ascends in (brick rank, cell word cx | cy << 3 | cz << 6).
+ * Cluster: a connected component of frontier cells of the field, in world cells across brick borders, 26-connected, or
+ * 6-connected with SDM_WORLD_FRONTIERS_FACE_CONNECTED.  Its identity is its first cell in the list; the table ascends in
+ * first_index.  min_cells <= 1 keeps every cluster; a larger value leaves smaller clusters out of the table, their cells
+ * stay in the list with cluster 0xffffffff.
+ * Float fields of a cluster, one IEEE operation at a time, no contraction: box_min = (float)cell_min * voxel_size,
+ * box_max = (float)(cell_max + 1) * voxel_size, centroid = (float)(((double)cell_sum / (double)n_cells + 0.5) *
+ * (double)voxel_size).  Everything accumulated is an integer sum, minimum or maximum and a cluster's identity is its
+ * smallest cell index: two builds give the same bytes.
+ * The build is a SNAPSHOT: the getters return the same bytes after any later sdm_world_update, sdm_world_import,
+ * sdm_world_retain or sdm_world_clear, until the next sdm_world_frontiers_update.  It holds lists, no pool slot, once it
+ * returns.  Nothing of the archive or of the map's state is modified.
+ * max_cells > 0 caps the cell-proportional buffers: with more frontier cells than that the build writes no list and
+ * returns SDM_ERR_CAPACITY; sdm_get_world_frontier_clusters then still fills info (n_cells is the true count, the cluster
+ * counts are 0) and sdm_get_world_frontier_cells still sets *n_out to the true count, and both return SDM_ERR_CAPACITY
+ * until a build with room.  max_cells == 0: no cap.
+ * sdm_get_world_frontier_clusters: the first min(n, cap) table entries, *n_out = n, the clusters listed; info may be NULL.
+ * sdm_get_world_frontier_cells: rows first .. first + cap - 1 of the cell list - cell_xyz three int32 a cell, cluster the
+ * index into the table (0xffffffff: below min_cells), unknown_faces - each array may be NULL; *n_out = the cells in all.
+ * Memory, allocated at the first build, grown by a build that needs more, freed by sdm_destroy:
+ *   SDM_WORLD_FRONTIERS_BYTES_PER_ARCHIVED_BRICK x (archived bricks + 1, in steps of 256) + 4 x max_bricks
+ * + SDM_WORLD_FRONTIERS_BYTES_PER_BRICK x (bricks of the field, in steps of 256) + 12
+ * + SDM_WORLD_FRONTIERS_BYTES_PER_CELL x (frontier cells, in steps of 4096) + 4.
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map or options, unknown flag bits, negative max_cells, cap or first, a NULL
+ * n_out, a NULL out with cap > 0, a Z-slab shard (shard_count > 1), a build before the archive has had an update or
+ * import, and a getter before any build. */
+#define SDM_WORLD_FRONTIERS_FACE_CONNECTED 0x1u  /* clusters under 6- instead of 26-connectivity */
+#define SDM_WORLD_FRONTIERS_BOX            0x2u  /* the field is the bricks inside bmin .. bmax (inclusive brick box) */
+#define SDM_WORLD_FRONTIERS_INSIDE_BRICKS  0x4u  /* a neighbour in no archived brick is NOT unknown */
+#define SDM_WORLD_FRONTIERS_BYTES_PER_ARCHIVED_BRICK 136  /* box flag, rank, the free and the unknown words */
+#define SDM_WORLD_FRONTIERS_BYTES_PER_BRICK 240  /* coordinates, place, 27 + 6 neighbours, frontier words and their prefix */
+#define SDM_WORLD_FRONTIERS_BYTES_PER_CELL  201  /* world cell, cluster, root, scan, unknown_faces, accumulator, table entry */
+typedef struct {            /* 40 bytes, every field naturally aligned */
+  uint32_t flags;
+  int32_t  min_cells;       /* <= 1: every cluster is listed */
+  int64_t  max_cells;       /* 0: no cap */
+  int32_t  bmin[3], bmax[3];/* inclusive brick box, read only with SDM_WORLD_FRONTIERS_BOX */
+} sdm_world_frontiers_options;
+typedef struct {            /* 120 bytes, every field naturally aligned */
+  uint32_t first_index;     /* of the cluster's first cell in the cell list: its identity */
+  uint32_t n_cells;
+  uint32_t n_unknown_faces; /* the sum of its cells' unknown_faces */
+  uint32_t pad0;            /* 0 */
+  int32_t  first_cell[3];   /* world cell of the first cell */
+  int32_t  cell_min[3], cell_max[3]; /* inclusive */
+  uint32_t pad1;            /* 0 */
+  int64_t  cell_sum[3];     /* signed */
+  float    box_min[3], box_max[3], centroid[3];
+  uint32_t pad2;            /* 0 */
+} sdm_world_frontier_cluster;
+typedef struct {            /* 48 bytes, every field naturally aligned */
+  uint32_t n_bricks;        /* bricks of the field */
+  uint32_t n_clusters;      /* clusters listed: the table's length */
+  uint32_t n_clusters_total;/* clusters in all, those below min_cells included */
+  uint32_t flags;
+  int64_t  n_cells;         /* frontier cells */
+  int64_t  n_unknown_faces; /* the sum of unknown_faces over the cells */
+  int64_t  n_absent_faces;  /* how many of those faces look into bricks the archive does not have */
+  int32_t  min_cells;       /* as given */
+  uint32_t stamp;           /* the archive's stamp at the build: sdm_world_info.stamp */
+} sdm_world_frontiers_info;
+sdm_status sdm_world_frontiers_update(sdm_map *m, const sdm_world_frontiers_options *o);
+sdm_status sdm_get_world_frontier_clusters(sdm_map *m, sdm_world_frontier_cluster *out, int32_t cap, int32_t *n_out,
+                                           sdm_world_frontiers_info *info);
+sdm_status sdm_get_world_frontier_cells(sdm_map *m, int32_t *cell_xyz, uint32_t *cluster, uint8_t *unknown_faces,
+                                        int64_t first, int64_t cap, int64_t *n_out);
+
 /* ---- owner sets of the object layer: ObjectParticleHashMap (object_layer.h:20-52) */
 sdm_status sdm_object_particle_count(sdm_map *m, int32_t track_id, int64_t *count);
 /* The keys of ObjectParticleHashMap::indices_map whose sets are not empty: every track id that owns at least one slot of

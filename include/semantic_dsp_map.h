@@ -814,6 +814,27 @@ class SemanticDSPMap {
       }
     return paths.size();
   }
+  /// Where, beyond the block, is it worth going (sdm.h, "world frontiers")?  Builds the frontier cells of the world archive
+  /// - free cells beside never-observed space, bricks the archive does not have included unless inside_bricks - and their
+  /// clusters across brick borders (26-connected, 6-connected with face_connected), and returns the table of the clusters
+  /// of at least min_cells cells in `out`, ascending in first_index; a cluster's first_cell is a world cell to hand to
+  /// sdm_query_world_reach.  The archive is what is read: call worldUpdate() first.  The call waits for the build.  info
+  /// (may be null): the build's counts.  Returns false before the first worldUpdate() or worldImport() or when a call fails.
+  bool worldFrontiers(std::vector<sdm_world_frontier_cluster> &out, int min_cells = 1, bool face_connected = false, bool inside_bricks = false,
+                      sdm_world_frontiers_info *info = nullptr) {
+    out.clear();
+    if (!map_) return false;
+    sdm_world_frontiers_options o;
+    std::memset(&o, 0, sizeof(o));
+    o.flags = (face_connected ? SDM_WORLD_FRONTIERS_FACE_CONNECTED : 0u) | (inside_bricks ? SDM_WORLD_FRONTIERS_INSIDE_BRICKS : 0u);
+    o.min_cells = min_cells;
+    if (!check(sdm_world_frontiers_update(map_, &o), "sdm_world_frontiers_update")) return false;
+    int32_t n = 0;
+    if (!check(sdm_get_world_frontier_clusters(map_, nullptr, 0, &n, info), "sdm_get_world_frontier_clusters")) return false;
+    out.resize((size_t)n);
+    if (n && !check(sdm_get_world_frontier_clusters(map_, out.data(), n, &n, nullptr), "sdm_get_world_frontier_clusters")) out.clear();
+    return (int32_t)out.size() == n;
+  }
   /// the ray table scoreViews uses at `stride`: three floats per ray
   const std::vector<float> &viewRays(int stride) {
     if (stride != view_rays_stride_ || view_rays_.empty()) {

@@ -139,6 +139,19 @@ WORLD_REACH_THROUGH_UNKNOWN = 0x02
 WORLD_REACH_IGNORE_MOVABLE = 0x04
 WORLD_REACH_BOX = 0x08
 WORLD_REACH_NO_CELL = -0x80000000   # what world_reach_paths fills its rows with behind a path
+# world frontiers (sdm.h: sdm_world_frontiers_update / sdm_get_world_frontier_clusters / sdm_get_world_frontier_cells)
+WORLD_FRONTIERS_OPTIONS = np.dtype([("flags", "<u4"), ("min_cells", "<i4"), ("max_cells", "<i8"), ("bmin", "<i4", (3,)), ("bmax", "<i4", (3,))])
+WORLD_FRONTIER_CLUSTER = np.dtype([("first_index", "<u4"), ("n_cells", "<u4"), ("n_unknown_faces", "<u4"), ("pad0", "<u4"),
+                                   ("first_cell", "<i4", (3,)), ("cell_min", "<i4", (3,)), ("cell_max", "<i4", (3,)), ("pad1", "<u4"),
+                                   ("cell_sum", "<i8", (3,)), ("box_min", "<f4", (3,)), ("box_max", "<f4", (3,)), ("centroid", "<f4", (3,)),
+                                   ("pad2", "<u4")])
+WORLD_FRONTIERS_INFO = np.dtype([("n_bricks", "<u4"), ("n_clusters", "<u4"), ("n_clusters_total", "<u4"), ("flags", "<u4"), ("n_cells", "<i8"),
+                                 ("n_unknown_faces", "<i8"), ("n_absent_faces", "<i8"), ("min_cells", "<i4"), ("stamp", "<u4")])
+assert WORLD_FRONTIERS_OPTIONS.itemsize == 40 and WORLD_FRONTIER_CLUSTER.itemsize == 120 and WORLD_FRONTIERS_INFO.itemsize == 48
+WORLD_FRONTIERS_FACE_CONNECTED = 0x1
+WORLD_FRONTIERS_BOX = 0x2
+WORLD_FRONTIERS_INSIDE_BRICKS = 0x4
+WORLD_FRONTIER_NO_CLUSTER = 0xFFFFFFFF
 
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
@@ -368,6 +381,9 @@ def load_library():
         "sdm_query_world_reach": [vp, vp, vp, i64, vp, u32],
         "sdm_world_reach_paths": [vp, vp, vp, i64, i32, vp, vp, u32],
         "sdm_debug_world_reach_bricks": [vp, C.POINTER(i64)],
+        "sdm_world_frontiers_update": [vp, vp],
+        "sdm_get_world_frontier_clusters": [vp, vp, i32, C.POINTER(i32), vp],
+        "sdm_get_world_frontier_cells": [vp, vp, vp, vp, i64, i64, C.POINTER(i64)],
         "sdm_forecast_stamps": [C.c_float, vp, i32, vp, i32, u32, vp, i64, C.POINTER(i64)],
         "sdm_forecast_update": [vp, vp, i32, vp, i32, u32],
         "sdm_get_forecast": [vp, vp, vp, vp, vp],
@@ -1186,6 +1202,40 @@ class SdmMap:
         n = C.c_int64(0)
         _check(self.L, self.L.sdm_debug_world_reach_bricks(self.h, C.byref(n)), "sdm_debug_world_reach_bricks")
         return n.value
+
+    # ---- world frontiers (sdm.h).  world_frontiers_update builds the frontier cells of the archive's bricks and their
+    # clusters and WAITS until they are complete; world_frontiers() and world_frontier_cells() answer for that build - a
+    # snapshot that later updates, imports, retains and clears of the archive do not touch - until the next one.
+    def world_frontiers_update(self, face_connected=False, box=None, inside_bricks=False, min_cells=1, max_cells=0):
+        """box: (bmin, bmax), an inclusive box of brick coordinates the field is cut to; inside_bricks: a neighbour in no
+        archived brick does not read unknown"""
+        o = np.zeros(1, WORLD_FRONTIERS_OPTIONS)
+        o["flags"] = ((WORLD_FRONTIERS_FACE_CONNECTED if face_connected else 0) | (WORLD_FRONTIERS_BOX if box is not None else 0) |
+                      (WORLD_FRONTIERS_INSIDE_BRICKS if inside_bricks else 0))
+        o["min_cells"], o["max_cells"] = int(min_cells), int(max_cells)
+        if box is not None:
+            o["bmin"], o["bmax"] = box[0], box[1]
+        _check(self.L, self.L.sdm_world_frontiers_update(self.h, _ptr(o)), "sdm_world_frontiers_update")
+
+    def world_frontiers(self):
+        """-> (clusters, info): WORLD_FRONTIER_CLUSTER entries in ascending first_index, a WORLD_FRONTIERS_INFO record"""
+        got = C.c_int32(0)
+        info = np.zeros(1, WORLD_FRONTIERS_INFO)
+        _check(self.L, self.L.sdm_get_world_frontier_clusters(self.h, None, 0, C.byref(got), _ptr(info)), "sdm_get_world_frontier_clusters")
+        out = np.empty(got.value, WORLD_FRONTIER_CLUSTER)
+        _check(self.L, self.L.sdm_get_world_frontier_clusters(self.h, _ptr(out), got.value, C.byref(got), None), "sdm_get_world_frontier_clusters")
+        return out, info[0]
+
+    def world_frontier_cells(self, first=0, cap=None):
+        """-> (cells int32 [n, 3] world cells, cluster uint32, unknown_faces uint8): rows first .. first + cap - 1 of the cell
+        list, ascending in (brick order, cell word); cluster indexes the table (WORLD_FRONTIER_NO_CLUSTER: below min_cells)"""
+        got = C.c_int64(0)
+        _check(self.L, self.L.sdm_get_world_frontier_cells(self.h, None, None, None, 0, 0, C.byref(got)), "sdm_get_world_frontier_cells")
+        take = max(min(got.value - int(first), got.value if cap is None else int(cap)), 0)
+        cells, cluster, faces = np.empty((take, 3), np.int32), np.empty(take, np.uint32), np.empty(take, np.uint8)
+        _check(self.L, self.L.sdm_get_world_frontier_cells(self.h, _ptr(cells), _ptr(cluster), _ptr(faces), int(first), take, C.byref(got)),
+               "sdm_get_world_frontier_cells")
+        return cells, cluster, faces
 
     def save_world(self, path):
         """the archive as a NumPy .npz: bricks (WORLD_BRICK), cells (uint32 [n, 512]) and the map's voxel_size (float32)"""

@@ -174,6 +174,31 @@ struct WorldReachLayer : Derived {
   uint32_t n = 0, hmask = 0, inflate = 0, max_cost = 0, stamp = 0;
 };
 
+// world frontiers (world_frontiers.hip): a snapshot of the archive's frontier cells and their clusters.  Per archived brick
+// (cap_arch) the box flag, the rank in the field and the free and unknown words; per pool slot (cap_slots) the brick's place
+// in brick order; per brick of the field (cap_bricks) its coordinates, its place in brick order, the ranks of the 27 bricks
+// round it, the places of the six face neighbours, the frontier words and their prefix - all of them the build's own, read
+// by nobody once it returns.  Per cell (cap_cells) the world cell, parent (the cluster index in the end), root, the
+// scanned flags, unknown_faces, the accumulators (empty between builds) and the table.  The build's counters (and their
+// page-locked landing area, whose last word takes a count the build waits for), its arguments, the archive's stamp; over:
+// the build found more cells than max_cells and wrote no list.  Every buffer is grown by the build that needs more.
+struct WorldFrontiersLayer : Derived {
+  uint32_t *flag = nullptr, *rank = nullptr, *place_of_slot = nullptr;
+  unsigned long long *free_m = nullptr, *unk_m = nullptr, *front = nullptr;
+  uint32_t *coord = nullptr, *place = nullptr, *nbr = nullptr, *face_place = nullptr, *pre = nullptr;
+  int32_t *xyz = nullptr;
+  uint32_t *parent = nullptr, *root = nullptr, *idx = nullptr;
+  uint8_t *faces = nullptr;
+  unsigned char *acc = nullptr;
+  sdm_world_frontier_cluster *table = nullptr;
+  unsigned long long *meta = nullptr, *h_meta = nullptr;
+  size_t cap_arch = 0, cap_slots = 0, cap_bricks = 0, cap_cells = 0;
+  uint32_t n = 0, stamp = 0;
+  int32_t min_cells = 0;
+  int64_t n_cells = 0, max_cells = 0;
+  bool over = false;
+};
+
 struct sdm_map {
   sdm_config cfg{};
   sdm_params prm{};
@@ -337,6 +362,7 @@ struct sdm_map {
   MeshLayer mesh;
   WorldLayer world;
   WorldReachLayer wreach;
+  WorldFrontiersLayer wfront;
   // the scan scratch the layers share (layer_scan_scratch): they all enqueue on `stream` only, so their scans are ordered
   uint32_t *layer_scan = nullptr;
   size_t layer_scan_elems = 0;  // its capacity in uint32
