@@ -1362,6 +1362,76 @@ sdm_status sdm_get_world_frontier_clusters(sdm_map *m, sdm_world_frontier_cluste
 sdm_status sdm_get_world_frontier_cells(sdm_map *m, int32_t *cell_xyz, uint32_t *cluster, uint8_t *unknown_faces,
                                         int64_t first, int64_t cap, int64_t *n_out);
 
+/* ---- world distance field: how close is a remembered place to an obstacle? ----
+ * sdm_world_esdf_update builds, on the map's stream, a TRUNCATED Euclidean distance field over the bricks of the world
+ * archive: for every cell of a field brick the squared distance, in world cells, to the nearest archived obstacle cell and
+ * the offset to it, exact up to `radius` cells (1 .. SDM_WORLD_ESDF_MAX_RADIUS) and "far" beyond.  IT WAITS ONCE, for the
+ * number of bricks of the field, which sizes the buffers; the field itself is enqueued and the getter waits for it.  Cells
+ * are world cells (int32 per axis, brick = cell >> 3), the archive's origin is the world's.
+ * Obstacles: an archived cell with occ >= 1; with SDM_WORLD_ESDF_STATIC_ONLY a cell on a movable track (1 <= track <=
+ * max_movable_track) is none - the rule of SDM_WORLD_REACH_IGNORE_MOVABLE; with SDM_WORLD_ESDF_UNKNOWN_IS_OBSTACLE every
+ * cell with occ == -1 is one too, and so is EVERY CELL OF A BRICK THE ARCHIVE DOES NOT HAVE (a brick beyond the int16 range
+ * is absent).  Obstacles come from the whole archive, not only from the field: a box hides no wall behind its side.
+ * Field: the archived bricks at the time of the build; with SDM_WORLD_ESDF_BOX those inside the inclusive brick box
+ * bmin .. bmax (bmax < bmin on an axis: no brick, which is no error).  Bricks are ranked in brick order - ascending in
+ * (bz, by, bx), signed: without a box row r of sdm_get_world_esdf is row r of sdm_get_world_bricks taken at the same moment.
+ * Values, for a cell c of a field brick and R = radius: d2(c) = min over obstacle cells q of |c - q|^2.  If d2(c) <= R^2 the
+ * field holds it and offset = q - c of the nearest obstacle; among equally near obstacles the one with the SMALLEST WORLD
+ * CELL IN (z, y, x) ORDER wins, so the whole field is defined bit for bit.  An obstacle cell reads 0 / (0, 0, 0).
+ * Otherwise d2 = SDM_WORLD_ESDF_NONE and offset (0, 0, 0).
+ * The build is a SNAPSHOT: it owns the bricks' coordinates, a hash table of its own from brick to rank and the field, holds
+ * no pool slot, and answers the same bytes after any later sdm_world_update, sdm_world_import, sdm_world_retain or
+ * sdm_world_clear, until the next sdm_world_esdf_update.  Nothing of the archive or of the map's state is modified.
+ * sdm_get_world_esdf waits: per brick of rows first .. first + cap - 1 coords takes three int16 (bx, by, bz), d2 512 uint16
+ * (cell word cx | cy << 3 | cz << 6) and offset 512 x 3 int8 (dx, dy, dz); each array and info may be NULL; *n_out = the
+ * bricks of the field.  info: n_obstacle_cells counts the field cells that are obstacles, n_near_cells those with
+ * d2 <= R^2, the obstacle cells included.
+ * sdm_query_world_distance answers for the last build, for points (three floats each; world cell = floorf(p * recip) per
+ * axis, the archive's rule) or world cells (three int32 each); exactly one of the two pointers is non-NULL, also with
+ * n == 0.  `cell` is as sdm_world_reach_result.cell: (0, 0, 0) for a point that is non-finite or beyond the brick range, a
+ * cell given is echoed as given.  A cell in no brick of the field, a non-finite point or one out of range: d2 0xffffffff,
+ * distance -1, nearest = cell.  A field cell beyond the radius: d2 SDM_WORLD_ESDF_FAR, nearest = cell, distance =
+ * sqrtf((float)(R * R + 1)) * voxel_size, a LOWER BOUND.  Otherwise d2, nearest = cell + offset, distance =
+ * sqrtf((float)d2) * voxel_size - float32, one IEEE operation at a time, no contraction.  SDM_QUERY_ON_DEVICE as for the
+ * other queries (device pointers, enqueued, no wait; out 8-byte aligned), host mode through the queries' staging area.
+ * Memory, allocated at the first build, grown by a build that needs more, freed by sdm_destroy:
+ *   SDM_WORLD_ESDF_BYTES_PER_ARCHIVED_BRICK x (archived bricks + 1, in steps of 256)
+ * + SDM_WORLD_ESDF_BYTES_PER_BRICK x (bricks of the field, in steps of 256) + 2056 (the counters and their landing area).
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map, options or output (n_out, out), unknown flag bits, radius 0 or > 16,
+ * negative counts, first or cap, none or both of xyz and cells, a Z-slab shard (shard_count > 1), a build before the
+ * archive has had an update or import, and the getter or the query before any build. */
+#define SDM_WORLD_ESDF_UNKNOWN_IS_OBSTACLE 0x1u  /* occ == -1 and every cell of a brick the archive does not have */
+#define SDM_WORLD_ESDF_STATIC_ONLY         0x2u  /* occupied cells on movable tracks are no obstacles */
+#define SDM_WORLD_ESDF_BOX                 0x4u  /* the field is the bricks inside bmin .. bmax (inclusive brick box) */
+#define SDM_WORLD_ESDF_MAX_RADIUS 16
+#define SDM_WORLD_ESDF_NONE 0xffffu              /* in the getter's d2: no obstacle within the radius */
+#define SDM_WORLD_ESDF_FAR  0xfffffffeu          /* in a query's d2: a field cell with no obstacle within the radius */
+#define SDM_WORLD_ESDF_BYTES_PER_ARCHIVED_BRICK 72  /* box flag, rank, the eight obstacle words */
+#define SDM_WORLD_ESDF_BYTES_PER_BRICK 2080      /* 512 packed field words, coordinates, two hash slots */
+typedef struct {            /* 32 bytes, every field naturally aligned */
+  uint32_t flags;
+  uint32_t radius;          /* 1 .. SDM_WORLD_ESDF_MAX_RADIUS cells */
+  int32_t  bmin[3], bmax[3];/* inclusive brick box, read only with SDM_WORLD_ESDF_BOX */
+} sdm_world_esdf_options;
+typedef struct {            /* 32 bytes, every field naturally aligned */
+  uint32_t n_bricks;        /* bricks of the field */
+  uint32_t flags, radius;   /* as given */
+  uint32_t stamp;           /* the archive's stamp at the build: sdm_world_info.stamp */
+  int64_t  n_obstacle_cells;/* field cells that are obstacles (d2 == 0) */
+  int64_t  n_near_cells;    /* field cells with d2 <= radius^2, the obstacle cells included */
+} sdm_world_esdf_info;
+typedef struct {            /* 32 bytes */
+  int32_t  cell[3];         /* the world cell asked about */
+  int32_t  nearest[3];      /* world cell of the nearest obstacle; = cell where there is none within reach */
+  uint32_t d2;              /* squared distance in cells; SDM_WORLD_ESDF_FAR; 0xffffffff: in no brick of the field */
+  float    distance;        /* metres; the lower bound for FAR; -1 in no brick of the field */
+} sdm_world_distance_result;
+sdm_status sdm_world_esdf_update(sdm_map *m, const sdm_world_esdf_options *o);
+sdm_status sdm_get_world_esdf(sdm_map *m, int16_t *coords, uint16_t *d2, int8_t *offset, int64_t first, int64_t cap,
+                              int64_t *n_out, sdm_world_esdf_info *info);
+sdm_status sdm_query_world_distance(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n,
+                                    sdm_world_distance_result *out, uint32_t flags);
+
 /* ---- owner sets of the object layer: ObjectParticleHashMap (object_layer.h:20-52) */
 sdm_status sdm_object_particle_count(sdm_map *m, int32_t track_id, int64_t *count);
 /* The keys of ObjectParticleHashMap::indices_map whose sets are not empty: every track id that owns at least one slot of

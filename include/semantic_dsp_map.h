@@ -835,6 +835,35 @@ class SemanticDSPMap {
     if (n && !check(sdm_get_world_frontier_clusters(map_, out.data(), n, &n, nullptr), "sdm_get_world_frontier_clusters")) out.clear();
     return (int32_t)out.size() == n;
   }
+  /// How close is a remembered place to an obstacle (sdm.h, "world distance field")?  Builds the truncated Euclidean
+  /// distance field over the bricks of the world archive: exact up to max_metres - radius = ceil(max_metres / voxel_size)
+  /// cells, at least 1 and at most SDM_WORLD_ESDF_MAX_RADIUS - and "far" beyond.  unknown_is_obstacle: never-observed
+  /// cells, and every cell of a brick the archive does not have, are obstacles too; static_only: obstacles on movable tracks
+  /// are none.  The build is a snapshot: queryWorldDistance() answers for it until the next worldEsdf(), whatever happens to
+  /// the archive.  The archive is what is read: call worldUpdate() first.  info (may be null): the build's counts (the call
+  /// then waits for them).  Returns false before the first worldUpdate() or worldImport() or when a call fails.
+  bool worldEsdf(float max_metres, bool unknown_is_obstacle = false, bool static_only = false, sdm_world_esdf_info *info = nullptr) {
+    if (!map_ || !(max_metres > 0.f)) return false;
+    sdm_world_esdf_options o;
+    std::memset(&o, 0, sizeof(o));
+    o.flags = (unknown_is_obstacle ? SDM_WORLD_ESDF_UNKNOWN_IS_OBSTACLE : 0u) | (static_only ? SDM_WORLD_ESDF_STATIC_ONLY : 0u);
+    o.radius = (uint32_t)std::min(std::max(std::ceil(max_metres / preset_.voxel_size), 1.f), (float)SDM_WORLD_ESDF_MAX_RADIUS);
+    if (!check(sdm_world_esdf_update(map_, &o), "sdm_world_esdf_update")) return false;
+    int64_t n = 0;
+    return !info || check(sdm_get_world_esdf(map_, nullptr, nullptr, nullptr, 0, 0, &n, info), "sdm_get_world_esdf");
+  }
+  /// Per position (global frame) of the last worldEsdf(): its world cell, the world cell of the nearest archived obstacle,
+  /// the squared distance in cells and the distance in metres - SDM_WORLD_ESDF_FAR and a lower bound beyond the radius,
+  /// 0xffffffff and -1 in no brick of the field.  Waits.  Returns the number of points answered; 0 (and an empty vector)
+  /// before the first worldEsdf() or when the call fails.
+  size_t queryWorldDistance(const std::vector<Eigen::Vector3d> &points, std::vector<sdm_world_distance_result> &out) {
+    out.clear();
+    if (!map_ || points.empty()) return 0;
+    const std::vector<float> xyz = flat_points(points);
+    out.resize(points.size());
+    if (!check(sdm_query_world_distance(map_, xyz.data(), nullptr, (int64_t)points.size(), out.data(), 0u), "sdm_query_world_distance")) out.clear();
+    return out.size();
+  }
   /// the ray table scoreViews uses at `stride`: three floats per ray
   const std::vector<float> &viewRays(int stride) {
     if (stride != view_rays_stride_ || view_rays_.empty()) {

@@ -152,6 +152,18 @@ WORLD_FRONTIERS_FACE_CONNECTED = 0x1
 WORLD_FRONTIERS_BOX = 0x2
 WORLD_FRONTIERS_INSIDE_BRICKS = 0x4
 WORLD_FRONTIER_NO_CLUSTER = 0xFFFFFFFF
+# world distance field (sdm.h: sdm_world_esdf_update / sdm_get_world_esdf / sdm_query_world_distance)
+WORLD_ESDF_OPTIONS = np.dtype([("flags", "<u4"), ("radius", "<u4"), ("bmin", "<i4", (3,)), ("bmax", "<i4", (3,))])
+WORLD_ESDF_INFO = np.dtype([("n_bricks", "<u4"), ("flags", "<u4"), ("radius", "<u4"), ("stamp", "<u4"), ("n_obstacle_cells", "<i8"),
+                            ("n_near_cells", "<i8")])
+WORLD_DISTANCE_RESULT = np.dtype([("cell", "<i4", (3,)), ("nearest", "<i4", (3,)), ("d2", "<u4"), ("distance", "<f4")])
+assert WORLD_ESDF_OPTIONS.itemsize == 32 and WORLD_ESDF_INFO.itemsize == 32 and WORLD_DISTANCE_RESULT.itemsize == 32
+WORLD_ESDF_UNKNOWN_IS_OBSTACLE = 0x1
+WORLD_ESDF_STATIC_ONLY = 0x2
+WORLD_ESDF_BOX = 0x4
+WORLD_ESDF_MAX_RADIUS = 16
+WORLD_ESDF_NONE = 0xFFFF          # in world_esdf()'s d2
+WORLD_ESDF_FAR = 0xFFFFFFFE       # in a WORLD_DISTANCE_RESULT's d2
 
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
@@ -384,6 +396,9 @@ def load_library():
         "sdm_world_frontiers_update": [vp, vp],
         "sdm_get_world_frontier_clusters": [vp, vp, i32, C.POINTER(i32), vp],
         "sdm_get_world_frontier_cells": [vp, vp, vp, vp, i64, i64, C.POINTER(i64)],
+        "sdm_world_esdf_update": [vp, vp],
+        "sdm_get_world_esdf": [vp, vp, vp, vp, i64, i64, C.POINTER(i64), vp],
+        "sdm_query_world_distance": [vp, vp, vp, i64, vp, u32],
         "sdm_forecast_stamps": [C.c_float, vp, i32, vp, i32, u32, vp, i64, C.POINTER(i64)],
         "sdm_forecast_update": [vp, vp, i32, vp, i32, u32],
         "sdm_get_forecast": [vp, vp, vp, vp, vp],
@@ -1236,6 +1251,47 @@ class SdmMap:
         _check(self.L, self.L.sdm_get_world_frontier_cells(self.h, _ptr(cells), _ptr(cluster), _ptr(faces), int(first), take, C.byref(got)),
                "sdm_get_world_frontier_cells")
         return cells, cluster, faces
+
+    # ---- world distance field (sdm.h).  world_esdf_update builds the truncated distance field over the archive's bricks
+    # (it waits once, for the field's brick count); world_esdf() and query_world_distance() answer for that build - a
+    # snapshot that later updates, imports, retains and clears of the archive do not touch - until the next one.
+    def world_esdf_update(self, radius, unknown_is_obstacle=False, static_only=False, box=None):
+        """radius: 1 .. WORLD_ESDF_MAX_RADIUS cells, up to which the field is exact; box: (bmin, bmax), an inclusive box of
+        brick coordinates the field is cut to (obstacles still come from the whole archive)"""
+        o = np.zeros(1, WORLD_ESDF_OPTIONS)
+        o["flags"] = ((WORLD_ESDF_UNKNOWN_IS_OBSTACLE if unknown_is_obstacle else 0) | (WORLD_ESDF_STATIC_ONLY if static_only else 0) |
+                      (WORLD_ESDF_BOX if box is not None else 0))
+        o["radius"] = int(radius)
+        if box is not None:
+            o["bmin"], o["bmax"] = box[0], box[1]
+        _check(self.L, self.L.sdm_world_esdf_update(self.h, _ptr(o)), "sdm_world_esdf_update")
+
+    def world_esdf(self, first=0, cap=None):
+        """-> (coords int16 [n, 3] (bx, by, bz), d2 uint16 [n, 512] (WORLD_ESDF_NONE: beyond the radius), offset int8
+        [n, 512, 3] (dx, dy, dz) to the nearest obstacle, info a WORLD_ESDF_INFO record): the bricks of the field in brick
+        order, rows first .. first + cap - 1"""
+        got = C.c_int64(0)
+        info = np.zeros(1, WORLD_ESDF_INFO)
+        _check(self.L, self.L.sdm_get_world_esdf(self.h, None, None, None, 0, 0, C.byref(got), _ptr(info)), "sdm_get_world_esdf")
+        take = max(min(got.value - int(first), got.value if cap is None else int(cap)), 0)
+        coords, d2, offset = np.empty((take, 3), np.int16), np.empty((take, 512), np.uint16), np.empty((take, 512, 3), np.int8)
+        _check(self.L, self.L.sdm_get_world_esdf(self.h, _ptr(coords), _ptr(d2), _ptr(offset), int(first), take, C.byref(got), None),
+               "sdm_get_world_esdf")
+        return coords, d2, offset, info[0]
+
+    def query_world_distance(self, xyz=None, cells=None, on_device=False, n=None, out=None):
+        """(n, 3) global positions or (n, 3) world cells -> WORLD_DISTANCE_RESULT per entry.  on_device: the one given of
+        xyz / cells and out (n WORLD_DISTANCE_RESULT) are device pointers."""
+        if on_device:
+            _check(self.L, self.L.sdm_query_world_distance(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
+                                                           _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_world_distance")
+            return None
+        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+        n = len(p) if p is not None else len(w) if w is not None else 0
+        res = np.empty(n, WORLD_DISTANCE_RESULT)
+        _check(self.L, self.L.sdm_query_world_distance(self.h, _ptr(p), _ptr(w), n, _ptr(res), 0), "sdm_query_world_distance")
+        return res
 
     def save_world(self, path):
         """the archive as a NumPy .npz: bricks (WORLD_BRICK), cells (uint32 [n, 512]) and the map's voxel_size (float32)"""

@@ -199,6 +199,19 @@ struct WorldFrontiersLayer : Derived {
   bool over = false;
 };
 
+// the world distance field (world_esdf.hip): a snapshot of the archive's bricks as a truncated distance field.  Per
+// archived brick (cap_arch) the box flag, the rank in the field and the eight obstacle words, indexed by pool slot - the
+// build's own, read by nobody once it has run; per brick of the field (cap_bricks) its coordinates and 512 packed field
+// words, and the hash table from brick key to rank (hmask + 1 slots in use).  The two info counters (and their page-locked
+// landing area, whose last word takes the count the build waits for), the build's radius, the archive's stamp.
+struct WorldEsdfLayer : Derived {
+  uint32_t *flag = nullptr, *rank = nullptr, *coord = nullptr, *vals = nullptr, *field = nullptr;
+  unsigned long long *obst = nullptr, *keys = nullptr;
+  unsigned long long *meta = nullptr, *h_meta = nullptr;
+  size_t cap_arch = 0, cap_bricks = 0;
+  uint32_t n = 0, hmask = 0, radius = 0, stamp = 0;
+};
+
 struct sdm_map {
   sdm_config cfg{};
   sdm_params prm{};
@@ -363,6 +376,7 @@ struct sdm_map {
   WorldLayer world;
   WorldReachLayer wreach;
   WorldFrontiersLayer wfront;
+  WorldEsdfLayer wesdf;
   // the scan scratch the layers share (layer_scan_scratch): they all enqueue on `stream` only, so their scans are ordered
   uint32_t *layer_scan = nullptr;
   size_t layer_scan_elems = 0;  // its capacity in uint32
