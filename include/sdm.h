@@ -1432,6 +1432,69 @@ sdm_status sdm_get_world_esdf(sdm_map *m, int16_t *coords, uint16_t *d2, int8_t 
 sdm_status sdm_query_world_distance(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n,
                                     sdm_world_distance_result *out, uint32_t flags);
 
+/* ---- world rays: is this straight leg free, and what would a camera at that remembered place see? ----
+ * sdm_query_world_segments and sdm_query_world_views are the archive's counterparts of sdm_query_segments and
+ * sdm_query_views: the same walks, through the bricks of the world archive instead of the block.  Both read the archive
+ * LIVE, in stream order on the map's stream: they see it as the last sdm_world_update, sdm_world_import, sdm_world_retain
+ * or sdm_world_clear enqueued before them left it, take no snapshot, and write only the caller's outputs and - the views - a
+ * pool of bitmasks of their own.  Positions are in the global frame.  World-index coordinate of a position p: u = p * recip
+ * per axis, the archive's own float32 rule; world cell floor(u); brick = cell >> 3; a brick beyond the int16 range is absent
+ * and never looked up.  Everything but t is an integer: the answers are bitwise reproducible.
+ * Cell classes: occupied - the archived word has occ >= 1; free - occ == 0; unknown - occ == -1 OR THE CELL LIES IN A BRICK
+ * THE ARCHIVE DOES NOT HAVE.  With SDM_WORLD_RAYS_IGNORE_MOVABLE an occupied cell on a movable track (1 <= track <=
+ * max_movable_track) counts as free - the rule of SDM_WORLD_REACH_IGNORE_MOVABLE.
+ *
+ * Segments a -> b (ab[6i..6i+5] = ax ay az bx by bz) are traversed in ascending t, u(t) = u(a) + t (u(b) - u(a)), t in
+ * [0, 1], as sdm_query_segments traverses them: a 3-D DDA in double, every crossing parameter computed fresh from the end
+ * points as (plane - u_a) * (1 / (u_b - u_a)), a plane crossed while its t <= 1, x before y before z at equal t; a
+ * zero-length segment is the cell of a.  The lattice is the unbounded lattice of world cells: nothing is clipped.  Occupied
+ * cells block; with SDM_QUERY_UNKNOWN_BLOCKS unknown cells block too, those of absent bricks included.
+ * Two rules keep the cost finite.  INVALID: an end point with a non-finite u, or whose cell lies in a brick beyond the int16
+ * range (floor(u) outside [-262144, 262144)): no hit, cells = 0, unknown = 0; with SDM_QUERY_UNKNOWN_BLOCKS a hit at t = 0
+ * with occ -1, cell (0, 0, 0), cells = 0.  TOO LONG: a valid segment with 1 + sum over the axes of |floor(u_b) - floor(u_a)|
+ * > SDM_WORLD_SEGMENT_MAX_CELLS (8192: 819 m at 0.1 m voxels, a second of a lane's time): t = -1, cells = -1, nothing is
+ * walked, under any flag.  (The walk itself may visit one cell more per axis: a plane at exactly t = 1, approached from
+ * above, is still crossed - as in sdm_query_segments.)
+ *
+ * Views: sdm_view, sdm_view_gain and the ray table are sdm_query_views': ray r of view v is the segment from a = pos to
+ * b = pos + range * (R(q) d_r) in the float32 order given there; range <= 0 is the zero-length segment.  Where the block
+ * query is bounded by the block, this one is bounded by a window the caller states: with c0 the cell of pos, the world cells
+ * with |c_i - c0_i| <= reach_cells per axis, 1 <= reach_cells <= SDM_WORLD_VIEW_MAX_REACH - a host integer, so that device
+ * mode never reads a view to size anything.  A ray is walked as a world segment without SDM_QUERY_UNKNOWN_BLOCKS and ends at
+ * its blocking cell, at b, or where its next step would leave the window (at most 3 reach_cells + 1 cells: the 8192 rule
+ * does not apply).  The blocking cell counts towards n_occupied, every cell before it towards n_unknown or n_free by its
+ * class - cells of absent bricks are unknown: they are the gain -, each cell ONCE per view however many rays visit it;
+ * rays_hit counts the rays that end in a blocking cell, rays_in_map those walked (>= 1 cell), ray_cells and ray_unknown are
+ * the sums over the rays.  A view is invalid - an all-zero gain, rays with t = -1 and cells = 0 - when pos, q or range is
+ * non-finite or the window reaches beyond the int16 brick range; a non-finite d_r or u(b) does that for its ray only.
+ * rays_out (may be NULL) holds one sdm_world_segment_hit per (view, ray) at [v * n_rays + r]: bit for bit what
+ * sdm_query_world_segments returns for (a, b) under the same SDM_WORLD_RAYS_IGNORE_MOVABLE whenever every cell of that
+ * segment lies in the window and the segment is not too long; otherwise the clipped walk's.
+ * Memory: one bit per window cell and view in flight, S^3 bits with S = 2 reach_cells + 1 (bit ((z - z0) S + (y - y0)) S +
+ * (x - x0)), in a pool of this layer's own of at most 64 MiB, grown on demand (a call that grows it waits for the stream
+ * once), freed by sdm_destroy and all zero whenever a call's work has completed (each batch's masks are zeroed by a memset
+ * behind it).  min(256, 64 MiB / mask bytes) views are in flight, at least 3 (the mask of reach 255 takes 16.7 MB); a call
+ * with more views works in batches.  Host mode is staged in chunks of whole views, like sdm_query_views.
+ * SDM_QUERY_ON_DEVICE as for the other queries (device pointers, enqueued, no wait; outputs 8-byte aligned).
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map, input or out, n < 0, unknown flag bits (the views refuse
+ * SDM_QUERY_UNKNOWN_BLOCKS), a NULL ray table, n_rays < 1 or > SDM_VIEW_MAX_RAYS, n_views * n_rays >= 2^31, reach_cells out of
+ * range, a Z-slab shard (shard_count > 1), and a call before any sdm_world_update / sdm_world_import or after
+ * sdm_world_clear.  n == 0 launches nothing. */
+#define SDM_WORLD_RAYS_IGNORE_MOVABLE 0x10u   /* occupied cells on movable tracks count as free */
+#define SDM_WORLD_SEGMENT_MAX_CELLS 8192      /* a segment of more world cells is "too long" and not walked */
+#define SDM_WORLD_VIEW_MAX_REACH 255          /* the largest reach_cells: a window of 511^3 cells */
+typedef struct {          /* 32 bytes */
+  float    t;             /* as sdm_segment_hit.t; -1: nothing blocks */
+  int32_t  cells;         /* world cells visited up to and including the hit; 0: invalid; -1: too long */
+  int32_t  cell[3];       /* world cell of the hit; (0, 0, 0) without one */
+  uint16_t track; uint8_t label; int8_t occ;  /* the hit cell's word; 0 / 0 / -1 without a hit or for an absent brick */
+  int32_t  unknown;       /* visited cells that are unknown, the hit included if it is one */
+  uint32_t stamp;         /* last_stamp of the hit cell's brick; 0 without one */
+} sdm_world_segment_hit;
+sdm_status sdm_query_world_segments(sdm_map *m, const float *ab, int64_t n, sdm_world_segment_hit *out, uint32_t flags);
+sdm_status sdm_query_world_views(sdm_map *m, const sdm_view *views, int64_t n_views, const float *dirs, int32_t n_rays,
+                                 int32_t reach_cells, sdm_view_gain *out, sdm_world_segment_hit *rays_out, uint32_t flags);
+
 /* ---- owner sets of the object layer: ObjectParticleHashMap (object_layer.h:20-52) */
 sdm_status sdm_object_particle_count(sdm_map *m, int32_t track_id, int64_t *count);
 /* The keys of ObjectParticleHashMap::indices_map whose sets are not empty: every track id that owns at least one slot of
@@ -1496,6 +1559,8 @@ sdm_status sdm_debug_world_reach_bricks(sdm_map *m, int64_t *bricks_out);
 /* Test hook.  sdm_query_views keeps at most max_views_in_flight views in flight (never more than its pool has masks);
  * <= 0: the library's choice.  A test on a small map can so force a call to take several batches. */
 sdm_status sdm_debug_view_batch(sdm_map *m, int32_t max_views_in_flight);
+/* Test hook.  The same for sdm_query_world_views and its pool. */
+sdm_status sdm_debug_world_view_batch(sdm_map *m, int32_t max_views_in_flight);
 
 /* ---- device-side unit tests of the hand-written primitives (tests/test_primitives_gpu.py) */
 sdm_status sdm_test_scan(const uint32_t *in, uint32_t *out, int64_t n);

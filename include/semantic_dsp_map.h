@@ -864,6 +864,44 @@ class SemanticDSPMap {
     if (!check(sdm_query_world_distance(map_, xyz.data(), nullptr, (int64_t)points.size(), out.data(), 0u), "sdm_query_world_distance")) out.clear();
     return out.size();
   }
+  /// Is this straight leg free, through everything the map remembers (sdm.h, "world rays")?  Per segment from[i] -> to[i]
+  /// (global frame), walked through the world archive without clipping: where it enters its first blocking cell, that
+  /// cell, its word and its brick's stamp, the cells visited and how many of them are unknown - cells of bricks the archive
+  /// does not have included.  unknown_blocks: unknown cells block as well as occupied ones; ignore_movable: occupied cells
+  /// on movable tracks count as free.  A segment of more than SDM_WORLD_SEGMENT_MAX_CELLS cells reads cells = -1.  Waits.
+  /// Returns the number of segments answered; 0 (and an empty vector) before the first worldUpdate() or worldImport(),
+  /// for lists of different lengths or when the call fails.
+  size_t queryWorldSegments(const std::vector<Eigen::Vector3d> &from, const std::vector<Eigen::Vector3d> &to, std::vector<sdm_world_segment_hit> &out,
+                            bool unknown_blocks = false, bool ignore_movable = false) {
+    out.clear();
+    if (!map_ || from.empty() || from.size() != to.size()) return 0;
+    const std::vector<float> a = flat_points(from), b = flat_points(to);
+    std::vector<float> ab(6 * from.size());
+    for (size_t i = 0; i < from.size(); ++i)
+      for (int k = 0; k < 3; ++k) ab[6 * i + k] = a[3 * i + k], ab[6 * i + 3 + k] = b[3 * i + k];
+    out.resize(from.size());
+    const uint32_t flags = (unknown_blocks ? SDM_QUERY_UNKNOWN_BLOCKS : 0u) | (ignore_movable ? SDM_WORLD_RAYS_IGNORE_MOVABLE : 0u);
+    if (!check(sdm_query_world_segments(map_, ab.data(), (int64_t)from.size(), out.data(), flags), "sdm_query_world_segments")) out.clear();
+    return out.size();
+  }
+  /// What would a camera at a remembered place see (sdm.h, "world rays")?  scoreViews() through the world archive instead of
+  /// the block: the same views and ray table (every stride-th pixel), every ray bounded by a window of reach_metres round the
+  /// view's cell (rounded up to cells, 1 .. SDM_WORLD_VIEW_MAX_REACH) instead of by the block; cells of bricks the archive
+  /// does not have count as unknown - they are the gain.  Waits.  Returns the number of views scored; 0 (and an empty
+  /// vector) before the first worldUpdate() or worldImport() or when the call fails.
+  size_t scoreWorldViews(const std::vector<sdm_view> &views, int stride, float reach_metres, std::vector<sdm_view_gain> &out,
+                         bool ignore_movable = false) {
+    out.clear();
+    if (!map_ || views.empty() || stride < 1 || !(reach_metres > 0.f)) return 0;
+    const std::vector<float> &rays = viewRays(stride);
+    const int32_t reach = (int32_t)std::min(std::max(std::ceil(reach_metres / preset_.voxel_size), 1.f), (float)SDM_WORLD_VIEW_MAX_REACH);
+    out.resize(views.size());
+    if (!check(sdm_query_world_views(map_, views.data(), (int64_t)views.size(), rays.data(), (int32_t)(rays.size() / 3), reach, out.data(), nullptr,
+                                     ignore_movable ? SDM_WORLD_RAYS_IGNORE_MOVABLE : 0u),
+               "sdm_query_world_views"))
+      out.clear();
+    return out.size();
+  }
   /// the ray table scoreViews uses at `stride`: three floats per ray
   const std::vector<float> &viewRays(int stride) {
     if (stride != view_rays_stride_ || view_rays_.empty()) {

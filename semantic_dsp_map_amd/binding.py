@@ -165,6 +165,12 @@ WORLD_ESDF_MAX_RADIUS = 16
 WORLD_ESDF_NONE = 0xFFFF          # in world_esdf()'s d2
 WORLD_ESDF_FAR = 0xFFFFFFFE       # in a WORLD_DISTANCE_RESULT's d2
 
+WORLD_SEGMENT_HIT = np.dtype([("t", "<f4"), ("cells", "<i4"), ("cell", "<i4", (3,)), ("track", "<u2"), ("label", "u1"), ("occ", "i1"),
+                              ("unknown", "<i4"), ("stamp", "<u4")])
+WORLD_RAYS_IGNORE_MOVABLE = 0x10
+WORLD_SEGMENT_MAX_CELLS = 8192
+WORLD_VIEW_MAX_REACH = 255
+
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
                 ("forget", np.uint8), ("owner", np.uint16)]
@@ -399,6 +405,9 @@ def load_library():
         "sdm_world_esdf_update": [vp, vp],
         "sdm_get_world_esdf": [vp, vp, vp, vp, i64, i64, C.POINTER(i64), vp],
         "sdm_query_world_distance": [vp, vp, vp, i64, vp, u32],
+        "sdm_query_world_segments": [vp, vp, i64, vp, u32],
+        "sdm_query_world_views": [vp, vp, i64, vp, i32, i32, vp, vp, u32],
+        "sdm_debug_world_view_batch": [vp, i32],
         "sdm_forecast_stamps": [C.c_float, vp, i32, vp, i32, u32, vp, i64, C.POINTER(i64)],
         "sdm_forecast_update": [vp, vp, i32, vp, i32, u32],
         "sdm_get_forecast": [vp, vp, vp, vp, vp],
@@ -1292,6 +1301,47 @@ class SdmMap:
         res = np.empty(n, WORLD_DISTANCE_RESULT)
         _check(self.L, self.L.sdm_query_world_distance(self.h, _ptr(p), _ptr(w), n, _ptr(res), 0), "sdm_query_world_distance")
         return res
+
+    # ---- world rays (sdm.h).  Segments and views through the archive, read live in stream order: host mode takes numpy
+    # and waits, on_device=True takes device pointers (outputs 8-byte aligned), enqueues on the map's stream and returns.
+    def query_world_segments(self, a, b=None, unknown_blocks=False, ignore_movable=False, on_device=False, n=None, out=None):
+        """a, b: (n, 3) end points -> WORLD_SEGMENT_HIT per segment.  on_device: a is a device pointer to n rows of
+        (ax ay az bx by bz) floats, b is None, out a device pointer to n WORLD_SEGMENT_HIT."""
+        fl = (QUERY_UNKNOWN_BLOCKS if unknown_blocks else 0) | (WORLD_RAYS_IGNORE_MOVABLE if ignore_movable else 0)
+        if on_device:
+            assert b is None
+            _check(self.L, self.L.sdm_query_world_segments(self.h, _ptr(int(a)), int(n), _ptr(int(out)), fl | QUERY_ON_DEVICE),
+                   "sdm_query_world_segments")
+            return None
+        ab = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float32).reshape(-1, 3), np.asarray(b, np.float32).reshape(-1, 3)], axis=1))
+        res = np.empty(len(ab), WORLD_SEGMENT_HIT)
+        _check(self.L, self.L.sdm_query_world_segments(self.h, _ptr(ab), len(ab), _ptr(res), fl), "sdm_query_world_segments")
+        return res
+
+    def query_world_views(self, views, dirs, reach_cells, with_rays=False, ignore_movable=False, on_device=False, n_views=None, n_rays=None,
+                          out=None, rays_out=None):
+        """views: VIEW records, dirs: (n_rays, 3) camera-frame ray vectors, reach_cells: the window's half width in world
+        cells (1 .. WORLD_VIEW_MAX_REACH) -> VIEW_GAIN per view; with_rays: also the WORLD_SEGMENT_HIT of every ray, shaped
+        (n_views, n_rays).  on_device: views, dirs, out (n_views VIEW_GAIN) and rays_out (n_views * n_rays
+        WORLD_SEGMENT_HIT, or None) are device pointers, n_views and n_rays their lengths."""
+        fl = WORLD_RAYS_IGNORE_MOVABLE if ignore_movable else 0
+        if on_device:
+            _check(self.L, self.L.sdm_query_world_views(self.h, _ptr(int(views)), int(n_views), _ptr(int(dirs)), int(n_rays), int(reach_cells),
+                                                        _ptr(int(out)), _ptr(int(rays_out)) if rays_out else None, fl | QUERY_ON_DEVICE),
+                   "sdm_query_world_views")
+            return None
+        v = np.ascontiguousarray(views, dtype=VIEW).reshape(-1)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        gain = np.empty(len(v), VIEW_GAIN)
+        rays = np.empty((len(v), len(d)), WORLD_SEGMENT_HIT) if with_rays else None
+        _check(self.L, self.L.sdm_query_world_views(self.h, _ptr(v), len(v), _ptr(d), len(d), int(reach_cells), _ptr(gain), _ptr(rays), fl),
+               "sdm_query_world_views")
+        return (gain, rays) if with_rays else gain
+
+    def set_world_view_batch(self, max_views_in_flight):
+        """Test hook: query_world_views keeps at most this many views in flight (<= 0: the library's choice)
+        (sdm_debug_world_view_batch)."""
+        _check(self.L, self.L.sdm_debug_world_view_batch(self.h, int(max_views_in_flight)), "sdm_debug_world_view_batch")
 
     def save_world(self, path):
         """the archive as a NumPy .npz: bricks (WORLD_BRICK), cells (uint32 [n, 512]) and the map's voxel_size (float32)"""

@@ -212,6 +212,15 @@ struct WorldEsdfLayer : Derived {
   uint32_t n = 0, hmask = 0, radius = 0, stamp = 0;
 };
 
+// world rays (world_rays.hip): the views' pool of bitmasks, `words` words, one mask of (2 reach + 1)^3 bits per view in
+// flight, grown on demand up to 64 MiB and zero between calls; batch: sdm_debug_world_view_batch's bound on the views in
+// flight (0: as many as the pool may hold masks)
+struct WorldRaysPool {
+  uint32_t *pool = nullptr;
+  size_t words = 0;
+  int32_t batch = 0;
+};
+
 struct sdm_map {
   sdm_config cfg{};
   sdm_params prm{};
@@ -377,6 +386,7 @@ struct sdm_map {
   WorldReachLayer wreach;
   WorldFrontiersLayer wfront;
   WorldEsdfLayer wesdf;
+  WorldRaysPool wrays;
   // the scan scratch the layers share (layer_scan_scratch): they all enqueue on `stream` only, so their scans are ordered
   uint32_t *layer_scan = nullptr;
   size_t layer_scan_elems = 0;  // its capacity in uint32
