@@ -1432,6 +1432,128 @@ sdm_status sdm_get_world_esdf(sdm_map *m, int16_t *coords, uint16_t *d2, int8_t 
 sdm_status sdm_query_world_distance(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n,
                                     sdm_world_distance_result *out, uint32_t flags);
 
+/* ---- world ground layer: is there floor under that remembered place, a kerb on the way, room for the robot's body? ----
+ * sdm_world_ground_update builds, on the map's stream, the ground layer of the block (sdm_ground_update) over the bricks of
+ * the world archive: a height map, a costmap and the truncated squared distance to the nearest lethal column, in tiles of
+ * 8 x 8 columns.  IT WAITS ONCE, for the number of tiles, which sizes the buffers; the rest is enqueued and the getter waits
+ * for it.  Cells are world cells (int32 per axis, brick = cell >> 3); everything is integer and bitwise reproducible.
+ * Up axis and heights: up_axis a in {0, 1, 2}, up_sign +1 or -1 as in sdm_ground_options.  The height of a world cell with
+ * coordinate g on axis a is h = g for sign +1 and h = -1 - g for sign -1, so height brick h >> 3 is brick g >> 3 or
+ * -1 - (g >> 3): bricks stay aligned.  The other two axes in ascending order are u and v; a column is (i_u, j_v).
+ * Band: h_lo <= h_hi, signed world heights, h_hi - h_lo <= SDM_WORLD_GROUND_MAX_SPAN - 1; clearance 0 .. 255, max_step
+ * 0 .. 65535.  The READ WINDOW is h_lo .. h_hi + clearance: no cell above or below it is read, whatever it holds.
+ * Tiles: a tile is the 8 x 8 columns over one (bu, bv) = (i_u >> 3, j_v >> 3).  A tile exists iff, at the time of the build,
+ * the archive holds at least one brick over (bu, bv) whose heights meet the read window - and, with SDM_WORLD_GROUND_BOX,
+ * tmin[0] <= bu <= tmax[0] and tmin[1] <= bv <= tmax[1] (tmax < tmin: no tile, which is no error).  Tiles are ranked
+ * ascending in (bv, bu), signed; a column's word inside its tile is cu | cv << 3.
+ * Cell classes, from an archived word (track, label, occ), exactly the block's:
+ *   solid     occ >= 1; with SDM_WORLD_GROUND_IGNORE_MOVABLE an occ >= 1 cell whose track is movable (1 <= track <=
+ *             max_movable_track) is not solid and is passable instead.
+ *   passable  occ == 0; with SDM_WORLD_GROUND_UNKNOWN_PASSABLE also occ == -1.
+ *   support at h: the cell is solid, its track is not movable, bit `label` of support_labels is set (bit l of word l / 32),
+ *             and the cells h + 1 .. h + clearance are all passable (they lie inside the read window).
+ *   A cell of a brick the archive does not have, or of a brick beyond the int16 range, reads unknown (occ == -1).
+ * Per column (sdm_ground_cell; level and top are heights RELATIVE TO h_lo, 0xffff = none): level = the highest support in
+ * [h_lo, h_hi]; top = the highest solid cell in the band; label = the level cell's label, 0 if none; headroom = the
+ * consecutive passable cells directly above the level INSIDE THE READ WINDOW, saturating at 255, 0 if no level - so it is
+ * >= clearance wherever there is a level, and a cell above h_hi + clearance never ends it; n_unknown = the unknown cells in
+ * the band, absent bricks included, saturating at 255.
+ * Class byte cls = class | step << 2 | lethal << 3, as the block's.  class: 1 ground (a level), 2 obstacle (no level, a top),
+ * 0 none.  step: the column P has a level and a 4-neighbour column Q of some tile of the layer has one with
+ * level(P) > level(Q) + max_step; only the higher side is marked; Q may lie across a tile's side; a neighbour in no tile
+ * gives no relation.  lethal: class 2, or step, or with SDM_WORLD_GROUND_NONE_IS_LETHAL class 0.
+ * Distance: radius R in 1 .. SDM_WORLD_GROUND_MAX_RADIUS.  Per column, d2 = the squared distance in columns to the nearest
+ * lethal column of any tile of the layer, stored exactly if d2 <= R^2 and as SDM_WORLD_GROUND_NONE otherwise.  With
+ * SDM_WORLD_GROUND_ABSENT_IS_LETHAL every column of no tile is lethal too: the archive's edge, for a cautious planner.  A box
+ * cuts the layer - columns outside it are columns of no tile, for the step as for the distance -, so a caller who wants the
+ * distance exact at the box's side GROWS THE BOX BY TWO TILES (R <= 16 columns) and ignores the rim.  No offset is stored.
+ * The build is a SNAPSHOT: it owns the tiles' coordinates, a hash table of its own from tile to rank, the cells and the
+ * distances, holds no pool slot, and answers the same bytes after any later sdm_world_update, sdm_world_import,
+ * sdm_world_retain or sdm_world_clear, until the next sdm_world_ground_update.  Nothing of the archive or of the map's state
+ * is modified; the sort and the scan run on the layers' shared scratch.
+ * sdm_get_world_ground waits: per tile of rows first .. first + cap - 1 coords takes two int16 (bu, bv), cells 64
+ * sdm_ground_cell and d2 64 uint16, both in column-word order; each array and info may be NULL; *n_out = the tiles of the
+ * layer.  info: the counts are columns of tiles; level_min / level_max are relative, over the ground columns, 0xffff if
+ * there is none; stamp is the archive's at the build (sdm_world_info.stamp); the options are the build's.
+ * sdm_query_world_ground answers for the last build, for points (three floats each; world cell = floorf(p * recip) per axis,
+ * the archive's rule) or world cells (three int32 each); exactly one of the two pointers is non-NULL, also with n == 0.
+ * An entry that is non-finite or beyond the brick range: col (0, 0), d2 0xffffffff, surface 0, above INT32_MIN, cell
+ * {0xffff, 0xffff, 0, 0, 0, 0}, dist -1, status 3.  A column of no tile: the same with col = the column.  In a tile:
+ * status 0, the column's cell; d2 as stored, or SDM_WORLD_GROUND_FAR beyond R; dist = sqrtf((float)d2) * voxel_size, and for
+ * FAR sqrtf((float)(R * R + 1)) * voxel_size, a LOWER BOUND; with a level, above = h(entry) - (h_lo + level) and surface =
+ * (float)k * voxel_size, k the world coordinate of the level cell's upper face: g + 1 for sign +1, g for sign -1 (the
+ * world's origin is the archive's).  Float32, one IEEE operation at a time, no contraction.
+ * sdm_query_world_footprints takes the block's sdm_footprint - centre in global metres along u and v, heading (dir_u, dir_v)
+ * a unit vector the caller supplies, half length and half width - and the block's rule: world column (i, j) is covered when
+ *   pu = ((float)i + 0.5f) * voxel_size, pv likewise; du = pu - center_u, dv = pv - center_v;
+ *   |du * dir_u + dv * dir_v| <= half_len  and  |dv * dir_u - du * dir_v| <= half_wid      (float32, no contraction).
+ * The answer is as if every column of the plane - the columns of the brick range, -262144 .. 262143 per axis - were tested.
+ * A non-finite field, half_len + half_wid > 64 * voxel_size (float32), or a heading with dir_u^2 + dir_v^2 < 0.5 (float32:
+ * the plane has no sides that would bound what such a rule covers) gives the answer of a footprint that covers nothing:
+ * the counts 0, level_min = level_max = 0xffff, min_d2 0xffffffff, first_lethal (0, 0).
+ * Both queries take SDM_QUERY_ON_DEVICE as the other queries do (device pointers, enqueued, no wait; out 8-byte aligned,
+ * inputs 4-byte aligned); host mode goes through the queries' staging area.
+ * Memory, allocated at the first build, grown by a build that needs more, freed by sdm_destroy:
+ *   SDM_WORLD_GROUND_BYTES_PER_ARCHIVED_BRICK x (archived bricks + 1, in steps of 256; the table's slots a power of two)
+ * + SDM_WORLD_GROUND_BYTES_PER_TILE x (tiles, in steps of 256) + 8200 (the counters and their landing area).
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map, options or output (n_out, out), unknown flag bits, up_axis not in 0..2,
+ * up_sign not +1 / -1, h_lo > h_hi or a span above SDM_WORLD_GROUND_MAX_SPAN, clearance > 255, max_step > 65535, radius 0 or
+ * > 16, negative counts, first or cap, none or both of xyz and cells, a NULL input of a query, a Z-slab shard
+ * (shard_count > 1), a build before the archive has had an update or import, and the getter or a query before any build. */
+#define SDM_WORLD_GROUND_UNKNOWN_PASSABLE 0x1u   /* occ == -1 cells, absent bricks included, are passable */
+#define SDM_WORLD_GROUND_IGNORE_MOVABLE   0x2u   /* occ >= 1 cells of a movable track are passable, not solid */
+#define SDM_WORLD_GROUND_NONE_IS_LETHAL   0x4u   /* columns of class 0 are lethal */
+#define SDM_WORLD_GROUND_ABSENT_IS_LETHAL 0x8u   /* for the distance, every column of no tile is lethal */
+#define SDM_WORLD_GROUND_BOX              0x10u  /* the layer is the tiles inside tmin .. tmax (inclusive tile box) */
+#define SDM_WORLD_GROUND_MAX_SPAN 4096           /* cells of the band, h_hi - h_lo + 1, at most */
+#define SDM_WORLD_GROUND_MAX_RADIUS 16
+#define SDM_WORLD_GROUND_NONE 0xffffu            /* in the getter's d2: no lethal column within the radius */
+#define SDM_WORLD_GROUND_FAR  0xfffffffeu        /* in a query's d2: a column of a tile with no lethal column within the radius */
+#define SDM_WORLD_GROUND_BYTES_PER_ARCHIVED_BRICK 32  /* claim flag, rank, two hash slots */
+#define SDM_WORLD_GROUND_BYTES_PER_TILE 668      /* 64 cells, 64 d2, the lethal word, the key, the sort's four words */
+typedef struct {              /* 80 bytes, every field naturally aligned */
+  uint32_t flags;
+  int32_t  up_axis, up_sign;
+  int32_t  h_lo, h_hi;        /* the band, world heights in cells */
+  uint32_t clearance;         /* 0..255 cells */
+  uint32_t max_step;          /* 0..65535 cells */
+  uint32_t radius;            /* 1 .. SDM_WORLD_GROUND_MAX_RADIUS columns */
+  int32_t  tmin[2], tmax[2];  /* inclusive tile box (bu, bv), read only with SDM_WORLD_GROUND_BOX */
+  uint32_t support_labels[8]; /* bit l of the 256: label l may carry the robot */
+} sdm_world_ground_options;
+typedef struct {              /* 136 bytes, every field naturally aligned */
+  uint32_t n_tiles;
+  uint32_t level_min, level_max;  /* relative to h_lo, over the ground columns; 0xffff if there is none */
+  uint32_t stamp;             /* the archive's stamp at the build: sdm_world_info.stamp */
+  int64_t  n_ground, n_obstacle, n_none, n_step, n_lethal; /* columns of tiles */
+  sdm_world_ground_options options;                        /* the build's, echoed */
+} sdm_world_ground_info;
+typedef struct {              /* 40 bytes */
+  int32_t  col[2];            /* the entry's column (i_u, j_v); (0, 0) if non-finite or beyond the brick range */
+  uint32_t d2;                /* squared distance in columns; SDM_WORLD_GROUND_FAR; 0xffffffff: in no tile */
+  float    surface;           /* world coordinate along the up axis of the level cell's upper face; 0 where there is no level */
+  int32_t  above;             /* h(entry) - (h_lo + level); INT32_MIN where there is no level */
+  sdm_ground_cell cell;
+  float    dist;              /* metres; the lower bound for FAR; -1 in no tile */
+  uint32_t status;            /* 0 in a tile, 3 otherwise */
+  uint32_t pad;               /* 0 */
+} sdm_world_ground_result;
+typedef struct {              /* 40 bytes */
+  uint32_t n_cols, n_lethal, n_none, n_ground; /* covered columns of tiles: all, lethal, of class 0, of class 1 */
+  uint32_t n_absent;          /* covered columns of no tile, in none of the other counts */
+  uint16_t level_min, level_max;               /* relative, over the covered ground columns; 0xffff if none */
+  uint32_t min_d2;            /* over the covered columns of tiles, FAR as SDM_WORLD_GROUND_FAR; 0xffffffff if n_cols == 0 */
+  int32_t  first_lethal[2];   /* (i_u, j_v) of the smallest covered lethal column in (v, u) order; (0, 0) with n_lethal == 0 */
+  uint32_t pad;               /* 0 */
+} sdm_world_footprint_result;
+sdm_status sdm_world_ground_update(sdm_map *m, const sdm_world_ground_options *o);
+sdm_status sdm_get_world_ground(sdm_map *m, int16_t *coords, sdm_ground_cell *cells, uint16_t *d2, int64_t first, int64_t cap,
+                                int64_t *n_out, sdm_world_ground_info *info);
+sdm_status sdm_query_world_ground(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n,
+                                  sdm_world_ground_result *out, uint32_t flags);
+sdm_status sdm_query_world_footprints(sdm_map *m, const sdm_footprint *fp, int64_t n,
+                                      sdm_world_footprint_result *out, uint32_t flags);
+
 /* ---- world rays: is this straight leg free, and what would a camera at that remembered place see? ----
  * sdm_query_world_segments and sdm_query_world_views are the archive's counterparts of sdm_query_segments and
  * sdm_query_views: the same walks, through the bricks of the world archive instead of the block.  Both read the archive

@@ -864,6 +864,65 @@ class SemanticDSPMap {
     if (!check(sdm_query_world_distance(map_, xyz.data(), nullptr, (int64_t)points.size(), out.data(), 0u), "sdm_query_world_distance")) out.clear();
     return out.size();
   }
+  /// Where can a ground robot stand at a place the map only remembers (sdm.h, "world ground layer")?  ground() over the
+  /// bricks of the world archive: builds the height map, the costmap and the truncated distance to the nearest lethal
+  /// column under `options` (all in world cells: the up axis and its sign, the band, the clearance, the largest step, the
+  /// radius, the labels that carry the robot, flags, the tile box) and copies them out: per tile of 8 x 8 columns its
+  /// coordinates (bu, bv), 64 cells - level and top relative to options.h_lo - and 64 squared distances
+  /// (SDM_WORLD_GROUND_NONE beyond the radius), a column's word cu | cv << 3.  info (may be null): the counts and the
+  /// options echoed.  The build is a snapshot: queryWorldGround() and checkWorldFootprints() answer for it until the next
+  /// worldGround(), whatever happens to the archive.  The call waits.  Returns the number of tiles; 0 (and empty vectors)
+  /// before the first worldUpdate() or worldImport(), for an archive with no brick in the band, or when a call fails
+  /// (ok, may be null, tells the last two apart).
+  size_t worldGround(const sdm_world_ground_options &options, std::vector<int16_t> &coords_out, std::vector<sdm_ground_cell> &cells_out,
+                     std::vector<uint16_t> &d2_out, sdm_world_ground_info *info = nullptr, bool *ok = nullptr) {
+    coords_out.clear();
+    cells_out.clear();
+    d2_out.clear();
+    if (ok) *ok = false;
+    if (!map_) return 0;
+    sdm_world_ground_info gi;
+    int64_t n = 0;
+    if (!check(sdm_world_ground_update(map_, &options), "sdm_world_ground_update")) return 0;
+    if (!check(sdm_get_world_ground(map_, nullptr, nullptr, nullptr, 0, 0, &n, &gi), "sdm_get_world_ground")) return 0;
+    coords_out.resize(2 * (size_t)n);
+    cells_out.resize(64 * (size_t)n);
+    d2_out.resize(64 * (size_t)n);
+    if (n && !check(sdm_get_world_ground(map_, coords_out.data(), cells_out.data(), d2_out.data(), 0, n, &n, nullptr), "sdm_get_world_ground")) {
+      coords_out.clear();
+      cells_out.clear();
+      d2_out.clear();
+      return 0;
+    }
+    if (info) *info = gi;
+    if (ok) *ok = true;
+    return (size_t)n;
+  }
+  /// Per position (global frame) of the last worldGround(): its column, the column's cell, the squared distance in columns
+  /// to the nearest lethal column and that distance in metres (SDM_WORLD_GROUND_FAR and a lower bound beyond the radius),
+  /// the height of the position above the level and the world coordinate of the level's surface; status 3, d2 0xffffffff
+  /// and dist -1 in no tile.  Waits.  Returns the number of points answered; 0 (and an empty vector) before the first
+  /// worldGround() or when the call fails.
+  size_t queryWorldGround(const std::vector<Eigen::Vector3d> &points, std::vector<sdm_world_ground_result> &out) {
+    out.clear();
+    if (!map_ || points.empty()) return 0;
+    const std::vector<float> xyz = flat_points(points);
+    out.resize(points.size());
+    if (!check(sdm_query_world_ground(map_, xyz.data(), nullptr, (int64_t)points.size(), out.data(), 0u), "sdm_query_world_ground")) out.clear();
+    return out.size();
+  }
+  /// Does the robot's body fit at that remembered place?  checkFootprints() against the layer worldGround() built last:
+  /// the footprints' centres are world metres along the layer's u and v axes; n_absent counts the covered columns of no
+  /// tile.  Waits.  Returns the number of footprints answered; 0 (and an empty vector) before the first worldGround() or
+  /// when the call fails.
+  size_t checkWorldFootprints(const std::vector<sdm_footprint> &footprints, std::vector<sdm_world_footprint_result> &out) {
+    out.clear();
+    if (!map_ || footprints.empty()) return 0;
+    out.resize(footprints.size());
+    if (!check(sdm_query_world_footprints(map_, footprints.data(), (int64_t)footprints.size(), out.data(), 0u), "sdm_query_world_footprints"))
+      out.clear();
+    return out.size();
+  }
   /// Is this straight leg free, through everything the map remembers (sdm.h, "world rays")?  Per segment from[i] -> to[i]
   /// (global frame), walked through the world archive without clipping: where it enters its first blocking cell, that
   /// cell, its word and its brick's stamp, the cells visited and how many of them are unknown - cells of bricks the archive

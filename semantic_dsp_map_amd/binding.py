@@ -164,6 +164,27 @@ WORLD_ESDF_BOX = 0x4
 WORLD_ESDF_MAX_RADIUS = 16
 WORLD_ESDF_NONE = 0xFFFF          # in world_esdf()'s d2
 WORLD_ESDF_FAR = 0xFFFFFFFE       # in a WORLD_DISTANCE_RESULT's d2
+# world ground layer (sdm.h: sdm_world_ground_update / sdm_get_world_ground / sdm_query_world_ground / sdm_query_world_footprints)
+WORLD_GROUND_OPTIONS = np.dtype([("flags", "<u4"), ("up_axis", "<i4"), ("up_sign", "<i4"), ("h_lo", "<i4"), ("h_hi", "<i4"), ("clearance", "<u4"),
+                                 ("max_step", "<u4"), ("radius", "<u4"), ("tmin", "<i4", (2,)), ("tmax", "<i4", (2,)),
+                                 ("support_labels", "<u4", (8,))])
+WORLD_GROUND_INFO = np.dtype([("n_tiles", "<u4"), ("level_min", "<u4"), ("level_max", "<u4"), ("stamp", "<u4"), ("n_ground", "<i8"),
+                              ("n_obstacle", "<i8"), ("n_none", "<i8"), ("n_step", "<i8"), ("n_lethal", "<i8"), ("options", WORLD_GROUND_OPTIONS)])
+WORLD_GROUND_RESULT = np.dtype([("col", "<i4", (2,)), ("d2", "<u4"), ("surface", "<f4"), ("above", "<i4"), ("cell", GROUND_CELL), ("dist", "<f4"),
+                                ("status", "<u4"), ("pad", "<u4")])
+WORLD_FOOTPRINT_RESULT = np.dtype([("n_cols", "<u4"), ("n_lethal", "<u4"), ("n_none", "<u4"), ("n_ground", "<u4"), ("n_absent", "<u4"),
+                                   ("level_min", "<u2"), ("level_max", "<u2"), ("min_d2", "<u4"), ("first_lethal", "<i4", (2,)), ("pad", "<u4")])
+assert WORLD_GROUND_OPTIONS.itemsize == 80 and WORLD_GROUND_INFO.itemsize == 136
+assert WORLD_GROUND_RESULT.itemsize == 40 and WORLD_FOOTPRINT_RESULT.itemsize == 40
+WORLD_GROUND_UNKNOWN_PASSABLE = 0x1
+WORLD_GROUND_IGNORE_MOVABLE = 0x2
+WORLD_GROUND_NONE_IS_LETHAL = 0x4
+WORLD_GROUND_ABSENT_IS_LETHAL = 0x8
+WORLD_GROUND_BOX = 0x10
+WORLD_GROUND_MAX_SPAN = 4096
+WORLD_GROUND_MAX_RADIUS = 16
+WORLD_GROUND_NONE = 0xFFFF        # in world_ground()'s d2
+WORLD_GROUND_FAR = 0xFFFFFFFE     # in a WORLD_GROUND_RESULT's d2 and a WORLD_FOOTPRINT_RESULT's min_d2
 
 WORLD_SEGMENT_HIT = np.dtype([("t", "<f4"), ("cells", "<i4"), ("cell", "<i4", (3,)), ("track", "<u2"), ("label", "u1"), ("occ", "i1"),
                               ("unknown", "<i4"), ("stamp", "<u4")])
@@ -234,6 +255,18 @@ def ground_band(cfg, origin, up, lo_m, hi_m):
     n = 1 << int(cfg[("x_n", "y_n", "z_n")[axis]])
     idx = [int(np.clip(np.floor((float(m) - float(origin[axis])) / float(cfg["voxel_size"])), 0, n - 1)) for m in (lo_m, hi_m)]
     h = idx if sign > 0 else [n - 1 - i for i in idx]
+    return min(h), max(h)
+
+
+def world_ground_band(voxel_size, up, lo_m, hi_m):
+    """the world ground layer's band from metres: world coordinates lo_m <= hi_m along the up axis -> (h_lo, h_hi), the
+    heights of the world cells that hold them (cell = floor(p / voxel_size); h = g for sign +1, -1 - g for -1).  up: (axis,
+    sign).  Host arithmetic in float64; the span is the caller's to keep within WORLD_GROUND_MAX_SPAN."""
+    axis, sign = int(up[0]), int(up[1])
+    if axis not in (0, 1, 2) or sign not in (1, -1) or not lo_m <= hi_m:
+        raise ValueError("up must be (0..2, +1 / -1) and lo_m <= hi_m")
+    g = [int(np.floor(float(m) / float(voxel_size))) for m in (lo_m, hi_m)]
+    h = g if sign > 0 else [-1 - v for v in g]
     return min(h), max(h)
 
 
@@ -405,6 +438,10 @@ def load_library():
         "sdm_world_esdf_update": [vp, vp],
         "sdm_get_world_esdf": [vp, vp, vp, vp, i64, i64, C.POINTER(i64), vp],
         "sdm_query_world_distance": [vp, vp, vp, i64, vp, u32],
+        "sdm_world_ground_update": [vp, vp],
+        "sdm_get_world_ground": [vp, vp, vp, vp, i64, i64, C.POINTER(i64), vp],
+        "sdm_query_world_ground": [vp, vp, vp, i64, vp, u32],
+        "sdm_query_world_footprints": [vp, vp, i64, vp, u32],
         "sdm_query_world_segments": [vp, vp, i64, vp, u32],
         "sdm_query_world_views": [vp, vp, i64, vp, i32, i32, vp, vp, u32],
         "sdm_debug_world_view_batch": [vp, i32],
@@ -1300,6 +1337,64 @@ class SdmMap:
         n = len(p) if p is not None else len(w) if w is not None else 0
         res = np.empty(n, WORLD_DISTANCE_RESULT)
         _check(self.L, self.L.sdm_query_world_distance(self.h, _ptr(p), _ptr(w), n, _ptr(res), 0), "sdm_query_world_distance")
+        return res
+
+    # ---- world ground layer (sdm.h).  world_ground_update builds the height map, the costmap and the truncated distance
+    # to the nearest lethal column over the archive's bricks (it waits once, for the tile count); world_ground(),
+    # query_world_ground() and query_world_footprints() answer for that build - a snapshot - until the next one.
+    def world_ground_update(self, up=(2, 1), h_lo=0, h_hi=0, clearance=0, max_step=0, radius=8, support_labels=None, unknown_passable=False,
+                            ignore_movable=False, none_is_lethal=False, absent_is_lethal=False, box=None):
+        """up: (axis, sign); h_lo, h_hi: world heights in cells (world_ground_band gives a band from metres); clearance,
+        max_step in cells; radius: 1 .. WORLD_GROUND_MAX_RADIUS columns; support_labels: label ids (label_mask); box:
+        (tmin, tmax), an inclusive box of tile coordinates (bu, bv) the layer is cut to"""
+        o = np.zeros(1, WORLD_GROUND_OPTIONS)
+        o["up_axis"], o["up_sign"] = int(up[0]), int(up[1])
+        o["h_lo"], o["h_hi"], o["clearance"], o["max_step"], o["radius"] = int(h_lo), int(h_hi), int(clearance), int(max_step), int(radius)
+        o["support_labels"] = label_mask(support_labels)
+        o["flags"] = ((WORLD_GROUND_UNKNOWN_PASSABLE if unknown_passable else 0) | (WORLD_GROUND_IGNORE_MOVABLE if ignore_movable else 0) |
+                      (WORLD_GROUND_NONE_IS_LETHAL if none_is_lethal else 0) | (WORLD_GROUND_ABSENT_IS_LETHAL if absent_is_lethal else 0) |
+                      (WORLD_GROUND_BOX if box is not None else 0))
+        if box is not None:
+            o["tmin"], o["tmax"] = box[0], box[1]
+        _check(self.L, self.L.sdm_world_ground_update(self.h, _ptr(o)), "sdm_world_ground_update")
+
+    def world_ground(self, first=0, cap=None):
+        """-> (coords int16 [n, 2] (bu, bv), cells GROUND_CELL [n, 64], d2 uint16 [n, 64] (WORLD_GROUND_NONE: beyond the
+        radius), info a WORLD_GROUND_INFO record): the tiles in (bv, bu) order, rows first .. first + cap - 1; a column's
+        word is cu | cv << 3; level and top are relative to h_lo"""
+        got = C.c_int64(0)
+        info = np.zeros(1, WORLD_GROUND_INFO)
+        _check(self.L, self.L.sdm_get_world_ground(self.h, None, None, None, 0, 0, C.byref(got), _ptr(info)), "sdm_get_world_ground")
+        take = max(min(got.value - int(first), got.value if cap is None else int(cap)), 0)
+        coords, cells, d2 = np.empty((take, 2), np.int16), np.empty((take, 64), GROUND_CELL), np.empty((take, 64), np.uint16)
+        _check(self.L, self.L.sdm_get_world_ground(self.h, _ptr(coords), _ptr(cells), _ptr(d2), int(first), take, C.byref(got), None),
+               "sdm_get_world_ground")
+        return coords, cells, d2, info[0]
+
+    def query_world_ground(self, xyz=None, cells=None, on_device=False, n=None, out=None):
+        """(n, 3) global positions or (n, 3) world cells -> WORLD_GROUND_RESULT per entry.  on_device: the one given of
+        xyz / cells and out (n WORLD_GROUND_RESULT) are device pointers."""
+        if on_device:
+            _check(self.L, self.L.sdm_query_world_ground(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
+                                                         _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_world_ground")
+            return None
+        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+        n = len(p) if p is not None else len(w) if w is not None else 0
+        res = np.empty(n, WORLD_GROUND_RESULT)
+        _check(self.L, self.L.sdm_query_world_ground(self.h, _ptr(p), _ptr(w), n, _ptr(res), 0), "sdm_query_world_ground")
+        return res
+
+    def query_world_footprints(self, footprints, on_device=False, n=None, out=None):
+        """footprints: FOOTPRINT records (centre in world metres along u and v) -> WORLD_FOOTPRINT_RESULT per footprint.
+        on_device: footprints and out (n WORLD_FOOTPRINT_RESULT) are device pointers."""
+        if on_device:
+            _check(self.L, self.L.sdm_query_world_footprints(self.h, _ptr(int(footprints)), int(n), _ptr(int(out)), QUERY_ON_DEVICE),
+                   "sdm_query_world_footprints")
+            return None
+        fp = np.ascontiguousarray(footprints, dtype=FOOTPRINT).reshape(-1)
+        res = np.empty(len(fp), WORLD_FOOTPRINT_RESULT)
+        _check(self.L, self.L.sdm_query_world_footprints(self.h, _ptr(fp), len(fp), _ptr(res), 0), "sdm_query_world_footprints")
         return res
 
     # ---- world rays (sdm.h).  Segments and views through the archive, read live in stream order: host mode takes numpy

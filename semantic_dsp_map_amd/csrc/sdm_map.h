@@ -212,6 +212,23 @@ struct WorldEsdfLayer : Derived {
   uint32_t n = 0, hmask = 0, radius = 0, stamp = 0;
 };
 
+// the world ground layer (world_ground.hip): a snapshot of the archive's bricks as a height map and costmap in tiles of
+// 8 x 8 columns.  Per archived brick (cap_arch) the flag of the one brick that claimed its tile and its rank - the build's
+// own - and the hash table from tile key to rank (hmask + 1 slots in use: it is filled before the tiles are counted); per
+// tile (cap_tiles) its key, 64 cells, 64 squared distances, the lethal word and the sort's four words.  The info counters
+// (and their page-locked landing area, whose last word takes the count the build waits for), the build's options (its
+// flags are Derived's), the archive's stamp.  No pool slot is kept.
+struct WorldGroundLayer : Derived {
+  uint32_t *flag = nullptr, *rank = nullptr, *vals = nullptr, *coord = nullptr, *sortbuf = nullptr;
+  unsigned long long *keys = nullptr, *lethal = nullptr;
+  sdm_ground_cell *cells = nullptr;
+  uint16_t *d2 = nullptr;
+  unsigned long long *meta = nullptr, *h_meta = nullptr;
+  size_t cap_arch = 0, cap_tiles = 0;
+  uint32_t n = 0, hmask = 0, stamp = 0;
+  sdm_world_ground_options opt{};
+};
+
 // world rays (world_rays.hip): the views' pool of bitmasks, `words` words, one mask of (2 reach + 1)^3 bits per view in
 // flight, grown on demand up to 64 MiB and zero between calls; batch: sdm_debug_world_view_batch's bound on the views in
 // flight (0: as many as the pool may hold masks)
@@ -386,6 +403,7 @@ struct sdm_map {
   WorldReachLayer wreach;
   WorldFrontiersLayer wfront;
   WorldEsdfLayer wesdf;
+  WorldGroundLayer wground;
   WorldRaysPool wrays;
   // the scan scratch the layers share (layer_scan_scratch): they all enqueue on `stream` only, so their scans are ordered
   uint32_t *layer_scan = nullptr;
