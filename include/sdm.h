@@ -1554,6 +1554,104 @@ sdm_status sdm_query_world_ground(sdm_map *m, const float *xyz, const int32_t *c
 sdm_status sdm_query_world_footprints(sdm_map *m, const sdm_footprint *fp, int64_t n,
                                       sdm_world_footprint_result *out, uint32_t flags);
 
+/* ---- world ground reach: how does a robot on wheels get from here to that remembered place, and how far is it? ----
+ * sdm_world_ground_reach_update builds, on the map's stream, a 2-D travel-cost field over the costmap of the world ground
+ * layer: the cheapest way ON THE GROUND from a set of start columns to every traversable column.  Like
+ * sdm_world_reach_update IT WAITS: the host decides when the relaxation is at rest, and no kernel ever waits for another
+ * workgroup.  Everything is integer and bitwise reproducible except `metres`.
+ * Source: the field is built from the last sdm_world_ground_update of the same map; columns, tiles, up axis, h_lo and R are
+ * that build's.  The tiles of the field are the ground layer's; with SDM_WORLD_GROUND_REACH_BOX only those with
+ * tmin[0] <= bu <= tmax[0] and tmin[1] <= bv <= tmax[1] (tmax < tmin: a field of no tiles, which is no error).  Tiles are
+ * ranked ascending in (bv, bu), the ground layer's order: without a box row r of sdm_get_world_ground_reach belongs to row
+ * r of sdm_get_world_ground.
+ * The build is a SNAPSHOT: it owns its copy of the tiles' coordinates, a hash table of its own from tile to rank, the eight
+ * neighbour ranks per tile, the masks, the levels and the costs, and answers the same bytes after any later
+ * sdm_world_ground_update, sdm_world_update, sdm_world_import, sdm_world_retain or sdm_world_clear, until the next
+ * sdm_world_ground_reach_update.  Nothing of the ground layer, the archive or the map's state is modified; the scan runs on
+ * the layers' shared scratch.
+ * Traversable: a column is traversable iff it lies in a tile of the field, its class is 1 (it has a level), its lethal bit
+ * is clear, and its stored d2 is SDM_WORLD_GROUND_NONE or >= min_d2.  min_d2 and soft_d2 range over 0 .. R^2 + 1 (beyond
+ * that the truncated distance cannot answer); min_d2 = R^2 + 1 means "only columns with nothing lethal within R".  A column
+ * of no tile of the field is never traversable: that bounds the search.
+ * Penalty: pen(Q) = penalty (0 .. 65535) if Q's stored d2 is not SDM_WORLD_GROUND_NONE and < soft_d2, otherwise 0.
+ * Moves: the eight offsets (du, dv) numbered (dv + 1) * 3 + (du + 1), 4 is "no move"; four with
+ * SDM_WORLD_GROUND_REACH_FACE_CONNECTED.  The tile across a side or a corner is the one the table finds; a neighbour tile
+ * whose coordinate would leave the int16 range is absent.  A move P -> P + o is allowed iff all 2 or 4 columns P + s,
+ * s_a in {0, o_a}, are traversable columns of the field (no squeezing through a diagonal) and the largest minus the smallest
+ * of their levels is <= max_climb (0 .. 65535 cells).  The rule is symmetric.
+ * Cost: weights 10 for a straight move, 14 for a diagonal one; cost(start) = 0; cost(Q) = the minimum over the allowed moves
+ * P -> Q of cost(P) + w + pen(Q).  The effective budget is max_cost if that is non-zero and 0xfffffffe otherwise; a column
+ * whose true cost exceeds it reads 0xffffffff, additions saturate, and the truncated field is still exact because every
+ * prefix of a cheapest path lies within the budget.
+ * Descent: from column c, the smallest allowed move number o with cost(c + o) + w(o) + pen(c) == cost(c).
+ * Starts and goals: points (three floats each; world cell = floorf(p * recip) per axis, the archive's rule) or world cells
+ * (three int32 each), as for sdm_query_world_ground; exactly one of the two pointers is non-NULL, also with a count of 0.
+ * Only the column counts: the VALUE of the coordinate along the up axis is ignored, so first_cell of a world frontier
+ * cluster goes in as it is (an entry with any of its three coordinates non-finite or beyond the brick range is not usable,
+ * the rule of sdm_query_world_ground).  A start that is not traversable, in no tile of the field, non-finite or out of range
+ * is ignored; duplicates are fine; no usable start is no error: every column then reads unreachable.
+ * sdm_get_world_ground_reach waits: per tile of rows first .. first + cap - 1 coords takes two int16 (bu, bv) and cost 64
+ * words in column-word order (cu | cv << 3; 0xffffffff: unreachable or not traversable); *n_out = the tiles of the field;
+ * coords, cost and info may each be NULL.
+ * sdm_query_world_ground_reach / sdm_world_ground_reach_paths answer for the last build; SDM_QUERY_ON_DEVICE as for the
+ * other queries (device pointers, enqueued, no wait; out 8-byte aligned), host mode through the queries' staging area.  A
+ * result's level is the column's as the ground build stored it (0xffff: none, or status 3).  Row g of cells_out (n rows of
+ * max_len * 3 int32) takes WORLD CELLS (x, y, z) of goal g's path from the goal to a start, both included: on the two plane
+ * axes the column, on the up axis the cell the robot's base stands in, height h = h_lo + level + 1, which is coordinate
+ * g = h for up_sign +1 and g = -1 - h for up_sign -1 - so a path feeds sdm_query_world_segments, sdm_query_world_distance
+ * and sdm_query_world_ground as it is.  len_out[g] is its true length, 0 where there is none, and may exceed max_len: only
+ * the first min(len, max_len) cells are written, the rest of the row is left untouched, in host mode too.
+ * Memory: SDM_WORLD_GROUND_REACH_BYTES_PER_TILE x (tiles of the field, in steps of 256; the table's slots a power of two)
+ * and a bit of activity per tile, + 64 (the counters and their landing area).  Allocated at the first build, grown by a
+ * build of more tiles, freed by sdm_destroy.  A build also holds 8 B per tile of the ground layer (flags, ranks) until it
+ * returns.
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map, options or output (n_out, out, len_out; cells_out with max_len > 0),
+ * none or both start / goal pointers, unknown flag bits, a non-zero pad, penalty or max_climb > 65535, min_d2 or soft_d2
+ * > R^2 + 1, negative counts, first, cap or max_len, a Z-slab shard (shard_count > 1), a build before any
+ * sdm_world_ground_update, and the getter or a query before any build.  SDM_ERR_NOT_CONVERGED if the relaxation has not come
+ * to rest after 64 x n_tiles + 8 rounds: a defect, never a result. */
+#define SDM_WORLD_GROUND_REACH_FACE_CONNECTED 0x1u  /* the four straight moves only */
+#define SDM_WORLD_GROUND_REACH_BOX            0x2u  /* the field is the ground layer's tiles inside tmin .. tmax */
+#define SDM_WORLD_GROUND_REACH_BYTES_PER_TILE 464   /* 64 costs, the traversable and the penalty word, 64 levels, eight
+                                                       neighbour ranks, the key, two hash slots, the list word */
+typedef struct {              /* 48 bytes, every field naturally aligned */
+  uint32_t flags;
+  uint32_t min_d2;            /* 0 .. R^2 + 1: a column whose stored d2 is below it is not traversable */
+  uint32_t soft_d2;           /* 0 .. R^2 + 1: a column whose stored d2 is below it costs `penalty` more to enter */
+  uint32_t penalty;           /* 0 .. 65535 */
+  uint32_t max_climb;         /* 0 .. 65535 cells */
+  uint32_t max_cost;          /* 0: no budget */
+  int32_t  tmin[2], tmax[2];  /* inclusive tile box (bu, bv), read only with SDM_WORLD_GROUND_REACH_BOX */
+  uint32_t pad[2];            /* 0 */
+} sdm_world_ground_reach_options;
+typedef struct {              /* 80 bytes: options at offset 32 */
+  uint32_t n_tiles;           /* tiles in the field */
+  uint32_t n_starts_used;     /* distinct start columns that were traversable */
+  uint32_t n_traversable, n_reached, max_cost_reached;
+  uint32_t rounds;            /* relaxation rounds the build took (diagnostic; not part of the bitwise contract) */
+  uint32_t stamp;             /* the archive's stamp the ground build carried: sdm_world_ground_info.stamp */
+  uint32_t pad;               /* 0 */
+  sdm_world_ground_reach_options options;  /* the build's, echoed */
+} sdm_world_ground_reach_info;
+typedef struct {              /* 24 bytes: col at 8, level at 16, next at 18, status at 19, pad at 20 */
+  uint32_t cost;              /* 0xffffffff: no path */
+  float    metres;            /* (float)cost * (voxel_size * 0.1f), float32, no contraction; -1 where no path */
+  int32_t  col[2];            /* the entry's column (i_u, j_v); (0, 0) if non-finite or beyond the brick range */
+  uint16_t level;             /* relative to the ground build's h_lo; 0xffff if none */
+  uint8_t  next;              /* move number of the first descent step; 4 at a start; 255 where no path */
+  uint8_t  status;            /* 0 reached, 1 traversable but unreached (or beyond the budget), 2 a column of a tile of the
+                                 field but not traversable, 3 in no tile of the field / non-finite / out of range */
+  uint32_t pad;               /* 0 */
+} sdm_world_ground_reach_result;
+sdm_status sdm_world_ground_reach_update(sdm_map *m, const sdm_world_ground_reach_options *o, const float *start_xyz,
+                                         const int32_t *start_cells, int64_t n_starts);
+sdm_status sdm_get_world_ground_reach(sdm_map *m, int16_t *coords, uint32_t *cost, int64_t first, int64_t cap, int64_t *n_out,
+                                      sdm_world_ground_reach_info *info);
+sdm_status sdm_query_world_ground_reach(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n,
+                                        sdm_world_ground_reach_result *out, uint32_t flags);
+sdm_status sdm_world_ground_reach_paths(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n, int32_t max_len,
+                                        int32_t *cells_out, int32_t *len_out, uint32_t flags);
+
 /* ---- world rays: is this straight leg free, and what would a camera at that remembered place see? ----
  * sdm_query_world_segments and sdm_query_world_views are the archive's counterparts of sdm_query_segments and
  * sdm_query_views: the same walks, through the bricks of the world archive instead of the block.  Both read the archive
@@ -1678,6 +1776,8 @@ sdm_status sdm_debug_alias_cap(sdm_map *m, int32_t cap);
 sdm_status sdm_debug_reach_tiles(sdm_map *m, int64_t *tiles_out);
 /* Diagnostic (tools/probes/world_reach_probe.py): the bricks relaxed by the last sdm_world_reach_update, summed over its rounds. */
 sdm_status sdm_debug_world_reach_bricks(sdm_map *m, int64_t *bricks_out);
+/* Diagnostic (tools/probes/world_ground_reach_probe.py): the tiles relaxed by the last sdm_world_ground_reach_update, summed over its rounds. */
+sdm_status sdm_debug_world_ground_reach_tiles(sdm_map *m, int64_t *tiles_out);
 /* Test hook.  sdm_query_views keeps at most max_views_in_flight views in flight (never more than its pool has masks);
  * <= 0: the library's choice.  A test on a small map can so force a call to take several batches. */
 sdm_status sdm_debug_view_batch(sdm_map *m, int32_t max_views_in_flight);

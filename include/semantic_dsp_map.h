@@ -923,6 +923,56 @@ class SemanticDSPMap {
       out.clear();
     return out.size();
   }
+  /// How does a robot on wheels get there, over everything the map remembers (sdm.h, "world ground reach")?  Builds the
+  /// 2-D travel-cost field over the costmap worldGround() built last, from `start` (a global position, the robot's: only
+  /// its column counts): straight moves weigh 10, diagonal ones 14, a column closer than options.min_d2 to a lethal one
+  /// cannot be entered, one closer than options.soft_d2 costs options.penalty more, a move climbs at most
+  /// options.max_climb cells.  The build is a snapshot: queryWorldGroundReach() and worldGroundReachPaths() answer for it
+  /// until the next worldGroundReach(), whatever happens to the ground layer or the archive.  The call waits for the
+  /// build.  info (may be null): the build's counts.  Returns false before the first worldGround() or when a call fails.
+  bool worldGroundReach(const Eigen::Vector3d &start, const sdm_world_ground_reach_options &options, sdm_world_ground_reach_info *info = nullptr) {
+    if (!map_) return false;
+    const float s[3] = {(float)start.x(), (float)start.y(), (float)start.z()};
+    if (!check(sdm_world_ground_reach_update(map_, &options, s, nullptr, 1), "sdm_world_ground_reach_update")) return false;
+    int64_t n = 0;
+    return !info || check(sdm_get_world_ground_reach(map_, nullptr, nullptr, 0, 0, &n, info), "sdm_get_world_ground_reach");
+  }
+  /// Per goal position (global frame) of the last worldGroundReach(): cost, the same in metres, the goal's column and its
+  /// level, the first step of the way back and a status.  Waits.  Returns the number of goals answered; 0 (and an empty
+  /// vector) before the first worldGroundReach() or when the call fails.
+  size_t queryWorldGroundReach(const std::vector<Eigen::Vector3d> &goals, std::vector<sdm_world_ground_reach_result> &out) {
+    out.clear();
+    if (!map_ || goals.empty()) return 0;
+    const std::vector<float> xyz = flat_points(goals);
+    out.resize(goals.size());
+    if (!check(sdm_query_world_ground_reach(map_, xyz.data(), nullptr, (int64_t)goals.size(), out.data(), 0u), "sdm_query_world_ground_reach"))
+      out.clear();
+    return out.size();
+  }
+  /// Per goal position of the last worldGroundReach() the world cells the robot's base stands in on the way from the goal
+  /// to the start, both included; empty where there is no path.  Waits.  Returns the number of goals answered; 0 (and an
+  /// empty vector) before the first worldGroundReach() or when a call fails.
+  size_t worldGroundReachPaths(const std::vector<Eigen::Vector3d> &goals, std::vector<std::vector<Eigen::Vector3i>> &paths) {
+    paths.clear();
+    if (!map_ || goals.empty()) return 0;
+    const std::vector<float> xyz = flat_points(goals);
+    std::vector<int32_t> lens(goals.size());
+    if (!check(sdm_world_ground_reach_paths(map_, xyz.data(), nullptr, (int64_t)goals.size(), 0, nullptr, lens.data(), 0u),
+               "sdm_world_ground_reach_paths"))
+      return 0;
+    const int32_t longest = *std::max_element(lens.begin(), lens.end());  // (the true lengths, whatever max_len)
+    std::vector<int32_t> rows(goals.size() * (size_t)longest * 3);
+    if (longest && !check(sdm_world_ground_reach_paths(map_, xyz.data(), nullptr, (int64_t)goals.size(), longest, rows.data(), lens.data(), 0u),
+                          "sdm_world_ground_reach_paths"))
+      return 0;
+    paths.resize(goals.size());
+    for (size_t i = 0; i < goals.size(); ++i)
+      for (int32_t k = 0; k < lens[i]; ++k) {
+        const int32_t *c = rows.data() + (i * (size_t)longest + (size_t)k) * 3;
+        paths[i].push_back(Eigen::Vector3i(c[0], c[1], c[2]));
+      }
+    return paths.size();
+  }
   /// Is this straight leg free, through everything the map remembers (sdm.h, "world rays")?  Per segment from[i] -> to[i]
   /// (global frame), walked through the world archive without clipping: where it enters its first blocking cell, that
   /// cell, its word and its brick's stamp, the cells visited and how many of them are unknown - cells of bricks the archive

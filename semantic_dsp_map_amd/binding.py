@@ -185,6 +185,19 @@ WORLD_GROUND_MAX_SPAN = 4096
 WORLD_GROUND_MAX_RADIUS = 16
 WORLD_GROUND_NONE = 0xFFFF        # in world_ground()'s d2
 WORLD_GROUND_FAR = 0xFFFFFFFE     # in a WORLD_GROUND_RESULT's d2 and a WORLD_FOOTPRINT_RESULT's min_d2
+# world ground reach (sdm.h: sdm_world_ground_reach_update / sdm_get_world_ground_reach / sdm_query_world_ground_reach /
+# sdm_world_ground_reach_paths)
+WORLD_GROUND_REACH_OPTIONS = np.dtype([("flags", "<u4"), ("min_d2", "<u4"), ("soft_d2", "<u4"), ("penalty", "<u4"), ("max_climb", "<u4"),
+                                       ("max_cost", "<u4"), ("tmin", "<i4", (2,)), ("tmax", "<i4", (2,)), ("pad", "<u4", (2,))])
+WORLD_GROUND_REACH_INFO = np.dtype([("n_tiles", "<u4"), ("n_starts_used", "<u4"), ("n_traversable", "<u4"), ("n_reached", "<u4"),
+                                    ("max_cost_reached", "<u4"), ("rounds", "<u4"), ("stamp", "<u4"), ("pad", "<u4"),
+                                    ("options", WORLD_GROUND_REACH_OPTIONS)])
+WORLD_GROUND_REACH_RESULT = np.dtype([("cost", "<u4"), ("metres", "<f4"), ("col", "<i4", (2,)), ("level", "<u2"), ("next", "u1"), ("status", "u1"),
+                                      ("pad", "<u4")])
+assert WORLD_GROUND_REACH_OPTIONS.itemsize == 48 and WORLD_GROUND_REACH_INFO.itemsize == 80 and WORLD_GROUND_REACH_RESULT.itemsize == 24
+WORLD_GROUND_REACH_FACE_CONNECTED = 0x1
+WORLD_GROUND_REACH_BOX = 0x2
+WORLD_GROUND_REACH_BYTES_PER_TILE = 464
 
 WORLD_SEGMENT_HIT = np.dtype([("t", "<f4"), ("cells", "<i4"), ("cell", "<i4", (3,)), ("track", "<u2"), ("label", "u1"), ("occ", "i1"),
                               ("unknown", "<i4"), ("stamp", "<u4")])
@@ -442,6 +455,11 @@ def load_library():
         "sdm_get_world_ground": [vp, vp, vp, vp, i64, i64, C.POINTER(i64), vp],
         "sdm_query_world_ground": [vp, vp, vp, i64, vp, u32],
         "sdm_query_world_footprints": [vp, vp, i64, vp, u32],
+        "sdm_world_ground_reach_update": [vp, vp, vp, vp, i64],
+        "sdm_get_world_ground_reach": [vp, vp, vp, i64, i64, C.POINTER(i64), vp],
+        "sdm_query_world_ground_reach": [vp, vp, vp, i64, vp, u32],
+        "sdm_world_ground_reach_paths": [vp, vp, vp, i64, i32, vp, vp, u32],
+        "sdm_debug_world_ground_reach_tiles": [vp, C.POINTER(i64)],
         "sdm_query_world_segments": [vp, vp, i64, vp, u32],
         "sdm_query_world_views": [vp, vp, i64, vp, i32, i32, vp, vp, u32],
         "sdm_debug_world_view_batch": [vp, i32],
@@ -1396,6 +1414,77 @@ class SdmMap:
         res = np.empty(len(fp), WORLD_FOOTPRINT_RESULT)
         _check(self.L, self.L.sdm_query_world_footprints(self.h, _ptr(fp), len(fp), _ptr(res), 0), "sdm_query_world_footprints")
         return res
+
+    # ---- world ground reach (sdm.h).  world_ground_reach_update builds the 2-D travel-cost field over the last
+    # world_ground_update's costmap and WAITS until it is complete; world_ground_reach(), query_world_ground_reach() and
+    # world_ground_reach_paths() answer for that build - a snapshot that later ground builds and changes of the archive do
+    # not touch - until the next one.
+    def world_ground_reach_update(self, starts=None, start_cells=None, min_d2=0, soft_d2=0, penalty=0, max_climb=0, max_cost=0,
+                                  face_connected=False, box=None):
+        """starts: (n, 3) global positions, or start_cells: (n, 3) world cells (exactly one of the two; only the column
+        counts); min_d2, soft_d2: thresholds on the ground layer's d2, 0 .. R^2 + 1; penalty: what a column below soft_d2
+        costs more; max_climb in cells; box: (tmin, tmax), an inclusive box of tile coordinates (bu, bv) the field is cut to"""
+        o = np.zeros(1, WORLD_GROUND_REACH_OPTIONS)
+        o["flags"] = (WORLD_GROUND_REACH_FACE_CONNECTED if face_connected else 0) | (WORLD_GROUND_REACH_BOX if box is not None else 0)
+        o["min_d2"], o["soft_d2"], o["penalty"], o["max_climb"], o["max_cost"] = int(min_d2), int(soft_d2), int(penalty), int(max_climb), int(max_cost)
+        if box is not None:
+            o["tmin"], o["tmax"] = box[0], box[1]
+        p = None if starts is None else np.ascontiguousarray(starts, dtype=np.float32).reshape(-1, 3)
+        w = None if start_cells is None else np.ascontiguousarray(start_cells, dtype=np.int32).reshape(-1, 3)
+        n = len(p) if p is not None else len(w) if w is not None else 0
+        _check(self.L, self.L.sdm_world_ground_reach_update(self.h, _ptr(o), _ptr(p), _ptr(w), n), "sdm_world_ground_reach_update")
+
+    def world_ground_reach(self, with_cost=True, first=0, cap=None):
+        """-> (coords int16 [n, 2] (bu, bv), cost uint32 [n, 64] or None, info a WORLD_GROUND_REACH_INFO record): the tiles
+        of the field in (bv, bu) order, rows first .. first + cap - 1; a column's word is cu | cv << 3"""
+        got = C.c_int64(0)
+        info = np.zeros(1, WORLD_GROUND_REACH_INFO)
+        _check(self.L, self.L.sdm_get_world_ground_reach(self.h, None, None, 0, 0, C.byref(got), _ptr(info)), "sdm_get_world_ground_reach")
+        take = max(min(got.value - int(first), got.value if cap is None else int(cap)), 0)
+        coords = np.empty((take, 2), np.int16)
+        cost = np.empty((take, 64), np.uint32) if with_cost else None
+        _check(self.L, self.L.sdm_get_world_ground_reach(self.h, _ptr(coords), _ptr(cost), int(first), take, C.byref(got), None),
+               "sdm_get_world_ground_reach")
+        return coords, cost, info[0]
+
+    def query_world_ground_reach(self, xyz=None, cells=None, on_device=False, n=None, out=None):
+        """goals as (n, 3) global positions or as (n, 3) world cells -> WORLD_GROUND_REACH_RESULT per goal.  on_device: the
+        one given of xyz / cells and out (n WORLD_GROUND_REACH_RESULT) are device pointers."""
+        if on_device:
+            _check(self.L, self.L.sdm_query_world_ground_reach(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
+                                                               _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_world_ground_reach")
+            return None
+        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+        n = len(p) if p is not None else len(w) if w is not None else 0
+        res = np.empty(n, WORLD_GROUND_REACH_RESULT)
+        _check(self.L, self.L.sdm_query_world_ground_reach(self.h, _ptr(p), _ptr(w), n, _ptr(res), 0), "sdm_query_world_ground_reach")
+        return res
+
+    def world_ground_reach_paths(self, xyz=None, cells=None, max_len=0, on_device=False, n=None, cells_out=None, len_out=None,
+                                 fill=WORLD_REACH_NO_CELL):
+        """-> (cells_out int32 [n, max_len, 3], len_out): row g holds the first min(len, max_len) world cells of goal g's
+        path, goal first - the cells the robot's base stands in -, and `fill` behind them; len_out the true lengths (int32,
+        0: no path).  on_device: the pointers are device pointers (cells_out n * max_len * 3 int32, len_out n int32) and
+        nothing is returned."""
+        if on_device:
+            _check(self.L, self.L.sdm_world_ground_reach_paths(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
+                                                               int(max_len), _ptr(int(cells_out)) if cells_out else None, _ptr(int(len_out)),
+                                                               QUERY_ON_DEVICE), "sdm_world_ground_reach_paths")
+            return None
+        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+        n = len(p) if p is not None else len(w) if w is not None else 0
+        rows, lens = np.full((n, int(max_len), 3), fill, np.int32), np.zeros(n, np.int32)
+        _check(self.L, self.L.sdm_world_ground_reach_paths(self.h, _ptr(p), _ptr(w), n, int(max_len), _ptr(rows), _ptr(lens), 0),
+               "sdm_world_ground_reach_paths")
+        return rows, lens
+
+    def world_ground_reach_tiles_relaxed(self):
+        """Diagnostic: the tiles the last world_ground_reach_update relaxed, summed over its rounds."""
+        n = C.c_int64(0)
+        _check(self.L, self.L.sdm_debug_world_ground_reach_tiles(self.h, C.byref(n)), "sdm_debug_world_ground_reach_tiles")
+        return n.value
 
     # ---- world rays (sdm.h).  Segments and views through the archive, read live in stream order: host mode takes numpy
     # and waits, on_device=True takes device pointers (outputs 8-byte aligned), enqueues on the map's stream and returns.

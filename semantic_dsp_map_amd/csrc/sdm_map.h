@@ -229,6 +229,23 @@ struct WorldGroundLayer : Derived {
   sdm_world_ground_options opt{};
 };
 
+// world ground reach (world_ground_reach.hip): a snapshot of the world ground layer's costmap as a 2-D travel-cost field,
+// laid out for `cap` tiles of which n are in use and grown by a build that needs more: per tile of rank r its key, the
+// ranks of the eight tiles round it, the traversable and the penalty word, 64 levels and 64 costs; the hash table from tile
+// key to rank (hmask + 1 slots in use); the tiles' activity bitmask and the list of a round's active tiles; the build's
+// counters (and their page-locked landing area), its options (its flags are Derived's), the options of the ground build it
+// stands on and the archive's stamp that build carried.  Nothing of the ground layer is kept.
+struct WorldGroundReachLayer : Derived {
+  uint32_t *cost = nullptr, *nbr = nullptr, *coord = nullptr, *vals = nullptr, *act = nullptr, *list = nullptr;
+  unsigned long long *trav = nullptr, *pen = nullptr, *keys = nullptr;
+  uint16_t *level = nullptr;
+  uint32_t *meta = nullptr, *h_meta = nullptr;
+  size_t cap = 0;
+  uint32_t n = 0, hmask = 0, stamp = 0;
+  sdm_world_ground_reach_options opt{};
+  sdm_world_ground_options ground{};
+};
+
 // world rays (world_rays.hip): the views' pool of bitmasks, `words` words, one mask of (2 reach + 1)^3 bits per view in
 // flight, grown on demand up to 64 MiB and zero between calls; batch: sdm_debug_world_view_batch's bound on the views in
 // flight (0: as many as the pool may hold masks)
@@ -404,6 +421,7 @@ struct sdm_map {
   WorldFrontiersLayer wfront;
   WorldEsdfLayer wesdf;
   WorldGroundLayer wground;
+  WorldGroundReachLayer wgreach;
   WorldRaysPool wrays;
   // the scan scratch the layers share (layer_scan_scratch): they all enqueue on `stream` only, so their scans are ordered
   uint32_t *layer_scan = nullptr;

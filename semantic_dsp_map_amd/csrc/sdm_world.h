@@ -1,7 +1,7 @@
 // sdm_world.h — what the units of the world archive share (world.hip: the update, the getters and the queries;
 // world_io.hip: import and retain; world_reach.hip: the travel-cost field over the bricks; world_frontiers.hip:
 // the frontiers of the bricks; world_esdf.hip: the truncated distance field of the bricks; world_ground.hip: the height map
-// and costmap over the bricks): the hash table's key, hash,
+// and costmap over the bricks; world_ground_reach.hip: the 2-D travel-cost field over that costmap): the hash table's key, hash,
 // lookup and insertion, which cells write, the header-word layout, the indices of the counters, an update's geometry and
 // its closing kernel, and the three host helpers of world.hip that the other units call.  Everything but those three
 // helpers has internal linkage: each unit compiles its own copy.
