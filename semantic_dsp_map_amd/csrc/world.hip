@@ -19,8 +19,8 @@
 // Which bricks get room depends on the scan alone, so everything is reproducible bit for bit.  The pool is in creation
 // order; the getters that promise brick order sort the pool slots by two passes of the stable radix sort (low word
 // (bx, by), then bz), lazily at the first such getter after an update.
-// The table's key, hash, lookup and insertion, cell_writes, the header words, the counters' indices and k_world_finish
-// are in sdm_world.h, shared with world_io.hip (import and retain).
+// The table's key, hash, lookup and insertion, cell_writes, the header words and the counters' indices are in sdm_world.h;
+// world_io.hip (import and retain) closes with k_world_finish too, through launch_world_finish.
 #include "sdm_world.h"
 
 #pragma clang fp contract(off)
@@ -135,6 +135,16 @@ __global__ __launch_bounds__(WTPB) void k_world_merge(Dims d, Frame f, const uin
   h[4] = g.gts;
 }
 
+__global__ __launch_bounds__(64) void k_world_finish(const uint32_t *__restrict__ wanted_at, uint32_t max_bricks, uint32_t *__restrict__ meta) {
+  if (threadIdx.x != 0u) return;
+  const uint32_t n = meta[M_N_BRICKS], wanted = *wanted_at, room = max_bricks - n;
+  const uint32_t created = wanted < room ? wanted : room;
+  meta[M_N_BRICKS] = n + created;
+  meta[M_CREATED] = created;
+  u64 *total = reinterpret_cast<u64 *>(meta + M_DROPPED_TOTAL);
+  *total += meta[M_DROPPED];
+}
+
 // ---- brick order ----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(WTPB) void k_world_order_lo(const uint32_t *__restrict__ hdr, const uint32_t *__restrict__ meta, uint32_t cap,
                                                           uint32_t *__restrict__ key, uint32_t *__restrict__ val) {
@@ -208,25 +218,14 @@ __global__ __launch_bounds__(WTPB) void k_world_occ_emit(const uint32_t *__restr
   }
 }
 
-// the world cell of a coordinate: floorf(p * recip); false for a non-finite one or a brick out of range
-__device__ __forceinline__ bool world_cell_of(float p, float recip, int &g) {
-  const float v = floorf(p * recip);
-  const bool ok = v >= -262144.f && v < 262144.f;  // (NaN fails; the cast sees values in range only)
-  g = ok ? (int)v : 0;
-  return ok;
-}
-
 __global__ __launch_bounds__(WTPB) void k_world_query(float recip, const float *__restrict__ xyz, uint32_t n, const u64 *__restrict__ keys,
                                                       const uint32_t *__restrict__ vals, const uint32_t *__restrict__ hdr,
                                                       const uint32_t *__restrict__ cells, uint32_t hmask, uint2 *__restrict__ out) {
   const uint32_t i = blockIdx.x * WTPB + threadIdx.x;
   if (i >= n) return;
   int g[3];
-  bool ok = true;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) ok = world_cell_of(xyz[3 * (size_t)i + a], recip, g[a]) && ok;
   uint2 r = make_uint2(RES_UNKNOWN_W1, 0u);
-  if (ok) {
+  if (entry_cell(xyz, nullptr, i, recip, g)) {
     const uint32_t slot = world_find(keys, vals, hmask, brick_key(g[0] >> 3, g[1] >> 3, g[2] >> 3));
     if (slot != NONE) {
       r.x = cells[(size_t)slot * 512u + (uint32_t)((g[0] & 7) | ((g[1] & 7) << 3) | ((g[2] & 7) << 6))];
@@ -276,8 +275,7 @@ void world_release(sdm_map *m) {
 sdm_status world_alloc(sdm_map *m, uint32_t bricks) {
   WorldLayer &L = m->world;
   world_release(m);
-  uint32_t slots = 2;
-  while (slots < 2 * bricks) slots <<= 1;
+  const uint32_t slots = table_slots(bricks);
   const size_t nc_max = candidates_max(m->d);
   SDM_TRY(alloc_tracked(m, &L.keys, slots));
   SDM_TRY(alloc_tracked(m, &L.vals, slots));
@@ -326,8 +324,7 @@ hipError_t launch_world_update(const Dims &d, const Frame &f, const State &st, c
   exclusive_scan_u32(need, rank, (size_t)g.nc_max + 1, scan_scratch, s);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   LAYER_LAUNCH(k_world_merge, (g.nc + WWAVES - 1) / WWAVES, WTPB, s, d, f, res, g, L.keys, L.vals, need, rank, cslot, cnw, L.cells, L.hdr, L.meta);
-  LAYER_LAUNCH(k_world_finish, 1, 64, s, g, rank, L.meta);
-  return hipSuccess;
+  return launch_world_finish(rank + g.nc_max, g.max_bricks, L.meta, s);
 }
 
 // the pool slots in brick order (WorldLayer::order), once per update
@@ -366,6 +363,11 @@ sdm_status world_sorted(sdm_map *m) {
 }
 
 }  // namespace
+
+hipError_t launch_world_finish(const uint32_t *wanted, uint32_t max_bricks, uint32_t *meta, hipStream_t s) {
+  LAYER_LAUNCH(k_world_finish, 1, 64, s, wanted, max_bricks, meta);
+  return hipSuccess;
+}
 
 sdm_status world_counters(sdm_map *m, uint32_t *meta) {
   uint32_t got[M_WORDS];

@@ -6,10 +6,8 @@
 // as obstacle BITS 1.7 KB (H = 1) or 8 KB (H = 2).  So one workgroup per brick does in LDS what esdf.hip needs three global
 // passes for, and the only global traffic of the build is the neighbour lookups, the obstacle words and one packed store a
 // cell.  The build is a snapshot: coordinates, a hash table of its own from brick key to rank and the field; no pool slot.
-//   k_we_flag        a thread per archived brick in brick order: 1 if it lies in the box (or there is none).
-//   exclusive_scan_u32   ranks the flags; the entry behind the last brick ends as the number of bricks of the field.
-//   k_we_index       a thread per archived brick: a brick of the field writes its coordinates at its rank and inserts
-//               key -> rank into the layer's table (every key by one thread, like world_insert).
+//   snapshot_bricks, launch_snapshot_index   world_snapshot.hip's: the bricks of the box flagged and ranked, their
+//               coordinates at their rank, key -> rank in the layer's table.
 //   k_we_classify    a wave per archived brick - all of them: a box reads across its sides -, a lane per (cx, cy), the
 //               eight layers' loads first, then a ballot a layer: the eight obstacle words (bit cx + 8 cy), 64 B, at the
 //               brick's pool slot, where the archive's own hash table leads.
@@ -54,11 +52,6 @@ constexpr size_t ARCH_BYTES = 4 + 4 + 8 * 8;            // flag, rank, obstacle 
 constexpr size_t BRICK_BYTES = 512 * 4 + 8 + 2 * (8 + 4);  // field, coordinates, two hash slots
 static_assert(ARCH_BYTES == SDM_WORLD_ESDF_BYTES_PER_ARCHIVED_BRICK && BRICK_BYTES == SDM_WORLD_ESDF_BYTES_PER_BRICK, "sdm.h states the bytes");
 
-struct BrickBox {
-  int lo[3], hi[3];
-  uint32_t use;
-};
-
 // what k_we_build<H> keeps in LDS: the obstacle words, the x pass' bytes, the y pass' words, the neighbours' slots (a
 // multiple of four words: the other arrays stay aligned wherever the compiler puts them), the waves' two counts
 template <int H>
@@ -68,36 +61,6 @@ struct BuildShape {
 };
 static_assert(BuildShape<1>::LDS == 1728 + 4608 + 6144 + 112 + 32 && BuildShape<2>::LDS == 8000 + 12800 + 10240 + 512 + 32,
               "DESIGN.md 5o states the bytes");
-
-// ---- the index ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(QT) void k_we_flag(const uint32_t *__restrict__ order, const uint32_t *__restrict__ hdr, uint32_t n_arch, BrickBox box,
-                                                uint32_t *__restrict__ flag) {
-  const uint32_t j = blockIdx.x * QT + threadIdx.x;
-  if (j > n_arch) return;
-  uint32_t in = 0u;
-  if (j < n_arch) {  // (the entry behind the last brick: the scan leaves the number of flags there)
-    const uint32_t slot = order[j];
-    const uint32_t h0 = hdr[(size_t)slot * HDR_WORDS], h1 = hdr[(size_t)slot * HDR_WORDS + 1];
-    const int b[3] = {(int16_t)(h0 & 0xffffu), (int16_t)(h0 >> 16), (int16_t)(h1 & 0xffffu)};
-    in = 1u;
-    if (box.use)
-      for (int a = 0; a < 3; ++a) in = in && b[a] >= box.lo[a] && b[a] <= box.hi[a] ? 1u : 0u;
-  }
-  flag[j] = in;
-}
-
-__global__ __launch_bounds__(QT) void k_we_index(const uint32_t *__restrict__ order, const uint32_t *__restrict__ hdr,
-                                                 const uint32_t *__restrict__ flag, const uint32_t *__restrict__ rank, uint32_t n_arch, uint32_t n,
-                                                 uint32_t *__restrict__ coord, u64 *__restrict__ keys, uint32_t *__restrict__ vals, uint32_t hmask) {
-  const uint32_t j = blockIdx.x * QT + threadIdx.x;
-  if (j >= n_arch || !flag[j]) return;
-  const uint32_t slot = order[j], r = rank[j];
-  if (r >= n) return;  // (never: the scan's total is n)
-  const uint32_t h0 = hdr[(size_t)slot * HDR_WORDS], h1 = hdr[(size_t)slot * HDR_WORDS + 1] & 0xffffu;
-  coord[2 * (size_t)r] = h0;
-  coord[2 * (size_t)r + 1] = h1;
-  world_insert(keys, vals, hmask, brick_key((int16_t)(h0 & 0xffffu), (int16_t)(h0 >> 16), (int16_t)h1), r);
-}
 
 // ---- the obstacle words --------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(QT) void k_we_classify(const uint32_t *__restrict__ order, const uint32_t *__restrict__ cells, uint32_t n_arch,
@@ -135,8 +98,9 @@ __global__ __launch_bounds__(BT) void k_we_build(const uint32_t *__restrict__ co
   const int tid = (int)threadIdx.x;
   const uint32_t r = blockIdx.x;
   if (tid < NB) {
-    const uint32_t c0 = coord[2 * (size_t)r], c1 = coord[2 * (size_t)r + 1];
-    const int bx = (int16_t)(c0 & 0xffffu) + tid % W - H, by = (int16_t)(c0 >> 16) + (tid / W) % W - H, bz = (int16_t)(c1 & 0xffffu) + tid / (W * W) - H;
+    int bx, by, bz;
+    coord_of(coord, r, bx, by, bz);
+    bx += tid % W - H, by += (tid / W) % W - H, bz += tid / (W * W) - H;
     // (a coordinate of 32768 would alias another brick's key)
     const uint32_t slot = brick_in_range(bx, by, bz) ? world_find(akeys, avals, ahmask, brick_key(bx, by, bz)) : NONE;
     s_slot[tid] = slot < n_arch ? slot : NONE;
@@ -210,26 +174,6 @@ __global__ __launch_bounds__(BT) void k_we_build(const uint32_t *__restrict__ co
 }
 
 // ---- the query ---------------------------------------------------------------------------------------------------------
-// entry i as a world cell: the cells given, or the cell of a point by the archive's rule, floorf(p * recip) per axis.  False
-// where its brick is out of range or the point is not finite; g is then (0, 0, 0) for a point and the entry itself for a cell.
-__device__ __forceinline__ bool entry_cell(const float *__restrict__ xyz, const int32_t *__restrict__ cells, uint32_t i, float recip, int (&g)[3]) {
-  bool ok = true;
-  if (cells) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) g[a] = cells[3 * (size_t)i + a];
-    return brick_in_range(g[0] >> 3, g[1] >> 3, g[2] >> 3);
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float v = floorf(xyz[3 * (size_t)i + a] * recip);
-    const bool in = v >= -262144.f && v < 262144.f;  // (NaN fails; the cast sees values in range only)
-    g[a] = in ? (int)v : 0;
-    ok = ok && in;
-  }
-  if (!ok) g[0] = g[1] = g[2] = 0;
-  return ok;
-}
-
 __global__ __launch_bounds__(QT) void k_query_world_distance(const float *__restrict__ xyz, const int32_t *__restrict__ cells, uint32_t n, float recip,
                                                              float voxel_size, const u64 *__restrict__ keys, const uint32_t *__restrict__ vals,
                                                              uint32_t hmask, uint32_t n_bricks, const uint32_t *__restrict__ field, uint32_t far_d2,
@@ -258,12 +202,6 @@ __global__ __launch_bounds__(QT) void k_query_world_distance(const float *__rest
   o[1] = make_uint2((uint32_t)g[2], (uint32_t)q[0]);
   o[2] = make_uint2((uint32_t)q[1], (uint32_t)q[2]);
   o[3] = make_uint2(d2, __float_as_uint(metres));
-}
-
-uint32_t table_slots(size_t bricks) {
-  uint32_t slots = 2;
-  while (slots < 2 * bricks) slots <<= 1;
-  return slots;
 }
 
 // the buffers for n_arch archived bricks / for `bricks` bricks of the field (the stream is idle when either is called)
@@ -304,7 +242,7 @@ hipError_t launch_we_build(const sdm_map *m, const uint32_t *order, uint32_t n_a
   if ((e = hipMemsetAsync(L.meta, 0, E_WORDS * sizeof(u64), s)) != hipSuccess) return e;
   if (!n) return hipSuccess;
   const uint32_t unknown_too = (flags & SDM_WORLD_ESDF_UNKNOWN_IS_OBSTACLE) ? 1u : 0u;
-  LAYER_LAUNCH(k_we_index, (n_arch + QT - 1) / QT, QT, s, order, W.hdr, L.flag, L.rank, n_arch, n, L.coord, L.keys, L.vals, L.hmask);
+  if ((e = launch_snapshot_index(m, order, L.flag, L.rank, n_arch, n, L.coord, nullptr, L.keys, L.vals, L.hmask)) != hipSuccess) return e;
   LAYER_LAUNCH(k_we_classify, (n_arch + QT / 64 - 1) / (QT / 64), QT, s, order, W.cells, n_arch, unknown_too,
                (flags & SDM_WORLD_ESDF_STATIC_ONLY) ? 1u : 0u, m->d.max_movable, L.obst);
   const u64 absent_reads = unknown_too ? ~0ull : 0ull;
@@ -346,29 +284,17 @@ sdm_status sdm_world_esdf_update(sdm_map *m, const sdm_world_esdf_options *o) {
   if (!L.meta) SDM_TRY(alloc_tracked(m, &L.meta, E_WORDS));
   if (!L.h_meta) SDM_TRY(alloc_tracked(m, &L.h_meta, E_WORDS + 1, true));
   // the bricks of the field: the archive's in brick order, those of the box ranked
-  uint32_t wmeta[M_WORDS];
-  SDM_TRY(world_counters(m, wmeta));  // (waits: the last build, if any, has run)
-  const uint32_t n_arch = wmeta[M_N_BRICKS];
-  const uint32_t *order = nullptr;
-  uint32_t n = 0;
-  if (n_arch) {
-    uint32_t *scan = nullptr;
-    SDM_TRY(world_order(m, &order));
-    SDM_TRY(layer_scan_scratch(m, (size_t)m->world.max_bricks + 1, &scan));
+  SnapshotBricks b;
+  SDM_TRY(snapshot_bricks(m, box, (size_t)m->world.max_bricks + 1, L.h_meta + E_WORDS, [&](uint32_t n_arch, uint32_t **flag, uint32_t **rank) -> sdm_status {
     HIP_TRY(hipStreamSynchronize(s));
     SDM_TRY(grow_arch(m, n_arch));
-    hipLaunchKernelGGL(k_we_flag, dim3(n_arch / QT + 1), dim3(QT), 0, s, order, m->world.hdr, n_arch, box, L.flag);
-    HIP_TRY(hipGetLastError());
-    exclusive_scan_u32(L.flag, L.rank, (size_t)n_arch + 1, scan, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(L.h_meta + E_WORDS, L.rank + n_arch, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));  // the one wait: the count sizes the buffers
-    n = (uint32_t)(L.h_meta[E_WORDS] & 0xffffffffull);
-  }
-  SDM_TRY(grow_bricks(m, n));
-  L.n = n;
-  L.hmask = table_slots(n) - 1;
-  HIP_TRY(launch_we_build(m, order, n_arch, n, o->flags, (int)o->radius));
+    *flag = L.flag, *rank = L.rank;
+    return SDM_OK;
+  }, &b));
+  SDM_TRY(grow_bricks(m, b.n));
+  L.n = b.n;
+  L.hmask = table_slots(b.n) - 1;
+  HIP_TRY(launch_we_build(m, b.order, b.n_arch, b.n, o->flags, (int)o->radius));
   HIP_TRY(hipMemcpyAsync(L.h_meta, L.meta, E_WORDS * sizeof(u64), hipMemcpyDeviceToHost, s));  // (the getter waits for them)
   L.radius = o->radius;
   L.stamp = m->world.f.gts;
@@ -388,11 +314,7 @@ sdm_status sdm_get_world_esdf(sdm_map *m, int16_t *coords, uint16_t *d2, int8_t 
   std::vector<uint32_t> pairs(coords ? 2 * take : 0);
   if (take && coords) HIP_TRY(hipMemcpyAsync(pairs.data(), L.coord + 2 * (size_t)first, 2 * take * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
   HIP_TRY(hipStreamSynchronize(m->stream));
-  for (size_t i = 0; i < pairs.size() / 2; ++i) {
-    coords[3 * i] = (int16_t)(pairs[2 * i] & 0xffffu);
-    coords[3 * i + 1] = (int16_t)(pairs[2 * i] >> 16);
-    coords[3 * i + 2] = (int16_t)(pairs[2 * i + 1] & 0xffffu);
-  }
+  unpack_coords(pairs, coords);
   if (take && (d2 || offset)) {  // the packed words, unpacked on the host a chunk of bricks at a time
     std::vector<uint32_t> words(std::min(take, GET_CHUNK) * 512);
     for (size_t at = 0; at < take; at += GET_CHUNK) {
@@ -428,11 +350,7 @@ sdm_status sdm_get_world_esdf(sdm_map *m, int16_t *coords, uint16_t *d2, int8_t 
 }
 
 sdm_status sdm_query_world_distance(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n, sdm_world_distance_result *out, uint32_t flags) {
-  const char *what = "sdm_query_world_distance";
-  if (!m) return SDM_ERR_INVALID_ARGUMENT;
-  if ((xyz != nullptr) == (cells != nullptr)) return LAYER_REFUSE(what, "exactly one of xyz and cells must be given");
-  SDM_TRY(query_check(m, xyz ? (const void *)xyz : (const void *)cells, n, out, flags, SDM_QUERY_ON_DEVICE, what));
-  SDM_TRY(layer_check(m, what, &m->wesdf, WORLD_ESDF));
+  SDM_TRY(goal_query_check(m, xyz, cells, n, out, flags, "sdm_query_world_distance", &sdm_map::wesdf, WORLD_ESDF));
   const WorldEsdfLayer L = m->wesdf;
   const float recip = m->d.recip, voxel_size = m->d.voxel_size;
   const uint32_t far_d2 = L.radius * L.radius + 1u;

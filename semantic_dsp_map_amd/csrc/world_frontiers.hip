@@ -6,8 +6,7 @@
 // archive's own hash table names.  The build is a snapshot: what it leaves are lists (cells, unknown faces, cluster
 // indices, the table, the counters), no pool slot.  Everything it accumulates is an integer sum, minimum or maximum, and a
 // component's root is its smallest rank whatever order the unions arrive in: two builds give the same bytes.
-//   k_wf_flag        a thread per archived brick in brick order: 1 if it lies in the box (or there is none).
-//   exclusive_scan_u32   ranks the flags; the entry behind the last brick ends as the number of bricks of the field.
+//   snapshot_bricks  world_snapshot.hip's: the bricks of the box flagged and ranked, the number of bricks of the field.
 //   k_wf_index       a thread per archived brick: its place in brick order goes to where its pool slot says (the
 //               key-to-brick map of the build: the archive's hash table gives the slot), a brick of the field writes its
 //               coordinates and its place at its rank.
@@ -65,11 +64,6 @@ constexpr uint32_t NO_LABEL = 0xffffu;
 // the build's counters, 64 bits each: unknown faces, those towards absent bricks, roots, clusters listed
 enum { F_FACES = 0, F_ABSENT, F_ROOTS, F_LISTED, F_WORDS };
 
-struct BrickBox {
-  int lo[3], hi[3];
-  uint32_t use;
-};
-
 struct WfAcc {  // per root; all zero = no cell yet.  nmin / max: the largest ~code / code, code = coordinate ^ 2^31
   u64 sum[3];
   uint32_t n, faces, nmin[3], max[3];
@@ -85,28 +79,9 @@ static_assert(CELL_BYTES == SDM_WORLD_FRONTIERS_BYTES_PER_CELL && BRICK_BYTES ==
 constexpr int off_d(int k, int a) { return a == 0 ? k % 3 - 1 : a == 1 ? (k / 3) % 3 - 1 : k / 9 - 1; }
 // the place of offset k among the six faces (x-, x+, y-, y+, z-, z+), -1 for an edge, a corner and the brick itself
 constexpr int face_of(int k) { return k == 12 ? 0 : k == 14 ? 1 : k == 10 ? 2 : k == 16 ? 3 : k == 4 ? 4 : k == 22 ? 5 : -1; }
-// the brick offset (-1, 0, 1) of coordinate c in -1 .. 8 of the brick's own cells 0 .. 7
-__device__ __forceinline__ int brick_off(int c) { return c < 0 ? -1 : c > 7 ? 1 : 0; }
-
 constexpr u64 COL0 = 0x0101010101010101ull, COL7 = 0x8080808080808080ull, ROW0 = 0xffull, ROW7 = 0xffull << 56;
 
 // ---- the index ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(QT) void k_wf_flag(const uint32_t *__restrict__ order, const uint32_t *__restrict__ hdr, uint32_t n_arch, BrickBox box,
-                                                uint32_t *__restrict__ flag) {
-  const uint32_t j = blockIdx.x * QT + threadIdx.x;
-  if (j > n_arch) return;
-  uint32_t in = 0u;
-  if (j < n_arch) {  // (the entry behind the last brick: the scan leaves the number of flags there)
-    const uint32_t slot = order[j];
-    const uint32_t h0 = hdr[(size_t)slot * HDR_WORDS], h1 = hdr[(size_t)slot * HDR_WORDS + 1];
-    const int b[3] = {(int16_t)(h0 & 0xffffu), (int16_t)(h0 >> 16), (int16_t)(h1 & 0xffffu)};
-    in = 1u;
-    if (box.use)
-      for (int a = 0; a < 3; ++a) in = in && b[a] >= box.lo[a] && b[a] <= box.hi[a] ? 1u : 0u;
-  }
-  flag[j] = in;
-}
-
 __global__ __launch_bounds__(QT) void k_wf_index(const uint32_t *__restrict__ order, const uint32_t *__restrict__ hdr,
                                                  const uint32_t *__restrict__ flag, const uint32_t *__restrict__ rank, uint32_t n_arch,
                                                  uint32_t max_bricks, uint32_t *__restrict__ place_of_slot, uint32_t *__restrict__ coord,
@@ -151,9 +126,9 @@ __global__ __launch_bounds__(QT) void k_wf_neighbours(const uint32_t *__restrict
   const uint32_t i = blockIdx.x * QT + threadIdx.x;
   if (i >= n * 27u) return;
   const uint32_t r = i / 27u, k = i - r * 27u;
-  const uint32_t c0 = coord[2 * (size_t)r], c1 = coord[2 * (size_t)r + 1];
-  const int bx = (int16_t)(c0 & 0xffffu) + off_d((int)k, 0), by = (int16_t)(c0 >> 16) + off_d((int)k, 1),
-            bz = (int16_t)(c1 & 0xffffu) + off_d((int)k, 2);
+  int bx, by, bz;
+  coord_of(coord, r, bx, by, bz);
+  bx += off_d((int)k, 0), by += off_d((int)k, 1), bz += off_d((int)k, 2);
   // (a coordinate of 32768 would alias another brick's key)
   const uint32_t slot = brick_in_range(bx, by, bz) ? world_find(keys, vals, hmask, brick_key(bx, by, bz)) : NONE;
   uint32_t j = slot < max_bricks ? place_of_slot[slot] : NONE;
@@ -242,13 +217,14 @@ __global__ __launch_bounds__(QT) void k_wf_compact(const uint32_t *__restrict__ 
   if (!((fw >> lane) & 1ull)) return;
   const uint32_t at = pre[i] + lane_rank(fw, lane);
   if (at >= n_cells) return;  // (never: the scan's total is n_cells)
-  const uint32_t c0 = coord[2 * (size_t)r], c1 = coord[2 * (size_t)r + 1];
+  int bx, by, bz;
+  coord_of(coord, r, bx, by, bz);
   uint32_t nf = 0;
 #pragma unroll
   for (int f = 0; f < 6; ++f) nf += (uint32_t)((m[f] >> lane) & 1ull);
-  xyz[3 * (size_t)at] = (int)(int16_t)(c0 & 0xffffu) * 8 + (int)(lane & 7u);
-  xyz[3 * (size_t)at + 1] = (int)(int16_t)(c0 >> 16) * 8 + (int)(lane >> 3);
-  xyz[3 * (size_t)at + 2] = (int)(int16_t)(c1 & 0xffffu) * 8 + z;
+  xyz[3 * (size_t)at] = bx * 8 + (int)(lane & 7u);
+  xyz[3 * (size_t)at + 1] = by * 8 + (int)(lane >> 3);
+  xyz[3 * (size_t)at + 2] = bz * 8 + z;
   faces[at] = (uint8_t)nf;
 }
 
@@ -626,30 +602,20 @@ sdm_status sdm_world_frontiers_update(sdm_map *m, const sdm_world_frontiers_opti
   if (!L.h_meta) SDM_TRY(alloc_tracked(m, &L.h_meta, F_WORDS + 1, true));
   HIP_TRY(hipMemsetAsync(L.meta, 0, F_WORDS * sizeof(u64), s));
   // the bricks of the field: the archive's in brick order, those of the box ranked
-  uint32_t wmeta[M_WORDS];
-  SDM_TRY(world_counters(m, wmeta));
-  const uint32_t n_arch = wmeta[M_N_BRICKS];
-  const uint32_t *order = nullptr;
-  uint32_t *scan = nullptr;
-  uint32_t n = 0;
-  if (n_arch) {
-    SDM_TRY(world_order(m, &order));
-    SDM_TRY(layer_scan_scratch(m, (size_t)m->world.max_bricks * 8 + 1, &scan));
+  SnapshotBricks b;
+  SDM_TRY(snapshot_bricks(m, box, (size_t)m->world.max_bricks * 8 + 1, L.h_meta + F_WORDS, [&](uint32_t n_arch, uint32_t **flag, uint32_t **rank) -> sdm_status {
     SDM_TRY(grow_arch(m, n_arch, m->world.max_bricks));
-    hipLaunchKernelGGL(k_wf_flag, dim3(n_arch / QT + 1), dim3(QT), 0, s, order, m->world.hdr, n_arch, box, L.flag);
-    HIP_TRY(hipGetLastError());
-    exclusive_scan_u32(L.flag, L.rank, (size_t)n_arch + 1, scan, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(L.h_meta + F_WORDS, L.rank + n_arch, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    n = (uint32_t)L.h_meta[F_WORDS] & 0xffffffffu;
-  }
+    *flag = L.flag, *rank = L.rank;
+    return SDM_OK;
+  }, &b));
+  const uint32_t n = b.n;
+  uint32_t *scan = b.scan;
   // the frontier words, and how many cells they hold
   const u64 absent_reads = (o->flags & SDM_WORLD_FRONTIERS_INSIDE_BRICKS) ? 0ull : ~0ull;
   uint32_t n_cells = 0;
   if (n) {
     SDM_TRY(grow_bricks(m, n));
-    HIP_TRY(launch_wf_words(m, order, n_arch, n, absent_reads));
+    HIP_TRY(launch_wf_words(m, b.order, b.n_arch, n, absent_reads));
     exclusive_scan_u32(L.pre, L.pre, (size_t)n * 8 + 1, scan, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(L.h_meta + F_WORDS, L.pre + (size_t)n * 8, sizeof(uint32_t), hipMemcpyDeviceToHost, s));

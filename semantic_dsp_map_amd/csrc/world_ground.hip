@@ -9,7 +9,7 @@
 //               the box) claims its tile key in the layer's table; the one thread whose compare-and-swap found the slot
 //               empty flags the brick.  So every tile is flagged exactly once, whatever the arrival order, and the sort
 //               below sees each tile once instead of once per brick of its column.
-//   exclusive_scan_u32   ranks the flags; the entry behind the last brick ends as the number of tiles.
+//   snapshot_rank  (world_snapshot.hip) ranks the flags; the entry behind the last brick ends as the number of tiles.
 //   k_wg_keys      a thread per archived brick: a flagged one writes its tile key at its rank.
 //   radix_sort_pairs 32 bits   the keys, bu + 32768 | (bv + 32768) << 16, ascending: tile order (bv, bu).
 //   k_wg_tiles     a thread per tile: the key at its rank, and the rank beside the key in the table.
@@ -79,13 +79,10 @@ struct DistShape {
 };
 static_assert(DistShape<1>::LDS == 72 + 192 && DistShape<2>::LDS == 200 + 320, "DESIGN.md 5q states the bytes");
 
-__device__ __forceinline__ u64 tile_key(int bu, int bv) { return (u64)(uint32_t)(bu + 32768) | ((u64)(uint32_t)(bv + 32768) << 16); }
-__device__ __forceinline__ bool tile_in_range(int bu, int bv) { return bu >= -32768 && bu <= 32767 && bv >= -32768 && bv <= 32767; }
-
 // the brick's coordinates as (up, u, v)
 __device__ __forceinline__ void brick_auv(const Band &b, const uint32_t *__restrict__ hdr, uint32_t slot, int &ba, int &bu, int &bv) {
-  const uint32_t h0 = hdr[(size_t)slot * HDR_WORDS], h1 = hdr[(size_t)slot * HDR_WORDS + 1];
-  const int c[3] = {(int16_t)(h0 & 0xffffu), (int16_t)(h0 >> 16), (int16_t)(h1 & 0xffffu)};
+  int c[3];
+  brick_of(hdr[(size_t)slot * HDR_WORDS], hdr[(size_t)slot * HDR_WORDS + 1], c[0], c[1], c[2]);
   ba = b.a == 0 ? c[0] : (b.a == 1 ? c[1] : c[2]);
   bu = b.au == 0 ? c[0] : c[1];
   bv = b.av == 1 ? c[1] : c[2];
@@ -169,8 +166,8 @@ __global__ __launch_bounds__(QT) void k_wg_columns(const uint32_t *__restrict__ 
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t t = blockIdx.x * (QT / 64) + (threadIdx.x >> 6);
   if (t >= n_tiles) return;  // (wave-uniform)
-  const uint32_t key = coord[t];
-  const int bu = (int)(key & 0xffffu) - 32768, bv = (int)(key >> 16) - 32768;
+  int bu, bv;
+  tile_of(coord[t], bu, bv);
   const uint32_t cu = lane & 7u, cv = lane >> 3;
   // the word of the column's cell c along the up axis: x | y << 3 | z << 6
   const uint32_t off = A == 2 ? lane : (A == 1 ? cu | (cv << 6) : lane << 3);
@@ -236,8 +233,8 @@ __global__ __launch_bounds__(QT) void k_wg_cost(const uint32_t *__restrict__ coo
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t t = blockIdx.x * (QT / 64) + (threadIdx.x >> 6);
   if (t >= n_tiles) return;  // (wave-uniform)
-  const uint32_t key = coord[t];
-  const int bu = (int)(key & 0xffffu) - 32768, bv = (int)(key >> 16) - 32768;
+  int bu, bv;
+  tile_of(coord[t], bu, bv);
   uint32_t nt[4];  // the tiles at u - 1, u + 1, v - 1, v + 1
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -327,25 +324,6 @@ __global__ __launch_bounds__(DT) void k_wg_dist(const uint32_t *__restrict__ coo
 }
 
 // ---- the queries -------------------------------------------------------------------------------------------------------
-// entry i as a world cell: the cell given, or the cell of a point by the archive's rule, floorf(p * recip) per axis.  False
-// where its brick is out of range or the point is not finite.
-__device__ __forceinline__ bool entry_cell(const float *__restrict__ xyz, const int32_t *__restrict__ cells, uint32_t i, float recip, int (&g)[3]) {
-  bool ok = true;
-  if (cells) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) g[a] = cells[3 * (size_t)i + a];
-    return brick_in_range(g[0] >> 3, g[1] >> 3, g[2] >> 3);
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float v = floorf(xyz[3 * (size_t)i + a] * recip);
-    const bool in = v >= -262144.f && v < 262144.f;  // (NaN fails; the cast sees values in range only)
-    g[a] = in ? (int)v : 0;
-    ok = ok && in;
-  }
-  return ok;
-}
-
 __global__ __launch_bounds__(QT) void k_query_world_ground(const float *__restrict__ xyz, const int32_t *__restrict__ in_cells, uint32_t n, float recip,
                                                            float voxel_size, Band b, int R, const u64 *__restrict__ keys,
                                                            const uint32_t *__restrict__ vals, uint32_t hmask, uint32_t n_tiles,
@@ -474,12 +452,6 @@ __global__ __launch_bounds__(QT) void k_query_world_footprints(const sdm_footpri
   }
 }
 
-uint32_t table_slots(size_t items) {
-  uint32_t slots = 2;
-  while (slots < 2 * items) slots <<= 1;
-  return slots;
-}
-
 // a length whose scan scratch holds `elems` words: the sort's histogram lies behind its scan's scratch, in the part of the
 // layers' shared scratch that needs no initialising (sdm_internal.h)
 size_t scan_length_for(size_t elems) { return std::max<size_t>(elems, 1032 + 513) * 2048 - (size_t)1032 * 2048; }
@@ -605,11 +577,7 @@ sdm_status sdm_world_ground_update(sdm_map *m, const sdm_world_ground_options *o
     SDM_TRY(layer_scan_scratch(m, std::max<size_t>((size_t)m->world.max_bricks + 1, scan_length_for(sort_scratch_elems(m->world.max_bricks))), &scan));
     hipLaunchKernelGGL(k_wg_claim, dim3(n_arch / QT + 1), dim3(QT), 0, s, order, m->world.hdr, n_arch, b, L.keys, L.hmask, L.flag);
     HIP_TRY(hipGetLastError());
-    exclusive_scan_u32(L.flag, L.rank, (size_t)n_arch + 1, scan, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(L.h_meta + G_WORDS, L.rank + n_arch, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));  // the one wait: the count sizes the buffers
-    n = (uint32_t)(L.h_meta[G_WORDS] & 0xffffffffull);
+    SDM_TRY(snapshot_rank(m, L.flag, L.rank, n_arch, scan, L.h_meta + G_WORDS, &n));
   }
   SDM_TRY(grow_tiles(m, n));
   L.n = n;
@@ -636,10 +604,7 @@ sdm_status sdm_get_world_ground(sdm_map *m, int16_t *coords, sdm_ground_cell *ce
     HIP_TRY(hipMemcpyAsync(cells, L.cells + (size_t)first * 64, take * 64 * sizeof(sdm_ground_cell), hipMemcpyDeviceToHost, m->stream));
   if (take && d2) HIP_TRY(hipMemcpyAsync(d2, L.d2 + (size_t)first * 64, take * 64 * sizeof(uint16_t), hipMemcpyDeviceToHost, m->stream));
   HIP_TRY(hipStreamSynchronize(m->stream));
-  for (size_t i = 0; i < keys.size(); ++i) {
-    coords[2 * i] = (int16_t)((int)(keys[i] & 0xffffu) - 32768);
-    coords[2 * i + 1] = (int16_t)((int)(keys[i] >> 16) - 32768);
-  }
+  unpack_tiles(keys, coords);
   *n_out = (int64_t)L.n;
   if (info) {
     const u64 *h = L.h_meta;  // (the stream has drained: the build's copy has landed)
@@ -662,11 +627,7 @@ sdm_status sdm_get_world_ground(sdm_map *m, int16_t *coords, sdm_ground_cell *ce
 }
 
 sdm_status sdm_query_world_ground(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n, sdm_world_ground_result *out, uint32_t flags) {
-  const char *what = "sdm_query_world_ground";
-  if (!m) return SDM_ERR_INVALID_ARGUMENT;
-  if ((xyz != nullptr) == (cells != nullptr)) return LAYER_REFUSE(what, "exactly one of xyz and cells must be given");
-  SDM_TRY(query_check(m, xyz ? (const void *)xyz : (const void *)cells, n, out, flags, SDM_QUERY_ON_DEVICE, what));
-  SDM_TRY(layer_check(m, what, &m->wground, WORLD_GROUND));
+  SDM_TRY(goal_query_check(m, xyz, cells, n, out, flags, "sdm_query_world_ground", &sdm_map::wground, WORLD_GROUND));
   const WorldGroundLayer L = m->wground;
   const Band b = band_of(L.opt);
   const float recip = m->d.recip, voxel_size = m->d.voxel_size;

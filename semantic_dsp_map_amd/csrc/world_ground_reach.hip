@@ -8,7 +8,7 @@
 // ground layer afterwards.  cost[] is the fixed point of the relaxation, so it is the same whatever order the device
 // relaxes in.
 //   k_wgr_flag        a thread per tile of the ground layer: 1 if it lies in the box (or there is none).
-//   exclusive_scan_u32   ranks the flags; the entry behind the last tile ends as the number of tiles of the field.
+//   snapshot_rank     (world_snapshot.hip) ranks the flags; the entry behind the last tile ends as the number of tiles.
 //   k_wgr_index       a thread per ground tile: a tile of the field writes its key at its rank and inserts key -> rank
 //               (a compare-and-swap on the key: every key by one thread).
 //   k_wgr_neighbours  a thread per (tile, one of 8): one lookup, the rank or NONE; the range test before every lookup.
@@ -17,8 +17,8 @@
 //               and 0xffffffff goes into the cost.
 //   k_wgr_seed        a thread per start: cost 0 by atomicMin - the thread that lowers it counts the start - and the
 //               activity bit of the tile and of its present neighbours.
-//   k_wgr_list / k_wgr_relax   a round: the activity bits become a list; ONE WAVE per listed tile holds the tile's 64 costs
-//               in a register a lane, takes the 36 columns of the halo through the neighbour ranks (an absent tile reads
+//   launch_snapshot_list / k_wgr_relax   a round: the activity bits become a list (world_snapshot.hip's k_ws_list); ONE
+//               WAVE per listed tile holds the tile's 64 costs in a register a lane, takes the 36 columns of the halo through the neighbour ranks (an absent tile reads
 //               not traversable, 0xffffffff) into registers of the lanes on the tile's rim, works out each lane's allowed
 //               moves once and sweeps - eight cross-lane reads of the neighbours' costs a sweep, no LDS, no barrier -
 //               until a ballot says that nothing fell; it stores what it lowered and wakes every side and corner
@@ -81,8 +81,6 @@ constexpr bool move_used(int k) {
 }
 static_assert(move_weight(1) == 10 && move_weight(0) == 14 && move_du(5) == 1 && move_dv(7) == 1 && !move_used<true>(8) && move_used<false>(8), "moves");
 
-__device__ __forceinline__ u64 tile_key(int bu, int bv) { return (u64)(uint32_t)(bu + 32768) | ((u64)(uint32_t)(bv + 32768) << 16); }
-__device__ __forceinline__ bool tile_in_range(int bu, int bv) { return bu >= -32768 && bu <= 32767 && bv >= -32768 && bv <= 32767; }
 // the tile offset (-1, 0, 1) of coordinate c in -1 .. 8 of the tile's own columns 0 .. 7
 __device__ __forceinline__ int tile_off(int c) { return c < 0 ? -1 : c > 7 ? 1 : 0; }
 // where tile r keeps the rank of its neighbour k (k != 4)
@@ -105,8 +103,8 @@ __global__ __launch_bounds__(QT) void k_wgr_flag(const uint32_t *__restrict__ gc
   if (j > n_g) return;
   uint32_t in = 0u;
   if (j < n_g) {  // (the entry behind the last tile: the scan leaves the number of flags there)
-    const uint32_t key = gcoord[j];
-    const int bu = (int)(key & 0xffffu) - 32768, bv = (int)(key >> 16) - 32768;
+    int bu, bv;
+    tile_of(gcoord[j], bu, bv);
     in = !box.use || (bu >= box.lo[0] && bu <= box.hi[0] && bv >= box.lo[1] && bv <= box.hi[1]) ? 1u : 0u;
   }
   flag[j] = in;
@@ -129,8 +127,9 @@ __global__ __launch_bounds__(QT) void k_wgr_neighbours(const uint32_t *__restric
   const uint32_t i = blockIdx.x * QT + threadIdx.x;
   if (i >= n * 8u) return;
   const uint32_t r = i >> 3, q = i & 7u, k = q < 4u ? q : q + 1u;
-  const uint32_t key = coord[r];
-  const int tu = (int)(key & 0xffffu) - 32768 + (int)(k % 3u) - 1, tv = (int)(key >> 16) - 32768 + (int)(k / 3u) - 1;
+  int tu, tv;
+  tile_of(coord[r], tu, tv);
+  tu += (int)(k % 3u) - 1, tv += (int)(k / 3u) - 1;
   // (a coordinate of 32768 would alias another tile's key)
   const uint32_t found = tile_in_range(tu, tv) ? world_find(keys, vals, hmask, tile_key(tu, tv)) : NONE;
   nbr[i] = found < n ? found : NONE;
@@ -160,25 +159,8 @@ __global__ __launch_bounds__(QT) void k_wgr_classify(const uint32_t *__restrict_
 }
 
 // ---- goals and starts --------------------------------------------------------------------------------------------------
-// entry i as a world cell: the cell given, or the cell of a point by the archive's rule, floorf(p * recip) per axis.  False
-// where its brick is out of range or the point is not finite (the rule of sdm_query_world_ground: all three coordinates).
-__device__ __forceinline__ bool entry_cell(const float *__restrict__ xyz, const int32_t *__restrict__ cells, uint32_t i, float recip, int (&g)[3]) {
-  bool ok = true;
-  if (cells) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) g[a] = cells[3 * (size_t)i + a];
-    return brick_in_range(g[0] >> 3, g[1] >> 3, g[2] >> 3);
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float v = floorf(xyz[3 * (size_t)i + a] * recip);
-    const bool in = v >= -262144.f && v < 262144.f;  // (NaN fails; the cast sees values in range only)
-    g[a] = in ? (int)v : 0;
-    ok = ok && in;
-  }
-  return ok;
-}
-// ... as a column (i_u, j_v): (0, 0) where the entry is not usable
+// entry i (sdm_world.h's entry_cell: the rule of sdm_query_world_ground, all three coordinates) as a column (i_u, j_v):
+// (0, 0) where the entry is not usable
 __device__ __forceinline__ bool entry_column(const Plane &p, const float *__restrict__ xyz, const int32_t *__restrict__ cells, uint32_t i, float recip,
                                              int &iu, int &iv) {
   int g[3];
@@ -211,22 +193,6 @@ __global__ __launch_bounds__(QT) void k_wgr_seed(const float *__restrict__ xyz, 
 }
 
 // ---- a round: the list of active tiles, then their relaxation --------------------------------------------------------
-__global__ __launch_bounds__(QT) void k_wgr_list(uint32_t *__restrict__ act, uint32_t *__restrict__ list, uint32_t *__restrict__ meta, uint32_t n,
-                                                 uint32_t round) {
-  const uint32_t i = blockIdx.x * QT + threadIdx.x;
-  if (i >= (n + 31u) / 32u) return;
-  uint32_t w = act[i];
-  if (!w) return;
-  act[i] = 0u;
-  uint32_t at = atomicAdd(meta + R_CNT + (round & 1u), (uint32_t)__popc(w));  // (<= n in all: a tile has one bit)
-  while (w) {
-    const uint32_t t = i * 32u + (uint32_t)__builtin_ctz(w);
-    if (at < n && t < n) list[at] = t;  // (always: the bits beyond n are never set)
-    ++at;
-    w &= w - 1u;
-  }
-}
-
 // One wave per listed tile; lane cu | cv << 3 holds column (cu, cv).  The costs of the tile live in `cur`, one a lane; a
 // neighbour inside the tile is read across the lanes, one outside it from fix[], which only the lanes on the rim need and
 // which does not change during the sweep: a neighbour tile's cost read here may be stale by this round's lowerings, but
@@ -490,12 +456,6 @@ __global__ __launch_bounds__(QT) void k_world_ground_reach_paths(const float *__
 
 constexpr uint32_t REACH_BATCH = 8;  // rounds issued between two looks at the count
 
-uint32_t table_slots(size_t tiles) {
-  uint32_t slots = 2;
-  while (slots < 2 * tiles) slots <<= 1;
-  return slots;
-}
-
 // the buffers for `tiles` tiles (the stream is idle if there were buffers before)
 sdm_status reach_alloc(sdm_map *m, size_t tiles) {
   WorldGroundReachLayer &L = m->wgreach;
@@ -548,7 +508,8 @@ hipError_t launch_prepare(const sdm_map *m, const sdm_world_ground_reach_options
 
 hipError_t launch_round(const WorldGroundReachLayer &L, const sdm_world_ground_reach_options &o, uint32_t limit, uint32_t grid, uint32_t round,
                         hipStream_t s) {
-  LAYER_LAUNCH(k_wgr_list, ((L.n + 31u) / 32u + QT - 1) / QT, QT, s, L.act, L.list, L.meta, L.n, round);
+  hipError_t e;
+  if ((e = launch_snapshot_list(L.act, L.list, L.meta + R_CNT + (round & 1u), L.n, s)) != hipSuccess) return e;
   if (o.flags & SDM_WORLD_GROUND_REACH_FACE_CONNECTED)
     LAYER_LAUNCH(k_wgr_relax<true>, grid, RT, s, L.cost, L.trav, L.pen, L.level, L.nbr, L.list, L.act, L.meta, L.n, o.penalty, o.max_climb, limit,
                  round);
@@ -566,14 +527,6 @@ hipError_t launch_round(const WorldGroundReachLayer &L, const sdm_world_ground_r
 namespace {
 constexpr LayerName WORLD_GROUND = {"the world ground layer", "world ground layer", "sdm_world_ground_update", false};
 constexpr LayerName WORLD_GROUND_REACH = {"world ground reach", "world ground reach field", "sdm_world_ground_reach_update", false};
-
-// the checks the two goal queries share
-sdm_status goal_query_check(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n, const void *out, uint32_t flags, const char *what) {
-  if (!m) return SDM_ERR_INVALID_ARGUMENT;
-  if ((xyz != nullptr) == (cells != nullptr)) return LAYER_REFUSE(what, "exactly one of xyz and cells must be given");
-  SDM_TRY(query_check(m, xyz ? (const void *)xyz : (const void *)cells, n, out, flags, SDM_QUERY_ON_DEVICE, what));
-  return layer_check(m, what, &m->wgreach, WORLD_GROUND_REACH);
-}
 }  // namespace
 
 extern "C" {
@@ -619,11 +572,8 @@ sdm_status sdm_world_ground_reach_update(sdm_map *m, const sdm_world_ground_reac
     HIP_TRY(tmp.alloc(&rank, (size_t)n_g + 1));
     hipLaunchKernelGGL(k_wgr_flag, dim3(n_g / QT + 1), dim3(QT), 0, s, G.coord, n_g, box, flag);
     HIP_TRY(hipGetLastError());
-    exclusive_scan_u32(flag, rank, (size_t)n_g + 1, scan, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(L.h_meta, rank + n_g, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    n = std::min(L.h_meta[0], n_g);
+    SDM_TRY(snapshot_rank(m, flag, rank, n_g, scan, L.h_meta, &n));
+    n = std::min(n, n_g);
   }
   if (!L.cap || n > L.cap) SDM_TRY(reach_alloc(m, ((size_t)std::max<uint32_t>(n, 1u) + 255) & ~(size_t)255));
   L.n = n;
@@ -638,21 +588,13 @@ sdm_status sdm_world_ground_reach_update(sdm_map *m, const sdm_world_ground_reac
   // rounds of plain launches; the count of the last round issued says whether anything is still moving
   const uint32_t limit = o->max_cost ? o->max_cost : NO_COST - 1u;
   if (n) {
-    const uint64_t cap = 64ull * n + REACH_BATCH;
-    uint64_t round = 0;
-    uint32_t grid = std::min<uint32_t>((n + RT / 64 - 1) / (RT / 64), 64u);
-    for (;;) {
-      for (uint32_t k = 0; k < REACH_BATCH; ++k, ++round) HIP_TRY(launch_round(L, *o, limit, grid, (uint32_t)round, s));
-      HIP_TRY(hipMemcpyAsync(L.h_meta, L.meta, R_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      const uint32_t last = L.h_meta[R_CNT + ((round - 1) & 1u)];
-      if (last == 0u) break;  // an empty round: nothing was lowered in the one before it, nothing ever will be
-      if (round >= cap) {
-        set_error(what, __FILE__, __LINE__, "the relaxation has not come to rest after 64 x n_tiles + 8 rounds");
-        return SDM_ERR_NOT_CONVERGED;
-      }
-      grid = std::min<uint32_t>((n + RT / 64 - 1) / (RT / 64), std::max<uint32_t>((last + RT / 64 - 1) / (RT / 64), 64u));  // (a wave a tile)
-    }
+    SDM_TRY(relax_rounds(
+        m, what, REACH_BATCH, 64ull * n + REACH_BATCH, L.meta, L.h_meta, R_WORDS, L.h_meta + R_CNT,
+        "the relaxation has not come to rest after 64 x n_tiles + 8 rounds",
+        [n](uint32_t last) {  // (a wave a tile)
+          return std::min<uint32_t>((n + RT / 64 - 1) / (RT / 64), std::max<uint32_t>((last + RT / 64 - 1) / (RT / 64), 64u));
+        },
+        [&](uint32_t grid, uint32_t round) { return launch_round(L, *o, limit, grid, round, s); }));
     hipLaunchKernelGGL(k_wgr_reduce, dim3(std::min<uint32_t>(RR_GRID, (n + QT / 64 - 1) / (QT / 64))), dim3(QT), 0, s, L.cost, L.trav, n, L.meta);
     HIP_TRY(hipGetLastError());
   }
@@ -679,10 +621,7 @@ sdm_status sdm_get_world_ground_reach(sdm_map *m, int16_t *coords, uint32_t *cos
   if (take && coords) HIP_TRY(hipMemcpyAsync(keys.data(), L.coord + (size_t)first, take * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
   if (take && cost) HIP_TRY(hipMemcpyAsync(cost, L.cost + 64 * (size_t)first, 64 * take * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
   HIP_TRY(hipStreamSynchronize(m->stream));
-  for (size_t i = 0; i < keys.size(); ++i) {
-    coords[2 * i] = (int16_t)((int)(keys[i] & 0xffffu) - 32768);
-    coords[2 * i + 1] = (int16_t)((int)(keys[i] >> 16) - 32768);
-  }
+  unpack_tiles(keys, coords);
   if (info) {
     const uint32_t *h = L.h_meta;  // (the build waited for them)
     info->n_tiles = L.n;
@@ -700,7 +639,7 @@ sdm_status sdm_get_world_ground_reach(sdm_map *m, int16_t *coords, uint32_t *cos
 
 sdm_status sdm_query_world_ground_reach(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n, sdm_world_ground_reach_result *out,
                                         uint32_t flags) {
-  SDM_TRY(goal_query_check(m, xyz, cells, n, out, flags, "sdm_query_world_ground_reach"));
+  SDM_TRY(goal_query_check(m, xyz, cells, n, out, flags, "sdm_query_world_ground_reach", &sdm_map::wgreach, WORLD_GROUND_REACH));
   const WorldGroundReachLayer L = m->wgreach;
   const Plane p = plane_of(L.ground);
   const float recip = m->d.recip, voxel_size = m->d.voxel_size;
@@ -723,50 +662,22 @@ sdm_status sdm_query_world_ground_reach(sdm_map *m, const float *xyz, const int3
 sdm_status sdm_world_ground_reach_paths(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n, int32_t max_len, int32_t *cells_out,
                                         int32_t *len_out, uint32_t flags) {
   const char *what = "sdm_world_ground_reach_paths";
-  SDM_TRY(goal_query_check(m, xyz, cells, n, len_out, flags, what));
-  if (max_len < 0 || (max_len > 0 && !cells_out)) return LAYER_REFUSE(what, "max_len < 0, or no cells_out for max_len > 0");
-  if (n == 0) return SDM_OK;
-  HIP_TRY(hipSetDevice(m->device));
+  SDM_TRY(goal_query_check(m, xyz, cells, n, len_out, flags, what, &sdm_map::wgreach, WORLD_GROUND_REACH));
   const WorldGroundReachLayer L = m->wgreach;
   const Plane p = plane_of(L.ground);
   const float recip = m->d.recip;
   const bool face = (L.flags & SDM_WORLD_GROUND_REACH_FACE_CONNECTED) != 0;
-  const unsigned char *in = xyz ? reinterpret_cast<const unsigned char *>(xyz) : reinterpret_cast<const unsigned char *>(cells);
-  auto launch = [&](const void *src, uint32_t c, uint32_t len_cap, size_t stride, int32_t *rows, int32_t *lens) {
-    const float *q = xyz ? static_cast<const float *>(src) : nullptr;
-    const int32_t *w = xyz ? nullptr : static_cast<const int32_t *>(src);
-    const uint32_t *trav32 = reinterpret_cast<const uint32_t *>(L.trav), *pen32 = reinterpret_cast<const uint32_t *>(L.pen);
-    const dim3 grid((c + QT - 1) / QT), tpb(QT);
-    if (face)
-      hipLaunchKernelGGL(k_world_ground_reach_paths<true>, grid, tpb, 0, m->stream, q, w, c, recip, p, L.keys, L.vals, L.hmask, L.n, L.nbr, trav32,
-                         pen32, L.level, L.cost, L.opt.penalty, L.opt.max_climb, len_cap, stride, rows, lens);
-    else
-      hipLaunchKernelGGL(k_world_ground_reach_paths<false>, grid, tpb, 0, m->stream, q, w, c, recip, p, L.keys, L.vals, L.hmask, L.n, L.nbr, trav32,
-                         pen32, L.level, L.cost, L.opt.penalty, L.opt.max_climb, len_cap, stride, rows, lens);
-  };
-  if (flags & SDM_QUERY_ON_DEVICE)  // (run_query's chunks: a row of the caller's is max_len cells of three words)
-    return run_query(m, in, 12, len_out, 4, cells_out, (size_t)max_len * 12, n, flags, [&](const void *src, void *lens, void *rows, uint32_t c, hipStream_t) {
-      launch(src, c, (uint32_t)max_len, (size_t)max_len, static_cast<int32_t *>(rows), static_cast<int32_t *>(lens));
-    });
-  constexpr size_t CHUNK = (size_t)1 << 20;
-  // host mode: through the queries' staging area, in chunks of whole rows; a staged row holds what a path can be long (no
-  // path has more cells than the field has columns), and only the cells a path has are copied into the caller's row
-  const size_t row = std::min<size_t>((size_t)max_len, std::max<size_t>((size_t)L.n * 64, 1));
-  const size_t chunk = std::min<size_t>((size_t)n, std::max<size_t>(1, std::min(CHUNK, ((size_t)16 << 20) / std::max<size_t>(row * 12, 1))));
-  return run_staged(
-      m, (size_t)n, chunk, nullptr, 0, {{StageCol::IN, const_cast<unsigned char *>(in), 12}, {StageCol::OUT, len_out, 4}, {StageCol::OUT_RAW, nullptr, row * 12}},
-      [&](const unsigned char *, unsigned char *const *col, size_t c) -> sdm_status {
-        launch(col[0], (uint32_t)c, (uint32_t)row, row, reinterpret_cast<int32_t *>(col[2]), reinterpret_cast<int32_t *>(col[1]));
-        HIP_TRY(hipGetLastError());
-        return SDM_OK;
-      },
-      [&](const unsigned char *const *col, size_t off, size_t c) {
-        const int32_t *lens = reinterpret_cast<const int32_t *>(col[1]);
-        for (size_t i = 0; i < c; ++i) {
-          const size_t take = std::min<size_t>((size_t)lens[i], row);
-          if (take) memcpy(cells_out + (off + i) * (size_t)max_len * 3, col[2] + i * row * 12, take * 12);
-        }
-      });
+  return goal_paths(m, xyz, cells, n, max_len, cells_out, len_out, flags, what, (size_t)L.n * 64,
+                    [&](const float *q, const int32_t *w, uint32_t c, uint32_t len_cap, size_t stride, int32_t *rows, int32_t *lens) {
+                      const uint32_t *trav32 = reinterpret_cast<const uint32_t *>(L.trav), *pen32 = reinterpret_cast<const uint32_t *>(L.pen);
+                      const dim3 grid((c + QT - 1) / QT), tpb(QT);
+                      if (face)
+                        hipLaunchKernelGGL(k_world_ground_reach_paths<true>, grid, tpb, 0, m->stream, q, w, c, recip, p, L.keys, L.vals, L.hmask, L.n, L.nbr,
+                                           trav32, pen32, L.level, L.cost, L.opt.penalty, L.opt.max_climb, len_cap, stride, rows, lens);
+                      else
+                        hipLaunchKernelGGL(k_world_ground_reach_paths<false>, grid, tpb, 0, m->stream, q, w, c, recip, p, L.keys, L.vals, L.hmask, L.n, L.nbr,
+                                           trav32, pen32, L.level, L.cost, L.opt.penalty, L.opt.max_climb, len_cap, stride, rows, lens);
+                    });
 }
 
 sdm_status sdm_debug_world_ground_reach_tiles(sdm_map *m, int64_t *tiles_out) {

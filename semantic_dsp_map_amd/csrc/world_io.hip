@@ -18,7 +18,7 @@
 //   k_wio_merge       a wave per destination with a writing cell: room by rank exactly as in k_world_merge; a fresh brick
 //                 is written whole, an archived one has its written cells replaced; counts by ballot, stamps min / max over
 //                 the sources that wrote.
-//   k_world_finish    n_bricks, created_last, dropped_total.
+//   launch_world_finish   world.hip's closing kernel: n_bricks, created_last, dropped_total.
 // The atomics are the CAS, the atomicMin and counters: all commute.  Every probe loop ends after one round of its table.
 //
 // A retain flags the bricks to keep, ranks them, packs them into a transient copy, empties the table, and copies them back
@@ -358,11 +358,7 @@ hipError_t launch_world_import(const IoGeo &g, const IoLayout &at, const WorldLa
   if ((e = hipGetLastError()) != hipSuccess) return e;
   LAYER_LAUNCH(k_wio_merge, per_wave, WTPB, s, g, src_hdr, src_cells, skeys, svals, count, cand, L.keys, L.vals, need, rank, cslot, cnw, L.cells,
                L.hdr, L.meta);
-  WGeo fin{};
-  fin.nc_max = g.cap;
-  fin.max_bricks = g.max_bricks;
-  LAYER_LAUNCH(k_world_finish, 1, 64, s, fin, rank, L.meta);
-  return hipSuccess;
+  return launch_world_finish(rank + g.cap, g.max_bricks, L.meta, s);
 }
 
 }  // namespace

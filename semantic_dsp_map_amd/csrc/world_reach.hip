@@ -7,10 +7,8 @@
 // rank, per brick the ranks of the 27 bricks round it, the traversable (and obstacle) masks and the costs, and reads
 // nothing of the archive afterwards - no pool slot outlives the build.  cost[] is the fixed point of reach.hip's
 // relaxation, so it is the same whatever order the device relaxes in.
-//   k_wr_flag        a thread per archived brick in brick order: 1 if it lies in the box (or there is none).
-//   exclusive_scan_u32   ranks the flags; the entry behind the last brick ends as the number of bricks of the field.
-//   k_wr_index       a thread per archived brick: a brick of the field writes its coordinates and its pool slot (a
-//               temporary of the build) at its rank and inserts key -> rank (every key by one thread, like world_insert).
+//   snapshot_bricks, launch_snapshot_index   world_snapshot.hip's: the bricks of the box flagged and ranked, their
+//               coordinates and pool slots (a temporary of the build) at their rank, key -> rank in the field's own table.
 //   k_wr_neighbours  a thread per (brick, one of 27): one lookup, the rank or NONE; brick_in_range before every lookup.
 //   k_wr_classify    a wave per brick, a lane per (cx, cy), the eight layers' loads first: ballots write the traversable
 //               and the obstacle mask, 8 x 64 bits each, and 0xffffffff goes into the 512 costs.
@@ -19,8 +17,8 @@
 //               index for z, the neighbour ranks for the bricks.  It reads obstacle words and writes traversable ones.
 //   k_wr_seed        a thread per start: cost 0 by atomicMin - the thread that lowers it counts the start - and the
 //               activity bit of the brick and of its present neighbours.
-//   k_wr_list / k_wr_relax   a round, exactly reach.hip's: the activity bits become a list, a workgroup per listed brick
-//               loads 10^3 costs and traversable bits through the neighbour ranks (an absent brick reads not traversable,
+//   launch_snapshot_list / k_wr_relax   a round, exactly reach.hip's: the activity bits become a list (world_snapshot.hip's
+//               k_ws_list), a workgroup per listed brick loads 10^3 costs and traversable bits through the neighbour ranks (an absent brick reads not traversable,
 //               0xffffffff), relaxes in LDS until a sweep lowers nothing, stores what it lowered and wakes every face,
 //               edge and corner neighbour whose halo holds a lowered cell.  No kernel waits for another workgroup; the
 //               host issues eight rounds between two looks at the count and caps them at 512 x n_bricks.
@@ -54,11 +52,6 @@ constexpr uint32_t ALL_REACH_FLAGS =
 // listed bricks, round r's in R_CNT + (r & 1)
 enum { R_STARTS = 0, R_TRAV, R_REACHED, R_MAXCOST, R_ROUNDS, R_BRICKS, R_CNT, R_WORDS = 8 };
 
-struct BrickBox {
-  int lo[3], hi[3];
-  uint32_t use;
-};
-
 // ---- moves (reach.hip's) ---------------------------------------------------------------------------------------------
 constexpr int move_d(int n, int a) { return a == 0 ? n % 3 - 1 : a == 1 ? (n / 3) % 3 - 1 : n / 9 - 1; }
 constexpr uint32_t move_weight(int n) {
@@ -87,48 +80,12 @@ __device__ __forceinline__ uint32_t allowed_moves(uint32_t nb) {
   return al;
 }
 
-__device__ __forceinline__ void coord_of(const uint32_t *__restrict__ coord, uint32_t r, int &bx, int &by, int &bz) {
-  const uint32_t c0 = coord[2 * (size_t)r], c1 = coord[2 * (size_t)r + 1];
-  bx = (int16_t)(c0 & 0xffffu), by = (int16_t)(c0 >> 16), bz = (int16_t)(c1 & 0xffffu);
-}
 // cell (cx, cy, cz) of a brick: its cost word, and its bit in the halves of the traversable mask
 __device__ __forceinline__ uint32_t cost_at(uint32_t r, int cx, int cy, int cz) { return r * 512u + (uint32_t)(cz * 64 + cy * 8 + cx); }
 __device__ __forceinline__ uint32_t trav_word(uint32_t r, int cy, int cz) { return (r * 8u + (uint32_t)cz) * 2u + (uint32_t)(cy >> 2); }
 __device__ __forceinline__ uint32_t trav_bit(int cx, int cy) { return (uint32_t)((cy & 3) * 8 + cx); }
-// the brick offset (-1, 0, 1) of coordinate c in -1 .. 8 of the brick's own cells 0 .. 7
-__device__ __forceinline__ int brick_off(int c) { return c < 0 ? -1 : c > 7 ? 1 : 0; }
 
 // ---- the index ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(QT) void k_wr_flag(const uint32_t *__restrict__ order, const uint32_t *__restrict__ hdr, uint32_t n_arch, BrickBox box,
-                                                uint32_t *__restrict__ flag) {
-  const uint32_t j = blockIdx.x * QT + threadIdx.x;
-  if (j > n_arch) return;
-  uint32_t in = 0u;
-  if (j < n_arch) {  // (the entry behind the last brick: the scan leaves the number of flags there)
-    const uint32_t slot = order[j];
-    const uint32_t h0 = hdr[(size_t)slot * HDR_WORDS], h1 = hdr[(size_t)slot * HDR_WORDS + 1];
-    const int b[3] = {(int16_t)(h0 & 0xffffu), (int16_t)(h0 >> 16), (int16_t)(h1 & 0xffffu)};
-    in = 1u;
-    if (box.use)
-      for (int a = 0; a < 3; ++a) in = in && b[a] >= box.lo[a] && b[a] <= box.hi[a] ? 1u : 0u;
-  }
-  flag[j] = in;
-}
-
-__global__ __launch_bounds__(QT) void k_wr_index(const uint32_t *__restrict__ order, const uint32_t *__restrict__ hdr,
-                                                 const uint32_t *__restrict__ flag, const uint32_t *__restrict__ rank, uint32_t n_arch,
-                                                 uint32_t *__restrict__ coord, uint32_t *__restrict__ slot_of, u64 *__restrict__ keys,
-                                                 uint32_t *__restrict__ vals, uint32_t hmask) {
-  const uint32_t j = blockIdx.x * QT + threadIdx.x;
-  if (j >= n_arch || !flag[j]) return;
-  const uint32_t slot = order[j], r = rank[j];
-  const uint32_t h0 = hdr[(size_t)slot * HDR_WORDS], h1 = hdr[(size_t)slot * HDR_WORDS + 1] & 0xffffu;
-  coord[2 * (size_t)r] = h0;
-  coord[2 * (size_t)r + 1] = h1;
-  slot_of[r] = slot;
-  world_insert(keys, vals, hmask, brick_key((int16_t)(h0 & 0xffffu), (int16_t)(h0 >> 16), (int16_t)h1), r);
-}
-
 __global__ __launch_bounds__(QT) void k_wr_neighbours(const uint32_t *__restrict__ coord, const u64 *__restrict__ keys,
                                                       const uint32_t *__restrict__ vals, uint32_t hmask, uint32_t n, uint32_t *__restrict__ nbr) {
   const uint32_t i = blockIdx.x * QT + threadIdx.x;
@@ -210,26 +167,6 @@ __global__ __launch_bounds__(QT) void k_wr_inflate(const uint32_t *__restrict__ 
 }
 
 // ---- goals and starts --------------------------------------------------------------------------------------------------
-// entry i as a world cell: the cells given, or the cell of a point by the archive's rule, floorf(p * recip) per axis.  False
-// where its brick is out of range or the point is not finite; g is then (0, 0, 0) for a point and the entry itself for a cell.
-__device__ __forceinline__ bool entry_cell(const float *__restrict__ xyz, const int32_t *__restrict__ cells, uint32_t i, float recip, int (&g)[3]) {
-  bool ok = true;
-  if (cells) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) g[a] = cells[3 * (size_t)i + a];
-    return brick_in_range(g[0] >> 3, g[1] >> 3, g[2] >> 3);
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float v = floorf(xyz[3 * (size_t)i + a] * recip);
-    const bool in = v >= -262144.f && v < 262144.f;  // (NaN fails; the cast sees values in range only)
-    g[a] = in ? (int)v : 0;
-    ok = ok && in;
-  }
-  if (!ok) g[0] = g[1] = g[2] = 0;
-  return ok;
-}
-
 __global__ __launch_bounds__(QT) void k_wr_seed(const float *__restrict__ xyz, const int32_t *__restrict__ cells, uint32_t n_starts, float recip,
                                                 const u64 *__restrict__ keys, const uint32_t *__restrict__ vals, uint32_t hmask,
                                                 const uint32_t *__restrict__ nbr, const uint32_t *__restrict__ trav, uint32_t *__restrict__ cost,
@@ -250,20 +187,6 @@ __global__ __launch_bounds__(QT) void k_wr_seed(const float *__restrict__ xyz, c
 }
 
 // ---- a round: the list of active bricks, then their relaxation -------------------------------------------------------
-__global__ __launch_bounds__(QT) void k_wr_list(uint32_t *__restrict__ act, uint32_t *__restrict__ list, uint32_t *__restrict__ meta, uint32_t n,
-                                                uint32_t round) {
-  const uint32_t i = blockIdx.x * QT + threadIdx.x;
-  if (i >= (n + 31u) / 32u) return;
-  uint32_t w = act[i];
-  if (!w) return;
-  act[i] = 0u;
-  uint32_t at = atomicAdd(meta + R_CNT + (round & 1u), (uint32_t)__popc(w));  // (<= n in all: a brick has one bit)
-  while (w) {
-    list[at++] = i * 32u + (uint32_t)__builtin_ctz(w);
-    w &= w - 1u;
-  }
-}
-
 template <bool FACE>
 __global__ __launch_bounds__(RT) void k_wr_relax(uint32_t *__restrict__ cost, const uint32_t *__restrict__ trav, const uint32_t *__restrict__ nbr,
                                                  const uint32_t *__restrict__ list, uint32_t *__restrict__ act, uint32_t *__restrict__ meta,
@@ -512,12 +435,6 @@ __global__ __launch_bounds__(QT) void k_world_reach_paths(const float *__restric
 
 constexpr uint32_t REACH_BATCH = 8;  // rounds issued between two looks at the count
 
-uint32_t table_slots(size_t bricks) {
-  uint32_t slots = 2;
-  while (slots < 2 * bricks) slots <<= 1;
-  return slots;
-}
-
 // the buffers for `bricks` bricks (the stream is idle if there were buffers before)
 sdm_status reach_alloc(sdm_map *m, size_t bricks) {
   WorldReachLayer &L = m->wreach;
@@ -550,7 +467,7 @@ hipError_t launch_reach_prepare(const sdm_map *m, const sdm_world_reach_options 
   if ((e = hipMemsetAsync(L.meta, 0, R_WORDS * sizeof(uint32_t), s)) != hipSuccess) return e;
   if (!n) return hipSuccess;
   if ((e = hipMemsetAsync(L.act, 0, (((size_t)n + 31) / 32) * sizeof(uint32_t), s)) != hipSuccess) return e;
-  LAYER_LAUNCH(k_wr_index, (n_arch + QT - 1) / QT, QT, s, order, W.hdr, flag, rank, n_arch, L.coord, slot_of, L.keys, L.vals, L.hmask);
+  if ((e = launch_snapshot_index(m, order, flag, rank, n_arch, n, L.coord, slot_of, L.keys, L.vals, L.hmask)) != hipSuccess) return e;
   LAYER_LAUNCH(k_wr_neighbours, (n * 27u + QT - 1) / QT, QT, s, L.coord, L.keys, L.vals, L.hmask, n, L.nbr);
   LAYER_LAUNCH(k_wr_classify, (n + QT / 64 - 1) / (QT / 64), QT, s, slot_of, W.cells, n, (o.flags & SDM_WORLD_REACH_THROUGH_UNKNOWN) ? 1u : 0u,
                (o.flags & SDM_WORLD_REACH_IGNORE_MOVABLE) ? 1u : 0u, m->d.max_movable, L.trav, L.obst, L.cost);
@@ -563,7 +480,8 @@ hipError_t launch_reach_prepare(const sdm_map *m, const sdm_world_reach_options 
 }
 
 hipError_t launch_reach_round(const WorldReachLayer &L, bool face, uint32_t limit, uint32_t grid, uint32_t round, hipStream_t s) {
-  LAYER_LAUNCH(k_wr_list, ((L.n + 31u) / 32u + QT - 1) / QT, QT, s, L.act, L.list, L.meta, L.n, round);
+  hipError_t e;
+  if ((e = launch_snapshot_list(L.act, L.list, L.meta + R_CNT + (round & 1u), L.n, s)) != hipSuccess) return e;
   const uint32_t *trav = reinterpret_cast<const uint32_t *>(L.trav);
   if (face)
     LAYER_LAUNCH(k_wr_relax<true>, grid, RT, s, L.cost, trav, L.nbr, L.list, L.act, L.meta, limit, round);
@@ -579,14 +497,6 @@ hipError_t launch_reach_round(const WorldReachLayer &L, bool face, uint32_t limi
 // ---- the host side: the entry points behind include/sdm.h ---------------------------------------------------------
 namespace {
 constexpr LayerName WORLD_REACH = {"world reach", "world reach field", "sdm_world_reach_update", false};
-
-// the checks the two goal queries share
-sdm_status goal_query_check(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n, const void *out, uint32_t flags, const char *what) {
-  if (!m) return SDM_ERR_INVALID_ARGUMENT;
-  if ((xyz != nullptr) == (cells != nullptr)) return LAYER_REFUSE(what, "exactly one of xyz and cells must be given");
-  SDM_TRY(query_check(m, xyz ? (const void *)xyz : (const void *)cells, n, out, flags, SDM_QUERY_ON_DEVICE, what));
-  return layer_check(m, what, &m->wreach, WORLD_REACH);
-}
 }  // namespace
 
 extern "C" {
@@ -616,27 +526,15 @@ sdm_status sdm_world_reach_update(sdm_map *m, const sdm_world_reach_options *o, 
   if (!L.meta) SDM_TRY(alloc_tracked(m, &L.meta, R_WORDS));
   if (!L.h_meta) SDM_TRY(alloc_tracked(m, &L.h_meta, R_WORDS, true));
   // the bricks of the field: the archive's in brick order, those of the box ranked
-  uint32_t wmeta[M_WORDS];
-  SDM_TRY(world_counters(m, wmeta));
-  const uint32_t n_arch = wmeta[M_N_BRICKS];
   DevTemps tmp;
-  uint32_t *flag = nullptr, *rank = nullptr, *slot_of = nullptr;
-  const uint32_t *order = nullptr;
-  uint32_t n = 0;
-  if (n_arch) {
-    SDM_TRY(world_order(m, &order));
-    uint32_t *scan = nullptr;
-    SDM_TRY(layer_scan_scratch(m, (size_t)m->world.max_bricks + 1, &scan));
-    HIP_TRY(tmp.alloc(&flag, (size_t)n_arch + 1));
-    HIP_TRY(tmp.alloc(&rank, (size_t)n_arch + 1));
-    hipLaunchKernelGGL(k_wr_flag, dim3(n_arch / QT + 1), dim3(QT), 0, s, order, m->world.hdr, n_arch, box, flag);
-    HIP_TRY(hipGetLastError());
-    exclusive_scan_u32(flag, rank, (size_t)n_arch + 1, scan, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(L.h_meta, rank + n_arch, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    n = L.h_meta[0];
-  }
+  SnapshotBricks b;
+  SDM_TRY(snapshot_bricks(m, box, (size_t)m->world.max_bricks + 1, L.h_meta, [&](uint32_t n_arch, uint32_t **flag, uint32_t **rank) -> sdm_status {
+    HIP_TRY(tmp.alloc(flag, (size_t)n_arch + 1));
+    HIP_TRY(tmp.alloc(rank, (size_t)n_arch + 1));
+    return SDM_OK;
+  }, &b));
+  const uint32_t n = b.n;
+  uint32_t *slot_of = nullptr;
   if (!L.cap || n > L.cap) SDM_TRY(reach_alloc(m, ((size_t)std::max<uint32_t>(n, 1u) + 255) & ~(size_t)255));
   L.n = n;
   L.hmask = table_slots(n) - 1;
@@ -646,27 +544,17 @@ sdm_status sdm_world_reach_update(sdm_map *m, const sdm_world_reach_options *o, 
     HIP_TRY(hipMemcpyAsync(d_starts, start_xyz ? (const void *)start_xyz : (const void *)start_cells, (size_t)n_starts * 12, hipMemcpyHostToDevice, s));
   }
   if (n) HIP_TRY(tmp.alloc(&slot_of, n));
-  HIP_TRY(launch_reach_prepare(m, *o, order, flag, rank, slot_of, n_arch, n, start_xyz ? reinterpret_cast<const float *>(d_starts) : nullptr,
+  HIP_TRY(launch_reach_prepare(m, *o, b.order, b.flag, b.rank, slot_of, b.n_arch, n, start_xyz ? reinterpret_cast<const float *>(d_starts) : nullptr,
                                start_xyz ? nullptr : reinterpret_cast<const int32_t *>(d_starts), (uint32_t)n_starts));
   // rounds of plain launches; the count of the last round issued says whether anything is still moving
   const bool face = (o->flags & SDM_WORLD_REACH_FACE_CONNECTED) != 0;
   const uint32_t limit = o->max_cost ? o->max_cost : NO_COST - 1u;
   if (n) {
-    const uint64_t cap = 512ull * n + REACH_BATCH;
-    uint64_t round = 0;
-    uint32_t grid = std::min<uint32_t>(n, 64u);
-    for (;;) {
-      for (uint32_t k = 0; k < REACH_BATCH; ++k, ++round) HIP_TRY(launch_reach_round(L, face, limit, grid, (uint32_t)round, s));
-      HIP_TRY(hipMemcpyAsync(L.h_meta, L.meta, R_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      const uint32_t last = L.h_meta[R_CNT + ((round - 1) & 1u)];
-      if (last == 0u) break;  // an empty round: nothing was lowered in the one before it, nothing ever will be
-      if (round >= cap) {
-        set_error(what, __FILE__, __LINE__, "the relaxation has not come to rest after 512 x n_bricks rounds");
-        return SDM_ERR_NOT_CONVERGED;
-      }
-      grid = std::min<uint32_t>(n, std::max<uint32_t>(2u * last, 64u));
-    }
+    SDM_TRY(relax_rounds(
+        m, what, REACH_BATCH, 512ull * n + REACH_BATCH, L.meta, L.h_meta, R_WORDS, L.h_meta + R_CNT,
+        "the relaxation has not come to rest after 512 x n_bricks rounds",
+        [n](uint32_t last) { return std::min<uint32_t>(n, std::max<uint32_t>(2u * last, 64u)); },
+        [&](uint32_t grid, uint32_t round) { return launch_reach_round(L, face, limit, grid, round, s); }));
     hipLaunchKernelGGL(k_wr_reduce, dim3(std::min<uint32_t>(RR_GRID, (n * 8u + QT / 64 - 1) / (QT / 64))), dim3(QT), 0, s, L.cost, L.trav, n * 8u,
                        L.meta);
     HIP_TRY(hipGetLastError());
@@ -693,11 +581,7 @@ sdm_status sdm_get_world_reach(sdm_map *m, int16_t *coords, uint32_t *cost, int6
   if (take && coords) HIP_TRY(hipMemcpyAsync(pairs.data(), L.coord + 2 * (size_t)first, 2 * take * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
   if (take && cost) HIP_TRY(hipMemcpyAsync(cost, L.cost + 512 * (size_t)first, 512 * take * sizeof(uint32_t), hipMemcpyDeviceToHost, m->stream));
   HIP_TRY(hipStreamSynchronize(m->stream));
-  for (size_t i = 0; i < pairs.size() / 2; ++i) {
-    coords[3 * i] = (int16_t)(pairs[2 * i] & 0xffffu);
-    coords[3 * i + 1] = (int16_t)(pairs[2 * i] >> 16);
-    coords[3 * i + 2] = (int16_t)(pairs[2 * i + 1] & 0xffffu);
-  }
+  unpack_coords(pairs, coords);
   if (info) {
     const uint32_t *h = L.h_meta;  // (the build waited for them)
     info->n_bricks = L.n;
@@ -715,7 +599,7 @@ sdm_status sdm_get_world_reach(sdm_map *m, int16_t *coords, uint32_t *cost, int6
 }
 
 sdm_status sdm_query_world_reach(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n, sdm_world_reach_result *out, uint32_t flags) {
-  SDM_TRY(goal_query_check(m, xyz, cells, n, out, flags, "sdm_query_world_reach"));
+  SDM_TRY(goal_query_check(m, xyz, cells, n, out, flags, "sdm_query_world_reach", &sdm_map::wreach, WORLD_REACH));
   const WorldReachLayer L = m->wreach;
   const float recip = m->d.recip, voxel_size = m->d.voxel_size;
   const bool face = (L.flags & SDM_WORLD_REACH_FACE_CONNECTED) != 0, points = xyz != nullptr;
@@ -737,49 +621,21 @@ sdm_status sdm_query_world_reach(sdm_map *m, const float *xyz, const int32_t *ce
 sdm_status sdm_world_reach_paths(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n, int32_t max_len, int32_t *cells_out,
                                  int32_t *len_out, uint32_t flags) {
   const char *what = "sdm_world_reach_paths";
-  SDM_TRY(goal_query_check(m, xyz, cells, n, len_out, flags, what));
-  if (max_len < 0 || (max_len > 0 && !cells_out)) return LAYER_REFUSE(what, "max_len < 0, or no cells_out for max_len > 0");
-  if (n == 0) return SDM_OK;
-  HIP_TRY(hipSetDevice(m->device));
+  SDM_TRY(goal_query_check(m, xyz, cells, n, len_out, flags, what, &sdm_map::wreach, WORLD_REACH));
   const WorldReachLayer L = m->wreach;
   const float recip = m->d.recip;
   const bool face = (L.flags & SDM_WORLD_REACH_FACE_CONNECTED) != 0;
-  const unsigned char *in = xyz ? reinterpret_cast<const unsigned char *>(xyz) : reinterpret_cast<const unsigned char *>(cells);
-  auto launch = [&](const void *src, uint32_t c, uint32_t len_cap, size_t stride, int32_t *rows, int32_t *lens) {
-    const float *p = xyz ? static_cast<const float *>(src) : nullptr;
-    const int32_t *w = xyz ? nullptr : static_cast<const int32_t *>(src);
-    const uint32_t *trav = reinterpret_cast<const uint32_t *>(L.trav);
-    const dim3 grid((c + QT - 1) / QT), tpb(QT);
-    if (face)
-      hipLaunchKernelGGL(k_world_reach_paths<true>, grid, tpb, 0, m->stream, p, w, c, recip, L.keys, L.vals, L.hmask, L.nbr, trav, L.cost, len_cap,
-                         stride, rows, lens);
-    else
-      hipLaunchKernelGGL(k_world_reach_paths<false>, grid, tpb, 0, m->stream, p, w, c, recip, L.keys, L.vals, L.hmask, L.nbr, trav, L.cost, len_cap,
-                         stride, rows, lens);
-  };
-  if (flags & SDM_QUERY_ON_DEVICE)  // (run_query's chunks: a row of the caller's is max_len cells of three words)
-    return run_query(m, in, 12, len_out, 4, cells_out, (size_t)max_len * 12, n, flags, [&](const void *src, void *lens, void *rows, uint32_t c, hipStream_t) {
-      launch(src, c, (uint32_t)max_len, (size_t)max_len, static_cast<int32_t *>(rows), static_cast<int32_t *>(lens));
-    });
-  constexpr size_t CHUNK = (size_t)1 << 20;
-  // host mode: through the queries' staging area, in chunks of whole rows; a staged row holds what a path can be long (no
-  // path has more cells than the field), and only the cells a path has are copied into the caller's row
-  const size_t row = std::min<size_t>((size_t)max_len, std::max<size_t>((size_t)L.n * 512, 1));
-  const size_t chunk = std::min<size_t>((size_t)n, std::max<size_t>(1, std::min(CHUNK, ((size_t)16 << 20) / std::max<size_t>(row * 12, 1))));
-  return run_staged(
-      m, (size_t)n, chunk, nullptr, 0, {{StageCol::IN, const_cast<unsigned char *>(in), 12}, {StageCol::OUT, len_out, 4}, {StageCol::OUT_RAW, nullptr, row * 12}},
-      [&](const unsigned char *, unsigned char *const *col, size_t c) -> sdm_status {
-        launch(col[0], (uint32_t)c, (uint32_t)row, row, reinterpret_cast<int32_t *>(col[2]), reinterpret_cast<int32_t *>(col[1]));
-        HIP_TRY(hipGetLastError());
-        return SDM_OK;
-      },
-      [&](const unsigned char *const *col, size_t off, size_t c) {
-        const int32_t *lens = reinterpret_cast<const int32_t *>(col[1]);
-        for (size_t i = 0; i < c; ++i) {
-          const size_t take = std::min<size_t>((size_t)lens[i], row);
-          if (take) memcpy(cells_out + (off + i) * (size_t)max_len * 3, col[2] + i * row * 12, take * 12);
-        }
-      });
+  return goal_paths(m, xyz, cells, n, max_len, cells_out, len_out, flags, what, (size_t)L.n * 512,
+                    [&](const float *p, const int32_t *w, uint32_t c, uint32_t len_cap, size_t stride, int32_t *rows, int32_t *lens) {
+                      const uint32_t *trav = reinterpret_cast<const uint32_t *>(L.trav);
+                      const dim3 grid((c + QT - 1) / QT), tpb(QT);
+                      if (face)
+                        hipLaunchKernelGGL(k_world_reach_paths<true>, grid, tpb, 0, m->stream, p, w, c, recip, L.keys, L.vals, L.hmask, L.nbr, trav,
+                                           L.cost, len_cap, stride, rows, lens);
+                      else
+                        hipLaunchKernelGGL(k_world_reach_paths<false>, grid, tpb, 0, m->stream, p, w, c, recip, L.keys, L.vals, L.hmask, L.nbr, trav,
+                                           L.cost, len_cap, stride, rows, lens);
+                    });
 }
 
 sdm_status sdm_debug_world_reach_bricks(sdm_map *m, int64_t *bricks_out) {

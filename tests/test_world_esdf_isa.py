@@ -5,8 +5,7 @@ from tests.test_isa_hygiene import device_elf, hip_units, kernels_meta
 from tests.test_reach_isa import sgpr_spills
 from tests.test_world_frontiers_isa import lds_bytes
 
-WORLD_ESDF_KERNELS = ("k_we_flag", "k_we_index", "k_we_classify", "k_we_buildILi1", "k_we_buildILi2", "k_query_world_distance")
-SHARED_KERNELS = ("k_world_finish",)   # sdm_world.h's, compiled into every unit that includes it; this unit never launches it
+WORLD_ESDF_KERNELS = ("k_we_classify", "k_we_buildILi1", "k_we_buildILi2", "k_query_world_distance")
 # obstacle words, the x pass' bytes, the y pass' words, the neighbours' slots, the waves' two counts
 BUILD_LDS_BYTES = {"k_we_buildILi1": 1728 + 4608 + 6144 + 112 + 32, "k_we_buildILi2": 8000 + 12800 + 10240 + 512 + 32}
 
@@ -18,8 +17,8 @@ def test_the_unit_is_listed():
 def test_world_esdf_kernels_use_no_scratch_and_spill_nothing(tmp_path):
     elf = device_elf(tmp_path, "world_esdf")
     meta, spills, lds = kernels_meta(elf), sgpr_spills(elf), lds_bytes(elf)
-    assert len(meta) == len(WORLD_ESDF_KERNELS) + len(SHARED_KERNELS), list(meta)   # (no kernel of the frame, none of esdf.hip)
-    for k in WORLD_ESDF_KERNELS + SHARED_KERNELS:
+    assert len(meta) == len(WORLD_ESDF_KERNELS), list(meta)   # (no kernel of the frame, none of esdf.hip or world_snapshot.hip)
+    for k in WORLD_ESDF_KERNELS:
         found = [(n, v) for n, v in meta.items() if k in n]
         assert len(found) == 1, (k, list(meta))
         name, v = found[0]

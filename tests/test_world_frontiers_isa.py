@@ -9,9 +9,8 @@ import subprocess
 from tests.test_isa_hygiene import LLVM, device_elf, hip_units, kernels_meta
 from tests.test_reach_isa import sgpr_spills
 
-WORLD_FRONTIERS_KERNELS = ("k_wf_flagE", "k_wf_index", "k_wf_classify", "k_wf_neighbours", "k_wf_mask", "k_wf_compact", "k_wf_label_localILb0",
+WORLD_FRONTIERS_KERNELS = ("k_wf_index", "k_wf_classify", "k_wf_neighbours", "k_wf_mask", "k_wf_compact", "k_wf_label_localILb0",
                            "k_wf_label_localILb1", "k_wf_seamsILb0", "k_wf_seamsILb1", "k_wf_accumulate", "k_wf_flags", "k_wf_table")
-SHARED_KERNELS = ("k_world_finish",)   # sdm_world.h's, compiled into every unit that includes it; this unit never launches it
 LOCAL_LABEL_LDS_BYTES = 0              # eight labels a lane in registers, neighbours by lane shuffles
 
 
@@ -34,8 +33,8 @@ def test_the_unit_is_listed():
 def test_world_frontiers_kernels_use_no_scratch_and_spill_nothing(tmp_path):
     elf = device_elf(tmp_path, "world_frontiers")
     meta, spills, lds = kernels_meta(elf), sgpr_spills(elf), lds_bytes(elf)
-    assert len(meta) == len(WORLD_FRONTIERS_KERNELS) + len(SHARED_KERNELS), list(meta)   # (no kernel of the frame, none of frontiers.hip)
-    for k in WORLD_FRONTIERS_KERNELS + SHARED_KERNELS:
+    assert len(meta) == len(WORLD_FRONTIERS_KERNELS), list(meta)   # (no kernel of the frame, none of frontiers.hip or world_snapshot.hip)
+    for k in WORLD_FRONTIERS_KERNELS:
         found = [(n, v) for n, v in meta.items() if k in n]
         assert len(found) == 1, (k, list(meta))
         name, v = found[0]

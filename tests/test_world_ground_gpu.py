@@ -142,6 +142,36 @@ def test_queries_and_footprints_in_host_and_device_mode():
     g.close()
 
 
+# ---- entries that stand for no world cell: nothing of such an entry reaches its result, whatever its other coordinates are
+def unusable_entries(size):
+    """points with a NaN, an infinity and a coordinate just outside +-262144 cells beside coordinates that are fine, and
+    cells whose brick is out of the int16 range beside coordinates that are fine"""
+    size = np.float32(size)
+    edge = np.float32(262144.5) * size
+    recip = np.float32(1) / size
+    assert np.floor(edge * recip) == 262144 and np.floor(-edge * recip) == -262145    # (float32, like the library's rule)
+    fine = (np.array([3.5, 2.5, 1.5], np.float32) * size).tolist()
+    pts = np.array([(np.nan, fine[1], fine[2]), (fine[0], np.inf, fine[2]), (fine[0], fine[1], -np.inf), (edge, fine[1], fine[2]),
+                    (fine[0], -edge, fine[2]), (fine[0], fine[1], edge)], np.float32)
+    cells = np.array([(262144, 2, 1), (3, -262145, 1), (3, 2, 1 << 30), (-(1 << 31), 2, 1), (3, 2, 262144)], np.int32)
+    return pts, cells
+
+
+def test_entries_that_stand_for_no_world_cell():
+    c = gc.corner_case()
+    g = world_of(c)
+    ref = check_build(g, **c["kw"])
+    pts, cells = unusable_entries(SIZE)
+    assert ref.query([(3, 2, 1)], SIZE)["status"][0] == 0      # (the coordinates that are fine name a column of the layer)
+    none = ref.query([(1 << 30, 0, 0)], SIZE)
+    assert none["status"][0] == 3
+    want_c, want_p = ref.query(cells, SIZE), np.repeat(none, len(pts))
+    assert want_c.tobytes() == np.repeat(none, len(cells)).tobytes()
+    assert g.query_world_ground(cells=cells).tobytes() == want_c.tobytes()
+    assert g.query_world_ground(xyz=pts).tobytes() == want_p.tobytes()
+    g.close()
+
+
 def test_a_footprint_over_an_absent_tile():
     c = gc.corner_case(skip=[(-1, 0)])
     g = world_of(c)

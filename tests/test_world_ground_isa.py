@@ -7,7 +7,6 @@ from tests.test_world_frontiers_isa import lds_bytes
 
 WORLD_GROUND_KERNELS = ("k_wg_claim", "k_wg_keys", "k_wg_tiles", "k_wg_columnsILi0", "k_wg_columnsILi1", "k_wg_columnsILi2", "k_wg_cost",
                         "k_wg_distILi1", "k_wg_distILi2", "k_query_world_ground", "k_query_world_footprints")
-SHARED_KERNELS = ("k_world_finish",)   # sdm_world.h's, compiled into every unit that includes it; this unit never launches it
 # the lethal words of the (2 H + 1)^2 tiles, eight bytes per row of the halo
 DIST_LDS_BYTES = {"k_wg_distILi1": 72 + 192, "k_wg_distILi2": 200 + 320}
 
@@ -19,8 +18,8 @@ def test_the_unit_is_listed():
 def test_world_ground_kernels_use_no_scratch_and_spill_nothing(tmp_path):
     elf = device_elf(tmp_path, "world_ground")
     meta, spills, lds = kernels_meta(elf), sgpr_spills(elf), lds_bytes(elf)
-    assert len(meta) == len(WORLD_GROUND_KERNELS) + len(SHARED_KERNELS), list(meta)   # exactly the expected kernel set
-    for k in WORLD_GROUND_KERNELS + SHARED_KERNELS:
+    assert len(meta) == len(WORLD_GROUND_KERNELS), list(meta)   # exactly the expected kernel set
+    for k in WORLD_GROUND_KERNELS:
         found = [(n, v) for n, v in meta.items() if k in n]
         assert len(found) == 1, (k, list(meta))
         name, v = found[0]

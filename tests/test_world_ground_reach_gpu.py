@@ -15,6 +15,7 @@ from tests import test_world_gpu as twg
 from tests import world_ground_reach_cases as rc
 from tests import world_ground_reach_ref as ref
 from tests.test_ground_gpu import _cells
+from tests.test_world_ground_gpu import unusable_entries
 
 pytestmark = pytest.mark.gpu
 
@@ -170,6 +171,30 @@ def test_queries_and_paths_in_host_and_device_mode():
     assert L.sdm_query_world_ground_reach(h, None, vp(goals), 0, vp(out), 0) == 0 and (out == CAN).all()
     assert L.sdm_world_ground_reach_paths(h, None, vp(goals), 0, 5, vp(out), vp(lens), 0) == 0 and (out == CAN).all() and (lens == 0x5A5A5A5A).all()
     assert L.sdm_world_ground_reach_paths(h, vp(pts), None, 2, 0, None, vp(lens), 0) == 0 and (lens[2:] == 0x5A5A5A5A).all()
+    g.close()
+
+
+# ---- entries that stand for no world cell: as starts they count for nothing, as goals nothing of them reaches the result
+def test_entries_that_stand_for_no_world_cell():
+    c = CASES["penalty 5"]
+    g = world_of(c)
+    g.world_ground_update(**c["gkw"])
+    pts, cells = unusable_entries(SIZE)
+    starts = np.asarray(c["starts"], np.int32).reshape(-1, 3)
+    m = check_build(g, np.concatenate([starts, cells]), **c["kw"])      # (by cells)
+    assert m.info["n_starts_used"] == len(set(map(tuple, starts.tolist()))) > 0
+    g.world_ground_reach_update(starts=np.concatenate([centres(starts), pts]), **c["kw"])
+    diff = ref.difference(g.world_ground_reach(), ref.answer(m))
+    assert diff is None, diff
+    none = m.query([(1 << 30, 0, 0)], SIZE)
+    assert none["status"][0] == 3
+    want_c, want_p = m.query(cells, SIZE), np.repeat(none, len(pts))
+    assert want_c.tobytes() == np.repeat(none, len(cells)).tobytes()
+    assert g.query_world_ground_reach(cells=cells).tobytes() == want_c.tobytes()
+    assert g.query_world_ground_reach(xyz=pts).tobytes() == want_p.tobytes()
+    for kw, src in (("cells", cells), ("xyz", pts)):
+        rows, lens = g.world_ground_reach_paths(**{kw: src}, max_len=4)
+        assert not lens.any() and (rows == FILL).all()
     g.close()
 
 

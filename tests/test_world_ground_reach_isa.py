@@ -6,10 +6,9 @@ from tests.test_isa_hygiene import device_elf, hip_units, kernels_meta
 from tests.test_reach_isa import sgpr_spills
 from tests.test_world_frontiers_isa import lds_bytes
 
-WORLD_GROUND_REACH_KERNELS = ("k_wgr_flag", "k_wgr_index", "k_wgr_neighbours", "k_wgr_classify", "k_wgr_seed", "k_wgr_list", "k_wgr_relaxILb0",
+WORLD_GROUND_REACH_KERNELS = ("k_wgr_flag", "k_wgr_index", "k_wgr_neighbours", "k_wgr_classify", "k_wgr_seed", "k_wgr_relaxILb0",
                               "k_wgr_relaxILb1", "k_wgr_reduce", "k_query_world_ground_reachILb0", "k_query_world_ground_reachILb1",
                               "k_world_ground_reach_pathsILb0", "k_world_ground_reach_pathsILb1")
-SHARED_KERNELS = ("k_world_finish",)   # sdm_world.h's, compiled into every unit that includes it; this unit never launches it
 RELAX_LDS_BYTES = {"k_wgr_relaxILb0": 0, "k_wgr_relaxILb1": 0}
 
 
@@ -20,8 +19,8 @@ def test_the_unit_is_listed():
 def test_world_ground_reach_kernels_use_no_scratch_and_spill_nothing(tmp_path):
     elf = device_elf(tmp_path, "world_ground_reach")
     meta, spills, lds = kernels_meta(elf), sgpr_spills(elf), lds_bytes(elf)
-    assert len(meta) == len(WORLD_GROUND_REACH_KERNELS) + len(SHARED_KERNELS), list(meta)   # exactly the expected kernel set
-    for k in WORLD_GROUND_REACH_KERNELS + SHARED_KERNELS:
+    assert len(meta) == len(WORLD_GROUND_REACH_KERNELS), list(meta)   # exactly the expected kernel set
+    for k in WORLD_GROUND_REACH_KERNELS:
         found = [(n, v) for n, v in meta.items() if k in n]
         assert len(found) == 1, (k, list(meta))
         name, v = found[0]

@@ -9,7 +9,6 @@ from tests.test_world_frontiers_isa import lds_bytes
 
 # what the build reports: three waves per SIMD, 168 registers at most
 VGPR_CEILING = {"k_world_segments": 157, "k_world_view_rays": 168}
-SHARED_KERNELS = ("k_world_finish",)   # sdm_world.h's, compiled into every unit that includes it; this unit never launches it
 
 
 def test_the_unit_is_listed():
@@ -19,8 +18,8 @@ def test_the_unit_is_listed():
 def test_world_rays_kernels_use_no_scratch_and_spill_nothing(tmp_path):
     elf = device_elf(tmp_path, "world_rays")
     meta, spills, lds = kernels_meta(elf), sgpr_spills(elf), lds_bytes(elf)
-    assert len(meta) == len(VGPR_CEILING) + len(SHARED_KERNELS), list(meta)   # (no kernel of the frame, none of another layer)
-    for k in tuple(VGPR_CEILING) + SHARED_KERNELS:
+    assert len(meta) == len(VGPR_CEILING), list(meta)   # (no kernel of the frame, none of another layer)
+    for k in VGPR_CEILING:
         found = [(n, v) for n, v in meta.items() if k in n]
         assert len(found) == 1, (k, list(meta))
         name, v = found[0]

@@ -5,11 +5,10 @@ scratch; the ceiling is what a build with csrc/Makefile's flags gives).  Reads t
 from tests.test_isa_hygiene import device_elf, hip_units, kernels_meta
 from tests.test_reach_isa import sgpr_spills
 
-WORLD_REACH_KERNELS = ("k_wr_flag", "k_wr_index", "k_wr_neighbours", "k_wr_classify", "k_wr_inflateILi1", "k_wr_inflateILi2", "k_wr_seed",
-                       "k_wr_list", "k_wr_relaxILb0", "k_wr_relaxILb1", "k_wr_reduce", "k_query_world_reachILb0", "k_query_world_reachILb1",
+WORLD_REACH_KERNELS = ("k_wr_neighbours", "k_wr_classify", "k_wr_inflateILi1", "k_wr_inflateILi2", "k_wr_seed",
+                       "k_wr_relaxILb0", "k_wr_relaxILb1", "k_wr_reduce", "k_query_world_reachILb0", "k_query_world_reachILb1",
                        "k_world_reach_pathsILb0", "k_world_reach_pathsILb1")
 SGPR_SPILL_CEILING = {"k_world_reach_pathsILb0": 6}   # every other kernel: 0
-SHARED_KERNELS = ("k_world_finish",)   # sdm_world.h's, compiled into every unit that includes it; this unit never launches it
 
 
 def test_the_unit_is_listed():
@@ -19,8 +18,8 @@ def test_the_unit_is_listed():
 def test_world_reach_kernels_use_no_scratch_and_spill_nothing(tmp_path):
     elf = device_elf(tmp_path, "world_reach")
     meta, spills = kernels_meta(elf), sgpr_spills(elf)
-    assert len(meta) == len(WORLD_REACH_KERNELS) + len(SHARED_KERNELS), list(meta)   # (no kernel of the frame)
-    for k in WORLD_REACH_KERNELS + SHARED_KERNELS:
+    assert len(meta) == len(WORLD_REACH_KERNELS), list(meta)   # (no kernel of the frame, none of world_snapshot.hip)
+    for k in WORLD_REACH_KERNELS:
         found = [(n, v) for n, v in meta.items() if k in n]
         assert len(found) == 1, (k, list(meta))
         name, v = found[0]
