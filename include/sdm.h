@@ -1715,6 +1715,106 @@ sdm_status sdm_query_world_segments(sdm_map *m, const float *ab, int64_t n, sdm_
 sdm_status sdm_query_world_views(sdm_map *m, const sdm_view *views, int64_t n_views, const float *dirs, int32_t n_rays,
                                  int32_t reach_cells, sdm_view_gain *out, sdm_world_segment_hit *rays_out, uint32_t flags);
 
+/* ---- world mesh: what does everything the map remembers look like - to a person, a simulator, a renderer? ----
+ * sdm_world_mesh_update builds, on the map's stream, the face mesh of sdm_mesh_update over the bricks of the world archive
+ * instead of the map block: one unit quad per face between a solid cell and a neighbour that is not solid, and the world
+ * lattice corners those faces use as welded vertices.  IT WAITS THREE TIMES: for the archive's counters, for the number of
+ * bricks of the field, and for the numbers of faces, vertex bricks and vertices together, and sizes its buffers from them;
+ * the lists themselves are enqueued and the getters wait for them.  Cells are world cells (int32 per axis, brick =
+ * cell >> 3), the archive's origin is the world's.  Everything is integer and bitwise reproducible.  The archive is what
+ * the layer reads: a mesh that mixes the live block and the archive does not exist - call sdm_world_update first.
+ * Field: the archived bricks at the time of the build; with SDM_WORLD_MESH_BOX those inside the inclusive brick box
+ * bmin .. bmax (bmax < bmin on an axis: no brick, which is no error).  Bricks are ranked in brick order - ascending in
+ * (bz, by, bx), signed: without a box rank r is row r of sdm_get_world_bricks taken at the same moment, as in
+ * sdm_get_world_esdf.
+ * Solid cell: a cell of a field brick whose archived word (track, label, occ) has occ >= 1 (occ == 1 with
+ * SDM_WORLD_MESH_OBSERVED_ONLY), bit `label` of `labels` set (bit l of word l / 32), track == options.track unless that
+ * is -1, and a track the static / movable flag admits (movable: 1 <= track <= max_movable_track) - sdm_mesh_update's rule.
+ * Face: a solid cell of the field and a direction whose face neighbour is not solid by the same rule.  The neighbour's word
+ * is read from the WHOLE ARCHIVE, not from the field, so the meshes of disjoint boxes tile: no face stands between two
+ * solid cells on either side of a box wall.  kind: what is behind the face - 0 a free cell (occ == 0), 1 a cell with
+ * occ == -1 in an archived brick, 2 a cell in no archived brick (a brick beyond the int16 range is absent), 3 a cell with
+ * occ >= 1 that is not solid under these options.  SDM_WORLD_MESH_SKIP_UNKNOWN_FACES and SDM_WORLD_MESH_SKIP_ABSENT_FACES
+ * leave kinds 1 and 2 out.  Faces ascend in (brick rank, cell word cx | cy << 3 | cz << 6, dir).
+ * dir, the corners q0..q3 of a face as offsets from its cell, the winding and the triangles are sdm_mesh_update's table:
+ * (q1 - q0) x (q3 - q0) is the outward unit normal and q0 is the quad's smallest corner in (z, y, x).
+ * Vertices: the world lattice corners used by at least one emitted face, each once, welded across brick seams.  Corner
+ * (gx, gy, gz), an int32 triple, is the min corner of world cell (gx, gy, gz).  Its owner brick is corner >> 3 per axis, its
+ * local word (gx & 7) | (gy & 7) << 3 | (gz & 7) << 6; the list ascends in (owner brick in brick order, local word).  The
+ * owner brick need be neither in the field nor in the archive - the +x face of a cell with cx == 7 uses corners of brick
+ * bx + 1 - and may be 32768 on an axis.  quads[4f .. 4f+3] index the vertex list.
+ * xyz[3v + a] = (float)corner_a * voxel_size, one float32 multiply: the archive's rule for a cell's min corner.
+ * The build is a SNAPSHOT: the getters return the same bytes after any later sdm_world_update, sdm_world_import,
+ * sdm_world_retain or sdm_world_clear, until the next sdm_world_mesh_update.  It holds lists, no pool slot, once it returns.
+ * Nothing of the archive or of the map's state is modified.
+ * max_faces / max_vertices > 0 cap the two lists: with more faces or more vertices than that the build writes no list and
+ * returns SDM_ERR_CAPACITY; sdm_get_world_mesh_info then still gives the true counts (faces_by_dir and faces_by_kind
+ * included: they count the faces of the build, listed or not), the two list getters still set *n_out to the true count,
+ * and they and sdm_world_mesh_device return SDM_ERR_CAPACITY until a build with room.  0: no cap.
+ * sdm_get_world_mesh_faces: rows first .. first + cap - 1 of the face list into faces and quads (4 per face); *n_out = the
+ * faces in all.  coords takes the field bricks' (bx, by, bz), three int16 for each of the info's n_bricks bricks - row r for
+ * brick rank r, which is what sdm_world_mesh_face.brick indexes - and is written whole by a call with first == 0, whatever
+ * cap is, and not at all by a call with first > 0: cap counts faces only.  sdm_get_world_mesh_vertices: rows first ..
+ * first + cap - 1 of the vertex list into corners (three int32) and xyz (three floats); *n_out = the vertices in all.  Every
+ * array may be NULL.  Both wait.
+ * sdm_world_mesh_device: device pointers to the three lists of the last build, for a renderer: valid until the next
+ * sdm_world_mesh_update or sdm_destroy, to be read in stream order on sdm_stream (the counts: sdm_get_world_mesh_info).
+ * Each may be NULL.
+ * Memory, allocated at the first build, grown by a build that needs more, freed by sdm_destroy:
+ *   SDM_WORLD_MESH_BYTES_PER_ARCHIVED_BRICK x (archived bricks + 1, in steps of 256)
+ * + (SDM_WORLD_MESH_BYTES_PER_BRICK + 5.5) x (bricks of the field, in steps of 256; 5.5: 44 bytes of counts per 8 bricks)
+ * + (SDM_WORLD_MESH_BYTES_PER_VERTEX_SLOT + 1 / 16) x (the power of two >= 16 x that number: a brick's corners have at most
+ *   eight owner bricks and the table of them is at most half full; 1 / 16: a count per 64 slots)
+ * + SDM_WORLD_MESH_BYTES_PER_VERTEX_BRICK x (vertex bricks, in steps of 256)
+ * + SDM_WORLD_MESH_BYTES_PER_FACE x (faces, in steps of 4096) + SDM_WORLD_MESH_BYTES_PER_VERTEX x (vertices, in steps of
+ *   4096) + 264 (the counters and their landing area).
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map, options, info or n_out, unknown flag bits, both
+ * SDM_WORLD_MESH_STATIC_ONLY and SDM_WORLD_MESH_MOVABLE_ONLY, track < -1 or > 65535, a negative max_faces, max_vertices,
+ * first or cap, a Z-slab shard (shard_count > 1), a build before the archive has had an update or import, and a getter or
+ * sdm_world_mesh_device before any build. */
+#define SDM_WORLD_MESH_STATIC_ONLY         0x01u  /* a cell whose winning track is movable is not solid */
+#define SDM_WORLD_MESH_MOVABLE_ONLY        0x02u  /* only such cells are solid (both bits: SDM_ERR_INVALID_ARGUMENT) */
+#define SDM_WORLD_MESH_OBSERVED_ONLY       0x04u  /* occ == 2 (guessed occupied) is not solid */
+#define SDM_WORLD_MESH_SKIP_UNKNOWN_FACES  0x08u  /* faces of kind 1 are left out */
+#define SDM_WORLD_MESH_SKIP_ABSENT_FACES   0x10u  /* faces of kind 2 are left out: the mesh is open where the archive ends */
+#define SDM_WORLD_MESH_BOX                 0x20u  /* the field is the bricks inside bmin .. bmax (inclusive brick box) */
+#define SDM_WORLD_MESH_BYTES_PER_ARCHIVED_BRICK 200  /* box flag, rank, the solid, unknown and occupied words */
+#define SDM_WORLD_MESH_BYTES_PER_BRICK 132   /* coordinates, pool slot, six neighbours, eight owners twice, the slices' prefix */
+#define SDM_WORLD_MESH_BYTES_PER_VERTEX_SLOT 80   /* key, rank, place in the list, the 512 corner bits */
+#define SDM_WORLD_MESH_BYTES_PER_VERTEX_BRICK 48  /* the sort's four words, the eight levels' prefix */
+#define SDM_WORLD_MESH_BYTES_PER_FACE 28     /* 12 B record, 16 B vertex ids */
+#define SDM_WORLD_MESH_BYTES_PER_VERTEX 12   /* the corner */
+typedef struct {          /* 80 bytes, every field naturally aligned */
+  uint32_t flags;
+  int32_t  track;         /* -1: any; 0..65535: only cells whose winning track is this one */
+  uint32_t labels[8];     /* bit l of the 256 (binding.label_mask): cells of label l may be solid */
+  int32_t  bmin[3], bmax[3];  /* inclusive brick box, read only with SDM_WORLD_MESH_BOX */
+  int64_t  max_faces;     /* 0: no cap */
+  int64_t  max_vertices;  /* 0: no cap */
+} sdm_world_mesh_options;
+typedef struct {          /* 12 bytes */
+  uint32_t brick;         /* rank of the cell's brick in the field: row of the faces getter's coords */
+  uint16_t cell;          /* cx | cy << 3 | cz << 6 */
+  uint8_t  dir;           /* 0 -x, 1 +x, 2 -y, 3 +y, 4 -z, 5 +z: the outward normal */
+  uint8_t  kind;          /* behind the face: 0 free, 1 unknown, 2 no archived brick, 3 occ >= 1 but not solid */
+  uint16_t track; uint8_t label; int8_t occ;   /* the solid cell's archived word */
+} sdm_world_mesh_face;
+typedef struct {          /* 200 bytes, every field naturally aligned */
+  uint32_t n_bricks;        /* bricks of the field */
+  uint32_t n_vertex_bricks; /* bricks that own at least one vertex */
+  int64_t  n_faces, n_vertices, n_solid;       /* true counts, also when over a cap; n_solid: solid cells of the field */
+  int64_t  faces_by_dir[6], faces_by_kind[4];  /* of the faces of the build */
+  uint32_t stamp;           /* the archive's stamp at the build: sdm_world_info.stamp */
+  uint32_t pad;             /* 0 */
+  sdm_world_mesh_options options;              /* echoed as given */
+} sdm_world_mesh_info;
+sdm_status sdm_world_mesh_update(sdm_map *m, const sdm_world_mesh_options *o);
+sdm_status sdm_get_world_mesh_info(sdm_map *m, sdm_world_mesh_info *info);
+sdm_status sdm_get_world_mesh_faces(sdm_map *m, int16_t *coords, sdm_world_mesh_face *faces, uint32_t *quads,
+                                    int64_t first, int64_t cap, int64_t *n_out);
+sdm_status sdm_get_world_mesh_vertices(sdm_map *m, int32_t *corners, float *xyz, int64_t first, int64_t cap, int64_t *n_out);
+sdm_status sdm_world_mesh_device(sdm_map *m, const sdm_world_mesh_face **faces, const uint32_t **quads, const int32_t **corners);
+
 /* ---- owner sets of the object layer: ObjectParticleHashMap (object_layer.h:20-52) */
 sdm_status sdm_object_particle_count(sdm_map *m, int32_t track_id, int64_t *count);
 /* The keys of ObjectParticleHashMap::indices_map whose sets are not empty: every track id that owns at least one slot of

@@ -664,6 +664,47 @@ class SemanticDSPMap {
     if (info) *info = mi;
     return 2 * (size_t)mi.n_faces;
   }
+  /// What does everything the map remembers look like (sdm.h, "world mesh")?  mesh() over the bricks of the world archive:
+  /// builds the face mesh of the archive under `options` (the solid rule, the skip flags, the brick box; caps 0: none) and
+  /// copies it out: xyz holds three floats per vertex in the global frame, triangles three vertex indices per triangle, two
+  /// triangles per face in the faces' order ((q0, q1, q2) and (q0, q2, q3), counter-clockwise seen from outside).  faces
+  /// (may be null): per face its brick's rank, cell, direction, what lies behind it and the cell's track, label and occ,
+  /// for colouring; coords (may be null): (bx, by, bz) per brick of the field, which a face's `brick` indexes.  info (may
+  /// be null): the counts and the options echoed.  The archive is what is read: call worldUpdate() first.  The call waits.
+  /// Returns the number of triangles; 0 (and empty vectors) before the first worldUpdate() or worldImport(), over a cap, or
+  /// when a call fails.
+  size_t worldMesh(const sdm_world_mesh_options &options, std::vector<float> &xyz, std::vector<uint32_t> &triangles,
+                   std::vector<sdm_world_mesh_face> *faces = nullptr, std::vector<int16_t> *coords = nullptr, sdm_world_mesh_info *info = nullptr) {
+    xyz.clear();
+    triangles.clear();
+    if (faces) faces->clear();
+    if (coords) coords->clear();
+    if (!map_) return 0;
+    sdm_world_mesh_info mi;
+    if (!check(sdm_world_mesh_update(map_, &options), "sdm_world_mesh_update")) return 0;
+    if (!check(sdm_get_world_mesh_info(map_, &mi), "sdm_get_world_mesh_info")) return 0;
+    std::vector<uint32_t> quads(4 * (size_t)mi.n_faces);
+    if (faces) faces->resize((size_t)mi.n_faces);
+    if (coords) coords->resize(3 * (size_t)mi.n_bricks);
+    xyz.resize(3 * (size_t)mi.n_vertices);
+    int64_t n = 0;
+    if (!check(sdm_get_world_mesh_faces(map_, coords ? coords->data() : nullptr, faces ? faces->data() : nullptr, quads.data(), 0, mi.n_faces, &n),
+               "sdm_get_world_mesh_faces") ||
+        !check(sdm_get_world_mesh_vertices(map_, nullptr, xyz.data(), 0, mi.n_vertices, &n), "sdm_get_world_mesh_vertices")) {
+      xyz.clear();
+      if (faces) faces->clear();
+      if (coords) coords->clear();
+      return 0;
+    }
+    triangles.resize(6 * (size_t)mi.n_faces);
+    for (size_t f = 0; f < (size_t)mi.n_faces; ++f) {
+      const uint32_t *q = &quads[4 * f];
+      uint32_t *t = &triangles[6 * f];
+      t[0] = q[0], t[1] = q[1], t[2] = q[2], t[3] = q[0], t[4] = q[2], t[5] = q[3];
+    }
+    if (info) *info = mi;
+    return 2 * (size_t)mi.n_faces;
+  }
   /// What did the map know about a place the block has left (sdm.h, "world archive")?  worldUpdate merges the results of
   /// the last update() into the world-fixed archive (flags: SDM_WORLD_STATIC_ONLY, SDM_WORLD_OBSERVED_ONLY; the
   /// library's default capacity); it does not wait.  Call it after every update() whose results are to be remembered.

@@ -205,6 +205,28 @@ WORLD_RAYS_IGNORE_MOVABLE = 0x10
 WORLD_SEGMENT_MAX_CELLS = 8192
 WORLD_VIEW_MAX_REACH = 255
 
+# the world mesh (sdm.h: sdm_world_mesh_update / sdm_get_world_mesh_info / sdm_get_world_mesh_faces / sdm_get_world_mesh_vertices /
+# sdm_world_mesh_device)
+WORLD_MESH_OPTIONS = np.dtype([("flags", "<u4"), ("track", "<i4"), ("labels", "<u4", (8,)), ("bmin", "<i4", (3,)), ("bmax", "<i4", (3,)),
+                               ("max_faces", "<i8"), ("max_vertices", "<i8")])
+WORLD_MESH_FACE = np.dtype([("brick", "<u4"), ("cell", "<u2"), ("dir", "u1"), ("kind", "u1"), ("track", "<u2"), ("label", "u1"), ("occ", "i1")])
+WORLD_MESH_INFO = np.dtype([("n_bricks", "<u4"), ("n_vertex_bricks", "<u4"), ("n_faces", "<i8"), ("n_vertices", "<i8"), ("n_solid", "<i8"),
+                            ("faces_by_dir", "<i8", (6,)), ("faces_by_kind", "<i8", (4,)), ("stamp", "<u4"), ("pad", "<u4"),
+                            ("options", WORLD_MESH_OPTIONS)])
+assert WORLD_MESH_OPTIONS.itemsize == 80 and WORLD_MESH_FACE.itemsize == 12 and WORLD_MESH_INFO.itemsize == 200
+WORLD_MESH_STATIC_ONLY = 0x01
+WORLD_MESH_MOVABLE_ONLY = 0x02
+WORLD_MESH_OBSERVED_ONLY = 0x04
+WORLD_MESH_SKIP_UNKNOWN_FACES = 0x08
+WORLD_MESH_SKIP_ABSENT_FACES = 0x10
+WORLD_MESH_BOX = 0x20
+WORLD_MESH_BYTES_PER_ARCHIVED_BRICK = 200
+WORLD_MESH_BYTES_PER_BRICK = 132
+WORLD_MESH_BYTES_PER_VERTEX_SLOT = 80
+WORLD_MESH_BYTES_PER_VERTEX_BRICK = 48
+WORLD_MESH_BYTES_PER_FACE = 28
+WORLD_MESH_BYTES_PER_VERTEX = 12
+
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
                 ("forget", np.uint8), ("owner", np.uint16)]
@@ -462,6 +484,11 @@ def load_library():
         "sdm_debug_world_ground_reach_tiles": [vp, C.POINTER(i64)],
         "sdm_query_world_segments": [vp, vp, i64, vp, u32],
         "sdm_query_world_views": [vp, vp, i64, vp, i32, i32, vp, vp, u32],
+        "sdm_world_mesh_update": [vp, vp],
+        "sdm_get_world_mesh_info": [vp, vp],
+        "sdm_get_world_mesh_faces": [vp, vp, vp, vp, i64, i64, C.POINTER(i64)],
+        "sdm_get_world_mesh_vertices": [vp, vp, vp, i64, i64, C.POINTER(i64)],
+        "sdm_world_mesh_device": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)],
         "sdm_debug_world_view_batch": [vp, i32],
         "sdm_forecast_stamps": [C.c_float, vp, i32, vp, i32, u32, vp, i64, C.POINTER(i64)],
         "sdm_forecast_update": [vp, vp, i32, vp, i32, u32],
@@ -1526,6 +1553,59 @@ class SdmMap:
         """Test hook: query_world_views keeps at most this many views in flight (<= 0: the library's choice)
         (sdm_debug_world_view_batch)."""
         _check(self.L, self.L.sdm_debug_world_view_batch(self.h, int(max_views_in_flight)), "sdm_debug_world_view_batch")
+
+    # ---- the world mesh (sdm.h).  world_mesh_update builds the faces and welded vertices of the archive's surface and WAITS
+    # for the counts that size its lists; world_mesh() and world_mesh_device() answer for that build - a snapshot - until the
+    # next one, whatever happens to the archive in between.
+    def world_mesh_update(self, labels=None, track=-1, static_only=False, movable_only=False, observed_only=False, skip_unknown_faces=False,
+                          skip_absent_faces=False, box=None, max_faces=0, max_vertices=0):
+        """labels: the label ids whose cells may be solid (None: all 256); track: -1 any, else that track's cells only; box:
+        (bmin, bmax), the inclusive brick box of the field (None: every archived brick); max_faces / max_vertices: caps of the
+        two lists (0: none) - a build over one raises SdmError (SDM_ERR_CAPACITY), world_mesh_info() has the true counts"""
+        o = np.zeros(1, WORLD_MESH_OPTIONS)
+        o["labels"] = np.full(8, 0xFFFFFFFF, np.uint32) if labels is None else label_mask(labels)
+        o["track"], o["max_faces"], o["max_vertices"] = track, max_faces, max_vertices
+        o["flags"] = ((WORLD_MESH_STATIC_ONLY if static_only else 0) | (WORLD_MESH_MOVABLE_ONLY if movable_only else 0) |
+                      (WORLD_MESH_OBSERVED_ONLY if observed_only else 0) | (WORLD_MESH_SKIP_UNKNOWN_FACES if skip_unknown_faces else 0) |
+                      (WORLD_MESH_SKIP_ABSENT_FACES if skip_absent_faces else 0) | (WORLD_MESH_BOX if box is not None else 0))
+        if box is not None:
+            o["bmin"], o["bmax"] = np.asarray(box[0], np.int32), np.asarray(box[1], np.int32)
+        _check(self.L, self.L.sdm_world_mesh_update(self.h, _ptr(o)), "sdm_world_mesh_update")
+
+    def world_mesh_info(self):
+        """-> a WORLD_MESH_INFO record (true counts, also of a build over a cap)"""
+        info = np.zeros(1, WORLD_MESH_INFO)
+        _check(self.L, self.L.sdm_get_world_mesh_info(self.h, _ptr(info)), "sdm_get_world_mesh_info")
+        return info[0]
+
+    def world_mesh(self):
+        """-> dict(coords int16[b, 3], faces WORLD_MESH_FACE[n], quads uint32[n, 4], corners int32[m, 3], xyz float32[m, 3],
+        info): the field bricks' coordinates (faces["brick"] indexes them), the faces, their vertex ids, the vertices as world
+        lattice corners and as positions.  A build over a cap raises SdmError (SDM_ERR_CAPACITY)."""
+        info = self.world_mesh_info()
+        n, k, b = int(info["n_faces"]), int(info["n_vertices"]), int(info["n_bricks"])
+        coords, faces, quads = np.empty((b, 3), np.int16), np.empty(n, WORLD_MESH_FACE), np.empty((n, 4), np.uint32)
+        corners, xyz = np.empty((k, 3), np.int32), np.empty((k, 3), np.float32)
+        got = C.c_int64(0)
+        _check(self.L, self.L.sdm_get_world_mesh_faces(self.h, _ptr(coords), _ptr(faces), _ptr(quads), 0, n, C.byref(got)),
+               "sdm_get_world_mesh_faces")
+        _check(self.L, self.L.sdm_get_world_mesh_vertices(self.h, _ptr(corners), _ptr(xyz), 0, k, C.byref(got)), "sdm_get_world_mesh_vertices")
+        return dict(coords=coords, faces=faces, quads=quads, corners=corners, xyz=xyz, info=info)
+
+    def world_mesh_device(self):
+        """-> (faces, quads, corners): device addresses of the last build's lists (WORLD_MESH_FACE, 4 uint32 per face, 3 int32
+        per vertex), valid until the next world_mesh_update, to be read in stream order on the map's stream"""
+        p = [C.c_void_p() for _ in range(3)]
+        _check(self.L, self.L.sdm_world_mesh_device(self.h, *(C.byref(x) for x in p)), "sdm_world_mesh_device")
+        return tuple(x.value for x in p)
+
+    def save_world_ply(self, path, **update_kwargs):
+        """world_mesh_update(**update_kwargs), then the mesh as an ASCII PLY (write_ply: two triangles a quad) -> the dict of
+        world_mesh().  Host code."""
+        self.world_mesh_update(**update_kwargs)
+        mesh = self.world_mesh()
+        write_ply(path, mesh["xyz"], mesh["quads"])
+        return mesh
 
     def save_world(self, path):
         """the archive as a NumPy .npz: bricks (WORLD_BRICK), cells (uint32 [n, 512]) and the map's voxel_size (float32)"""

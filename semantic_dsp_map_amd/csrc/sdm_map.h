@@ -255,6 +255,33 @@ struct WorldRaysPool {
   int32_t batch = 0;
 };
 
+// the world mesh (world_mesh.hip): a snapshot of the archive's surface as faces and welded vertices.  Per archived brick
+// (cap_arch) the box flag, the rank in the field and the solid, unknown and occupied words, indexed by pool slot; per brick
+// of the field (cap_bricks) its coordinates, its pool slot, the pool slots of the six face neighbours, table slot and rank
+// of its corners' eight owner bricks and the prefix of its slices' face counts, and a row of counts per 64 slices; the vertex
+// bricks' hash table (cap_slots: key, rank, the scanned claim flag, 512 corner bits a slot, a count per 64 slots) and per
+// vertex brick (cap_vb) the sort's four words and the prefix of its levels' corner counts - all of them the build's own,
+// read by nobody once it has run, the coordinates apart.  The lists: 12-byte
+// face records and four vertex ids per face (cap_f), an int32 triple per vertex (cap_v).  The build's counters (and their
+// page-locked landing area, whose last word takes a count the build waits for), the counts it waited for, its options
+// (its flags are Derived's), the archive's stamp; over: the build found more than a cap allows and wrote no list.
+struct WorldMeshLayer : Derived {
+  uint32_t *flag = nullptr, *rank = nullptr;
+  unsigned long long *solid_m = nullptr, *unk_m = nullptr, *occ_m = nullptr;
+  uint32_t *coord = nullptr, *slot_of = nullptr, *nbr = nullptr, *own_h = nullptr, *own_i = nullptr, *pre = nullptr;
+  unsigned long long *vkeys = nullptr, *vmask = nullptr;
+  uint32_t *vvals = nullptr, *vflag = nullptr, *rows = nullptr, *vrows = nullptr, *sortbuf = nullptr, *vpre = nullptr;
+  uint32_t *faces = nullptr, *quads = nullptr;
+  int32_t *corners = nullptr;
+  unsigned long long *meta = nullptr, *h_meta = nullptr;
+  size_t cap_arch = 0, cap_bricks = 0, cap_slots = 0, cap_vb = 0, cap_f = 0, cap_v = 0;
+  uint32_t n = 0, n_vb = 0, stamp = 0;
+  int64_t n_faces = 0, n_vertices = 0;
+  int64_t counts[11] = {};  // solid cells, faces by direction, faces by kind
+  sdm_world_mesh_options opt{};
+  bool over = false;
+};
+
 struct sdm_map {
   sdm_config cfg{};
   sdm_params prm{};
@@ -423,6 +450,7 @@ struct sdm_map {
   WorldGroundLayer wground;
   WorldGroundReachLayer wgreach;
   WorldRaysPool wrays;
+  WorldMeshLayer wmesh;
   // the scan scratch the layers share (layer_scan_scratch): they all enqueue on `stream` only, so their scans are ordered
   uint32_t *layer_scan = nullptr;
   size_t layer_scan_elems = 0;  // its capacity in uint32

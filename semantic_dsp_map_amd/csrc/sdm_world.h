@@ -3,10 +3,10 @@
 // world_reach.hip: the travel-cost field over the bricks; world_frontiers.hip: the frontiers of the bricks; world_esdf.hip:
 // the truncated distance field of the bricks; world_ground.hip: the height map and costmap over the bricks;
 // world_ground_reach.hip: the 2-D travel-cost field over that costmap; world_rays.hip: segments and views through the
-// bricks): the hash table's key, hash, lookup and insertion, which cells write, the header-word layout, the indices of the
-// counters, an update's geometry, how an entry of a query becomes a world cell, the packing of brick coordinates and tile
-// keys, the host scaffold of a snapshot build and of the two route planners, and the host entry points of world.hip and
-// world_snapshot.hip that the other units call.  No kernel lives here: everything in the unnamed namespace has internal
+// bricks; world_mesh.hip: the faces and welded vertices of the bricks' surface): the hash table's key, hash, lookup and
+// insertion, which cells write, the header-word layout, the indices of the counters, an update's geometry, how an entry of
+// a query becomes a world cell, the packing of brick coordinates and tile keys, the host scaffold of a snapshot build and
+// of the two route planners, and the host entry points of world.hip and world_snapshot.hip that the other units call.  No kernel lives here: everything in the unnamed namespace has internal
 // linkage and each unit compiles its own copy, so a kernel here would land in every object.
 #pragma once
 #include "sdm_layer.h"
