@@ -1196,6 +1196,60 @@ typedef struct {            /* 32 bytes, every field naturally aligned */
   uint32_t flags;              /* 0 */
 } sdm_world_retain_options;
 sdm_status sdm_world_retain(sdm_map *m, const sdm_world_retain_options *o, int64_t *n_removed);
+/* ---- world match: under which whole-cell offset do foreign bricks fit the archive?  sdm_world_match scores every offset
+ * of a small window - the 3-D, integer form of a correlative scan matcher - and names the best by a fixed rule: the step
+ * in front of sdm_world_import, whose cell_offset it finds.  It reads the archive and writes nothing to it; it is integer
+ * and bitwise reproducible like every call of the archive.
+ * Sources: exactly as for sdm_world_import - n headers and 512 words each, in any order; of a header only bx, by, bz are
+ * read; of several source bricks with the same coordinates the one with the lowest array index is used and the others are
+ * ignored entirely.
+ * Which source cells count: a cell counts iff its word would write in an import under the same SDM_WORLD_STATIC_ONLY /
+ * SDM_WORLD_OBSERVED_ONLY (occ >= 0, movable: 1 <= track <= the map's max_movable_track), so a score predicts what that
+ * import would write.  A counted cell with occ >= 1 is OCCUPIED, one with occ == 0 is FREE.
+ * Archive cells: the archive's cell at source world cell + candidate offset is classed by the same rule.  It is UNKNOWN
+ * where the archive has no brick, the brick lies outside the int16 range, occ < 0 or the word does not pass the flags;
+ * otherwise occupied or free by its occ.  A pair with an unknown side counts nowhere.  n_oo, n_of, n_fo, n_ff: the pairs by
+ * source class / archive class; n_same: those of n_oo whose label bytes (bits 16 .. 23 of the words) are equal.
+ * Candidates: the offsets cell_offset + d, |d[a]| <= radius[a] (0 .. SDM_WORLD_MATCH_MAX_RADIUS per axis), in the order
+ * k = ((dz + rz) * (2 ry + 1) + (dy + ry)) * (2 rx + 1) + (dx + rx).  score = w_oo * n_oo + w_same * n_same + w_of * n_of +
+ * w_fo * n_fo + w_ff * n_ff in int64.  best: the highest score; ties go to the smallest dx^2 + dy^2 + dz^2, then to the
+ * smallest k.  runner_up: the best score among the candidates at Chebyshev distance >= 2 from best, INT64_MIN if there is
+ * none - how far the peak stands above everything that is not its own shoulder.  n == 0 is SDM_OK: every count is 0, so
+ * the rule picks the centre.
+ * The archive is read LIVE, in stream order on the map's stream, as the last sdm_world_update, sdm_world_import or
+ * sdm_world_retain before the call left it.  Nothing of the archive, of a snapshot layer or of the map's state changes.
+ * Without SDM_WORLD_MATCH_ON_DEVICE every pointer is a host pointer: the sources are uploaded whole, the call waits and
+ * frees its device temporaries - the sources' copies, 2068 bytes per brick, the results and the work arrays - before it
+ * returns.  With it bricks, cells, scores and result are device pointers, the call enqueues on the map's stream and does
+ * not wait (best and runner-up are reduced on the device); the work arrays (at most 48 bytes per source brick, 20 per
+ * candidate) then stay with the map until sdm_destroy, and a call that needs larger ones than the last waits for the
+ * stream once.  scores may be NULL; otherwise it takes n_candidates records in candidate order.
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map, options or result, NULL bricks or cells with n > 0, n < 0 or n > 2^21,
+ * unknown flag bits or a non-zero pad, a radius outside 0 .. 8, an offset beyond +-2^19, a Z-slab shard, and a call before
+ * any sdm_world_update / sdm_world_import or after sdm_world_clear. */
+#define SDM_WORLD_MATCH_ON_DEVICE 0x20u   /* same value and meaning as SDM_WORLD_IMPORT_ON_DEVICE */
+#define SDM_WORLD_MATCH_MAX_RADIUS 8
+typedef struct {            /* 56 bytes, every field naturally aligned */
+  uint32_t flags;           /* SDM_WORLD_STATIC_ONLY | SDM_WORLD_OBSERVED_ONLY | SDM_WORLD_MATCH_ON_DEVICE */
+  int32_t  cell_offset[3];  /* the centre candidate, as sdm_world_import_options.cell_offset; |.| <= 2^19 */
+  int32_t  radius[3];       /* 0 .. 8 per axis: candidates centre + d, |d[a]| <= radius[a] */
+  int32_t  w_oo, w_same, w_of, w_fo, w_ff;   /* signed weights of the five counts */
+  uint32_t pad[2];          /* 0 */
+} sdm_world_match_options;
+typedef struct {            /* 32 bytes */
+  int32_t  offset[3];       /* the candidate itself (centre + d) */
+  uint32_t n_oo, n_of, n_fo, n_ff;   /* source class / archive class: occupied-occupied, occupied-free, free-occupied, free-free */
+  uint32_t n_same;          /* those of n_oo whose label bytes are equal */
+} sdm_world_match_score;
+typedef struct {            /* 56 bytes: 48 of fields and the pad, every field naturally aligned */
+  uint32_t n_candidates, n_sources;  /* (2rx+1)(2ry+1)(2rz+1); distinct source coordinates */
+  uint32_t src_occupied, src_free;   /* counted source cells by class */
+  int64_t  best_score, runner_up;    /* runner_up: the best score among candidates at Chebyshev distance >= 2 from best; INT64_MIN if none */
+  int32_t  best, best_offset[3];     /* candidate index and its offset */
+  uint32_t pad[2];                   /* written as 0 */
+} sdm_world_match_result;
+sdm_status sdm_world_match(sdm_map *m, const sdm_world_match_options *o, const sdm_world_brick *bricks, const uint32_t *cells,
+                           int64_t n, sdm_world_match_score *scores /* may be NULL */, sdm_world_match_result *result);
 
 /* ---- world reach: how far is it, through everything the map remembers, to a place the block has left? ----
  * sdm_world_reach_update builds, on the map's stream, the travel-cost field of sdm_reach_update over the bricks of the

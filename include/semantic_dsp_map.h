@@ -777,6 +777,37 @@ class SemanticDSPMap {
     o.cell_offset[0] = offset.x(), o.cell_offset[1] = offset.y(), o.cell_offset[2] = offset.z();
     return check(sdm_world_import(map_, &o, bricks.data(), cells.data(), (int64_t)bricks.size()), "sdm_world_import");
   }
+  /// Which whole-cell offset fits?  Scores foreign bricks (as for worldImport) against the archive under every offset
+  /// centre + d, |d| <= radius per axis (0 .. SDM_WORLD_MATCH_MAX_RADIUS), and returns the best one in `offset` - what
+  /// worldImport takes - with the counts and the runner-up in `result` (may be null) and every candidate's counts in
+  /// `scores` (may be null).  Reads the archive, writes nothing.  weights: w_oo, w_same, w_of, w_fo, w_ff; null: 4, 1, -2,
+  /// -2, 0, a default that is not tuned on anything.  flags: SDM_WORLD_STATIC_ONLY | SDM_WORLD_OBSERVED_ONLY.  Waits.
+  /// Returns false before the first worldUpdate() or worldImport() or when the call fails.
+  bool worldMatch(const std::vector<sdm_world_brick> &bricks, const std::vector<uint32_t> &cells, Eigen::Vector3i &offset,
+                  const Eigen::Vector3i &centre = Eigen::Vector3i(0, 0, 0), const Eigen::Vector3i &radius = Eigen::Vector3i(2, 2, 1),
+                  sdm_world_match_result *result = nullptr, std::vector<sdm_world_match_score> *scores = nullptr, const int32_t *weights = nullptr,
+                  uint32_t flags = 0) {
+    if (scores) scores->clear();
+    if (!map_ || cells.size() != 512 * bricks.size()) return false;
+    for (int a = 0; a < 3; ++a)
+      if (radius(a) < 0 || radius(a) > SDM_WORLD_MATCH_MAX_RADIUS) return false;
+    sdm_world_match_options o;
+    std::memset(&o, 0, sizeof(o));
+    o.flags = flags & ~(uint32_t)SDM_WORLD_MATCH_ON_DEVICE;
+    o.cell_offset[0] = centre.x(), o.cell_offset[1] = centre.y(), o.cell_offset[2] = centre.z();
+    o.radius[0] = radius.x(), o.radius[1] = radius.y(), o.radius[2] = radius.z();
+    o.w_oo = weights ? weights[0] : 4, o.w_same = weights ? weights[1] : 1, o.w_of = weights ? weights[2] : -2;
+    o.w_fo = weights ? weights[3] : -2, o.w_ff = weights ? weights[4] : 0;
+    if (scores) scores->resize((size_t)(2 * radius.x() + 1) * (size_t)(2 * radius.y() + 1) * (size_t)(2 * radius.z() + 1));
+    sdm_world_match_result r;
+    if (!check(sdm_world_match(map_, &o, bricks.data(), cells.data(), (int64_t)bricks.size(), scores ? scores->data() : nullptr, &r), "sdm_world_match")) {
+      if (scores) scores->clear();
+      return false;
+    }
+    offset = Eigen::Vector3i(r.best_offset[0], r.best_offset[1], r.best_offset[2]);
+    if (result) *result = r;
+    return true;
+  }
   /// Keeps the archived bricks inside the inclusive brick box bmin .. bmax whose last_stamp >= min_last_stamp and removes
   /// the others.  Waits.  Returns the number of bricks removed; -1 before the first worldUpdate() or worldImport() or when
   /// the call fails.

@@ -126,6 +126,16 @@ WORLD_RETAIN_OPTIONS = np.dtype([("bmin", "<i4", (3,)), ("bmax", "<i4", (3,)), (
 assert WORLD_IMPORT_OPTIONS.itemsize == 24 and WORLD_RETAIN_OPTIONS.itemsize == 32
 WORLD_IMPORT_FILL = 0x10
 WORLD_IMPORT_ON_DEVICE = 0x20
+# ... and the step in front of an import: which whole-cell offset fits (sdm.h: sdm_world_match)
+WORLD_MATCH_OPTIONS = np.dtype([("flags", "<u4"), ("cell_offset", "<i4", (3,)), ("radius", "<i4", (3,)), ("w_oo", "<i4"), ("w_same", "<i4"),
+                                ("w_of", "<i4"), ("w_fo", "<i4"), ("w_ff", "<i4"), ("pad", "<u4", (2,))])
+WORLD_MATCH_SCORE = np.dtype([("offset", "<i4", (3,)), ("n_oo", "<u4"), ("n_of", "<u4"), ("n_fo", "<u4"), ("n_ff", "<u4"), ("n_same", "<u4")])
+WORLD_MATCH_RESULT = np.dtype([("n_candidates", "<u4"), ("n_sources", "<u4"), ("src_occupied", "<u4"), ("src_free", "<u4"),
+                               ("best_score", "<i8"), ("runner_up", "<i8"), ("best", "<i4"), ("best_offset", "<i4", (3,)), ("pad", "<u4", (2,))])
+assert WORLD_MATCH_OPTIONS.itemsize == 56 and WORLD_MATCH_SCORE.itemsize == 32 and WORLD_MATCH_RESULT.itemsize == 56
+WORLD_MATCH_ON_DEVICE = 0x20
+WORLD_MATCH_MAX_RADIUS = 8
+WORLD_MATCH_WEIGHTS = (4, 1, -2, -2, 0)     # w_oo, w_same, w_of, w_fo, w_ff: the binding's default, not tuned
 # world reach (sdm.h: sdm_world_reach_update / sdm_get_world_reach / sdm_query_world_reach / sdm_world_reach_paths)
 WORLD_REACH_OPTIONS = np.dtype([("flags", "<u4"), ("inflate", "<u4"), ("max_cost", "<u4"), ("pad", "<u4"), ("bmin", "<i4", (3,)),
                                 ("bmax", "<i4", (3,))])
@@ -462,6 +472,7 @@ def load_library():
         "sdm_get_world_region": [vp, vp, vp, vp, u32],
         "sdm_world_import": [vp, vp, vp, vp, i64],
         "sdm_world_retain": [vp, vp, C.POINTER(i64)],
+        "sdm_world_match": [vp, vp, vp, vp, i64, vp, vp],
         "sdm_world_reach_update": [vp, vp, vp, vp, i64],
         "sdm_get_world_reach": [vp, vp, vp, i64, i64, C.POINTER(i64), vp],
         "sdm_query_world_reach": [vp, vp, vp, i64, vp, u32],
@@ -1230,6 +1241,81 @@ class SdmMap:
         if len(b) != len(c):
             raise ValueError("world_import: %d headers and %d bricks of cells" % (len(b), len(c)))
         _check(self.L, self.L.sdm_world_import(self.h, _ptr(o), _ptr(b), _ptr(c), len(b) if n is None else int(n)), "sdm_world_import")
+
+    def world_match(self, bricks, cells, offset=(0, 0, 0), radius=(2, 2, 1), weights=WORLD_MATCH_WEIGHTS, static_only=False,
+                    observed_only=False, on_device=False, n=None, scores=True, result=None):
+        """Scores foreign bricks - as for world_import - against the archive under every whole-cell offset `offset` + d,
+        |d| <= radius per axis (0 .. 8) -> (result WORLD_MATCH_RESULT, scores WORLD_MATCH_SCORE[n_candidates] in candidate
+        order, x fastest).  Reads the archive, writes nothing; result["best_offset"] is what world_import takes as offset.
+        weights: (w_oo, w_same, w_of, w_fo, w_ff); the default (4, 1, -2, -2, 0) is this binding's - agreement of occupied
+        cells counts, a conflict costs half as much, free on free counts nothing - and is not tuned on anything.
+        scores False: only the result.  on_device: bricks and cells are device pointers to n bricks, scores (or None) and
+        result device pointers the call fills in stream order on the map's stream; it does not wait and returns None."""
+        o = np.zeros(1, WORLD_MATCH_OPTIONS)
+        o["flags"] = ((WORLD_STATIC_ONLY if static_only else 0) | (WORLD_OBSERVED_ONLY if observed_only else 0) |
+                      (WORLD_MATCH_ON_DEVICE if on_device else 0))
+        o["cell_offset"][0] = np.asarray(offset, np.int64).reshape(3)
+        o["radius"][0] = np.asarray(radius, np.int64).reshape(3)
+        for name, w in zip(("w_oo", "w_same", "w_of", "w_fo", "w_ff"), weights):
+            o[name] = int(w)
+        if on_device:
+            _check(self.L, self.L.sdm_world_match(self.h, _ptr(o), _ptr(int(bricks)), _ptr(int(cells)), int(n),
+                                                  None if scores is None or isinstance(scores, bool) else _ptr(int(scores)), _ptr(int(result))),
+                   "sdm_world_match")
+            return None
+        b = np.ascontiguousarray(bricks, WORLD_BRICK).reshape(-1)
+        c = np.ascontiguousarray(cells, np.uint32).reshape(-1, 512)
+        if len(b) != len(c):
+            raise ValueError("world_match: %d headers and %d bricks of cells" % (len(b), len(c)))
+        r = [int(v) for v in o["radius"][0]]
+        res = np.zeros(1, WORLD_MATCH_RESULT)
+        sc = np.zeros(max((2 * r[0] + 1) * (2 * r[1] + 1) * (2 * r[2] + 1), 0), WORLD_MATCH_SCORE) if scores else None
+        _check(self.L, self.L.sdm_world_match(self.h, _ptr(o), _ptr(b), _ptr(c), len(b) if n is None else int(n), _ptr(sc), _ptr(res)),
+               "sdm_world_match")
+        return res[0], sc
+
+    def world_align(self, bricks, cells, offset=(0, 0, 0), search=(8, 8, 2), **kw):
+        """world_match over a search of `search` cells per axis round `offset`, wider than one match may be: tiled on the host
+        into windows of at most 17 candidates per axis, combined under the same rule relative to `offset` - the highest
+        score, then the smallest squared distance from `offset`, then the candidate order of the whole search ->
+        (best_offset int32[3], best_score, runner_up); runner_up: the best score among the candidates of the whole search
+        at Chebyshev distance >= 2 from the best, None if there is none.  Host pointers only; kw: world_match's."""
+        if kw.get("on_device"):
+            raise ValueError("world_align works on host arrays")
+        c0, R = np.asarray(offset, np.int64).reshape(3), np.asarray(search, np.int64).reshape(3)
+        if (R < 0).any():
+            raise ValueError("world_align: a negative search")
+        tiles = []
+        for a in range(3):                                # per axis: windows (centre d, radius) that cover -R .. R once
+            axis, lo = [], -int(R[a])
+            while lo <= R[a]:
+                hi = min(lo + 2 * WORLD_MATCH_MAX_RADIUS, int(R[a]))
+                r = (hi - lo + 1) // 2                     # (an even count is covered by one candidate more, inside the search's hull or not)
+                axis.append((lo + r, r, lo, hi))
+                lo = hi + 1
+            tiles.append(axis)
+        n = [2 * int(v) + 1 for v in R]
+        score = np.zeros((n[2], n[1], n[0]), np.int64)
+        w = [int(v) for v in kw.get("weights", WORLD_MATCH_WEIGHTS)]
+        for tz in tiles[2]:
+            for ty in tiles[1]:
+                for tx in tiles[0]:
+                    t = (tx, ty, tz)
+                    _, sc = self.world_match(bricks, cells, offset=c0 + [v[0] for v in t], radius=[v[1] for v in t], **kw)
+                    d = sc["offset"].astype(np.int64) - c0
+                    keep = np.all([(d[:, a] >= t[a][2]) & (d[:, a] <= t[a][3]) for a in range(3)], axis=0)
+                    s = (w[0] * sc["n_oo"].astype(np.int64) + w[1] * sc["n_same"].astype(np.int64) + w[2] * sc["n_of"].astype(np.int64) +
+                         w[3] * sc["n_fo"].astype(np.int64) + w[4] * sc["n_ff"].astype(np.int64))
+                    d = d[keep] + R
+                    score[d[:, 2], d[:, 1], d[:, 0]] = s[keep]
+        dz, dy, dx = np.meshgrid(*(np.arange(-int(v), int(v) + 1) for v in R[::-1]), indexing="ij")
+        d2 = dx * dx + dy * dy + dz * dz
+        flat = np.lexsort((np.arange(score.size), d2.ravel(), -score.ravel()))[0]      # the smallest k last among the keys
+        bz, by, bx = np.unravel_index(flat, score.shape)
+        best = np.array([bx, by, bz], np.int64) - R
+        far = np.maximum(np.maximum(np.abs(dx - best[0]), np.abs(dy - best[1])), np.abs(dz - best[2])) >= 2
+        runner_up = int(score[far].max()) if far.any() else None
+        return (c0 + best).astype(np.int32), int(score[bz, by, bx]), runner_up
 
     def world_retain(self, bmin=None, bmax=None, min_last_stamp=0):
         """Keeps the bricks inside the inclusive brick box bmin .. bmax (None: no bound) whose last_stamp >= min_last_stamp,

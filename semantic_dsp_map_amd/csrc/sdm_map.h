@@ -255,6 +255,14 @@ struct WorldRaysPool {
   int32_t batch = 0;
 };
 
+// world match (world_match.hip): the work arrays of a match, `words` words - the transient source table (64-bit keys, the
+// lowest source index beside each), five counts per candidate and the totals -, grown on demand, kept by a match in device
+// mode and released by one in host mode
+struct WorldMatchPool {
+  uint32_t *work = nullptr;
+  size_t words = 0;
+};
+
 // the world mesh (world_mesh.hip): a snapshot of the archive's surface as faces and welded vertices.  Per archived brick
 // (cap_arch) the box flag, the rank in the field and the solid, unknown and occupied words, indexed by pool slot; per brick
 // of the field (cap_bricks) its coordinates, its pool slot, the pool slots of the six face neighbours, table slot and rank
@@ -450,6 +458,7 @@ struct sdm_map {
   WorldGroundLayer wground;
   WorldGroundReachLayer wgreach;
   WorldRaysPool wrays;
+  WorldMatchPool wmatch;
   WorldMeshLayer wmesh;
   // the scan scratch the layers share (layer_scan_scratch): they all enqueue on `stream` only, so their scans are ordered
   uint32_t *layer_scan = nullptr;

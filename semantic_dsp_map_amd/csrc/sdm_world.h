@@ -3,7 +3,8 @@
 // world_reach.hip: the travel-cost field over the bricks; world_frontiers.hip: the frontiers of the bricks; world_esdf.hip:
 // the truncated distance field of the bricks; world_ground.hip: the height map and costmap over the bricks;
 // world_ground_reach.hip: the 2-D travel-cost field over that costmap; world_rays.hip: segments and views through the
-// bricks; world_mesh.hip: the faces and welded vertices of the bricks' surface): the hash table's key, hash, lookup and
+// bricks; world_mesh.hip: the faces and welded vertices of the bricks' surface; world_match.hip: foreign bricks scored
+// against the archive under a window of whole-cell offsets): the hash table's key, hash, lookup and
 // insertion, which cells write, the header-word layout, the indices of the counters, an update's geometry, how an entry of
 // a query becomes a world cell, the packing of brick coordinates and tile keys, the host scaffold of a snapshot build and
 // of the two route planners, and the host entry points of world.hip and world_snapshot.hip that the other units call.  No kernel lives here: everything in the unnamed namespace has internal
@@ -25,6 +26,9 @@ sdm_status world_order(sdm_map *m, const uint32_t **order);
 // world.hip: the kernel that closes an update or an import - n_bricks, created_last, dropped_total from *wanted, the number
 // of bricks that asked for room
 hipError_t launch_world_finish(const uint32_t *wanted, uint32_t max_bricks, uint32_t *meta, hipStream_t s);
+// world_io.hip: the import's source table over n source headers - every key once, the lowest source index with these
+// coordinates beside it; the caller hands in smask + 1 slots (a power of two >= 2 n) of keys and indices, all ones
+hipError_t launch_world_sources(const uint32_t *src_hdr, uint32_t n, uint32_t smask, unsigned long long *skeys, uint32_t *svals, hipStream_t s);
 
 struct BrickBox {  // the bricks lo .. hi per axis; use 0: every brick
   int lo[3], hi[3];

@@ -363,6 +363,15 @@ hipError_t launch_world_import(const IoGeo &g, const IoLayout &at, const WorldLa
 
 }  // namespace
 
+// the source table alone, for world_match.hip (sdm_world.h)
+hipError_t launch_world_sources(const uint32_t *src_hdr, uint32_t n, uint32_t smask, unsigned long long *skeys, uint32_t *svals, hipStream_t s) {
+  IoGeo g{};
+  g.n = n;
+  g.smask = smask;
+  LAYER_LAUNCH(k_wio_src_insert, (n + WTPB - 1) / WTPB, WTPB, s, g, src_hdr, skeys, svals);
+  return hipSuccess;
+}
+
 }  // namespace sdm
 
 extern "C" {
