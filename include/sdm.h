@@ -1251,6 +1251,124 @@ typedef struct {            /* 56 bytes: 48 of fields and the pad, every field n
 sdm_status sdm_world_match(sdm_map *m, const sdm_world_match_options *o, const sdm_world_brick *bricks, const uint32_t *cells,
                            int64_t n, sdm_world_match_score *scores /* may be NULL */, sdm_world_match_result *result);
 
+/* ---- world objects: what things does the map remember out there, where is each of them, and how large? ----
+ * sdm_world_objects_update builds, on the map's stream, the connected components of occupied archived cells that carry the
+ * same label, across brick borders, and a table of them.  Track ids are not stable between sessions and static cells share
+ * one id per label, so on the archive an object is a component, not a track (sdm_instances_update is the block's table).
+ * Like sdm_world_frontiers_update IT WAITS: for the number of bricks of the field, for the number of counted cells and for
+ * the number of objects, and sizes its buffers from them.  Cells are world cells (int32 per axis, brick = cell >> 3).  The
+ * archive is what the layer reads: call sdm_world_update first for what is still in the block.
+ * Field: the archived bricks at the time of the build; with SDM_WORLD_OBJECTS_BOX those inside the inclusive brick box
+ * bmin .. bmax (bmax < bmin on an axis: no brick, which is no error).  Bricks are ranked in brick order - ascending in
+ * (bz, by, bx), signed, the order of sdm_get_world_bricks.
+ * Counted cell: a cell of a field brick with occ >= 1 whose label l has bit l & 31 of labels[l >> 5] set (all zero: no cell
+ * counts, which is no error).  SDM_WORLD_OBJECTS_STATIC_ONLY: a cell on a movable track (1 <= track <= max_movable_track)
+ * does not count; SDM_WORLD_OBJECTS_MOVABLE_ONLY: only such cells count (both: SDM_ERR_INVALID_ARGUMENT);
+ * SDM_WORLD_OBJECTS_OBSERVED_ONLY: occ == 2 does not count.
+ * Key: the label byte of a counted cell; with SDM_WORLD_OBJECTS_BY_TRACK the low 24 bits of its word, label and track.
+ * Object: a connected component of counted cells of the field with EQUAL KEYS, in world cells across brick borders,
+ * 26-connected, or 6-connected with SDM_WORLD_OBJECTS_FACE_CONNECTED.  Only a counted cell of a field brick joins: a box
+ * cuts objects at its sides, a brick beyond the int16 range is absent.  Two cells of one key that touch only at an edge or
+ * a corner are joined under 26-connectivity whatever lies between them; a cell of another key carries nothing across.
+ * Cell list: the counted cells, ascending in (brick rank, cell word cx | cy << 3 | cz << 6).  An object's identity is the
+ * index of its first cell in that list; the table ascends in first_index.  min_cells <= 1 lists every object; a larger
+ * value leaves smaller ones out of the table, their cells stay in the list with object SDM_WORLD_OBJECT_UNLISTED.
+ * Table entry: track and label are the first cell's; mixed_tracks is 1 if not every cell carries that track (always 0 with
+ * BY_TRACK); n_guessed counts occ == 2.  cell_sum: signed sums of the world cells.  cell_sq: the sums of dx dx, dy dy, dz dz,
+ * dx dy, dx dz, dy dz with d = cell - first_cell, two's-complement adds modulo 2^64: they cannot wrap while n_cells x E^2 <
+ * 2^63, E the largest |d| on any axis - so for every object that stays within 46340 cells of its first cell, and for every
+ * object of up to 2^25 cells anywhere (cells lie in +-2^18, so E < 2^19).  Float fields, one IEEE operation at a time, no
+ * contraction: box_min = (float)cell_min * voxel_size, box_max = (float)(cell_max + 1) * voxel_size, centroid =
+ * (float)(((double)cell_sum / (double)n_cells + 0.5) * (double)voxel_size).  Everything accumulated is an integer sum,
+ * minimum, maximum or OR and an object's identity is its smallest cell index: two builds give the same bytes.
+ * The build is a SNAPSHOT: it owns the field's coordinates, a hash table of its own from brick to rank, the counted words
+ * with their prefix, the lists and the table, holds no pool slot once it returns, and answers the same bytes after any
+ * later sdm_world_update, sdm_world_import, sdm_world_retain or sdm_world_clear, until the next sdm_world_objects_update.
+ * Nothing of the archive or of the map's state is modified.
+ * max_cells > 0 caps the cell-proportional buffers: with more counted cells than that the build writes no list and returns
+ * SDM_ERR_CAPACITY; sdm_get_world_objects then still fills info (n_cells and n_guessed are the true counts, the object
+ * counts are 0), sdm_get_world_object_cells still sets *n_out to the true count, and they, sdm_get_world_object_labels and
+ * sdm_query_world_objects return SDM_ERR_CAPACITY until a build with room.  max_cells == 0: no cap.
+ * sdm_get_world_objects: the first min(n, cap) table entries, *n_out = n, the objects listed; info may be NULL.
+ * sdm_get_world_object_cells: rows first .. first + cap - 1 of the cell list - cell_xyz three int32 a cell, object the index
+ * into the table (SDM_WORLD_OBJECT_UNLISTED: below min_cells), words the archived word - each array may be NULL; *n_out =
+ * the cells in all.  sdm_get_world_object_labels: per label the counted cells and the objects in all (those below min_cells
+ * included); either array may be NULL.
+ * sdm_query_world_objects answers for the last build, for points (three floats each; world cell = floorf(p * recip) per
+ * axis) or world cells (three int32 each); exactly one of the two pointers is non-NULL, also with n == 0.  `cell` is as in
+ * sdm_query_world_distance: (0, 0, 0) for a point that is non-finite or beyond the brick range, a cell given is echoed as
+ * given.  object: the table index; SDM_WORLD_OBJECT_UNLISTED for a counted cell of an object below min_cells;
+ * SDM_WORLD_OBJECT_NONE where the cell is no counted cell of the field, the point is not finite, or point or cell are out of
+ * range.  index: the cell's place in the cell list, SDM_WORLD_OBJECT_NONE if it has none.  SDM_QUERY_ON_DEVICE as for the
+ * other queries (device pointers, enqueued, no wait; out 8-byte aligned), host mode through the queries' staging area.
+ * Memory, allocated at the first build, grown by a build that needs more, freed by sdm_destroy:
+ *   SDM_WORLD_OBJECTS_BYTES_PER_ARCHIVED_BRICK x (archived bricks + 1, in steps of 256)
+ * + SDM_WORLD_OBJECTS_BYTES_PER_BRICK x (bricks of the field, in steps of 256) + 12
+ * + SDM_WORLD_OBJECTS_BYTES_PER_CELL x (counted cells, in steps of 4096) + 4
+ * + SDM_WORLD_OBJECTS_BYTES_PER_OBJECT x (objects in all, in steps of 1024) + 4
+ * + 7192 (the counters, the per-label counters and their landing area).
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map, options or output (n_out, out), unknown flag bits, STATIC_ONLY together
+ * with MOVABLE_ONLY, negative max_cells, counts, cap or first, a NULL out with cap > 0, none or both of xyz and cells, a
+ * Z-slab shard (shard_count > 1), a build before the archive has had an update or import, and a getter or the query before
+ * any build. */
+#define SDM_WORLD_OBJECTS_FACE_CONNECTED 0x01u  /* objects under 6- instead of 26-connectivity */
+#define SDM_WORLD_OBJECTS_BOX            0x02u  /* the field is the bricks inside bmin .. bmax (inclusive brick box) */
+#define SDM_WORLD_OBJECTS_BY_TRACK       0x04u  /* the key is label and track, not the label alone */
+#define SDM_WORLD_OBJECTS_STATIC_ONLY    0x08u  /* cells on movable tracks do not count */
+#define SDM_WORLD_OBJECTS_MOVABLE_ONLY   0x10u  /* only cells on movable tracks count */
+#define SDM_WORLD_OBJECTS_OBSERVED_ONLY  0x20u  /* occ == 2 does not count */
+#define SDM_WORLD_OBJECT_UNLISTED 0xfffffffeu   /* a counted cell of an object below min_cells */
+#define SDM_WORLD_OBJECT_NONE     0xffffffffu   /* no counted cell of the field */
+#define SDM_WORLD_OBJECTS_BYTES_PER_ARCHIVED_BRICK 8  /* box flag, rank */
+#define SDM_WORLD_OBJECTS_BYTES_PER_BRICK 240   /* coordinates, pool slot, 27 neighbours, counted words and prefix, two hash slots */
+#define SDM_WORLD_OBJECTS_BYTES_PER_CELL  28    /* world cell, word, object, root, scan */
+#define SDM_WORLD_OBJECTS_BYTES_PER_OBJECT 288  /* table entry 168, accumulator 112, first cell's index, scan */
+typedef struct {            /* 72 bytes, every field naturally aligned */
+  uint32_t flags;
+  int32_t  min_cells;       /* <= 1: every object is listed */
+  int64_t  max_cells;       /* 0: no cap */
+  uint32_t labels[8];       /* bit l & 31 of word l >> 5 admits label l */
+  int32_t  bmin[3], bmax[3];/* inclusive brick box, read only with SDM_WORLD_OBJECTS_BOX */
+} sdm_world_objects_options;
+typedef struct {            /* 168 bytes, every field naturally aligned */
+  uint32_t first_index;     /* of the object's first cell in the cell list: its identity */
+  uint32_t n_cells;
+  uint32_t n_guessed;       /* those with occ == 2 */
+  uint16_t track;           /* of the first cell */
+  uint8_t  label;           /* of the first cell, and of every other */
+  uint8_t  mixed_tracks;    /* 1: not every cell carries `track` */
+  int32_t  first_cell[3];   /* world cell of the first cell */
+  int32_t  cell_min[3], cell_max[3]; /* inclusive */
+  uint32_t pad0;            /* 0 */
+  int64_t  cell_sum[3];     /* signed */
+  int64_t  cell_sq[6];      /* xx yy zz xy xz yz of d = cell - first_cell, modulo 2^64 */
+  float    box_min[3], box_max[3], centroid[3];
+  uint32_t pad1;            /* 0 */
+} sdm_world_object;
+typedef struct {            /* 40 bytes, every field naturally aligned */
+  uint32_t n_bricks;        /* bricks of the field */
+  uint32_t n_objects;       /* objects listed: the table's length */
+  uint32_t n_objects_total; /* objects in all, those below min_cells included */
+  uint32_t flags;
+  int64_t  n_cells;         /* counted cells */
+  int64_t  n_guessed;       /* those with occ == 2 */
+  int32_t  min_cells;       /* as given */
+  uint32_t stamp;           /* the archive's stamp at the build: sdm_world_info.stamp */
+} sdm_world_objects_info;
+typedef struct {            /* 24 bytes */
+  int32_t  cell[3];         /* the world cell asked about */
+  uint32_t object;          /* table index, SDM_WORLD_OBJECT_UNLISTED or SDM_WORLD_OBJECT_NONE */
+  uint32_t index;           /* place in the cell list; SDM_WORLD_OBJECT_NONE if none */
+  uint32_t pad;             /* 0 */
+} sdm_world_object_result;
+sdm_status sdm_world_objects_update(sdm_map *m, const sdm_world_objects_options *o);
+sdm_status sdm_get_world_objects(sdm_map *m, sdm_world_object *out, int32_t cap, int32_t *n_out, sdm_world_objects_info *info);
+sdm_status sdm_get_world_object_cells(sdm_map *m, int32_t *cell_xyz, uint32_t *object, uint32_t *words, int64_t first,
+                                      int64_t cap, int64_t *n_out);
+sdm_status sdm_get_world_object_labels(sdm_map *m, uint64_t cells[256], uint32_t objects[256]);
+sdm_status sdm_query_world_objects(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n,
+                                   sdm_world_object_result *out, uint32_t flags);
+
 /* ---- world reach: how far is it, through everything the map remembers, to a place the block has left? ----
  * sdm_world_reach_update builds, on the map's stream, the travel-cost field of sdm_reach_update over the bricks of the
  * world archive instead of the map block, from a set of start cells.  Like sdm_reach_update IT WAITS: the host decides

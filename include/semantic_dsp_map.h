@@ -907,6 +907,55 @@ class SemanticDSPMap {
     if (n && !check(sdm_get_world_frontier_clusters(map_, out.data(), n, &n, nullptr), "sdm_get_world_frontier_clusters")) out.clear();
     return (int32_t)out.size() == n;
   }
+  /// What things does the map remember out there, where is each and how large (sdm.h, "world objects")?  Builds the
+  /// connected components of occupied archived cells that carry the same label, across brick borders (26-connected,
+  /// 6-connected with face_connected), of the labels whose bit is set in label_mask (bit l & 31 of word l >> 5), and
+  /// returns the table of the objects of at least min_cells cells in `out`, ascending in first_index: count, box, sums and
+  /// second moments in world cells, box and centroid in metres; an object's first_cell or centroid is what to hand to
+  /// sdm_query_world_reach.  static_only: cells on movable tracks do not count.  The build is a snapshot:
+  /// queryWorldObjects() answers for it until the next worldObjects(), whatever happens to the archive.  The archive is what
+  /// is read: call worldUpdate() first.  The call waits for the build.  info (may be null): the build's counts.  Returns
+  /// false before the first worldUpdate() or worldImport() or when a call fails.
+  bool worldObjects(std::vector<sdm_world_object> &out, const uint32_t label_mask[8], int min_cells = 1, bool face_connected = false,
+                    bool static_only = false, sdm_world_objects_info *info = nullptr) {
+    out.clear();
+    if (!map_ || !label_mask) return false;
+    sdm_world_objects_options o;
+    std::memset(&o, 0, sizeof(o));
+    o.flags = (face_connected ? SDM_WORLD_OBJECTS_FACE_CONNECTED : 0u) | (static_only ? SDM_WORLD_OBJECTS_STATIC_ONLY : 0u);
+    o.min_cells = min_cells;
+    for (int i = 0; i < 8; ++i) o.labels[i] = label_mask[i];
+    if (!check(sdm_world_objects_update(map_, &o), "sdm_world_objects_update")) return false;
+    int32_t n = 0;
+    if (!check(sdm_get_world_objects(map_, nullptr, 0, &n, info), "sdm_get_world_objects")) return false;
+    out.resize((size_t)n);
+    if (n && !check(sdm_get_world_objects(map_, out.data(), n, &n, nullptr), "sdm_get_world_objects")) out.clear();
+    return (int32_t)out.size() == n;
+  }
+  /// ... of a single label (0 .. 255); a negative label: of every label
+  bool worldObjects(std::vector<sdm_world_object> &out, int label, int min_cells = 1, bool face_connected = false, bool static_only = false,
+                    sdm_world_objects_info *info = nullptr) {
+    uint32_t mask[8];
+    for (int i = 0; i < 8; ++i) mask[i] = label < 0 ? 0xffffffffu : 0u;
+    if (label > 255) {
+      out.clear();
+      return false;
+    }
+    if (label >= 0) mask[label >> 5] = 1u << (label & 31);
+    return worldObjects(out, mask, min_cells, face_connected, static_only, info);
+  }
+  /// Per position (global frame) of the last worldObjects(): its world cell, the index of the object it belongs to in that
+  /// call's table - SDM_WORLD_OBJECT_UNLISTED for a cell of an object below min_cells, SDM_WORLD_OBJECT_NONE where nothing
+  /// was counted - and its place in the cell list.  Waits.  Returns the number of points answered; 0 (and an empty vector)
+  /// before the first worldObjects() or when the call fails.
+  size_t queryWorldObjects(const std::vector<Eigen::Vector3d> &points, std::vector<sdm_world_object_result> &out) {
+    out.clear();
+    if (!map_ || points.empty()) return 0;
+    const std::vector<float> xyz = flat_points(points);
+    out.resize(points.size());
+    if (!check(sdm_query_world_objects(map_, xyz.data(), nullptr, (int64_t)points.size(), out.data(), 0u), "sdm_query_world_objects")) out.clear();
+    return out.size();
+  }
   /// How close is a remembered place to an obstacle (sdm.h, "world distance field")?  Builds the truncated Euclidean
   /// distance field over the bricks of the world archive: exact up to max_metres - radius = ceil(max_metres / voxel_size)
   /// cells, at least 1 and at most SDM_WORLD_ESDF_MAX_RADIUS - and "far" beyond.  unknown_is_obstacle: never-observed

@@ -237,6 +237,33 @@ WORLD_MESH_BYTES_PER_VERTEX_BRICK = 48
 WORLD_MESH_BYTES_PER_FACE = 28
 WORLD_MESH_BYTES_PER_VERTEX = 12
 
+# world objects (sdm.h: sdm_world_objects_update / sdm_get_world_objects / sdm_get_world_object_cells /
+# sdm_get_world_object_labels / sdm_query_world_objects)
+WORLD_OBJECTS_OPTIONS = np.dtype([("flags", "<u4"), ("min_cells", "<i4"), ("max_cells", "<i8"), ("labels", "<u4", (8,)), ("bmin", "<i4", (3,)),
+                                  ("bmax", "<i4", (3,))])
+WORLD_OBJECT = np.dtype([("first_index", "<u4"), ("n_cells", "<u4"), ("n_guessed", "<u4"), ("track", "<u2"), ("label", "u1"), ("mixed_tracks", "u1"),
+                         ("first_cell", "<i4", (3,)), ("cell_min", "<i4", (3,)), ("cell_max", "<i4", (3,)), ("pad0", "<u4"),
+                         ("cell_sum", "<i8", (3,)), ("cell_sq", "<i8", (6,)), ("box_min", "<f4", (3,)), ("box_max", "<f4", (3,)),
+                         ("centroid", "<f4", (3,)), ("pad1", "<u4")])
+WORLD_OBJECTS_INFO = np.dtype([("n_bricks", "<u4"), ("n_objects", "<u4"), ("n_objects_total", "<u4"), ("flags", "<u4"), ("n_cells", "<i8"),
+                               ("n_guessed", "<i8"), ("min_cells", "<i4"), ("stamp", "<u4")])
+WORLD_OBJECT_RESULT = np.dtype([("cell", "<i4", (3,)), ("object", "<u4"), ("index", "<u4"), ("pad", "<u4")])
+assert WORLD_OBJECTS_OPTIONS.itemsize == 72 and WORLD_OBJECT.itemsize == 168 and WORLD_OBJECTS_INFO.itemsize == 40
+assert WORLD_OBJECT_RESULT.itemsize == 24
+WORLD_OBJECTS_FACE_CONNECTED = 0x01
+WORLD_OBJECTS_BOX = 0x02
+WORLD_OBJECTS_BY_TRACK = 0x04
+WORLD_OBJECTS_STATIC_ONLY = 0x08
+WORLD_OBJECTS_MOVABLE_ONLY = 0x10
+WORLD_OBJECTS_OBSERVED_ONLY = 0x20
+WORLD_OBJECT_UNLISTED = 0xFFFFFFFE   # a counted cell of an object below min_cells
+WORLD_OBJECT_NONE = 0xFFFFFFFF       # no counted cell of the field
+WORLD_OBJECTS_BYTES_PER_ARCHIVED_BRICK = 8
+WORLD_OBJECTS_BYTES_PER_BRICK = 240
+WORLD_OBJECTS_BYTES_PER_CELL = 28
+WORLD_OBJECTS_BYTES_PER_OBJECT = 288
+ALL_LABELS = tuple(range(256))
+
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
                 ("forget", np.uint8), ("owner", np.uint16)]
@@ -481,6 +508,11 @@ def load_library():
         "sdm_world_frontiers_update": [vp, vp],
         "sdm_get_world_frontier_clusters": [vp, vp, i32, C.POINTER(i32), vp],
         "sdm_get_world_frontier_cells": [vp, vp, vp, vp, i64, i64, C.POINTER(i64)],
+        "sdm_world_objects_update": [vp, vp],
+        "sdm_get_world_objects": [vp, vp, i32, C.POINTER(i32), vp],
+        "sdm_get_world_object_cells": [vp, vp, vp, vp, i64, i64, C.POINTER(i64)],
+        "sdm_get_world_object_labels": [vp, vp, vp],
+        "sdm_query_world_objects": [vp, vp, vp, i64, vp, u32],
         "sdm_world_esdf_update": [vp, vp],
         "sdm_get_world_esdf": [vp, vp, vp, vp, i64, i64, C.POINTER(i64), vp],
         "sdm_query_world_distance": [vp, vp, vp, i64, vp, u32],
@@ -1428,6 +1460,70 @@ class SdmMap:
         _check(self.L, self.L.sdm_get_world_frontier_cells(self.h, _ptr(cells), _ptr(cluster), _ptr(faces), int(first), take, C.byref(got)),
                "sdm_get_world_frontier_cells")
         return cells, cluster, faces
+
+    # ---- world objects (sdm.h).  world_objects_update builds the connected same-key components of the archive's occupied
+    # cells and WAITS until they are complete; world_objects(), world_object_cells(), world_object_labels() and
+    # query_world_objects() answer for that build - a snapshot that later updates, imports, retains and clears of the
+    # archive do not touch - until the next one.
+    def world_objects_update(self, face_connected=False, by_track=False, static_only=False, movable_only=False, observed_only=False,
+                             labels=ALL_LABELS, box=None, min_cells=1, max_cells=0):
+        """labels: the label ids whose cells count (default: all; none: a field without objects); by_track: the key is label
+        and track; box: (bmin, bmax), an inclusive box of brick coordinates the field is cut to"""
+        o = np.zeros(1, WORLD_OBJECTS_OPTIONS)
+        o["flags"] = ((WORLD_OBJECTS_FACE_CONNECTED if face_connected else 0) | (WORLD_OBJECTS_BOX if box is not None else 0) |
+                      (WORLD_OBJECTS_BY_TRACK if by_track else 0) | (WORLD_OBJECTS_STATIC_ONLY if static_only else 0) |
+                      (WORLD_OBJECTS_MOVABLE_ONLY if movable_only else 0) | (WORLD_OBJECTS_OBSERVED_ONLY if observed_only else 0))
+        o["min_cells"], o["max_cells"] = int(min_cells), int(max_cells)
+        o["labels"] = label_mask(labels)
+        if box is not None:
+            o["bmin"], o["bmax"] = box[0], box[1]
+        _check(self.L, self.L.sdm_world_objects_update(self.h, _ptr(o)), "sdm_world_objects_update")
+
+    def world_objects(self):
+        """-> (table, info): WORLD_OBJECT entries in ascending first_index, a WORLD_OBJECTS_INFO record"""
+        got = C.c_int32(0)
+        info = np.zeros(1, WORLD_OBJECTS_INFO)
+        _check(self.L, self.L.sdm_get_world_objects(self.h, None, 0, C.byref(got), _ptr(info)), "sdm_get_world_objects")
+        out = np.empty(got.value, WORLD_OBJECT)
+        _check(self.L, self.L.sdm_get_world_objects(self.h, _ptr(out), got.value, C.byref(got), None), "sdm_get_world_objects")
+        return out, info[0]
+
+    def world_object_cells(self, first=0, cap=None):
+        """-> (cells int32 [n, 3] world cells, object uint32, words uint32): rows first .. first + cap - 1 of the cell list,
+        ascending in (brick order, cell word); object indexes the table (WORLD_OBJECT_UNLISTED: below min_cells)"""
+        got = C.c_int64(0)
+        _check(self.L, self.L.sdm_get_world_object_cells(self.h, None, None, None, 0, 0, C.byref(got)), "sdm_get_world_object_cells")
+        take = max(min(got.value - int(first), got.value if cap is None else int(cap)), 0)
+        cells, obj, words = np.empty((take, 3), np.int32), np.empty(take, np.uint32), np.empty(take, np.uint32)
+        _check(self.L, self.L.sdm_get_world_object_cells(self.h, _ptr(cells), _ptr(obj), _ptr(words), int(first), take, C.byref(got)),
+               "sdm_get_world_object_cells")
+        return cells, obj, words
+
+    def world_object_labels(self):
+        """-> (cells uint64 [256], objects uint32 [256]): per label the counted cells and the objects in all"""
+        cells, objects = np.zeros(256, np.uint64), np.zeros(256, np.uint32)
+        _check(self.L, self.L.sdm_get_world_object_labels(self.h, _ptr(cells), _ptr(objects)), "sdm_get_world_object_labels")
+        return cells, objects
+
+    def world_object_members(self, i):
+        """-> (cells, words) of table entry i: its rows of the cell list, selected on the host"""
+        cells, obj, words = self.world_object_cells()
+        mine = obj == np.uint32(i)
+        return cells[mine], words[mine]
+
+    def query_world_objects(self, xyz=None, cells=None, on_device=False, n=None, out=None):
+        """(n, 3) global positions or (n, 3) world cells -> WORLD_OBJECT_RESULT per entry.  on_device: the one given of
+        xyz / cells and out (n WORLD_OBJECT_RESULT) are device pointers."""
+        if on_device:
+            _check(self.L, self.L.sdm_query_world_objects(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
+                                                          _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_world_objects")
+            return None
+        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+        n = len(p) if p is not None else len(w) if w is not None else 0
+        res = np.empty(n, WORLD_OBJECT_RESULT)
+        _check(self.L, self.L.sdm_query_world_objects(self.h, _ptr(p), _ptr(w), n, _ptr(res), 0), "sdm_query_world_objects")
+        return res
 
     # ---- world distance field (sdm.h).  world_esdf_update builds the truncated distance field over the archive's bricks
     # (it waits once, for the field's brick count); world_esdf() and query_world_distance() answer for that build - a

@@ -290,6 +290,32 @@ struct WorldMeshLayer : Derived {
   bool over = false;
 };
 
+// world objects (world_objects.hip): a snapshot of the archive's occupied cells as connected same-key components.  Per
+// archived brick (cap_arch) the box flag and the rank in the field - the build's own; per brick of the field (cap_bricks)
+// its coordinates, its pool slot and the ranks of the 27 bricks round it (the build's own), the eight counted words and
+// their prefix, and the hash table from brick key to rank (hmask + 1 slots in use) - what the query reads.  Per counted
+// cell (cap_cells) the world cell, the archived word, parent (the object index in the end), root and the scanned root
+// flags; per object (cap_objects) the accumulator (empty between builds), the index of its first cell, the scanned
+// listing flags and the table.  The build's counters and per-label counters (and their page-locked landing area, whose
+// last word takes a count the build waits for), its arguments, the archive's stamp; over: the build found more cells than
+// max_cells and wrote no list.  Every buffer is grown by the build that needs more.
+struct WorldObjectsLayer : Derived {
+  uint32_t *flag = nullptr, *rank = nullptr;
+  uint32_t *coord = nullptr, *slot_of = nullptr, *nbr = nullptr, *pre = nullptr, *vals = nullptr;
+  unsigned long long *cw = nullptr, *keys = nullptr;
+  int32_t *xyz = nullptr;
+  uint32_t *word = nullptr, *parent = nullptr, *root = nullptr, *idx = nullptr;
+  unsigned char *acc = nullptr;
+  uint32_t *first = nullptr, *lidx = nullptr;
+  sdm_world_object *table = nullptr;
+  unsigned long long *meta = nullptr, *h_meta = nullptr;
+  size_t cap_arch = 0, cap_bricks = 0, cap_cells = 0, cap_objects = 0;
+  uint32_t n = 0, hmask = 0, n_roots = 0, stamp = 0;
+  int32_t min_cells = 0;
+  int64_t n_cells = 0, max_cells = 0;
+  bool over = false;
+};
+
 struct sdm_map {
   sdm_config cfg{};
   sdm_params prm{};
@@ -460,6 +486,7 @@ struct sdm_map {
   WorldRaysPool wrays;
   WorldMatchPool wmatch;
   WorldMeshLayer wmesh;
+  WorldObjectsLayer wobj;
   // the scan scratch the layers share (layer_scan_scratch): they all enqueue on `stream` only, so their scans are ordered
   uint32_t *layer_scan = nullptr;
   size_t layer_scan_elems = 0;  // its capacity in uint32

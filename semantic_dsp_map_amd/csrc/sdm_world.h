@@ -4,7 +4,8 @@
 // the truncated distance field of the bricks; world_ground.hip: the height map and costmap over the bricks;
 // world_ground_reach.hip: the 2-D travel-cost field over that costmap; world_rays.hip: segments and views through the
 // bricks; world_mesh.hip: the faces and welded vertices of the bricks' surface; world_match.hip: foreign bricks scored
-// against the archive under a window of whole-cell offsets): the hash table's key, hash, lookup and
+// against the archive under a window of whole-cell offsets; world_objects.hip: the connected same-key components of the
+// bricks' occupied cells): the hash table's key, hash, lookup and
 // insertion, which cells write, the header-word layout, the indices of the counters, an update's geometry, how an entry of
 // a query becomes a world cell, the packing of brick coordinates and tile keys, the host scaffold of a snapshot build and
 // of the two route planners, and the host entry points of world.hip and world_snapshot.hip that the other units call.  No kernel lives here: everything in the unnamed namespace has internal
