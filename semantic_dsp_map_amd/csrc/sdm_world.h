@@ -7,9 +7,13 @@
 // against the archive under a window of whole-cell offsets; world_objects.hip: the connected same-key components of the
 // bricks' occupied cells): the hash table's key, hash, lookup and
 // insertion, which cells write, the header-word layout, the indices of the counters, an update's geometry, how an entry of
-// a query becomes a world cell, the packing of brick coordinates and tile keys, the host scaffold of a snapshot build and
-// of the two route planners, and the host entry points of world.hip and world_snapshot.hip that the other units call.  No kernel lives here: everything in the unnamed namespace has internal
-// linkage and each unit compiles its own copy, so a kernel here would land in every object.
+// a query becomes a world cell, the packing of brick coordinates and tile keys; the inline device code the layers share
+//  - the 3 x 3 x 3 offset tables, a wave's loads of a brick, list indices, the 64-bit layer words and the
+// lateral shifts inside them, the min-linking union-find with the seam body and the two ends of the brick-local labelling
+// over it; the host scaffold of a snapshot build (its buffers' one way to grow included) and of the two route planners, and
+// the host entry points of world.hip and world_snapshot.hip that the other units call.  No kernel lives here: everything
+// in the unnamed namespace has internal linkage and each unit compiles its own copy, so a kernel here would land in every
+// object.
 #pragma once
 #include "sdm_layer.h"
 #include "sdm_map.h"
@@ -45,6 +49,10 @@ sdm_status snapshot_flag_bricks(sdm_map *m, const uint32_t *order, uint32_t n_ar
 // inserts key -> rank into the caller's table
 hipError_t launch_snapshot_index(const sdm_map *m, const uint32_t *order, const uint32_t *flag, const uint32_t *rank, uint32_t n_arch, uint32_t n,
                                  uint32_t *coord, uint32_t *slot_of, unsigned long long *keys, uint32_t *vals, uint32_t hmask);
+// world_snapshot.hip: nbr[27 r + k] = the rank in the caller's table of the brick at offset k (off_d) from brick r of the n of
+// `coord`, NONE where the table has none or the offset leaves the int16 range; nbr[27 r + 13] = r
+hipError_t launch_snapshot_neighbours(const uint32_t *coord, const unsigned long long *keys, const uint32_t *vals, uint32_t hmask, uint32_t n,
+                                      uint32_t *nbr, hipStream_t s);
 // world_snapshot.hip: the activity bits of n items become a list (and are cleared); *count grows by its length
 hipError_t launch_snapshot_list(uint32_t *act, uint32_t *list, uint32_t *count, uint32_t n, hipStream_t s);
 
@@ -148,6 +156,164 @@ __device__ __forceinline__ u64 tile_key(int bu, int bv) { return (u64)(uint32_t)
 __device__ __forceinline__ bool tile_in_range(int bu, int bv) { return bu >= -32768 && bu <= 32767 && bv >= -32768 && bv <= 32767; }
 __host__ __device__ __forceinline__ void tile_of(uint32_t key, int &bu, int &bv) { bu = (int)(key & 0xffffu) - 32768, bv = (int)(key >> 16) - 32768; }
 
+// ---- the 3 x 3 x 3 offsets: k = 13 + dx + 3 dy + 9 dz, a cell's neighbours and a brick's alike --------------------------
+constexpr int off_d(int k, int a) { return a == 0 ? k % 3 - 1 : a == 1 ? (k / 3) % 3 - 1 : k / 9 - 1; }
+constexpr int nb_bit(int dx, int dy, int dz) { return (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1); }
+constexpr int FACE_K[6] = {12, 14, 10, 16, 4, 22};  // the six faces: x-, x+, y-, y+, z-, z+
+// the place of offset k among the six faces, -1 for an edge, a corner and the cell itself
+constexpr int face_of(int k) {
+  for (int f = 0; f < 6; ++f)
+    if (FACE_K[f] == k) return f;
+  return -1;
+}
+constexpr bool is_face(int k) { return face_of(k) >= 0; }
+constexpr uint32_t face_moves() {
+  uint32_t m = 0;
+  for (int f = 0; f < 6; ++f) m |= 1u << FACE_K[f];
+  return m;
+}
+constexpr uint32_t FACE_MOVES = face_moves();  // bit k: offset k is a face
+constexpr bool offsets_agree() {
+  uint32_t faces = 0;
+  for (int k = 0; k < 27; ++k) {
+    if (nb_bit(off_d(k, 0), off_d(k, 1), off_d(k, 2)) != k || is_face(k) != (face_of(k) >= 0)) return false;
+    if (is_face(k) != (off_d(k, 0) * off_d(k, 0) + off_d(k, 1) * off_d(k, 1) + off_d(k, 2) * off_d(k, 2) == 1)) return false;
+    faces |= is_face(k) ? 1u << k : 0u;
+  }
+  for (int f = 0; f < 6; ++f)  // (the order of the six: the axis, then the sign)
+    if (off_d(FACE_K[f], f >> 1) != ((f & 1) ? 1 : -1)) return false;
+  return faces == FACE_MOVES;
+}
+static_assert(offsets_agree(), "off_d, nb_bit, face_of, is_face and FACE_MOVES are one table");
+
+// ---- a brick's cells, list indices ---------------------------------------------------------------------------------------
+// "a wave per brick, a lane per (cx, cy)": the lane's cell of each of the eight layers of the brick at pool slot `slot`,
+// every load issued before anything uses one
+__device__ __forceinline__ void load_brick(const uint32_t *__restrict__ cells, uint32_t slot, uint32_t lane, uint32_t (&w)[8]) {
+  const uint32_t *__restrict__ src = cells + (size_t)slot * 512u + lane;
+#pragma unroll
+  for (int l = 0; l < 8; ++l) w[l] = src[l * 64];
+}
+// the list index of bit b of word wi: the word's first index (the exclusive scan of the popcounts) + the set bits below b
+__device__ __forceinline__ uint32_t list_index(const u64 *__restrict__ words, const uint32_t *__restrict__ pre, size_t wi, uint32_t b) {
+  return pre[wi] + lane_rank(words[wi], b);
+}
+// the world cell of lane (cx + 8 cy) of layer z of brick (bx, by, bz), at list index `at`
+__device__ __forceinline__ void store_world_cell(int32_t *__restrict__ xyz, uint32_t at, int bx, int by, int bz, uint32_t lane, int z) {
+  xyz[3 * (size_t)at] = bx * 8 + (int)(lane & 7u);
+  xyz[3 * (size_t)at + 1] = by * 8 + (int)(lane >> 3);
+  xyz[3 * (size_t)at + 2] = bz * 8 + z;
+}
+
+// ---- 64-bit layer words: bit cx + 8 cy -----------------------------------------------------------------------------------
+constexpr u64 COL0 = 0x0101010101010101ull, COL7 = 0x8080808080808080ull, ROW0 = 0xffull, ROW7 = 0xffull << 56;
+// what the cells of a layer (own) see across lateral face DIR (x-, x+, y-, y+), nbr_word being the same layer of the brick
+// beyond that face: a shift inside the word, the wrapping column masked out and the neighbour's column shifted in, or the
+// neighbour's row.  What an absent brick reads, and where a brick's words lie, is the caller's.
+template <int DIR>
+__device__ __forceinline__ u64 across_lateral(u64 own, u64 nbr_word) {
+  static_assert(DIR >= 0 && DIR < 4, "the four lateral faces");
+  if (DIR == 0) return ((own << 1) & ~COL0) | ((nbr_word >> 7) & COL0);  // cx - 1: the bit below; column 0 looks at the neighbour's column 7
+  if (DIR == 1) return ((own >> 1) & ~COL7) | ((nbr_word << 7) & COL7);
+  if (DIR == 2) return (own << 8) | (nbr_word >> 56);                    // cy - 1: the row below; row 0 looks at the neighbour's row 7
+  return (own >> 8) | (nbr_word << 56);
+}
+
+// ---- labels: the min-linking union-find over list indices, and what the two labelled layers do with it -------------------
+// parent[a] <= a; a root is its own parent, and a component's root ends up as its smallest index whatever order the unions
+// arrive in.  Within the launch that unites, every read of parent[] is a relaxed agent-scope atomic load or an atomic's
+// return value: the L2s of the XCDs are not coherent for plain loads, and a plain load might also be kept in a register
+// across the loop.  Relaxed is enough: nothing but parent[] itself is published through it, and the next launch reads with
+// plain loads.  Lock-free: no thread waits for another; a failed link hands the loop a strictly smaller root.
+__device__ __forceinline__ uint32_t parent_of(uint32_t *__restrict__ parent, uint32_t a) {
+  return __hip_atomic_load(parent + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint32_t lower_parent(uint32_t *__restrict__ parent, uint32_t a, uint32_t v) {  // -> what it was
+  return __hip_atomic_fetch_min(parent + a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// the root of a, halving the path on the way (a parent is only ever lowered to an ancestor: still the same component;
+// every step goes to a strictly smaller index: at most n_cells steps)
+__device__ __forceinline__ uint32_t find_root(uint32_t *__restrict__ parent, uint32_t a) {
+  for (;;) {
+    const uint32_t p = parent_of(parent, a);
+    if (p >= a) return a;  // (p == a: a root; never above)
+    const uint32_t gp = parent_of(parent, p);
+    if (gp >= p) return p;
+    lower_parent(parent, a, gp);
+    a = gp;
+  }
+}
+__device__ __forceinline__ void unite(uint32_t *__restrict__ parent, uint32_t a, uint32_t b) {
+  for (;;) {
+    a = find_root(parent, a);
+    b = find_root(parent, b);
+    if (a == b) return;
+    const uint32_t hi = max(a, b), lo = min(a, b);
+    const uint32_t old = lower_parent(parent, hi, lo);
+    if (old == hi) return;  // hi was still a root and now hangs below lo
+    a = old;                // somebody linked hi below `old` (< hi) first: old and lo remain to be united
+    b = lo;
+  }
+}
+
+constexpr uint32_t NO_LABEL = 0xffffu;  // the local labelling: the cell is not listed
+// The opening of a brick's local labelling: the eight words of brick r and, per layer, the lane's start label - its own
+// cell word z * 64 + lane, NO_LABEL for a cell that is not listed.  False (wave-uniform) for a brick without a listed cell.
+__device__ __forceinline__ bool local_labels(const u64 *__restrict__ words, uint32_t r, uint32_t lane, u64 (&m)[8], uint32_t (&v)[8]) {
+#pragma unroll
+  for (int z = 0; z < 8; ++z) m[z] = words[(size_t)r * 8u + z];
+  if (!(m[0] | m[1] | m[2] | m[3] | m[4] | m[5] | m[6] | m[7])) return false;
+#pragma unroll
+  for (int z = 0; z < 8; ++z) v[z] = ((m[z] >> lane) & 1ull) ? (uint32_t)z * 64u + lane : NO_LABEL;
+  return true;
+}
+// ... and its end: v[z] is the smallest cell word of the local component of the lane's cell of layer z; parent[] of the cell
+// becomes the list index of that cell - one root per local component, no LDS, no global atomic
+__device__ __forceinline__ void store_local_roots(const uint32_t (&v)[8], const u64 (&m)[8], const u64 *__restrict__ words,
+                                                  const uint32_t *__restrict__ pre, uint32_t r, uint32_t lane, uint32_t n_cells,
+                                                  uint32_t *__restrict__ parent) {
+#pragma unroll
+  for (int z = 0; z < 8; ++z) {
+    if (v[z] == NO_LABEL) continue;
+    const uint32_t lz = v[z] >> 6, lb = v[z] & 63u;  // the local root: a cell word <= this cell's
+    const uint32_t at = pre[(size_t)r * 8u + z] + lane_rank(m[z], lane);  // (list_index, on the word the lane holds since the opening)
+    const uint32_t root = list_index(words, pre, (size_t)r * 8u + lz, lb);
+    if (at < n_cells) parent[at] = root;
+  }
+}
+// The seams, a wave per word and a lane per cell: the cell `lane` of layer lz of brick r (of n), if it is listed and lies on
+// the brick's shell, looks at its 26 (FACE: 6) neighbours that lie in a field brick of lower rank and unites with those that
+// are listed and carry its key.  nbr: the 27 ranks round every brick, NONE for none.  key_of_cell(list index): "the same key"
+// is the predicate under which two listed cells join - an equivalence whatever the caller passes, as a union-find needs it,
+// and the cell's own key is fetched once, before the first neighbour; a constant key joins every listed pair.
+template <bool FACE, class Key>
+__device__ __forceinline__ void seam_unions(const uint32_t *__restrict__ nbr, const u64 *__restrict__ words, const uint32_t *__restrict__ pre,
+                                            uint32_t r, int lz, uint32_t lane, uint32_t n, uint32_t n_cells, uint32_t *__restrict__ parent,
+                                            Key key_of_cell) {
+  if (r >= n) return;  // (wave-uniform)
+  const u64 mw = words[(size_t)r * 8u + (uint32_t)lz];
+  const int lx = (int)(lane & 7u), ly = (int)(lane >> 3);
+  const bool shell = lx == 0 || lx == 7 || ly == 0 || ly == 7 || lz == 0 || lz == 7;
+  if (!((mw >> lane) & 1ull) || !shell) return;
+  const uint32_t at = list_index(words, pre, (size_t)r * 8u + (uint32_t)lz, lane);
+  if (at >= n_cells) return;  // (never)
+  const auto key = key_of_cell(at);
+#pragma unroll
+  for (int k = 0; k < 27; ++k) {
+    if (k == 13 || (FACE && !is_face(k))) continue;
+    const int x = lx + off_d(k, 0), y = ly + off_d(k, 1), z = lz + off_d(k, 2);
+    const int ox = brick_off(x), oy = brick_off(y), oz = brick_off(z);
+    if (ox == 0 && oy == 0 && oz == 0) continue;  // inside the brick: the local labelling has united them
+    const uint32_t nr = nbr[(size_t)r * 27u + (uint32_t)(13 + ox + 3 * oy + 9 * oz)];
+    if (nr >= r) continue;  // absent, outside the field, or later in cell order: that cell unites with this one
+    const uint32_t wi = nr * 8u + (uint32_t)(z & 7), b = (uint32_t)((x & 7) + 8 * (y & 7));
+    const u64 nw = words[wi];
+    if (!((nw >> b) & 1ull)) continue;
+    const uint32_t other = list_index(words, pre, wi, b);
+    if (other < n_cells && key_of_cell(other) == key) unite(parent, at, other);
+  }
+}
+
 // ---- the host scaffold --------------------------------------------------------------------------------------------------
 // the slots of a table that is at most half full with `items` keys
 inline uint32_t table_slots(size_t items) {
@@ -155,6 +321,36 @@ inline uint32_t table_slots(size_t items) {
   while (slots < 2 * items) slots <<= 1;
   return slots;
 }
+// The one way a snapshot's buffers grow.  A set of buffers shares a capacity, *cap; while need <= *cap nothing happens.
+// Otherwise every buffer listed is released, *cap is 0, every buffer is allocated - in the order listed - at the size the
+// caller states for the new capacity `to`, and only then *cap = to: an allocation that fails leaves *cap == 0 and the next
+// build starts over.  The caller rounds `to` (256 bricks or tiles, the route planners' too; 1024 objects; 4096 cells, faces
+// and vertices; frontiers' pool slots not at all) and writes every buffer's elements out, where a reader checks them against
+// the BYTES_PER_* constants of sdm.h.  The stream is idle when this is called, or there were no buffers before.  then():
+// what else has to succeed before the capacity counts - it runs only when the buffers grew, after the last allocation.  A
+// set with a second capacity (the mesh's cap_slots) sets it there; to have it 0 while the first is, the caller zeroes it
+// before the call under this function's own test, need > *cap - the one thing a caller has to know of the inside.
+struct GrowBuf {
+  void **p;
+  size_t bytes;
+};
+template <typename T>
+GrowBuf buf(T **p, size_t n) { return {(void **)p, std::max<size_t>(n, 1) * sizeof(T)}; }  // (alloc_tracked's size)
+template <class Then>
+sdm_status grow_buffers(sdm_map *m, size_t need, size_t to, size_t *cap, std::initializer_list<GrowBuf> bufs, Then then) {
+  if (need <= *cap) return SDM_OK;
+  for (const GrowBuf &b : bufs) map_release(m, b.p);
+  *cap = 0;
+  for (const GrowBuf &b : bufs) SDM_TRY(map_alloc(m, b.p, b.bytes, false));
+  SDM_TRY(then());
+  *cap = to;
+  return SDM_OK;
+}
+inline sdm_status grow_buffers(sdm_map *m, size_t need, size_t to, size_t *cap, std::initializer_list<GrowBuf> bufs) {
+  return grow_buffers(m, need, to, cap, bufs, [] { return SDM_OK; });
+}
+inline size_t round_up(size_t n, size_t to) { return (n + to - 1) & ~(to - 1); }  // (to: a power of two)
+
 // the getters: coordinate pairs / tile keys as int16 triples / pairs
 inline void unpack_coords(const std::vector<uint32_t> &pairs, int16_t *coords) {
   for (size_t i = 0; i < pairs.size() / 2; ++i) {

@@ -70,10 +70,8 @@ __global__ __launch_bounds__(QT) void k_we_classify(const uint32_t *__restrict__
   if (j >= n_arch) return;  // (wave-uniform)
   const uint32_t slot = order[j];
   if (slot >= n_arch) return;  // (never: the pool is dense, n_arch slots are in use; wave-uniform)
-  const uint32_t *__restrict__ src = cells + (size_t)slot * 512u + lane;
   uint32_t w[8];
-#pragma unroll
-  for (int l = 0; l < 8; ++l) w[l] = src[l * 64];
+  load_brick(cells, slot, lane, w);
 #pragma unroll
   for (int l = 0; l < 8; ++l) {
     const int occ = occ_of(w[l]);
@@ -207,29 +205,15 @@ __global__ __launch_bounds__(QT) void k_query_world_distance(const float *__rest
 // the buffers for n_arch archived bricks / for `bricks` bricks of the field (the stream is idle when either is called)
 sdm_status grow_arch(sdm_map *m, size_t n_arch) {
   WorldEsdfLayer &L = m->wesdf;
-  if (n_arch + 1 <= L.cap_arch) return SDM_OK;
-  release(m, &L.flag), release(m, &L.rank), release(m, &L.obst);
-  L.cap_arch = 0;
-  const size_t cap = (n_arch + 1 + 255) & ~(size_t)255;
-  SDM_TRY(alloc_tracked(m, &L.flag, cap));
-  SDM_TRY(alloc_tracked(m, &L.rank, cap));
-  SDM_TRY(alloc_tracked(m, &L.obst, cap * 8));
-  L.cap_arch = cap;
-  return SDM_OK;
+  const size_t cap = round_up(n_arch + 1, 256);
+  return grow_buffers(m, n_arch + 1, cap, &L.cap_arch, {buf(&L.flag, cap), buf(&L.rank, cap), buf(&L.obst, cap * 8)});
 }
 
-sdm_status grow_bricks(sdm_map *m, size_t bricks) {
+sdm_status grow_bricks(sdm_map *m, size_t bricks) {  // (no brick: still a table to look up in)
   WorldEsdfLayer &L = m->wesdf;
-  if (L.cap_bricks && bricks <= L.cap_bricks) return SDM_OK;
-  release(m, &L.coord), release(m, &L.field), release(m, &L.keys), release(m, &L.vals);
-  L.cap_bricks = 0;
-  const size_t cap = (std::max<size_t>(bricks, 1) + 255) & ~(size_t)255;
-  SDM_TRY(alloc_tracked(m, &L.coord, cap * 2));
-  SDM_TRY(alloc_tracked(m, &L.field, cap * 512));
-  SDM_TRY(alloc_tracked(m, &L.keys, table_slots(cap)));
-  SDM_TRY(alloc_tracked(m, &L.vals, table_slots(cap)));
-  L.cap_bricks = cap;
-  return SDM_OK;
+  const size_t need = std::max<size_t>(bricks, 1), cap = round_up(need, 256);
+  return grow_buffers(m, need, cap, &L.cap_bricks,
+                      {buf(&L.coord, cap * 2), buf(&L.field, cap * 512), buf(&L.keys, table_slots(cap)), buf(&L.vals, table_slots(cap))});
 }
 
 // the index, the obstacle words and the field of a build of n bricks

@@ -29,8 +29,9 @@
 //               a sweep changes nothing (at most 512 sweeps).  parent[] of a cell becomes the global index of its local
 //               component's smallest cell: one root per local component, no LDS, no global atomic.
 //   k_wf_seams       a wave per word, a lane per cell: a frontier cell on the brick's shell looks at its 26 (6) neighbours
-//               that lie in a field brick of lower rank and unites with those that are frontier cells, by frontiers.hip's
-//               min-linking union-find.  Every read of parent[] in this launch is an agent-scope atomic load or an
+//               that lie in a field brick of lower rank and unites with those that are frontier cells: sdm_world.h's
+//               seam_unions over its min-linking union-find (frontiers.hip's scheme; world_objects.hip runs the same body
+//               with a key comparison).  Every read of parent[] in this launch is an agent-scope atomic load or an
 //               atomic's return value (the L2s of the XCDs are not coherent for plain loads).  Lock-free: no thread
 //               waits for another; a failed link hands the loop a strictly smaller root.
 //   k_wf_accumulate  a thread per cell: follows parent[] to the root (plain loads: a later launch), writes root[] and adds
@@ -40,7 +41,9 @@
 //   k_wf_table       a thread per cell: its cluster index (over parent[]); a root writes its table entry and stores zeros
 //               back into its accumulator, so the next build starts from empty accumulators.
 // The build waits twice: for the number of bricks of the field, then for the number of cells, and sizes its buffers from
-// them.  This unit shares no code with frontiers.hip (DESIGN.md 5n says why); it includes none of a frame unit.
+// them.  This unit shares no code with frontiers.hip (DESIGN.md 5n says why); it includes none of a frame unit.  With
+// world_objects.hip it shares, through sdm_world.h, the union-find, the seam body and the two ends of the local labelling;
+// with every world layer the offset tables, the brick loads and the lateral shifts of a layer word (5w).
 #include "sdm_world.h"
 
 #pragma clang fp contract(off)
@@ -60,7 +63,6 @@ namespace {
 constexpr int QT = 256;             // the kernels of a thread or a wave per item
 constexpr uint32_t WF_GRID = 4096;  // the largest grid of the kernels over cells: they stride
 constexpr uint32_t ALL_WF_FLAGS = SDM_WORLD_FRONTIERS_FACE_CONNECTED | SDM_WORLD_FRONTIERS_BOX | SDM_WORLD_FRONTIERS_INSIDE_BRICKS;
-constexpr uint32_t NO_LABEL = 0xffffu;
 // the build's counters, 64 bits each: unknown faces, those towards absent bricks, roots, clusters listed
 enum { F_FACES = 0, F_ABSENT, F_ROOTS, F_LISTED, F_WORDS };
 
@@ -75,11 +77,6 @@ constexpr size_t ARCH_BYTES = 4 + 4 + 2 * 8 * 8;                                
 static_assert(CELL_BYTES == SDM_WORLD_FRONTIERS_BYTES_PER_CELL && BRICK_BYTES == SDM_WORLD_FRONTIERS_BYTES_PER_BRICK &&
                   ARCH_BYTES == SDM_WORLD_FRONTIERS_BYTES_PER_ARCHIVED_BRICK,
               "sdm.h states the bytes");
-
-constexpr int off_d(int k, int a) { return a == 0 ? k % 3 - 1 : a == 1 ? (k / 3) % 3 - 1 : k / 9 - 1; }
-// the place of offset k among the six faces (x-, x+, y-, y+, z-, z+), -1 for an edge, a corner and the brick itself
-constexpr int face_of(int k) { return k == 12 ? 0 : k == 14 ? 1 : k == 10 ? 2 : k == 16 ? 3 : k == 4 ? 4 : k == 22 ? 5 : -1; }
-constexpr u64 COL0 = 0x0101010101010101ull, COL7 = 0x8080808080808080ull, ROW0 = 0xffull, ROW7 = 0xffull << 56;
 
 // ---- the index ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(QT) void k_wf_index(const uint32_t *__restrict__ order, const uint32_t *__restrict__ hdr,
@@ -103,10 +100,8 @@ __global__ __launch_bounds__(QT) void k_wf_classify(const uint32_t *__restrict__
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t j = blockIdx.x * (QT / 64) + (threadIdx.x >> 6);
   if (j >= n_arch) return;  // (wave-uniform)
-  const uint32_t *__restrict__ src = cells + (size_t)order[j] * 512u + lane;
   uint32_t w[8];
-#pragma unroll
-  for (int l = 0; l < 8; ++l) w[l] = src[l * 64];
+  load_brick(cells, order[j], lane, w);
 #pragma unroll
   for (int l = 0; l < 8; ++l) {
     const int occ = occ_of(w[l]);
@@ -154,10 +149,10 @@ __device__ __forceinline__ void face_masks(const uint32_t *__restrict__ place, c
   for (int f = 0; f < 4; ++f) w[f] = fj[f] != NONE ? unk_m[(size_t)fj[f] * 8u + z] : absent_reads;
   w[4] = z > 0 ? unk_m[(size_t)j * 8u + (z - 1)] : fj[4] != NONE ? unk_m[(size_t)fj[4] * 8u + 7u] : absent_reads;
   w[5] = z < 7 ? unk_m[(size_t)j * 8u + (z + 1)] : fj[5] != NONE ? unk_m[(size_t)fj[5] * 8u] : absent_reads;
-  m[0] = ((own << 1) & ~COL0) | ((w[0] >> 7) & COL0);  // cx - 1: the bit below; column 0 looks at the neighbour's column 7
-  m[1] = ((own >> 1) & ~COL7) | ((w[1] << 7) & COL7);
-  m[2] = (own << 8) | (w[2] >> 56);                    // cy - 1: the row below; row 0 looks at the neighbour's row 7
-  m[3] = (own >> 8) | (w[3] << 56);
+  m[0] = across_lateral<0>(own, w[0]);
+  m[1] = across_lateral<1>(own, w[1]);
+  m[2] = across_lateral<2>(own, w[2]);
+  m[3] = across_lateral<3>(own, w[3]);
   m[4] = w[4];
   m[5] = w[5];
   absent = 0u;
@@ -215,16 +210,14 @@ __global__ __launch_bounds__(QT) void k_wf_compact(const uint32_t *__restrict__ 
   uint32_t j, absent;
   face_masks(place, face_place, unk_m, r, z, absent_reads, j, m, absent);
   if (!((fw >> lane) & 1ull)) return;
-  const uint32_t at = pre[i] + lane_rank(fw, lane);
+  const uint32_t at = list_index(front, pre, i, lane);
   if (at >= n_cells) return;  // (never: the scan's total is n_cells)
   int bx, by, bz;
   coord_of(coord, r, bx, by, bz);
   uint32_t nf = 0;
 #pragma unroll
   for (int f = 0; f < 6; ++f) nf += (uint32_t)((m[f] >> lane) & 1ull);
-  xyz[3 * (size_t)at] = bx * 8 + (int)(lane & 7u);
-  xyz[3 * (size_t)at + 1] = by * 8 + (int)(lane >> 3);
-  xyz[3 * (size_t)at + 2] = bz * 8 + z;
+  store_world_cell(xyz, at, bx, by, bz, lane, z);
   faces[at] = (uint8_t)nf;
 }
 
@@ -236,16 +229,12 @@ __global__ __launch_bounds__(QT) void k_wf_label_local(const u64 *__restrict__ f
   const uint32_t r = blockIdx.x * (QT / 64) + (threadIdx.x >> 6);
   if (r >= n) return;  // (wave-uniform: nothing below waits for another wave)
   u64 fw[8];
-#pragma unroll
-  for (int z = 0; z < 8; ++z) fw[z] = front[(size_t)r * 8u + z];
-  if (!(fw[0] | fw[1] | fw[2] | fw[3] | fw[4] | fw[5] | fw[6] | fw[7])) return;
+  uint32_t v[8];
+  if (!local_labels(front, r, lane, fw, v)) return;
   const int cx = (int)(lane & 7u), cy = (int)(lane >> 3);
   // the lanes of the four lateral neighbours; at the brick's border the lane itself, which changes no minimum
   const int lx0 = cx > 0 ? (int)lane - 1 : (int)lane, lx1 = cx < 7 ? (int)lane + 1 : (int)lane;
   const int ly0 = cy > 0 ? (int)lane - 8 : (int)lane, ly1 = cy < 7 ? (int)lane + 8 : (int)lane;
-  uint32_t v[8];
-#pragma unroll
-  for (int z = 0; z < 8; ++z) v[z] = ((fw[z] >> lane) & 1ull) ? (uint32_t)z * 64u + lane : NO_LABEL;
   for (int sweep = 0; sweep < 512; ++sweep) {  // a label falls by at least one cell of its component a sweep
     uint32_t nv[8];
     bool changed = false;
@@ -268,75 +257,15 @@ __global__ __launch_bounds__(QT) void k_wf_label_local(const u64 *__restrict__ f
     for (int z = 0; z < 8; ++z) v[z] = nv[z];
     if (!__ballot(changed)) break;
   }
-#pragma unroll
-  for (int z = 0; z < 8; ++z) {
-    if (v[z] == NO_LABEL) continue;
-    const uint32_t lz = v[z] >> 6, lb = v[z] & 63u;  // the local root: a cell word <= this cell's
-    const uint32_t at = pre[(size_t)r * 8u + z] + lane_rank(fw[z], lane);
-    const uint32_t root = pre[(size_t)r * 8u + lz] + lane_rank(front[(size_t)r * 8u + lz], lb);
-    if (at < n_cells) parent[at] = root;
-  }
+  store_local_roots(v, fw, front, pre, r, lane, n_cells, parent);
 }
 
 // ---- labels, across the seams -------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t parent_of(uint32_t *__restrict__ parent, uint32_t a) {
-  return __hip_atomic_load(parent + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t lower_parent(uint32_t *__restrict__ parent, uint32_t a, uint32_t v) {  // -> what it was
-  return __hip_atomic_fetch_min(parent + a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// the root of a, halving the path on the way (a parent is only ever lowered to an ancestor: still the same component;
-// every step goes to a strictly smaller index: at most n_cells steps)
-__device__ __forceinline__ uint32_t find_root(uint32_t *__restrict__ parent, uint32_t a) {
-  for (;;) {
-    const uint32_t p = parent_of(parent, a);
-    if (p >= a) return a;  // (p == a: a root; never above)
-    const uint32_t gp = parent_of(parent, p);
-    if (gp >= p) return p;
-    lower_parent(parent, a, gp);
-    a = gp;
-  }
-}
-__device__ __forceinline__ void unite(uint32_t *__restrict__ parent, uint32_t a, uint32_t b) {
-  for (;;) {
-    a = find_root(parent, a);
-    b = find_root(parent, b);
-    if (a == b) return;
-    const uint32_t hi = max(a, b), lo = min(a, b);
-    const uint32_t old = lower_parent(parent, hi, lo);
-    if (old == hi) return;  // hi was still a root and now hangs below lo
-    a = old;                // somebody linked hi below `old` (< hi) first: old and lo remain to be united
-    b = lo;
-  }
-}
-
 template <bool FACE>
 __global__ __launch_bounds__(QT) void k_wf_seams(const uint32_t *__restrict__ nbr, const u64 *__restrict__ front, const uint32_t *__restrict__ pre,
                                                  uint32_t n, uint32_t n_cells, uint32_t *__restrict__ parent) {
-  const uint32_t lane = threadIdx.x & 63u;
   const uint32_t i = blockIdx.x * (QT / 64) + (threadIdx.x >> 6);
-  if (i >= n * 8u) return;  // (wave-uniform)
-  const u64 fw = front[i];
-  const uint32_t r = i >> 3;
-  const int lx = (int)(lane & 7u), ly = (int)(lane >> 3), lz = (int)(i & 7u);
-  const bool shell = lx == 0 || lx == 7 || ly == 0 || ly == 7 || lz == 0 || lz == 7;
-  if (!((fw >> lane) & 1ull) || !shell) return;
-  const uint32_t at = pre[i] + lane_rank(fw, lane);
-  if (at >= n_cells) return;  // (never)
-#pragma unroll
-  for (int k = 0; k < 27; ++k) {
-    if (k == 13 || (FACE && face_of(k) < 0)) continue;
-    const int x = lx + off_d(k, 0), y = ly + off_d(k, 1), z = lz + off_d(k, 2);
-    const int ox = brick_off(x), oy = brick_off(y), oz = brick_off(z);
-    if (ox == 0 && oy == 0 && oz == 0) continue;  // inside the brick: k_wf_label_local has united them
-    const uint32_t nr = nbr[(size_t)r * 27u + (uint32_t)(13 + ox + 3 * oy + 9 * oz)];
-    if (nr >= r) continue;  // absent, outside the field, or later in cell order: that cell unites with this one
-    const uint32_t wi = nr * 8u + (uint32_t)(z & 7), b = (uint32_t)((x & 7) + 8 * (y & 7));
-    const u64 nw = front[wi];
-    if (!((nw >> b) & 1ull)) continue;
-    const uint32_t other = pre[wi] + lane_rank(nw, b);
-    if (other < n_cells) unite(parent, at, other);
-  }
+  seam_unions<FACE>(nbr, front, pre, i >> 3, (int)(i & 7u), threadIdx.x & 63u, n, n_cells, parent, [](uint32_t) { return 0u; });  // (one key: every frontier cell joins every other)
 }
 
 // ---- accumulators ------------------------------------------------------------------------------------------------------
@@ -457,58 +386,29 @@ __global__ __launch_bounds__(QT) void k_wf_table(const uint32_t *__restrict__ ro
 // stream is idle if there were buffers before)
 sdm_status grow_arch(sdm_map *m, size_t n_arch, size_t slots) {
   WorldFrontiersLayer &L = m->wfront;
-  if (n_arch + 1 > L.cap_arch) {
-    release(m, &L.flag), release(m, &L.rank), release(m, &L.free_m), release(m, &L.unk_m);
-    L.cap_arch = 0;
-    const size_t cap = (n_arch + 1 + 255) & ~(size_t)255;
-    SDM_TRY(alloc_tracked(m, &L.flag, cap));
-    SDM_TRY(alloc_tracked(m, &L.rank, cap));
-    SDM_TRY(alloc_tracked(m, &L.free_m, cap * 8));
-    SDM_TRY(alloc_tracked(m, &L.unk_m, cap * 8));
-    L.cap_arch = cap;
-  }
-  if (slots > L.cap_slots) {
-    release(m, &L.place_of_slot);
-    L.cap_slots = 0;
-    SDM_TRY(alloc_tracked(m, &L.place_of_slot, slots));
-    L.cap_slots = slots;
-  }
-  return SDM_OK;
+  const size_t cap = round_up(n_arch + 1, 256);
+  SDM_TRY(grow_buffers(m, n_arch + 1, cap, &L.cap_arch, {buf(&L.flag, cap), buf(&L.rank, cap), buf(&L.free_m, cap * 8), buf(&L.unk_m, cap * 8)}));
+  return grow_buffers(m, slots, slots, &L.cap_slots, {buf(&L.place_of_slot, slots)});
 }
 
 sdm_status grow_bricks(sdm_map *m, size_t bricks) {
   WorldFrontiersLayer &L = m->wfront;
-  if (bricks <= L.cap_bricks) return SDM_OK;
-  release(m, &L.coord), release(m, &L.place), release(m, &L.nbr), release(m, &L.face_place), release(m, &L.front), release(m, &L.pre);
-  L.cap_bricks = 0;
-  const size_t cap = (bricks + 255) & ~(size_t)255;
-  SDM_TRY(alloc_tracked(m, &L.coord, cap * 2));
-  SDM_TRY(alloc_tracked(m, &L.place, cap));
-  SDM_TRY(alloc_tracked(m, &L.nbr, cap * 27));
-  SDM_TRY(alloc_tracked(m, &L.face_place, cap * 6));
-  SDM_TRY(alloc_tracked(m, &L.front, cap * 8 + 1));
-  SDM_TRY(alloc_tracked(m, &L.pre, cap * 8 + 1));
-  L.cap_bricks = cap;
-  return SDM_OK;
+  const size_t cap = round_up(bricks, 256);
+  return grow_buffers(m, bricks, cap, &L.cap_bricks,
+                      {buf(&L.coord, cap * 2), buf(&L.place, cap), buf(&L.nbr, cap * 27), buf(&L.face_place, cap * 6), buf(&L.front, cap * 8 + 1),
+                       buf(&L.pre, cap * 8 + 1)});
 }
 
 sdm_status grow_cells(sdm_map *m, size_t cells) {
   WorldFrontiersLayer &L = m->wfront;
-  if (cells <= L.cap_cells) return SDM_OK;
-  release(m, &L.acc), release(m, &L.table), release(m, &L.xyz), release(m, &L.parent), release(m, &L.root), release(m, &L.idx);
-  release(m, &L.faces);
-  L.cap_cells = 0;
-  const size_t cap = (cells + 4095) & ~(size_t)4095;
-  SDM_TRY(alloc_tracked(m, &L.acc, cap * sizeof(WfAcc)));
-  SDM_TRY(alloc_tracked(m, &L.table, cap));
-  SDM_TRY(alloc_tracked(m, &L.xyz, cap * 3));
-  SDM_TRY(alloc_tracked(m, &L.parent, cap));
-  SDM_TRY(alloc_tracked(m, &L.root, cap));
-  SDM_TRY(alloc_tracked(m, &L.idx, cap + 1));
-  SDM_TRY(alloc_tracked(m, &L.faces, cap));
-  HIP_TRY(hipMemsetAsync(L.acc, 0, cap * sizeof(WfAcc), m->stream));  // empty; every build leaves them empty again
-  L.cap_cells = cap;
-  return SDM_OK;
+  const size_t cap = round_up(cells, 4096);
+  return grow_buffers(m, cells, cap, &L.cap_cells,
+                      {buf(&L.acc, cap * sizeof(WfAcc)), buf(&L.table, cap), buf(&L.xyz, cap * 3), buf(&L.parent, cap), buf(&L.root, cap),
+                       buf(&L.idx, cap + 1), buf(&L.faces, cap)},
+                      [&]() -> sdm_status {
+                        HIP_TRY(hipMemsetAsync(L.acc, 0, cap * sizeof(WfAcc), m->stream));  // empty; every build leaves them empty again
+                        return SDM_OK;
+                      });
 }
 
 // up to the frontier words and their counts

@@ -459,31 +459,16 @@ size_t scan_length_for(size_t elems) { return std::max<size_t>(elems, 1032 + 513
 // the buffers for n_arch archived bricks / for `tiles` tiles (the stream is idle when either is called)
 sdm_status grow_arch(sdm_map *m, size_t n_arch) {
   WorldGroundLayer &L = m->wground;
-  if (n_arch + 1 <= L.cap_arch) return SDM_OK;
-  release(m, &L.flag), release(m, &L.rank), release(m, &L.keys), release(m, &L.vals);
-  L.cap_arch = 0;
-  const size_t cap = (n_arch + 1 + 255) & ~(size_t)255;
-  SDM_TRY(alloc_tracked(m, &L.flag, cap));
-  SDM_TRY(alloc_tracked(m, &L.rank, cap));
-  SDM_TRY(alloc_tracked(m, &L.keys, table_slots(cap)));
-  SDM_TRY(alloc_tracked(m, &L.vals, table_slots(cap)));
-  L.cap_arch = cap;
-  return SDM_OK;
+  const size_t cap = round_up(n_arch + 1, 256);
+  return grow_buffers(m, n_arch + 1, cap, &L.cap_arch,
+                      {buf(&L.flag, cap), buf(&L.rank, cap), buf(&L.keys, table_slots(cap)), buf(&L.vals, table_slots(cap))});
 }
 
-sdm_status grow_tiles(sdm_map *m, size_t tiles) {
+sdm_status grow_tiles(sdm_map *m, size_t tiles) {  // (no tile: still buffers to hand out)
   WorldGroundLayer &L = m->wground;
-  if (L.cap_tiles && tiles <= L.cap_tiles) return SDM_OK;
-  release(m, &L.coord), release(m, &L.cells), release(m, &L.d2), release(m, &L.lethal), release(m, &L.sortbuf);
-  L.cap_tiles = 0;
-  const size_t cap = (std::max<size_t>(tiles, 1) + 255) & ~(size_t)255;
-  SDM_TRY(alloc_tracked(m, &L.coord, cap));
-  SDM_TRY(alloc_tracked(m, &L.cells, cap * 64));
-  SDM_TRY(alloc_tracked(m, &L.d2, cap * 64));
-  SDM_TRY(alloc_tracked(m, &L.lethal, cap));
-  SDM_TRY(alloc_tracked(m, &L.sortbuf, cap * 4));
-  L.cap_tiles = cap;
-  return SDM_OK;
+  const size_t need = std::max<size_t>(tiles, 1), cap = round_up(need, 256);
+  return grow_buffers(m, need, cap, &L.cap_tiles,
+                      {buf(&L.coord, cap), buf(&L.cells, cap * 64), buf(&L.d2, cap * 64), buf(&L.lethal, cap), buf(&L.sortbuf, cap * 4)});
 }
 
 Band band_of(const sdm_world_ground_options &o) {

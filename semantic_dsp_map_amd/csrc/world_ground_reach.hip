@@ -457,24 +457,13 @@ __global__ __launch_bounds__(QT) void k_world_ground_reach_paths(const float *__
 constexpr uint32_t REACH_BATCH = 8;  // rounds issued between two looks at the count
 
 // the buffers for `tiles` tiles (the stream is idle if there were buffers before)
-sdm_status reach_alloc(sdm_map *m, size_t tiles) {
+sdm_status reach_alloc(sdm_map *m, size_t need) {  // (no tile: still a table to look up in)
   WorldGroundReachLayer &L = m->wgreach;
-  release(m, &L.cost), release(m, &L.trav), release(m, &L.pen), release(m, &L.level), release(m, &L.nbr), release(m, &L.coord);
-  release(m, &L.keys), release(m, &L.vals), release(m, &L.act), release(m, &L.list);
-  L.cap = 0;
-  const uint32_t slots = table_slots(tiles);
-  SDM_TRY(alloc_tracked(m, &L.cost, tiles * 64));
-  SDM_TRY(alloc_tracked(m, &L.trav, tiles));
-  SDM_TRY(alloc_tracked(m, &L.pen, tiles));
-  SDM_TRY(alloc_tracked(m, &L.level, tiles * 64));
-  SDM_TRY(alloc_tracked(m, &L.nbr, tiles * 8));
-  SDM_TRY(alloc_tracked(m, &L.coord, tiles));
-  SDM_TRY(alloc_tracked(m, &L.keys, slots));
-  SDM_TRY(alloc_tracked(m, &L.vals, slots));
-  SDM_TRY(alloc_tracked(m, &L.act, (tiles + 31) / 32));
-  SDM_TRY(alloc_tracked(m, &L.list, tiles));
-  L.cap = tiles;
-  return SDM_OK;
+  need = std::max<size_t>(need, 1);
+  const size_t tiles = round_up(need, 256), slots = table_slots(tiles);
+  return grow_buffers(m, need, tiles, &L.cap,
+                      {buf(&L.cost, tiles * 64), buf(&L.trav, tiles), buf(&L.pen, tiles), buf(&L.level, tiles * 64), buf(&L.nbr, tiles * 8),
+                       buf(&L.coord, tiles), buf(&L.keys, slots), buf(&L.vals, slots), buf(&L.act, (tiles + 31) / 32), buf(&L.list, tiles)});
 }
 
 Plane plane_of(const sdm_world_ground_options &g) {
@@ -575,7 +564,7 @@ sdm_status sdm_world_ground_reach_update(sdm_map *m, const sdm_world_ground_reac
     SDM_TRY(snapshot_rank(m, flag, rank, n_g, scan, L.h_meta, &n));
     n = std::min(n, n_g);
   }
-  if (!L.cap || n > L.cap) SDM_TRY(reach_alloc(m, ((size_t)std::max<uint32_t>(n, 1u) + 255) & ~(size_t)255));
+  SDM_TRY(reach_alloc(m, n));
   L.n = n;
   L.hmask = table_slots(n) - 1;
   unsigned char *d_starts = nullptr;

@@ -70,7 +70,6 @@ constexpr uint32_t ALL_WM_FLAGS = SDM_WORLD_MESH_STATIC_ONLY | SDM_WORLD_MESH_MO
 enum { C_SOLID = 0, C_DIR = 1, C_KIND = 7, C_COUNTS = 11, C_VB = 11, C_VERTS = 12, C_FACES = 13, C_WORDS = 16 };
 constexpr int SUM_BLOCKS = 16;   // workgroups of k_wm_sums
 constexpr uint32_t KEY_LO_BITS = 27;  // a vertex brick's key is sorted as 27 + 24 bits: three 9-bit digits each
-constexpr u64 COL0 = 0x0101010101010101ull, COL7 = 0x8080808080808080ull, ROW0 = 0xffull, ROW7 = 0xffull << 56;
 
 constexpr size_t ARCH_BYTES = 4 + 4 + 3 * 8 * 8;              // flag, rank, solid, unknown and occupied words
 constexpr size_t BRICK_BYTES = 8 + 4 + 6 * 4 + 2 * 8 * 4 + 8 * 4;  // coord, slot, nbr, owners' slot and rank, pre (and 44 B of counts per 8)
@@ -132,10 +131,8 @@ __global__ __launch_bounds__(QT) void k_wm_classify(const uint32_t *__restrict__
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t slot = blockIdx.x * (QT / 64) + (threadIdx.x >> 6);  // (the pool is dense: n_arch slots are in use)
   if (slot >= n_arch) return;                                          // (wave-uniform)
-  const uint32_t *__restrict__ src = cells + (size_t)slot * 512u + lane;
   uint32_t w[8];
-#pragma unroll
-  for (int l = 0; l < 8; ++l) w[l] = src[l * 64];
+  load_brick(cells, slot, lane, w);
 #pragma unroll
   for (int l = 0; l < 8; ++l) {
     const int occ = occ_of(w[l]);
@@ -179,13 +176,7 @@ __global__ __launch_bounds__(QT) void k_wm_neighbours(const uint32_t *__restrict
 // of an absent brick read 0
 template <int DIR>
 __device__ __forceinline__ u64 across(const u64 *__restrict__ M, uint32_t slot, const uint32_t (&nb)[6], int z, u64 own) {
-  if (DIR < 4) {
-    const u64 w = nb[DIR] != NONE ? M[(size_t)nb[DIR] * 8u + (uint32_t)z] : 0ull;
-    if (DIR == 0) return ((own << 1) & ~COL0) | ((w >> 7) & COL0);  // cx - 1: the bit below; column 0 looks at the neighbour's column 7
-    if (DIR == 1) return ((own >> 1) & ~COL7) | ((w << 7) & COL7);
-    if (DIR == 2) return (own << 8) | (w >> 56);                    // cy - 1: the row below; row 0 looks at the neighbour's row 7
-    return (own >> 8) | (w << 56);
-  }
+  if constexpr (DIR < 4) return across_lateral<DIR>(own, nb[DIR] != NONE ? M[(size_t)nb[DIR] * 8u + (uint32_t)z] : 0ull);
   if (DIR == 4) return z > 0 ? M[(size_t)slot * 8u + (uint32_t)(z - 1)] : nb[4] != NONE ? M[(size_t)nb[4] * 8u + 7u] : 0ull;
   return z < 7 ? M[(size_t)slot * 8u + (uint32_t)(z + 1)] : nb[5] != NONE ? M[(size_t)nb[5] * 8u] : 0ull;
 }
@@ -511,69 +502,31 @@ size_t scan_length_for(size_t elems) { return std::max<size_t>(elems, 1032 + 513
 // idle when any of them is called)
 sdm_status grow_arch(sdm_map *m, size_t n_arch) {
   WorldMeshLayer &L = m->wmesh;
-  if (n_arch + 1 <= L.cap_arch) return SDM_OK;
-  release(m, &L.flag), release(m, &L.rank), release(m, &L.solid_m), release(m, &L.unk_m), release(m, &L.occ_m);
-  L.cap_arch = 0;
-  const size_t cap = (n_arch + 1 + 255) & ~(size_t)255;
-  SDM_TRY(alloc_tracked(m, &L.flag, cap));
-  SDM_TRY(alloc_tracked(m, &L.rank, cap));
-  SDM_TRY(alloc_tracked(m, &L.solid_m, cap * 8));
-  SDM_TRY(alloc_tracked(m, &L.unk_m, cap * 8));
-  SDM_TRY(alloc_tracked(m, &L.occ_m, cap * 8));
-  L.cap_arch = cap;
-  return SDM_OK;
+  const size_t cap = round_up(n_arch + 1, 256);
+  return grow_buffers(m, n_arch + 1, cap, &L.cap_arch,
+                      {buf(&L.flag, cap), buf(&L.rank, cap), buf(&L.solid_m, cap * 8), buf(&L.unk_m, cap * 8), buf(&L.occ_m, cap * 8)});
 }
 
 sdm_status grow_bricks(sdm_map *m, size_t bricks) {
   WorldMeshLayer &L = m->wmesh;
-  if (bricks <= L.cap_bricks) return SDM_OK;
-  release(m, &L.coord), release(m, &L.slot_of), release(m, &L.nbr), release(m, &L.own_h), release(m, &L.own_i), release(m, &L.pre);
-  release(m, &L.vkeys), release(m, &L.vvals), release(m, &L.vmask), release(m, &L.vflag), release(m, &L.rows), release(m, &L.vrows);
-  L.cap_bricks = L.cap_slots = 0;
-  const size_t cap = (bricks + 255) & ~(size_t)255, slots = table_slots(8 * cap);
-  SDM_TRY(alloc_tracked(m, &L.coord, cap * 2));
-  SDM_TRY(alloc_tracked(m, &L.slot_of, cap));
-  SDM_TRY(alloc_tracked(m, &L.nbr, cap * 6));
-  SDM_TRY(alloc_tracked(m, &L.own_h, cap * 8));
-  SDM_TRY(alloc_tracked(m, &L.own_i, cap * 8));
-  SDM_TRY(alloc_tracked(m, &L.pre, cap * 8 + 1));
-  SDM_TRY(alloc_tracked(m, &L.vkeys, slots));
-  SDM_TRY(alloc_tracked(m, &L.vvals, slots));
-  SDM_TRY(alloc_tracked(m, &L.vmask, slots * 8));
-  SDM_TRY(alloc_tracked(m, &L.vflag, slots + 1));
-  SDM_TRY(alloc_tracked(m, &L.rows, (cap / 8 + 1) * C_COUNTS));
-  SDM_TRY(alloc_tracked(m, &L.vrows, slots / 64 + 1));
-  L.cap_bricks = cap;
-  L.cap_slots = slots;
-  return SDM_OK;
+  const size_t cap = round_up(bricks, 256), slots = table_slots(8 * cap);
+  if (bricks > L.cap_bricks) L.cap_slots = 0;  // (grow_buffers' own test: the two capacities fall and rise together)
+  return grow_buffers(m, bricks, cap, &L.cap_bricks,
+                      {buf(&L.coord, cap * 2), buf(&L.slot_of, cap), buf(&L.nbr, cap * 6), buf(&L.own_h, cap * 8), buf(&L.own_i, cap * 8),
+                       buf(&L.pre, cap * 8 + 1), buf(&L.vkeys, slots), buf(&L.vvals, slots), buf(&L.vmask, slots * 8), buf(&L.vflag, slots + 1),
+                       buf(&L.rows, (cap / 8 + 1) * C_COUNTS), buf(&L.vrows, slots / 64 + 1)},
+                      [&]() -> sdm_status {
+                        L.cap_slots = slots;
+                        return SDM_OK;
+                      });
 }
 
 sdm_status grow_lists(sdm_map *m, size_t vb, size_t n_faces, size_t n_verts) {
   WorldMeshLayer &L = m->wmesh;
-  if (vb > L.cap_vb) {
-    release(m, &L.sortbuf), release(m, &L.vpre);
-    L.cap_vb = 0;
-    const size_t cap = (vb + 255) & ~(size_t)255;
-    SDM_TRY(alloc_tracked(m, &L.sortbuf, cap * 4));
-    SDM_TRY(alloc_tracked(m, &L.vpre, cap * 8 + 1));
-    L.cap_vb = cap;
-  }
-  if (n_faces > L.cap_f) {
-    release(m, &L.faces), release(m, &L.quads);
-    L.cap_f = 0;
-    const size_t cap = (n_faces + 4095) & ~(size_t)4095;
-    SDM_TRY(alloc_tracked(m, &L.faces, cap * 3));
-    SDM_TRY(alloc_tracked(m, &L.quads, cap * 4));
-    L.cap_f = cap;
-  }
-  if (n_verts > L.cap_v) {
-    release(m, &L.corners);
-    L.cap_v = 0;
-    const size_t cap = (n_verts + 4095) & ~(size_t)4095;
-    SDM_TRY(alloc_tracked(m, &L.corners, cap * 3));
-    L.cap_v = cap;
-  }
-  return SDM_OK;
+  const size_t cap_vb = round_up(vb, 256), cap_f = round_up(n_faces, 4096), cap_v = round_up(n_verts, 4096);
+  SDM_TRY(grow_buffers(m, vb, cap_vb, &L.cap_vb, {buf(&L.sortbuf, cap_vb * 4), buf(&L.vpre, cap_vb * 8 + 1)}));
+  SDM_TRY(grow_buffers(m, n_faces, cap_f, &L.cap_f, {buf(&L.faces, cap_f * 3), buf(&L.quads, cap_f * 4)}));
+  return grow_buffers(m, n_verts, cap_v, &L.cap_v, {buf(&L.corners, cap_v * 3)});
 }
 
 Masks masks_of(const WorldMeshLayer &L) { return Masks{L.solid_m, L.unk_m, L.occ_m}; }

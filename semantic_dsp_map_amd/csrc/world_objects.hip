@@ -8,8 +8,8 @@
 // smallest list index whatever order the unions arrive in: two builds give the same bytes.
 //   snapshot_bricks, launch_snapshot_index   world_snapshot.hip's: the bricks of the box flagged and ranked, their
 //               coordinates and pool slots at their rank, key -> rank in the layer's table.
-//   k_wo_neighbours  a thread per (brick of the field, one of 27): one lookup in the layer's table, the neighbour's rank
-//               or NONE.  brick_in_range before every lookup.
+//   launch_snapshot_neighbours   world_snapshot.hip's k_ws_neighbours: a thread per (brick of the field, one of 27): one
+//               lookup in the layer's table, the neighbour's rank or NONE.  brick_in_range before every lookup.
 //   k_wo_classify    a wave per field brick, a lane per (cx, cy), the eight layers' loads first: a ballot a layer writes the
 //               counted word (occ >= 1, the flags, the label mask) and its popcount, a second one counts occ == 2.
 //               exclusive_scan_u32 over the 8 n + 1 popcounts gives every word's first list index and the cell count.
@@ -25,9 +25,10 @@
 //               nothing (at most 512 sweeps).  parent[] of a cell becomes the list index of its local component's smallest
 //               cell: no LDS, no global atomic.
 //   k_wo_seams       a wave per word, a lane per cell: a counted cell on the brick's shell looks at its 26 (6) neighbours
-//               that lie in a field brick of lower rank and unites with those that are counted and carry an equal key, by
-//               the min-linking union-find of world_frontiers.hip.  Every read of parent[] in this launch is an agent-scope
-//               atomic load or an atomic's return value.  Lock-free: a failed link hands the loop a strictly smaller root.
+//               that lie in a field brick of lower rank and unites with those that are counted and carry an equal key:
+//               sdm_world.h's seam_unions over its min-linking union-find, which world_frontiers.hip runs with one key for
+//               all.  Every read of parent[] in this launch is an agent-scope atomic load or an atomic's return value.
+//               Lock-free: a failed link hands the loop a strictly smaller root.
 //   k_wo_roots       a thread per cell: follows parent[] to the root (plain loads: a later launch), writes root[] and the
 //               root flag; exclusive_scan_u32 over n + 1 flags ranks the roots and counts them - the build's third wait,
 //               after which accumulators and table are sized by objects, not by cells.
@@ -42,7 +43,9 @@
 //   k_query_world_objects   a thread per entry: its cell, the layer's own table -> rank, the bit of the counted word,
 //               index = prefix + popcount of the lower bits, object[index]; three 8-byte stores.
 // The build waits three times: for the number of bricks of the field, for the number of cells, for the number of objects.
-// This unit includes no code of a frame unit and defines every kernel it launches but those of world_snapshot.hip.
+// This unit includes no code of a frame unit and defines every kernel it launches but those of world_snapshot.hip; the
+// opening and the end of the local labelling, the seam body, the union-find, the offset tables and the brick loads are
+// sdm_world.h's, shared with world_frontiers.hip; the sweeps are its own (5v says why they differ).
 #include "sdm_world.h"
 
 #pragma clang fp contract(off)
@@ -66,8 +69,7 @@ constexpr int QT = 256;             // the kernels of a thread or a wave per ite
 constexpr uint32_t WO_GRID = 4096;  // the largest grid of the kernels over cells: they stride
 constexpr uint32_t ALL_WO_FLAGS = SDM_WORLD_OBJECTS_FACE_CONNECTED | SDM_WORLD_OBJECTS_BOX | SDM_WORLD_OBJECTS_BY_TRACK |
                                   SDM_WORLD_OBJECTS_STATIC_ONLY | SDM_WORLD_OBJECTS_MOVABLE_ONLY | SDM_WORLD_OBJECTS_OBSERVED_ONLY;
-constexpr uint32_t NO_LABEL = 0xffffu;     // k_wo_label_local: the cell is not counted
-constexpr uint32_t NO_KEY = 0xffffffffu;   // ... and its key (a key has 24 bits at most)
+constexpr uint32_t NO_KEY = 0xffffffffu;   // k_wo_label_local: the key of a cell that is not counted (a key has 24 bits at most)
 // the build's counters, 64 bits each: the guessed cells in G_SPREAD copies (a wave adds to copy rank & 63, the getter sums
 // them), the objects listed, per label the cells, per label the objects (32 bits each, two a word)
 enum { G_GUESSED = 0, G_SPREAD = 64, G_LISTED = G_SPREAD, G_LAB_CELLS, G_LAB_OBJS = G_LAB_CELLS + 256, G_WORDS = G_LAB_OBJS + 128 };
@@ -91,10 +93,6 @@ static_assert(ARCH_BYTES == SDM_WORLD_OBJECTS_BYTES_PER_ARCHIVED_BRICK && BRICK_
                   (2 * G_WORDS + 1) * 8 == 7192,
               "sdm.h states the bytes");
 
-constexpr int off_d(int k, int a) { return a == 0 ? k % 3 - 1 : a == 1 ? (k / 3) % 3 - 1 : k / 9 - 1; }
-constexpr bool is_face(int k) { return k == 12 || k == 14 || k == 10 || k == 16 || k == 4 || k == 22; }
-constexpr int nb_bit(int dx, int dy, int dz) { return (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1); }
-
 __device__ __forceinline__ uint32_t key_of(uint32_t w, uint32_t by_track) { return by_track ? (w & 0xffffffu) : ((w >> 16) & 0xffu); }
 
 __device__ __forceinline__ bool counts(uint32_t w, const WoRule &q) {
@@ -108,20 +106,7 @@ __device__ __forceinline__ bool counts(uint32_t w, const WoRule &q) {
          !(q.observed_only && occ == 2);
 }
 
-// ---- neighbours, counted words -----------------------------------------------------------------------------------------
-__global__ __launch_bounds__(QT) void k_wo_neighbours(const uint32_t *__restrict__ coord, const u64 *__restrict__ keys,
-                                                      const uint32_t *__restrict__ vals, uint32_t hmask, uint32_t n, uint32_t *__restrict__ nbr) {
-  const uint32_t i = blockIdx.x * QT + threadIdx.x;
-  if (i >= n * 27u) return;
-  const uint32_t r = i / 27u, k = i - r * 27u;
-  int bx, by, bz;
-  coord_of(coord, r, bx, by, bz);
-  bx += off_d((int)k, 0), by += off_d((int)k, 1), bz += off_d((int)k, 2);
-  // (a coordinate of 32768 would alias another brick's key)
-  const uint32_t nr = brick_in_range(bx, by, bz) ? world_find(keys, vals, hmask, brick_key(bx, by, bz)) : NONE;
-  nbr[i] = nr < n ? nr : NONE;
-}
-
+// ---- counted words -----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(QT) void k_wo_classify(const uint32_t *__restrict__ slot_of, const uint32_t *__restrict__ cells, uint32_t n,
                                                     uint32_t max_bricks, WoRule rule, u64 *__restrict__ cw, uint32_t *__restrict__ cnt,
                                                     u64 *__restrict__ meta) {
@@ -131,10 +116,8 @@ __global__ __launch_bounds__(QT) void k_wo_classify(const uint32_t *__restrict__
   if (r == 0u && lane == 0u) cw[(size_t)n * 8u] = 0ull, cnt[(size_t)n * 8u] = 0u;  // the entry behind the last word: the scan's total
   const uint32_t slot = slot_of[r];
   if (slot >= max_bricks) return;  // (never: the pool has max_bricks slots; wave-uniform)
-  const uint32_t *__restrict__ src = cells + (size_t)slot * 512u + lane;
   uint32_t w[8];
-#pragma unroll
-  for (int l = 0; l < 8; ++l) w[l] = src[l * 64];
+  load_brick(cells, slot, lane, w);
   uint32_t guessed = 0u;
 #pragma unroll
   for (int l = 0; l < 8; ++l) {
@@ -159,21 +142,17 @@ __global__ __launch_bounds__(QT) void k_wo_compact(const uint32_t *__restrict__ 
   if (r >= n) return;  // (wave-uniform)
   const uint32_t slot = slot_of[r];
   if (slot >= max_bricks) return;  // (never)
-  const uint32_t *__restrict__ src = cells + (size_t)slot * 512u + lane;
   uint32_t w[8];
-#pragma unroll
-  for (int l = 0; l < 8; ++l) w[l] = src[l * 64];
+  load_brick(cells, slot, lane, w);
   int bx, by, bz;
   coord_of(coord, r, bx, by, bz);
 #pragma unroll
   for (int l = 0; l < 8; ++l) {
     const u64 cm = cw[(size_t)r * 8u + l];
     if (!((cm >> lane) & 1ull)) continue;
-    const uint32_t at = pre[(size_t)r * 8u + l] + lane_rank(cm, lane);
+    const uint32_t at = list_index(cw, pre, (size_t)r * 8u + l, lane);
     if (at >= n_cells) continue;  // (never: the scan's total is n_cells)
-    xyz[3 * (size_t)at] = bx * 8 + (int)(lane & 7u);
-    xyz[3 * (size_t)at + 1] = by * 8 + (int)(lane >> 3);
-    xyz[3 * (size_t)at + 2] = bz * 8 + l;
+    store_world_cell(xyz, at, bx, by, bz, lane, l);
     word[at] = w[l];
   }
 }
@@ -193,20 +172,14 @@ __global__ __launch_bounds__(QT) void k_wo_label_local(const uint32_t *__restric
   const uint32_t r = blockIdx.x * (QT / 64) + (threadIdx.x >> 6);
   if (r >= n) return;  // (wave-uniform: nothing below waits for another wave)
   u64 cm[8];
-#pragma unroll
-  for (int z = 0; z < 8; ++z) cm[z] = cw[(size_t)r * 8u + z];
-  if (!(cm[0] | cm[1] | cm[2] | cm[3] | cm[4] | cm[5] | cm[6] | cm[7])) return;
+  uint32_t k[8], v[8], eq[8];
+  if (!local_labels(cw, r, lane, cm, v)) return;
   const uint32_t slot = slot_of[r];
   if (slot >= max_bricks) return;  // (never)
-  const uint32_t *__restrict__ src = cells + (size_t)slot * 512u + lane;
-  uint32_t k[8], v[8], eq[8];
-#pragma unroll
-  for (int z = 0; z < 8; ++z) k[z] = src[z * 64];
+  load_brick(cells, slot, lane, k);
 #pragma unroll
   for (int z = 0; z < 8; ++z) {
-    const bool c = (cm[z] >> lane) & 1ull;
-    k[z] = c ? key_of(k[z], by_track) : NO_KEY;
-    v[z] = c ? (uint32_t)z * 64u + lane : NO_LABEL;
+    k[z] = v[z] != NO_LABEL ? key_of(k[z], by_track) : NO_KEY;  // (a start label: the cell is counted)
     eq[z] = 0u;
   }
   const int cx = (int)(lane & 7u), cy = (int)(lane >> 3);
@@ -272,77 +245,17 @@ __global__ __launch_bounds__(QT) void k_wo_label_local(const uint32_t *__restric
     }
     if (!__ballot(changed)) break;
   }
-#pragma unroll
-  for (int z = 0; z < 8; ++z) {
-    if (v[z] == NO_LABEL) continue;
-    const uint32_t lz = v[z] >> 6, lb = v[z] & 63u;  // the local root: a cell word <= this cell's
-    const uint32_t at = pre[(size_t)r * 8u + z] + lane_rank(cm[z], lane);
-    const uint32_t root = pre[(size_t)r * 8u + lz] + lane_rank(cw[(size_t)r * 8u + lz], lb);
-    if (at < n_cells) parent[at] = root;
-  }
+  store_local_roots(v, cm, cw, pre, r, lane, n_cells, parent);
 }
 
 // ---- labels, across the seams -------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t parent_of(uint32_t *__restrict__ parent, uint32_t a) {
-  return __hip_atomic_load(parent + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t lower_parent(uint32_t *__restrict__ parent, uint32_t a, uint32_t v) {  // -> what it was
-  return __hip_atomic_fetch_min(parent + a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// the root of a, halving the path on the way (a parent is only ever lowered to an ancestor: still the same component;
-// every step goes to a strictly smaller index: at most n_cells steps)
-__device__ __forceinline__ uint32_t find_root(uint32_t *__restrict__ parent, uint32_t a) {
-  for (;;) {
-    const uint32_t p = parent_of(parent, a);
-    if (p >= a) return a;  // (p == a: a root; never above)
-    const uint32_t gp = parent_of(parent, p);
-    if (gp >= p) return p;
-    lower_parent(parent, a, gp);
-    a = gp;
-  }
-}
-__device__ __forceinline__ void unite(uint32_t *__restrict__ parent, uint32_t a, uint32_t b) {
-  for (;;) {
-    a = find_root(parent, a);
-    b = find_root(parent, b);
-    if (a == b) return;
-    const uint32_t hi = max(a, b), lo = min(a, b);
-    const uint32_t old = lower_parent(parent, hi, lo);
-    if (old == hi) return;  // hi was still a root and now hangs below lo
-    a = old;                // somebody linked hi below `old` (< hi) first: old and lo remain to be united
-    b = lo;
-  }
-}
-
 template <bool FACE>
 __global__ __launch_bounds__(QT) void k_wo_seams(const uint32_t *__restrict__ nbr, const u64 *__restrict__ cw, const uint32_t *__restrict__ pre,
                                                  const uint32_t *__restrict__ word, uint32_t n, uint32_t n_cells, uint32_t by_track,
                                                  uint32_t *__restrict__ parent) {
-  const uint32_t lane = threadIdx.x & 63u;
   const uint32_t i = blockIdx.x * (QT / 64) + (threadIdx.x >> 6);
-  if (i >= n * 8u) return;  // (wave-uniform)
-  const u64 cm = cw[i];
-  const uint32_t r = i >> 3;
-  const int lx = (int)(lane & 7u), ly = (int)(lane >> 3), lz = (int)(i & 7u);
-  const bool shell = lx == 0 || lx == 7 || ly == 0 || ly == 7 || lz == 0 || lz == 7;
-  if (!((cm >> lane) & 1ull) || !shell) return;
-  const uint32_t at = pre[i] + lane_rank(cm, lane);
-  if (at >= n_cells) return;  // (never)
-  const uint32_t key = key_of(word[at], by_track);
-#pragma unroll
-  for (int k = 0; k < 27; ++k) {
-    if (k == 13 || (FACE && !is_face(k))) continue;
-    const int x = lx + off_d(k, 0), y = ly + off_d(k, 1), z = lz + off_d(k, 2);
-    const int ox = brick_off(x), oy = brick_off(y), oz = brick_off(z);
-    if (ox == 0 && oy == 0 && oz == 0) continue;  // inside the brick: k_wo_label_local has united them
-    const uint32_t nr = nbr[(size_t)r * 27u + (uint32_t)(13 + ox + 3 * oy + 9 * oz)];
-    if (nr >= r) continue;  // absent, outside the field, or later in cell order: that cell unites with this one
-    const uint32_t wi = nr * 8u + (uint32_t)(z & 7), b = (uint32_t)((x & 7) + 8 * (y & 7));
-    const u64 nw = cw[wi];
-    if (!((nw >> b) & 1ull)) continue;
-    const uint32_t other = pre[wi] + lane_rank(nw, b);
-    if (other < n_cells && key_of(word[other], by_track) == key) unite(parent, at, other);
-  }
+  seam_unions<FACE>(nbr, cw, pre, i >> 3, (int)(i & 7u), threadIdx.x & 63u, n, n_cells, parent,
+                    [=](uint32_t c) { return key_of(word[c], by_track); });
 }
 
 // ---- roots -------------------------------------------------------------------------------------------------------------
@@ -524,7 +437,7 @@ __global__ __launch_bounds__(QT) void k_query_world_objects(const float *__restr
     const uint32_t wi = r * 8u + (uint32_t)(g[2] & 7), b = (uint32_t)((g[0] & 7) | ((g[1] & 7) << 3));
     const u64 cm = cw[wi];
     if ((cm >> b) & 1ull) {
-      const uint32_t at = pre[wi] + lane_rank(cm, b);
+      const uint32_t at = list_index(cw, pre, wi, b);
       if (at < n_cells) index = at, obj = object[at];
     }
   }
@@ -538,61 +451,33 @@ __global__ __launch_bounds__(QT) void k_query_world_objects(const float *__restr
 // idle if there were buffers before)
 sdm_status grow_arch(sdm_map *m, size_t n_arch) {
   WorldObjectsLayer &L = m->wobj;
-  if (n_arch + 1 <= L.cap_arch) return SDM_OK;
-  release(m, &L.flag), release(m, &L.rank);
-  L.cap_arch = 0;
-  const size_t cap = (n_arch + 1 + 255) & ~(size_t)255;
-  SDM_TRY(alloc_tracked(m, &L.flag, cap));
-  SDM_TRY(alloc_tracked(m, &L.rank, cap));
-  L.cap_arch = cap;
-  return SDM_OK;
+  const size_t cap = round_up(n_arch + 1, 256);
+  return grow_buffers(m, n_arch + 1, cap, &L.cap_arch, {buf(&L.flag, cap), buf(&L.rank, cap)});
 }
 
-sdm_status grow_bricks(sdm_map *m, size_t bricks) {
+sdm_status grow_bricks(sdm_map *m, size_t bricks) {  // (no brick: still a table to look up in)
   WorldObjectsLayer &L = m->wobj;
-  if (L.cap_bricks && bricks <= L.cap_bricks) return SDM_OK;
-  release(m, &L.coord), release(m, &L.slot_of), release(m, &L.nbr), release(m, &L.cw), release(m, &L.pre), release(m, &L.keys), release(m, &L.vals);
-  L.cap_bricks = 0;
-  const size_t cap = (std::max<size_t>(bricks, 1) + 255) & ~(size_t)255;
-  SDM_TRY(alloc_tracked(m, &L.coord, cap * 2));
-  SDM_TRY(alloc_tracked(m, &L.slot_of, cap));
-  SDM_TRY(alloc_tracked(m, &L.nbr, cap * 27));
-  SDM_TRY(alloc_tracked(m, &L.cw, cap * 8 + 1));
-  SDM_TRY(alloc_tracked(m, &L.pre, cap * 8 + 1));
-  SDM_TRY(alloc_tracked(m, &L.keys, table_slots(cap)));
-  SDM_TRY(alloc_tracked(m, &L.vals, table_slots(cap)));
-  L.cap_bricks = cap;
-  return SDM_OK;
+  const size_t need = std::max<size_t>(bricks, 1), cap = round_up(need, 256);
+  return grow_buffers(m, need, cap, &L.cap_bricks,
+                      {buf(&L.coord, cap * 2), buf(&L.slot_of, cap), buf(&L.nbr, cap * 27), buf(&L.cw, cap * 8 + 1), buf(&L.pre, cap * 8 + 1),
+                       buf(&L.keys, table_slots(cap)), buf(&L.vals, table_slots(cap))});
 }
 
 sdm_status grow_cells(sdm_map *m, size_t cells) {
   WorldObjectsLayer &L = m->wobj;
-  if (cells <= L.cap_cells) return SDM_OK;
-  release(m, &L.xyz), release(m, &L.word), release(m, &L.parent), release(m, &L.root), release(m, &L.idx);
-  L.cap_cells = 0;
-  const size_t cap = (cells + 4095) & ~(size_t)4095;
-  SDM_TRY(alloc_tracked(m, &L.xyz, cap * 3));
-  SDM_TRY(alloc_tracked(m, &L.word, cap));
-  SDM_TRY(alloc_tracked(m, &L.parent, cap));
-  SDM_TRY(alloc_tracked(m, &L.root, cap));
-  SDM_TRY(alloc_tracked(m, &L.idx, cap + 1));
-  L.cap_cells = cap;
-  return SDM_OK;
+  const size_t cap = round_up(cells, 4096);
+  return grow_buffers(m, cells, cap, &L.cap_cells,
+                      {buf(&L.xyz, cap * 3), buf(&L.word, cap), buf(&L.parent, cap), buf(&L.root, cap), buf(&L.idx, cap + 1)});
 }
 
 sdm_status grow_objects(sdm_map *m, size_t objects) {
   WorldObjectsLayer &L = m->wobj;
-  if (objects <= L.cap_objects) return SDM_OK;
-  release(m, &L.acc), release(m, &L.first), release(m, &L.lidx), release(m, &L.table);
-  L.cap_objects = 0;
-  const size_t cap = (objects + 1023) & ~(size_t)1023;
-  SDM_TRY(alloc_tracked(m, &L.acc, cap * sizeof(WoAcc)));
-  SDM_TRY(alloc_tracked(m, &L.first, cap));
-  SDM_TRY(alloc_tracked(m, &L.lidx, cap + 1));
-  SDM_TRY(alloc_tracked(m, &L.table, cap));
-  HIP_TRY(hipMemsetAsync(L.acc, 0, cap * sizeof(WoAcc), m->stream));  // empty; every build leaves them empty again
-  L.cap_objects = cap;
-  return SDM_OK;
+  const size_t cap = round_up(objects, 1024);
+  return grow_buffers(m, objects, cap, &L.cap_objects,
+                      {buf(&L.acc, cap * sizeof(WoAcc)), buf(&L.first, cap), buf(&L.lidx, cap + 1), buf(&L.table, cap)}, [&]() -> sdm_status {
+                        HIP_TRY(hipMemsetAsync(L.acc, 0, cap * sizeof(WoAcc), m->stream));  // empty; every build leaves them empty again
+                        return SDM_OK;
+                      });
 }
 
 WoRule rule_of(const sdm_map *m, const sdm_world_objects_options *o) {
@@ -615,7 +500,7 @@ hipError_t launch_wo_words(const sdm_map *m, const uint32_t *order, uint32_t n_a
   if ((e = hipMemsetAsync(L.keys, 0xff, ((size_t)L.hmask + 1) * sizeof(u64), s)) != hipSuccess) return e;
   if (!n) return hipSuccess;
   if ((e = launch_snapshot_index(m, order, L.flag, L.rank, n_arch, n, L.coord, L.slot_of, L.keys, L.vals, L.hmask)) != hipSuccess) return e;
-  LAYER_LAUNCH(k_wo_neighbours, (n * 27u + QT - 1) / QT, QT, s, L.coord, L.keys, L.vals, L.hmask, n, L.nbr);
+  if ((e = launch_snapshot_neighbours(L.coord, L.keys, L.vals, L.hmask, n, L.nbr, s)) != hipSuccess) return e;
   LAYER_LAUNCH(k_wo_classify, (n + QT / 64 - 1) / (QT / 64), QT, s, L.slot_of, W.cells, n, W.max_bricks, rule, L.cw, L.pre, L.meta);
   return hipSuccess;
 }

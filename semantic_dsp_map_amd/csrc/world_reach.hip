@@ -9,7 +9,8 @@
 // relaxation, so it is the same whatever order the device relaxes in.
 //   snapshot_bricks, launch_snapshot_index   world_snapshot.hip's: the bricks of the box flagged and ranked, their
 //               coordinates and pool slots (a temporary of the build) at their rank, key -> rank in the field's own table.
-//   k_wr_neighbours  a thread per (brick, one of 27): one lookup, the rank or NONE; brick_in_range before every lookup.
+//   launch_snapshot_neighbours   world_snapshot.hip's k_ws_neighbours: a thread per (brick, one of 27): one lookup, the rank
+//               or NONE; brick_in_range before every lookup.
 //   k_wr_classify    a wave per brick, a lane per (cx, cy), the eight layers' loads first: ballots write the traversable
 //               and the obstacle mask, 8 x 64 bits each, and 0xffffffff goes into the 512 costs.
 //   k_wr_inflate     (inflate > 0) a thread per (brick, layer): clears from the traversable word the dilation of the
@@ -26,7 +27,8 @@
 //   k_query_world_reach   a lane per goal: its cell, one lookup, then the ranks and the 27 costs and traversable words
 //               round the goal issued together; the result leaves in three 8-byte stores.
 //   k_world_reach_paths   a lane per goal, one descent step per two round trips to memory (ranks, then costs).
-// The move masks and the sweep are this unit's own copy of reach.hip's (DESIGN.md 5m says why).
+// The move masks and the sweep are this unit's own copy of reach.hip's (DESIGN.md 5m says why); the 27 offsets and the face
+// moves under them are sdm_world.h's, the world layers' one table (5w).
 #include "sdm_world.h"
 
 #pragma clang fp contract(off)
@@ -52,21 +54,19 @@ constexpr uint32_t ALL_REACH_FLAGS =
 // listed bricks, round r's in R_CNT + (r & 1)
 enum { R_STARTS = 0, R_TRAV, R_REACHED, R_MAXCOST, R_ROUNDS, R_BRICKS, R_CNT, R_WORDS = 8 };
 
-// ---- moves (reach.hip's) ---------------------------------------------------------------------------------------------
-constexpr int move_d(int n, int a) { return a == 0 ? n % 3 - 1 : a == 1 ? (n / 3) % 3 - 1 : n / 9 - 1; }
+// ---- moves (reach.hip's; move n goes by off_d(n, .), the face moves are FACE_MOVES: sdm_world.h) -----------------------
 constexpr uint32_t move_weight(int n) {
-  const int k = (move_d(n, 0) != 0) + (move_d(n, 1) != 0) + (move_d(n, 2) != 0);
+  const int k = (off_d(n, 0) != 0) + (off_d(n, 1) != 0) + (off_d(n, 2) != 0);
   return k == 1 ? 10u : k == 2 ? 14u : 17u;
 }
 constexpr uint32_t move_needs(int n) {
   uint32_t m = 0;
   for (int k = 0; k < 8; ++k) {
-    const int sx = (k & 1) ? move_d(n, 0) : 0, sy = (k & 2) ? move_d(n, 1) : 0, sz = (k & 4) ? move_d(n, 2) : 0;
+    const int sx = (k & 1) ? off_d(n, 0) : 0, sy = (k & 2) ? off_d(n, 1) : 0, sz = (k & 4) ? off_d(n, 2) : 0;
     m |= 1u << ((sz + 1) * 9 + (sy + 1) * 3 + (sx + 1));
   }
   return m;
 }
-constexpr uint32_t FACE_MOVES = (1u << 4) | (1u << 10) | (1u << 12) | (1u << 14) | (1u << 16) | (1u << 22);
 static_assert(move_weight(12) == 10 && move_weight(0) == 17 && move_weight(1) == 14 && move_needs(14) == ((1u << 13) | (1u << 14)), "moves");
 
 template <bool FACE>
@@ -85,19 +85,6 @@ __device__ __forceinline__ uint32_t cost_at(uint32_t r, int cx, int cy, int cz) 
 __device__ __forceinline__ uint32_t trav_word(uint32_t r, int cy, int cz) { return (r * 8u + (uint32_t)cz) * 2u + (uint32_t)(cy >> 2); }
 __device__ __forceinline__ uint32_t trav_bit(int cx, int cy) { return (uint32_t)((cy & 3) * 8 + cx); }
 
-// ---- the index ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(QT) void k_wr_neighbours(const uint32_t *__restrict__ coord, const u64 *__restrict__ keys,
-                                                      const uint32_t *__restrict__ vals, uint32_t hmask, uint32_t n, uint32_t *__restrict__ nbr) {
-  const uint32_t i = blockIdx.x * QT + threadIdx.x;
-  if (i >= n * 27u) return;
-  const uint32_t r = i / 27u, k = i - r * 27u;
-  int bx, by, bz;
-  coord_of(coord, r, bx, by, bz);
-  bx += move_d((int)k, 0), by += move_d((int)k, 1), bz += move_d((int)k, 2);
-  // (a coordinate of 32768 would alias another brick's key)
-  nbr[i] = k == 13u ? r : brick_in_range(bx, by, bz) ? world_find(keys, vals, hmask, brick_key(bx, by, bz)) : NONE;
-}
-
 // ---- the classes -------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(QT) void k_wr_classify(const uint32_t *__restrict__ slot_of, const uint32_t *__restrict__ cells, uint32_t n,
                                                     uint32_t through_unknown, uint32_t ignore_movable, int max_movable, u64 *__restrict__ trav,
@@ -105,10 +92,8 @@ __global__ __launch_bounds__(QT) void k_wr_classify(const uint32_t *__restrict__
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t r = blockIdx.x * (QT / 64) + (threadIdx.x >> 6);
   if (r >= n) return;  // (wave-uniform)
-  const uint32_t *__restrict__ src = cells + (size_t)slot_of[r] * 512u + lane;
   uint32_t w[8];
-#pragma unroll
-  for (int l = 0; l < 8; ++l) w[l] = src[l * 64];
+  load_brick(cells, slot_of[r], lane, w);
 #pragma unroll
   for (int l = 0; l < 8; ++l) {
     int occ = occ_of(w[l]);
@@ -245,7 +230,7 @@ __global__ __launch_bounds__(RT) void k_wr_relax(uint32_t *__restrict__ cost, co
       ri[k] = ((i & 7) + 1) + (((i >> 3) & 7) + 1) * RX + ((i >> 6) + 1) * RXY;
       uint32_t nb = 0u;
 #pragma unroll
-      for (int n = 0; n < 27; ++n) nb |= (uint32_t)s_trav[ri[k] + move_d(n, 0) + move_d(n, 1) * RX + move_d(n, 2) * RXY] << n;
+      for (int n = 0; n < 27; ++n) nb |= (uint32_t)s_trav[ri[k] + off_d(n, 0) + off_d(n, 1) * RX + off_d(n, 2) * RXY] << n;
       al[k] = allowed_moves<FACE>(nb);
       cur[k] = was[k] = s_cost[ri[k]];
     }
@@ -262,7 +247,7 @@ __global__ __launch_bounds__(RT) void k_wr_relax(uint32_t *__restrict__ cost, co
           if (n == 13 || (FACE && !((FACE_MOVES >> n) & 1u))) continue;
           // arithmetic, not a condition: a move that is not allowed makes its neighbour NO_COST, and NO_COST plus a
           // weight saturates and stays above the limit
-          const uint32_t v = s_cost[ri[k] + move_d(n, 0) + move_d(n, 1) * RX + move_d(n, 2) * RXY] | (((al[k] >> n) & 1u) - 1u);
+          const uint32_t v = s_cost[ri[k] + off_d(n, 0) + off_d(n, 1) * RX + off_d(n, 2) * RXY] | (((al[k] >> n) & 1u) - 1u);
           const uint32_t via = __builtin_elementwise_add_sat(v, move_weight(n));
           best = min(best, via > limit ? NO_COST : via);
         }
@@ -287,7 +272,7 @@ __global__ __launch_bounds__(RT) void k_wr_relax(uint32_t *__restrict__ cost, co
 #pragma unroll
         for (int n = 0; n < 27; ++n) {
           if (n == 13 || (FACE && !((FACE_MOVES >> n) & 1u))) continue;  // (face moves never read an edge or corner halo)
-          wake |= ((ax >> (move_d(n, 0) + 1)) & (ay >> (move_d(n, 1) + 1)) & (az >> (move_d(n, 2) + 1)) & 1u) << n;
+          wake |= ((ax >> (off_d(n, 0) + 1)) & (ay >> (off_d(n, 1) + 1)) & (az >> (off_d(n, 2) + 1)) & 1u) << n;
         }
       }
     }
@@ -333,7 +318,7 @@ __device__ __forceinline__ void descent_step(const uint32_t *__restrict__ cost, 
   for (int n = 0; n < 27; ++n) {
     nr[n] = NONE;
     if (FACE && n != 13 && !((FACE_MOVES >> n) & 1u)) continue;
-    const int x = lx + move_d(n, 0), y = ly + move_d(n, 1), z = lz + move_d(n, 2);
+    const int x = lx + off_d(n, 0), y = ly + off_d(n, 1), z = lz + off_d(n, 2);
     nr[n] = nbr[(size_t)b * 27u + (uint32_t)(13 + brick_off(x) + 3 * brick_off(y) + 9 * brick_off(z))];
   }
 #pragma unroll
@@ -341,14 +326,14 @@ __device__ __forceinline__ void descent_step(const uint32_t *__restrict__ cost, 
     cw[n] = NO_COST;
     tw[n] = 0u;
     if (nr[n] != NONE) {  // (no brick: no cost, not traversable)
-      const int cx = (lx + move_d(n, 0)) & 7, cy = (ly + move_d(n, 1)) & 7, cz = (lz + move_d(n, 2)) & 7;
+      const int cx = (lx + off_d(n, 0)) & 7, cy = (ly + off_d(n, 1)) & 7, cz = (lz + off_d(n, 2)) & 7;
       cw[n] = cost[cost_at(nr[n], cx, cy, cz)];
       tw[n] = trav[trav_word(nr[n], cy, cz)];
     }
   }
   uint32_t nb = 0u;
 #pragma unroll
-  for (int n = 0; n < 27; ++n) nb |= ((tw[n] >> trav_bit((lx + move_d(n, 0)) & 7, (ly + move_d(n, 1)) & 7)) & 1u) << n;  // (no brick: the word is 0)
+  for (int n = 0; n < 27; ++n) nb |= ((tw[n] >> trav_bit((lx + off_d(n, 0)) & 7, (ly + off_d(n, 1)) & 7)) & 1u) << n;  // (no brick: the word is 0)
   const uint32_t al = allowed_moves<FACE>(nb);
   next = 255u;
   next_brick = NONE;
@@ -436,23 +421,13 @@ __global__ __launch_bounds__(QT) void k_world_reach_paths(const float *__restric
 constexpr uint32_t REACH_BATCH = 8;  // rounds issued between two looks at the count
 
 // the buffers for `bricks` bricks (the stream is idle if there were buffers before)
-sdm_status reach_alloc(sdm_map *m, size_t bricks) {
+sdm_status reach_alloc(sdm_map *m, size_t need) {  // (no brick: still a table to look up in)
   WorldReachLayer &L = m->wreach;
-  release(m, &L.cost), release(m, &L.trav), release(m, &L.obst), release(m, &L.nbr), release(m, &L.coord), release(m, &L.keys);
-  release(m, &L.vals), release(m, &L.act), release(m, &L.list);
-  L.cap = 0;
-  const uint32_t slots = table_slots(bricks);
-  SDM_TRY(alloc_tracked(m, &L.cost, bricks * 512));
-  SDM_TRY(alloc_tracked(m, &L.trav, bricks * 8));
-  SDM_TRY(alloc_tracked(m, &L.obst, bricks * 8));
-  SDM_TRY(alloc_tracked(m, &L.nbr, bricks * 27));
-  SDM_TRY(alloc_tracked(m, &L.coord, bricks * 2));
-  SDM_TRY(alloc_tracked(m, &L.keys, slots));
-  SDM_TRY(alloc_tracked(m, &L.vals, slots));
-  SDM_TRY(alloc_tracked(m, &L.act, (bricks + 31) / 32));
-  SDM_TRY(alloc_tracked(m, &L.list, bricks));
-  L.cap = bricks;
-  return SDM_OK;
+  need = std::max<size_t>(need, 1);
+  const size_t bricks = round_up(need, 256), slots = table_slots(bricks);
+  return grow_buffers(m, need, bricks, &L.cap,
+                      {buf(&L.cost, bricks * 512), buf(&L.trav, bricks * 8), buf(&L.obst, bricks * 8), buf(&L.nbr, bricks * 27), buf(&L.coord, bricks * 2),
+                       buf(&L.keys, slots), buf(&L.vals, slots), buf(&L.act, (bricks + 31) / 32), buf(&L.list, bricks)});
 }
 
 // the index, the neighbour ranks, the classes and the seeds of a build of n bricks
@@ -468,7 +443,7 @@ hipError_t launch_reach_prepare(const sdm_map *m, const sdm_world_reach_options 
   if (!n) return hipSuccess;
   if ((e = hipMemsetAsync(L.act, 0, (((size_t)n + 31) / 32) * sizeof(uint32_t), s)) != hipSuccess) return e;
   if ((e = launch_snapshot_index(m, order, flag, rank, n_arch, n, L.coord, slot_of, L.keys, L.vals, L.hmask)) != hipSuccess) return e;
-  LAYER_LAUNCH(k_wr_neighbours, (n * 27u + QT - 1) / QT, QT, s, L.coord, L.keys, L.vals, L.hmask, n, L.nbr);
+  if ((e = launch_snapshot_neighbours(L.coord, L.keys, L.vals, L.hmask, n, L.nbr, s)) != hipSuccess) return e;
   LAYER_LAUNCH(k_wr_classify, (n + QT / 64 - 1) / (QT / 64), QT, s, slot_of, W.cells, n, (o.flags & SDM_WORLD_REACH_THROUGH_UNKNOWN) ? 1u : 0u,
                (o.flags & SDM_WORLD_REACH_IGNORE_MOVABLE) ? 1u : 0u, m->d.max_movable, L.trav, L.obst, L.cost);
   if (o.inflate == 1) LAYER_LAUNCH(k_wr_inflate<1>, (n * 8u + QT - 1) / QT, QT, s, L.nbr, L.obst, L.trav, n);
@@ -535,7 +510,7 @@ sdm_status sdm_world_reach_update(sdm_map *m, const sdm_world_reach_options *o, 
   }, &b));
   const uint32_t n = b.n;
   uint32_t *slot_of = nullptr;
-  if (!L.cap || n > L.cap) SDM_TRY(reach_alloc(m, ((size_t)std::max<uint32_t>(n, 1u) + 255) & ~(size_t)255));
+  SDM_TRY(reach_alloc(m, n));
   L.n = n;
   L.hmask = table_slots(n) - 1;
   unsigned char *d_starts = nullptr;

@@ -7,6 +7,8 @@
 //   k_ws_index   a thread per archived brick: a flagged one writes its coordinates at its rank, its pool slot beside them if
 //             the caller keeps it, and inserts key -> rank into the caller's table (every key by one thread, like
 //             world_insert).
+//   k_ws_neighbours  a thread per (brick of the field, one of 27): one lookup in the caller's own table, the neighbour's rank
+//             or NONE (anything >= n); brick_in_range before every lookup.  World reach's and world objects' (DESIGN.md 5w).
 //   k_ws_list    a thread per word of activity bits: clears it and appends its items to the list, counted where the caller
 //             says.
 #include "sdm_world.h"
@@ -50,6 +52,19 @@ __global__ __launch_bounds__(QT) void k_ws_index(const uint32_t *__restrict__ or
   world_insert(keys, vals, hmask, brick_key(bx, by, bz), r);
 }
 
+__global__ __launch_bounds__(QT) void k_ws_neighbours(const uint32_t *__restrict__ coord, const u64 *__restrict__ keys,
+                                                      const uint32_t *__restrict__ vals, uint32_t hmask, uint32_t n, uint32_t *__restrict__ nbr) {
+  const uint32_t i = blockIdx.x * QT + threadIdx.x;
+  if (i >= n * 27u) return;
+  const uint32_t r = i / 27u, k = i - r * 27u;
+  int bx, by, bz;
+  coord_of(coord, r, bx, by, bz);
+  bx += off_d((int)k, 0), by += off_d((int)k, 1), bz += off_d((int)k, 2);
+  // (a coordinate of 32768 would alias another brick's key; k == 13 finds the brick's own rank, which k_ws_index inserted)
+  const uint32_t nr = brick_in_range(bx, by, bz) ? world_find(keys, vals, hmask, brick_key(bx, by, bz)) : NONE;
+  nbr[i] = nr < n ? nr : NONE;
+}
+
 __global__ __launch_bounds__(QT) void k_ws_list(uint32_t *__restrict__ act, uint32_t *__restrict__ list, uint32_t *__restrict__ count, uint32_t n) {
   const uint32_t i = blockIdx.x * QT + threadIdx.x;
   if (i >= (n + 31u) / 32u) return;
@@ -86,6 +101,12 @@ sdm_status snapshot_flag_bricks(sdm_map *m, const uint32_t *order, uint32_t n_ar
 hipError_t launch_snapshot_index(const sdm_map *m, const uint32_t *order, const uint32_t *flag, const uint32_t *rank, uint32_t n_arch, uint32_t n,
                                  uint32_t *coord, uint32_t *slot_of, u64 *keys, uint32_t *vals, uint32_t hmask) {
   LAYER_LAUNCH(k_ws_index, (n_arch + QT - 1) / QT, QT, m->stream, order, m->world.hdr, flag, rank, n_arch, n, coord, slot_of, keys, vals, hmask);
+  return hipSuccess;
+}
+
+hipError_t launch_snapshot_neighbours(const uint32_t *coord, const u64 *keys, const uint32_t *vals, uint32_t hmask, uint32_t n, uint32_t *nbr,
+                                      hipStream_t s) {
+  LAYER_LAUNCH(k_ws_neighbours, (n * 27u + QT - 1) / QT, QT, s, coord, keys, vals, hmask, n, nbr);
   return hipSuccess;
 }
 

@@ -6,7 +6,7 @@ from tests.test_isa_hygiene import device_elf, hip_units, kernels_meta
 from tests.test_reach_isa import sgpr_spills
 from tests.test_world_frontiers_isa import lds_bytes
 
-WORLD_OBJECTS_KERNELS = ("k_wo_neighbours", "k_wo_classify", "k_wo_compact", "k_wo_label_localILb0", "k_wo_label_localILb1", "k_wo_seamsILb0",
+WORLD_OBJECTS_KERNELS = ("k_wo_classify", "k_wo_compact", "k_wo_label_localILb0", "k_wo_label_localILb1", "k_wo_seamsILb0",
                          "k_wo_seamsILb1", "k_wo_roots", "k_wo_accumulate", "k_wo_flags", "k_wo_table", "k_wo_assign", "k_query_world_objects")
 LDS_BYTES = {"k_wo_assign": 2048}      # 256 cell counts and 256 object counts a workgroup; every other kernel none
 

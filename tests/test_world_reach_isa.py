@@ -5,7 +5,7 @@ scratch; the ceiling is what a build with csrc/Makefile's flags gives).  Reads t
 from tests.test_isa_hygiene import device_elf, hip_units, kernels_meta
 from tests.test_reach_isa import sgpr_spills
 
-WORLD_REACH_KERNELS = ("k_wr_neighbours", "k_wr_classify", "k_wr_inflateILi1", "k_wr_inflateILi2", "k_wr_seed",
+WORLD_REACH_KERNELS = ("k_wr_classify", "k_wr_inflateILi1", "k_wr_inflateILi2", "k_wr_seed",
                        "k_wr_relaxILb0", "k_wr_relaxILb1", "k_wr_reduce", "k_query_world_reachILb0", "k_query_world_reachILb1",
                        "k_world_reach_pathsILb0", "k_world_reach_pathsILb1")
 SGPR_SPILL_CEILING = {"k_world_reach_pathsILb0": 6}   # every other kernel: 0

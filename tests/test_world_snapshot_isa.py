@@ -1,11 +1,12 @@
-"""The kernels the builds over the world archive share (world_snapshot.hip) are exactly the box flag, the index and the
-active list, use no scratch and no LDS and spill no vector and no scalar register.  Reads the code object's metadata only.
+"""The kernels the builds over the world archive share (world_snapshot.hip) are exactly the box flag, the index, the 27
+neighbour ranks (world reach's and world objects') and the active list, use no scratch and no LDS and spill no
+vector and no scalar register.  Reads the code object's metadata only.
 (tests/test_isa_hygiene.py scans the object for FLAT memory instructions, like every other unit of the library.)"""
 from tests.test_isa_hygiene import device_elf, hip_units, kernels_meta
 from tests.test_reach_isa import sgpr_spills
 from tests.test_world_frontiers_isa import lds_bytes
 
-WORLD_SNAPSHOT_KERNELS = ("k_ws_flag", "k_ws_index", "k_ws_list")
+WORLD_SNAPSHOT_KERNELS = ("k_ws_flag", "k_ws_index", "k_ws_neighbours", "k_ws_list")
 
 
 def test_the_unit_is_listed():
