@@ -613,11 +613,7 @@ class SemanticDSPMap {
   /// lethal, unknown ground or ground, the levels under it and the distance to the nearest lethal column.  Waits.  Returns
   /// the number of footprints answered; 0 (and an empty vector) before the first ground() or when the call fails.
   size_t checkFootprints(const std::vector<sdm_footprint> &footprints, std::vector<sdm_footprint_result> &out) {
-    out.clear();
-    if (!map_ || footprints.empty()) return 0;
-    out.resize(footprints.size());
-    if (!check(sdm_query_footprints(map_, footprints.data(), (int64_t)footprints.size(), out.data(), 0u), "sdm_query_footprints")) out.clear();
-    return out.size();
+    return batched(sdm_query_footprints, "sdm_query_footprints", footprints, 1, out);
   }
   /// What does the map look like (sdm.h, "surface mesh")?  Builds the face mesh of the results of the last update() under
   /// `options` - one unit quad per face between a solid cell and a neighbour that is not, the lattice corners as welded
@@ -738,17 +734,7 @@ class SemanticDSPMap {
   /// update that wrote into its brick; occ -1 where nothing is archived.  Waits.  Returns the number of points answered;
   /// 0 (and an empty vector) before the first worldUpdate() or when the call fails.
   size_t queryWorld(const std::vector<Eigen::Vector3d> &points, std::vector<sdm_world_cell> &out) {
-    out.clear();
-    if (!map_ || points.empty()) return 0;
-    std::vector<float> xyz(3 * points.size());
-    for (size_t i = 0; i < points.size(); ++i) {
-      xyz[3 * i] = (float)points[i].x();
-      xyz[3 * i + 1] = (float)points[i].y();
-      xyz[3 * i + 2] = (float)points[i].z();
-    }
-    out.resize(points.size());
-    if (!check(sdm_query_world_points(map_, xyz.data(), (int64_t)points.size(), out.data(), 0u), "sdm_query_world_points")) out.clear();
-    return out.size();
+    return batched(sdm_query_world_points, "sdm_query_world_points", flat_points(points), 3, out);
   }
   /// The archive as sdm_get_world_bricks gives it: headers and 512 words per brick, in brick order - what worldImport of this
   /// or of another map takes.  Waits.  Returns the number of bricks; 0 (and empty vectors) before the first worldUpdate() or
@@ -857,34 +843,13 @@ class SemanticDSPMap {
   /// step of the way back and a status.  Waits.  Returns the number of goals answered; 0 (and an empty vector) before the
   /// first worldReach() or when the call fails.
   size_t queryWorldReach(const std::vector<Eigen::Vector3d> &goals, std::vector<sdm_world_reach_result> &out) {
-    out.clear();
-    if (!map_ || goals.empty()) return 0;
-    const std::vector<float> xyz = flat_points(goals);
-    out.resize(goals.size());
-    if (!check(sdm_query_world_reach(map_, xyz.data(), nullptr, (int64_t)goals.size(), out.data(), 0u), "sdm_query_world_reach")) out.clear();
-    return out.size();
+    return batched(sdm_query_world_reach, "sdm_query_world_reach", flat_points(goals), 3, out, nullptr);
   }
   /// Per goal position of the last worldReach() the world cells from the goal to the start, both included; empty where
   /// there is no path.  Waits.  Returns the number of goals answered; 0 (and an empty vector) before the first worldReach()
   /// or when a call fails.
   size_t worldReachPaths(const std::vector<Eigen::Vector3d> &goals, std::vector<std::vector<Eigen::Vector3i>> &paths) {
-    paths.clear();
-    if (!map_ || goals.empty()) return 0;
-    const std::vector<float> xyz = flat_points(goals);
-    std::vector<int32_t> lens(goals.size());
-    if (!check(sdm_world_reach_paths(map_, xyz.data(), nullptr, (int64_t)goals.size(), 0, nullptr, lens.data(), 0u), "sdm_world_reach_paths")) return 0;
-    const int32_t longest = *std::max_element(lens.begin(), lens.end());  // (the true lengths, whatever max_len)
-    std::vector<int32_t> rows(goals.size() * (size_t)longest * 3);
-    if (longest && !check(sdm_world_reach_paths(map_, xyz.data(), nullptr, (int64_t)goals.size(), longest, rows.data(), lens.data(), 0u),
-                          "sdm_world_reach_paths"))
-      return 0;
-    paths.resize(goals.size());
-    for (size_t i = 0; i < goals.size(); ++i)
-      for (int32_t k = 0; k < lens[i]; ++k) {
-        const int32_t *c = rows.data() + (i * (size_t)longest + (size_t)k) * 3;
-        paths[i].push_back(Eigen::Vector3i(c[0], c[1], c[2]));
-      }
-    return paths.size();
+    return goalPaths(sdm_world_reach_paths, "sdm_world_reach_paths", goals, paths);
   }
   /// Where, beyond the block, is it worth going (sdm.h, "world frontiers")?  Builds the frontier cells of the world archive
   /// - free cells beside never-observed space, bricks the archive does not have included unless inside_bricks - and their
@@ -949,12 +914,7 @@ class SemanticDSPMap {
   /// was counted - and its place in the cell list.  Waits.  Returns the number of points answered; 0 (and an empty vector)
   /// before the first worldObjects() or when the call fails.
   size_t queryWorldObjects(const std::vector<Eigen::Vector3d> &points, std::vector<sdm_world_object_result> &out) {
-    out.clear();
-    if (!map_ || points.empty()) return 0;
-    const std::vector<float> xyz = flat_points(points);
-    out.resize(points.size());
-    if (!check(sdm_query_world_objects(map_, xyz.data(), nullptr, (int64_t)points.size(), out.data(), 0u), "sdm_query_world_objects")) out.clear();
-    return out.size();
+    return batched(sdm_query_world_objects, "sdm_query_world_objects", flat_points(points), 3, out, nullptr);
   }
   /// How close is a remembered place to an obstacle (sdm.h, "world distance field")?  Builds the truncated Euclidean
   /// distance field over the bricks of the world archive: exact up to max_metres - radius = ceil(max_metres / voxel_size)
@@ -978,12 +938,7 @@ class SemanticDSPMap {
   /// 0xffffffff and -1 in no brick of the field.  Waits.  Returns the number of points answered; 0 (and an empty vector)
   /// before the first worldEsdf() or when the call fails.
   size_t queryWorldDistance(const std::vector<Eigen::Vector3d> &points, std::vector<sdm_world_distance_result> &out) {
-    out.clear();
-    if (!map_ || points.empty()) return 0;
-    const std::vector<float> xyz = flat_points(points);
-    out.resize(points.size());
-    if (!check(sdm_query_world_distance(map_, xyz.data(), nullptr, (int64_t)points.size(), out.data(), 0u), "sdm_query_world_distance")) out.clear();
-    return out.size();
+    return batched(sdm_query_world_distance, "sdm_query_world_distance", flat_points(points), 3, out, nullptr);
   }
   /// Where can a ground robot stand at a place the map only remembers (sdm.h, "world ground layer")?  ground() over the
   /// bricks of the world archive: builds the height map, the costmap and the truncated distance to the nearest lethal
@@ -1025,24 +980,14 @@ class SemanticDSPMap {
   /// and dist -1 in no tile.  Waits.  Returns the number of points answered; 0 (and an empty vector) before the first
   /// worldGround() or when the call fails.
   size_t queryWorldGround(const std::vector<Eigen::Vector3d> &points, std::vector<sdm_world_ground_result> &out) {
-    out.clear();
-    if (!map_ || points.empty()) return 0;
-    const std::vector<float> xyz = flat_points(points);
-    out.resize(points.size());
-    if (!check(sdm_query_world_ground(map_, xyz.data(), nullptr, (int64_t)points.size(), out.data(), 0u), "sdm_query_world_ground")) out.clear();
-    return out.size();
+    return batched(sdm_query_world_ground, "sdm_query_world_ground", flat_points(points), 3, out, nullptr);
   }
   /// Does the robot's body fit at that remembered place?  checkFootprints() against the layer worldGround() built last:
   /// the footprints' centres are world metres along the layer's u and v axes; n_absent counts the covered columns of no
   /// tile.  Waits.  Returns the number of footprints answered; 0 (and an empty vector) before the first worldGround() or
   /// when the call fails.
   size_t checkWorldFootprints(const std::vector<sdm_footprint> &footprints, std::vector<sdm_world_footprint_result> &out) {
-    out.clear();
-    if (!map_ || footprints.empty()) return 0;
-    out.resize(footprints.size());
-    if (!check(sdm_query_world_footprints(map_, footprints.data(), (int64_t)footprints.size(), out.data(), 0u), "sdm_query_world_footprints"))
-      out.clear();
-    return out.size();
+    return batched(sdm_query_world_footprints, "sdm_query_world_footprints", footprints, 1, out);
   }
   /// How does a robot on wheels get there, over everything the map remembers (sdm.h, "world ground reach")?  Builds the
   /// 2-D travel-cost field over the costmap worldGround() built last, from `start` (a global position, the robot's: only
@@ -1062,37 +1007,13 @@ class SemanticDSPMap {
   /// level, the first step of the way back and a status.  Waits.  Returns the number of goals answered; 0 (and an empty
   /// vector) before the first worldGroundReach() or when the call fails.
   size_t queryWorldGroundReach(const std::vector<Eigen::Vector3d> &goals, std::vector<sdm_world_ground_reach_result> &out) {
-    out.clear();
-    if (!map_ || goals.empty()) return 0;
-    const std::vector<float> xyz = flat_points(goals);
-    out.resize(goals.size());
-    if (!check(sdm_query_world_ground_reach(map_, xyz.data(), nullptr, (int64_t)goals.size(), out.data(), 0u), "sdm_query_world_ground_reach"))
-      out.clear();
-    return out.size();
+    return batched(sdm_query_world_ground_reach, "sdm_query_world_ground_reach", flat_points(goals), 3, out, nullptr);
   }
   /// Per goal position of the last worldGroundReach() the world cells the robot's base stands in on the way from the goal
   /// to the start, both included; empty where there is no path.  Waits.  Returns the number of goals answered; 0 (and an
   /// empty vector) before the first worldGroundReach() or when a call fails.
   size_t worldGroundReachPaths(const std::vector<Eigen::Vector3d> &goals, std::vector<std::vector<Eigen::Vector3i>> &paths) {
-    paths.clear();
-    if (!map_ || goals.empty()) return 0;
-    const std::vector<float> xyz = flat_points(goals);
-    std::vector<int32_t> lens(goals.size());
-    if (!check(sdm_world_ground_reach_paths(map_, xyz.data(), nullptr, (int64_t)goals.size(), 0, nullptr, lens.data(), 0u),
-               "sdm_world_ground_reach_paths"))
-      return 0;
-    const int32_t longest = *std::max_element(lens.begin(), lens.end());  // (the true lengths, whatever max_len)
-    std::vector<int32_t> rows(goals.size() * (size_t)longest * 3);
-    if (longest && !check(sdm_world_ground_reach_paths(map_, xyz.data(), nullptr, (int64_t)goals.size(), longest, rows.data(), lens.data(), 0u),
-                          "sdm_world_ground_reach_paths"))
-      return 0;
-    paths.resize(goals.size());
-    for (size_t i = 0; i < goals.size(); ++i)
-      for (int32_t k = 0; k < lens[i]; ++k) {
-        const int32_t *c = rows.data() + (i * (size_t)longest + (size_t)k) * 3;
-        paths[i].push_back(Eigen::Vector3i(c[0], c[1], c[2]));
-      }
-    return paths.size();
+    return goalPaths(sdm_world_ground_reach_paths, "sdm_world_ground_reach_paths", goals, paths);
   }
   /// Is this straight leg free, through everything the map remembers (sdm.h, "world rays")?  Per segment from[i] -> to[i]
   /// (global frame), walked through the world archive without clipping: where it enters its first blocking cell, that
@@ -1352,6 +1273,39 @@ class SemanticDSPMap {
     if (s == SDM_OK) return true;
     std::cerr << what << " failed: " << sdm_last_error() << std::endl;  // the reference reports on stdout/stderr and carries on
     return false;
+  }
+  /// The batched queries' one body: sizes `out` to the entries of `in` (`per` values each: flat_points' three floats, or
+  /// one record), calls `query` - `what` by name -, and clears `out` if the call fails -> the number of entries answered.
+  /// cells: the null `cells` argument, for the entry points that take their entries as positions or as cells.  (A caller
+  /// that hands in flat_points(...) has flattened its points before the map is looked at: one copy more on a map that was
+  /// never made, the same return value.)
+  template <class Query, class In, class Out, class... Cells>
+  size_t batched(Query query, const char *what, const std::vector<In> &in, size_t per, std::vector<Out> &out, Cells... cells) {
+    out.clear();
+    if (!map_ || in.empty()) return 0;
+    out.resize(in.size() / per);
+    if (!check(query(map_, in.data(), cells..., (int64_t)out.size(), out.data(), 0u), what)) out.clear();
+    return out.size();
+  }
+  /// The world layers' paths: the true lengths first (whatever max_len), then the rows at the longest of them, unpacked into
+  /// one list of world cells per goal -> the number of goals answered
+  template <class Paths>
+  size_t goalPaths(Paths query, const char *what, const std::vector<Eigen::Vector3d> &goals, std::vector<std::vector<Eigen::Vector3i>> &paths) {
+    paths.clear();
+    if (!map_ || goals.empty()) return 0;
+    const std::vector<float> xyz = flat_points(goals);
+    std::vector<int32_t> lens(goals.size());
+    if (!check(query(map_, xyz.data(), nullptr, (int64_t)goals.size(), 0, nullptr, lens.data(), 0u), what)) return 0;
+    const int32_t longest = *std::max_element(lens.begin(), lens.end());
+    std::vector<int32_t> rows(goals.size() * (size_t)longest * 3);
+    if (longest && !check(query(map_, xyz.data(), nullptr, (int64_t)goals.size(), longest, rows.data(), lens.data(), 0u), what)) return 0;
+    paths.resize(goals.size());
+    for (size_t i = 0; i < goals.size(); ++i)
+      for (int32_t k = 0; k < lens[i]; ++k) {
+        const int32_t *c = rows.data() + (i * (size_t)longest + (size_t)k) * 3;
+        paths[i].push_back(Eigen::Vector3i(c[0], c[1], c[2]));
+      }
+    return paths.size();
   }
   void pushParams() {
     if (map_) check(sdm_set_params(map_, &params_), "sdm_set_params");

@@ -598,6 +598,37 @@ def _check(L, rc, what):
         raise SdmError("%s failed: %s (%s)" % (what, STATUS_NAMES.get(rc, rc), L.sdm_last_error().decode()))
 
 
+def _call(name, *args):
+    """Calls the library function `name`, which takes no map, and raises SdmError on any status but SDM_OK."""
+    L = load_library()
+    _check(L, getattr(L, name)(*args), name)
+
+
+def _dev(p):
+    """an optional device address as a pointer: a falsy one (None, 0) is the null pointer"""
+    return _ptr(int(p)) if p else None
+
+
+def _goals(xyz, cells, cell_dtype, cell_row):
+    """The goal form "exactly one of xyz / cells" -> (positions float32 [n, 3] or None, cells of cell_dtype shaped cell_row or
+    None, n).  With neither, n is 0 and the library refuses the call."""
+    p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    w = None if cells is None else np.ascontiguousarray(cells, dtype=cell_dtype).reshape(cell_row)
+    return p, w, len(p) if p is not None else len(w) if w is not None else 0
+
+
+def _rows6(a, b, on_device):
+    """two (n, 3) arrays side by side as float32 [n, 6]; on_device: a already is the device address of such rows and b None"""
+    if on_device:
+        assert b is None
+        return a
+    return np.concatenate([np.asarray(a, np.float32).reshape(-1, 3), np.asarray(b, np.float32).reshape(-1, 3)], axis=1)
+
+
+_WORDS = (np.uint32, (-1,))        # how the block's layers name a cell: its map-index word
+_WORLD_CELLS = (np.int32, (-1, 3))  # how the world layers name one: (x, y, z)
+
+
 class SdmMap:
     """One map on one GPU (or one Z-slab shard of a map)."""
 
@@ -632,33 +663,99 @@ class SdmMap:
         except Exception:
             pass
 
+    # ---- the calling protocols of sdm.h, each stated once; the methods below name the function and its types.
+    def _call(self, name, *args):
+        """Calls the library function `name` on this map and raises SdmError on any status but SDM_OK."""
+        rc = getattr(self.L, name)(self.h, *args)
+        if rc != 0:
+            _check(self.L, rc, name)
+
+    def _out(self, name, ctype, *args):
+        """_call for a function whose last argument is one scalar it writes -> that scalar's value"""
+        v = ctype()
+        self._call(name, *args, C.byref(v))
+        return v.value
+
+    def _query(self, name, src, dtype, row, res, flags, on_device, n, out):
+        """A batched query `name(map, in, n, out, flags)` in either of its modes (the comment above query_points).
+        on_device: src and out are device addresses of n entries, QUERY_ON_DEVICE joins the flags and nothing is returned.
+        Otherwise src becomes an array of dtype shaped `row`, and an array of res, one entry per row, is filled and returned.
+        A function with a second, optional output takes res and out as pairs (None: not asked for) and returns a pair."""
+        res, out = (res, out) if isinstance(res, tuple) else ((res,), (out,))
+        if on_device:
+            self._call(name, _ptr(int(src)), int(n), _ptr(int(out[0])), *[_dev(o) for o in out[1:]], flags | QUERY_ON_DEVICE)
+            return None
+        p = np.ascontiguousarray(src, dtype=dtype).reshape(row)
+        r = [None if d is None else np.empty(len(p), d) for d in res]
+        self._call(name, _ptr(p), len(p), *[_ptr(a) for a in r], flags)
+        return r[0] if len(r) == 1 else tuple(r)
+
+    def _goal_query(self, name, xyz, cells, cell_form, res, on_device, n, out):
+        """_query for `name(map, xyz, cells, n, out, flags)`, whose entries come in the goal form (_goals); cell_form: _WORDS
+        or _WORLD_CELLS.  on_device: the one given of xyz / cells is a device address, the other falsy."""
+        if on_device:
+            self._call(name, _dev(xyz), _dev(cells), int(n), _ptr(int(out)), QUERY_ON_DEVICE)
+            return None
+        p, w, n = _goals(xyz, cells, *cell_form)
+        r = np.empty(n, res)
+        self._call(name, _ptr(p), _ptr(w), n, _ptr(r), 0)
+        return r
+
+    def _goal_paths(self, name, xyz, cells, cell_form, max_len, fill, on_device, n, cells_out, len_out):
+        """The same for `name(map, xyz, cells, n, max_len, cells_out, len_out, flags)` -> (rows of max_len cells in the cell
+        form, holding `fill` where the call writes nothing; lengths int32 [n]).  on_device: cells_out may be falsy."""
+        if on_device:
+            self._call(name, _dev(xyz), _dev(cells), int(n), int(max_len), _dev(cells_out), _ptr(int(len_out)), QUERY_ON_DEVICE)
+            return None
+        p, w, n = _goals(xyz, cells, *cell_form)
+        rows, lens = np.full((n, int(max_len)) + cell_form[1][1:], fill, cell_form[0]), np.zeros(n, np.int32)
+        self._call(name, _ptr(p), _ptr(w), n, int(max_len), _ptr(rows), _ptr(lens), 0)
+        return rows, lens
+
+    def _window(self, name, cols, first=0, cap=None, info=None):
+        """Count, then fetch, for `name(map, columns..., [first,] cap, &count[, info])`: one call with null columns for the
+        count (and the info record, where info names its dtype), one for rows first .. first + cap - 1 of what there is (cap
+        None: all of them).  cols: (dtype, shape of one row) per column, None for a column not asked for; first None: the
+        function has no such argument -> (the columns, the info record or None, the count)"""
+        got = C.c_int64(0)
+        rec = None if info is None else np.zeros(1, info)
+        at = () if first is None else (0,)
+        self._call(name, *[None] * len(cols), *at, 0, C.byref(got), *(() if info is None else (_ptr(rec),)))
+        take = max(min(got.value - int(first or 0), got.value if cap is None else int(cap)), 0)
+        out = [None if c is None else np.empty((take,) + c[1], c[0]) for c in cols]
+        at = () if first is None else (int(first),)
+        self._call(name, *[_ptr(a) for a in out], *at, take, C.byref(got), *(() if info is None else (None,)))
+        return out, None if info is None else rec[0], got.value
+
     def clear(self):
-        _check(self.L, self.L.sdm_clear(self.h), "sdm_clear")
+        self._call("sdm_clear")
 
     def set_params(self, params):
         p = Params()
         for k, _ in Params._fields_:
             setattr(p, k, params[k])
-        _check(self.L, self.L.sdm_set_params(self.h, C.byref(p)), "sdm_set_params")
+        self._call("sdm_set_params", C.byref(p))
 
     def generate_noise_table(self, seed=20250217, n=1000000, stddev=0.05):
-        _check(self.L, self.L.sdm_generate_noise_table(self.h, seed, n, stddev), "sdm_generate_noise_table")
+        self._call("sdm_generate_noise_table", seed, n, stddev)
 
     def upload_noise_table(self, table):
         t = np.ascontiguousarray(table, dtype=np.float32)
-        _check(self.L, self.L.sdm_upload_noise_table(self.h, _ptr(t), t.size), "sdm_upload_noise_table")
+        self._call("sdm_upload_noise_table", _ptr(t), t.size)
 
     def download_noise_table(self, n=1000000):
         t = np.empty(n, np.float32)
-        _check(self.L, self.L.sdm_download_noise_table(self.h, _ptr(t), n), "sdm_download_noise_table")
+        self._call("sdm_download_noise_table", _ptr(t), n)
         return t
 
     def download_pdf_table(self):
         t = np.empty(20000, np.float32)
-        _check(self.L, self.L.sdm_download_pdf_table(self.h, _ptr(t), 20000), "sdm_download_pdf_table")
+        self._call("sdm_download_pdf_table", _ptr(t), 20000)
         return t
 
-    def _frame_args(self, depth, cloud, cam_pos, cam_q, moves, remove_tracks, on_device):
+    def _frame_args(self, depth, cloud, cam_pos, cam_q, moves, remove_tracks, on_device, flags, stop_after=None):
+        """-> (the arrays the pointers point into, the arguments of a frame entry point behind the map: the frame, the flags
+        and, where stop_after is given, the stage)"""
         keep = []
         if on_device:
             dp, cp = _ptr(int(depth)), _ptr(int(cloud))
@@ -673,15 +770,16 @@ class SdmMap:
         mv = np.ascontiguousarray(moves if moves is not None else np.zeros(0, OBJECT_MOVE), dtype=OBJECT_MOVE)
         rm = np.ascontiguousarray(remove_tracks if remove_tracks is not None else [], dtype=np.int32)
         keep += [pos, q, mv, rm]
-        return keep, (dp, cp, _ptr(pos), _ptr(q), _ptr(mv) if mv.size else None, mv.size,
-                      _ptr(rm) if rm.size else None, rm.size)
+        fl = flags | (INPUT_ON_DEVICE if on_device else 0)
+        if stop_after is None:
+            return keep, (dp, cp, _ptr(pos), _ptr(q), _ptr(mv) if mv.size else None, mv.size, _ptr(rm) if rm.size else None, rm.size, fl)
+        return keep, (dp, cp, _ptr(pos), _ptr(q), _ptr(mv) if mv.size else None, mv.size, _ptr(rm) if rm.size else None, rm.size, fl,
+                      STAGES[stop_after] if isinstance(stop_after, str) else stop_after)
 
     def update(self, depth, cloud, cam_pos, cam_q, moves=None, remove_tracks=None, stop_after="all",
                on_device=False, flags=0, sync=False):
-        keep, args = self._frame_args(depth, cloud, cam_pos, cam_q, moves, remove_tracks, on_device)
-        fl = flags | (INPUT_ON_DEVICE if on_device else 0)
-        st = STAGES[stop_after] if isinstance(stop_after, str) else stop_after
-        _check(self.L, self.L.sdm_update(self.h, *args, fl, st), "sdm_update")
+        keep, args = self._frame_args(depth, cloud, cam_pos, cam_q, moves, remove_tracks, on_device, flags, stop_after)
+        self._call("sdm_update", *args)
         if sync:
             self.synchronize()
 
@@ -715,105 +813,87 @@ class SdmMap:
         opt.sky_instance = int(sky_instance)
         bb = None if object_bbox is None else np.ascontiguousarray(object_bbox, dtype=np.float64)
         opt.object_bbox = bb.ctypes.data if bb is not None else None
-        _check(self.L, self.L.sdm_update_raw_ex(self.h, _ptr(depth), _ptr(sm), _ptr(tab), C.cast(arr, C.c_void_p), len(objects),
-                                                _ptr(pos), _ptr(q), _ptr(mv) if mv.size else None, mv.size,
-                                                _ptr(rm) if rm.size else None, rm.size, flags, st, C.byref(opt)),
-               "sdm_update_raw_ex")
+        self._call("sdm_update_raw_ex", _ptr(depth), _ptr(sm), _ptr(tab), C.cast(arr, C.c_void_p), len(objects), _ptr(pos), _ptr(q),
+                   _ptr(mv) if mv.size else None, mv.size, _ptr(rm) if rm.size else None, rm.size, flags, st, C.byref(opt))
         if sync:
             self.synchronize()
 
     def labeled_cloud(self):
         out = np.empty(self.W * self.H, LABELED_POINT)
-        _check(self.L, self.L.sdm_get_labeled_cloud(self.h, _ptr(out)), "sdm_get_labeled_cloud")
+        self._call("sdm_get_labeled_cloud", _ptr(out))
         return out
 
     def update_begin(self, depth, cloud, cam_pos, cam_q, moves=None, remove_tracks=None, stop_after="all",
                      on_device=False, flags=0):
-        keep, args = self._frame_args(depth, cloud, cam_pos, cam_q, moves, remove_tracks, on_device)
-        fl = flags | (INPUT_ON_DEVICE if on_device else 0)
-        st = STAGES[stop_after] if isinstance(stop_after, str) else stop_after
-        ck = C.c_void_p()
-        _check(self.L, self.L.sdm_update_begin(self.h, *args, fl, st, C.byref(ck)), "sdm_update_begin")
-        return ck.value
+        keep, args = self._frame_args(depth, cloud, cam_pos, cam_q, moves, remove_tracks, on_device, flags, stop_after)
+        return self._out("sdm_update_begin", C.c_void_p, *args)
 
     def frame_start(self, depth, cloud, cam_pos, cam_q, moves=None, remove_tracks=None, stop_after="all", on_device=False, flags=0):
-        keep, args = self._frame_args(depth, cloud, cam_pos, cam_q, moves, remove_tracks, on_device)
-        fl = flags | (INPUT_ON_DEVICE if on_device else 0)
-        st = STAGES[stop_after] if isinstance(stop_after, str) else stop_after
-        _check(self.L, self.L.sdm_frame_start(self.h, *args, fl, st), "sdm_frame_start")
+        keep, args = self._frame_args(depth, cloud, cam_pos, cam_q, moves, remove_tracks, on_device, flags, stop_after)
+        self._call("sdm_frame_start", *args)
 
     def frame_moves(self):
-        _check(self.L, self.L.sdm_frame_moves(self.h), "sdm_frame_moves")
+        self._call("sdm_frame_moves")
 
     def frame_moves_pending(self):
         """True: a further batch of a long object list has published its counts and waits for their exchange"""
-        n = C.c_int32()
-        _check(self.L, self.L.sdm_frame_moves_pending(self.h, C.byref(n)), "sdm_frame_moves_pending")
-        return bool(n.value)
+        return bool(self._out("sdm_frame_moves_pending", C.c_int32))
 
     def frame_predict(self):
-        ck = C.c_void_p()
-        _check(self.L, self.L.sdm_frame_predict(self.h, C.byref(ck)), "sdm_frame_predict")
-        return ck.value
+        return self._out("sdm_frame_predict", C.c_void_p)
 
     def set_halo_buffers(self, counts_local, counts_all, send, recv_all, cap_records):
-        _check(self.L, self.L.sdm_set_halo_buffers(self.h, _ptr(int(counts_local)), _ptr(int(counts_all)), _ptr(int(send)),
-                                                    _ptr(int(recv_all)), cap_records), "sdm_set_halo_buffers")
+        self._call("sdm_set_halo_buffers", _ptr(int(counts_local)), _ptr(int(counts_all)), _ptr(int(send)), _ptr(int(recv_all)), cap_records)
 
     def comm_init(self, id_bytes, halo_cap=0):
         buf = np.frombuffer(bytes(id_bytes), np.uint8).copy()
         assert buf.size == 128
-        _check(self.L, self.L.sdm_comm_init(self.h, _ptr(buf), halo_cap), "sdm_comm_init")
+        self._call("sdm_comm_init", _ptr(buf), halo_cap)
 
     def ipc_create(self, halo_cap=0):
         """This shard's receive arena for the exchanges without RCCL; returns its 64-byte hipIpc handle (sdm_ipc_create)."""
         buf = np.zeros(64, np.uint8)
-        _check(self.L, self.L.sdm_ipc_create(self.h, halo_cap, _ptr(buf)), "sdm_ipc_create")
+        self._call("sdm_ipc_create", halo_cap, _ptr(buf))
         return buf.tobytes()
 
     def ipc_connect(self, handles_all):
         """handles_all: the handles of all shards, in shard order (shard_count x 64 bytes)"""
         buf = np.frombuffer(bytes(handles_all), np.uint8).copy()
-        _check(self.L, self.L.sdm_ipc_connect(self.h, _ptr(buf)), "sdm_ipc_connect")
+        self._call("sdm_ipc_connect", _ptr(buf))
 
     def comm_set_options(self, ck_exchange=-1, timeout_ms=0):
         """ck_exchange: 0 chunk-owner reduction, 1 one all-gather of the whole partial images, -1 unchanged"""
-        _check(self.L, self.L.sdm_comm_set_options(self.h, ck_exchange, timeout_ms), "sdm_comm_set_options")
+        self._call("sdm_comm_set_options", ck_exchange, timeout_ms)
 
     def update_sharded(self, depth, cloud, cam_pos, cam_q, moves=None, remove_tracks=None, on_device=False, flags=0):
-        keep, args = self._frame_args(depth, cloud, cam_pos, cam_q, moves, remove_tracks, on_device)
-        fl = flags | (INPUT_ON_DEVICE if on_device else 0)
-        _check(self.L, self.L.sdm_update_sharded(self.h, *args, fl), "sdm_update_sharded")
+        keep, args = self._frame_args(depth, cloud, cam_pos, cam_q, moves, remove_tracks, on_device, flags)
+        self._call("sdm_update_sharded", *args)
 
     def ck_chunk_elems(self):
         """pixels per shard of the chunk-owner ck exchange (sdm_ck_chunk_elems)"""
-        n = C.c_int64()
-        _check(self.L, self.L.sdm_ck_chunk_elems(self.h, C.byref(n)), "sdm_ck_chunk_elems")
-        return int(n.value)
+        return int(self._out("sdm_ck_chunk_elems", C.c_int64))
 
     def ck_reduce(self, stage_dev, full_dev):
-        _check(self.L, self.L.sdm_ck_reduce(self.h, _ptr(int(stage_dev)), _ptr(int(full_dev))), "sdm_ck_reduce")
+        self._call("sdm_ck_reduce", _ptr(int(stage_dev)), _ptr(int(full_dev)))
 
     def comm_timing(self, on=True):
-        _check(self.L, self.L.sdm_comm_timing(self.h, 1 if on else 0), "sdm_comm_timing")
+        self._call("sdm_comm_timing", 1 if on else 0)
 
     def comm_times(self):
         """GPU microseconds of the last sharded frame's collectives: counts, halo, ck all-to-all, ck all-gather."""
         out = np.zeros(4, np.float64)
-        _check(self.L, self.L.sdm_get_comm_times(self.h, _ptr(out)), "sdm_get_comm_times")
+        self._call("sdm_get_comm_times", _ptr(out))
         return dict(zip(("counts_allgather", "halo_alltoall", "ck_alltoall", "ck_allgather"), [float(x) for x in out]))
 
     def device_alloc(self, nbytes):
-        p = C.c_void_p()
-        _check(self.L, self.L.sdm_device_alloc(self.h, nbytes, C.byref(p)), "sdm_device_alloc")
-        return p.value
+        return self._out("sdm_device_alloc", C.c_void_p, nbytes)
 
     def device_free(self, ptr):
-        _check(self.L, self.L.sdm_device_free(self.h, _ptr(int(ptr))), "sdm_device_free")
+        self._call("sdm_device_free", _ptr(int(ptr)))
 
     def device_upload(self, ptr, array):
         a = np.ascontiguousarray(array)
-        _check(self.L, self.L.sdm_device_upload(self.h, _ptr(int(ptr)), _ptr(a), a.nbytes), "sdm_device_upload")
+        self._call("sdm_device_upload", _ptr(int(ptr)), _ptr(a), a.nbytes)
 
     def device_put(self, array):
         a = np.ascontiguousarray(array)
@@ -823,37 +903,35 @@ class SdmMap:
 
     def device_download(self, ptr, nbytes, dtype=np.uint8):
         out = np.empty(nbytes // np.dtype(dtype).itemsize, dtype)
-        _check(self.L, self.L.sdm_device_download(self.h, _ptr(out), _ptr(int(ptr)), out.nbytes), "sdm_device_download")
+        self._call("sdm_device_download", _ptr(out), _ptr(int(ptr)), out.nbytes)
         return out
 
     def device_synchronize(self):
-        _check(self.L, self.L.sdm_device_synchronize(self.h), "sdm_device_synchronize")
+        self._call("sdm_device_synchronize")
 
     def update_finish(self, ck_parts_dev=None, n_parts=1, stop_after="all", flags=0):
         st = STAGES[stop_after] if isinstance(stop_after, str) else stop_after
-        _check(self.L, self.L.sdm_update_finish(self.h, _ptr(ck_parts_dev), n_parts, flags, st), "sdm_update_finish")
+        self._call("sdm_update_finish", _ptr(ck_parts_dev), n_parts, flags, st)
 
     def stream(self):
-        s = C.c_void_p()
-        _check(self.L, self.L.sdm_stream(self.h, C.byref(s)), "sdm_stream")
-        return s.value or 0
+        return self._out("sdm_stream", C.c_void_p) or 0
 
     def set_stream(self, hip_stream):
-        _check(self.L, self.L.sdm_set_stream(self.h, _ptr(int(hip_stream)) if hip_stream else None), "sdm_set_stream")
+        self._call("sdm_set_stream", _ptr(int(hip_stream)) if hip_stream else None)
 
     def set_ck_buffer(self, dev_ptr):
-        _check(self.L, self.L.sdm_set_ck_buffer(self.h, _ptr(int(dev_ptr)) if dev_ptr else None), "sdm_set_ck_buffer")
+        self._call("sdm_set_ck_buffer", _ptr(int(dev_ptr)) if dev_ptr else None)
 
     def set_issue_mode(self, mode):
         """0 launch by launch, 1 branched graph, 2 by the host's speed, 3 chain graph, 4 five chain graphs (sdm.h SDM_ISSUE_*)"""
-        _check(self.L, self.L.sdm_set_issue_mode(self.h, int(mode)), "sdm_set_issue_mode")
+        self._call("sdm_set_issue_mode", int(mode))
 
     def synchronize(self):
-        _check(self.L, self.L.sdm_synchronize(self.h), "sdm_synchronize")
+        self._call("sdm_synchronize")
 
     def voxels(self):
         out = np.empty(self.v_count, VOXEL_RESULT)
-        _check(self.L, self.L.sdm_get_voxels(self.h, _ptr(out)), "sdm_get_voxels")
+        self._call("sdm_get_voxels", _ptr(out))
         return out
 
     # ---- batched map queries (sdm.h).  Host mode: numpy in, numpy structured arrays out, the call waits.  on_device=True:
@@ -864,46 +942,26 @@ class SdmMap:
     def query_points(self, xyz, with_index=False, on_device=False, n=None, out=None, voxel_out=None):
         """xyz: (n, 3) global positions -> VOXEL_RESULT per point (and the storage indices if with_index).
         on_device: xyz, out (n VOXEL_RESULT) and voxel_out (n uint32, or None) are device pointers."""
-        if on_device:
-            _check(self.L, self.L.sdm_query_points(self.h, _ptr(int(xyz)), int(n), _ptr(int(out)), _ptr(int(voxel_out)) if voxel_out else None,
-                                                   QUERY_ON_DEVICE), "sdm_query_points")
-            return None
-        p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
-        res = np.empty(len(p), VOXEL_RESULT)
-        idx = np.empty(len(p), np.uint32) if with_index else None
-        _check(self.L, self.L.sdm_query_points(self.h, _ptr(p), len(p), _ptr(res), _ptr(idx), 0), "sdm_query_points")
-        return (res, idx) if with_index else res
+        r = self._query("sdm_query_points", xyz, np.float32, (-1, 3), (VOXEL_RESULT, np.uint32 if with_index else None), 0, on_device, n,
+                        (out, voxel_out))
+        return r if with_index or on_device else r[0]
 
     def query_segments(self, a, b=None, unknown_blocks=False, on_device=False, n=None, out=None):
         """a, b: (n, 3) end points -> SEGMENT_HIT per segment.  on_device: a is a device pointer to n rows of
         (ax ay az bx by bz) floats, b is None, out a device pointer to n SEGMENT_HIT."""
         fl = QUERY_UNKNOWN_BLOCKS if unknown_blocks else 0
-        if on_device:
-            assert b is None
-            _check(self.L, self.L.sdm_query_segments(self.h, _ptr(int(a)), int(n), _ptr(int(out)), fl | QUERY_ON_DEVICE), "sdm_query_segments")
-            return None
-        ab = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float32).reshape(-1, 3), np.asarray(b, np.float32).reshape(-1, 3)], axis=1))
-        res = np.empty(len(ab), SEGMENT_HIT)
-        _check(self.L, self.L.sdm_query_segments(self.h, _ptr(ab), len(ab), _ptr(res), fl), "sdm_query_segments")
-        return res
+        return self._query("sdm_query_segments", _rows6(a, b, on_device), np.float32, (-1, 6), SEGMENT_HIT, fl, on_device, n, out)
 
     def query_boxes(self, lo, hi=None, on_device=False, n=None, out=None):
         """lo, hi: (n, 3) box corners (min, max) -> BOX_RESULT per box.  on_device: lo is a device pointer to n rows of
         (min xyz, max xyz) floats, hi is None, out a device pointer to n BOX_RESULT."""
-        if on_device:
-            assert hi is None
-            _check(self.L, self.L.sdm_query_boxes(self.h, _ptr(int(lo)), int(n), _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_boxes")
-            return None
-        bx = np.ascontiguousarray(np.concatenate([np.asarray(lo, np.float32).reshape(-1, 3), np.asarray(hi, np.float32).reshape(-1, 3)], axis=1))
-        res = np.empty(len(bx), BOX_RESULT)
-        _check(self.L, self.L.sdm_query_boxes(self.h, _ptr(bx), len(bx), _ptr(res), 0), "sdm_query_boxes")
-        return res
+        return self._query("sdm_query_boxes", _rows6(lo, hi, on_device), np.float32, (-1, 6), BOX_RESULT, 0, on_device, n, out)
 
     # ---- the distance field (sdm.h).  esdf_update enqueues a build on the map's stream from the last frame's results;
     # esdf() and query_distance() answer for that frame until the next build.
     def esdf_update(self, unknown_is_obstacle=False, static_only=False):
         fl = (ESDF_UNKNOWN_IS_OBSTACLE if unknown_is_obstacle else 0) | (ESDF_STATIC_ONLY if static_only else 0)
-        _check(self.L, self.L.sdm_esdf_update(self.h, fl), "sdm_esdf_update")
+        self._call("sdm_esdf_update", fl)
 
     def esdf(self):
         """-> (d2, site, origin): uint32 arrays shaped [NZ, NY, NX] in map-index order, origin the global position of the
@@ -911,25 +969,19 @@ class SdmMap:
         c = self.cfg
         shape = (1 << c.z_n, 1 << c.y_n, 1 << c.x_n)
         d2, site, origin = np.empty(shape, np.uint32), np.empty(shape, np.uint32), np.empty(3, np.float32)
-        _check(self.L, self.L.sdm_get_esdf(self.h, _ptr(d2), _ptr(site), _ptr(origin)), "sdm_get_esdf")
+        self._call("sdm_get_esdf", _ptr(d2), _ptr(site), _ptr(origin))
         return d2, site, origin
 
     def query_distance(self, xyz, on_device=False, n=None, out=None):
         """xyz: (n, 3) global positions -> DISTANCE_RESULT per point.  on_device: xyz and out (n DISTANCE_RESULT) are
         device pointers, as for query_points."""
-        if on_device:
-            _check(self.L, self.L.sdm_query_distance(self.h, _ptr(int(xyz)), int(n), _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_distance")
-            return None
-        p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
-        res = np.empty(len(p), DISTANCE_RESULT)
-        _check(self.L, self.L.sdm_query_distance(self.h, _ptr(p), len(p), _ptr(res), 0), "sdm_query_distance")
-        return res
+        return self._query("sdm_query_distance", xyz, np.float32, (-1, 3), DISTANCE_RESULT, 0, on_device, n, out)
 
     # ---- the instance table (sdm.h).  instances_update enqueues a build on the map's stream from the last frame's
     # results; instances() and label_cells() answer for that frame until the next build.
     def instances_update(self, movable_only=False, observed_only=False):
         fl = (INSTANCES_MOVABLE_ONLY if movable_only else 0) | (INSTANCES_OBSERVED_ONLY if observed_only else 0)
-        _check(self.L, self.L.sdm_instances_update(self.h, fl), "sdm_instances_update")
+        self._call("sdm_instances_update", fl)
 
     def instances(self, cap=64):
         """-> (table, origin): INSTANCE entries in ascending track id, origin the global position of the min corner of
@@ -937,7 +989,7 @@ class SdmMap:
         origin, n = np.empty(3, np.float32), C.c_int32(0)
         while True:
             out = np.empty(cap, INSTANCE)
-            _check(self.L, self.L.sdm_get_instances(self.h, _ptr(out), cap, C.byref(n), _ptr(origin)), "sdm_get_instances")
+            self._call("sdm_get_instances", _ptr(out), cap, C.byref(n), _ptr(origin))
             if n.value <= cap:
                 return out[:n.value].copy(), origin
             cap = n.value
@@ -945,14 +997,14 @@ class SdmMap:
     def label_cells(self):
         """counted cells per label id (256 uint32) under the flags of the last instances_update"""
         out = np.empty(256, np.uint32)
-        _check(self.L, self.L.sdm_get_label_cells(self.h, _ptr(out)), "sdm_get_label_cells")
+        self._call("sdm_get_label_cells", _ptr(out))
         return out
 
     # ---- the frontiers (sdm.h).  frontiers_update enqueues a build on the map's stream from the last frame's results;
     # frontiers() and frontier_cells() answer for that frame until the next build.
     def frontiers_update(self, face_connected=False, min_cells=1, max_cells=0):
         fl = FRONTIERS_FACE_CONNECTED if face_connected else 0
-        _check(self.L, self.L.sdm_frontiers_update(self.h, fl, int(min_cells), int(max_cells)), "sdm_frontiers_update")
+        self._call("sdm_frontiers_update", fl, int(min_cells), int(max_cells))
 
     def frontiers(self, cap=64):
         """-> (table, origin): FRONTIER_CLUSTER entries in ascending first_cell, origin the global position of the min
@@ -960,7 +1012,7 @@ class SdmMap:
         origin, n = np.empty(3, np.float32), C.c_int32(0)
         while True:
             out = np.empty(cap, FRONTIER_CLUSTER)
-            _check(self.L, self.L.sdm_get_frontier_clusters(self.h, _ptr(out), cap, C.byref(n), _ptr(origin)), "sdm_get_frontier_clusters")
+            self._call("sdm_get_frontier_clusters", _ptr(out), cap, C.byref(n), _ptr(origin))
             if n.value <= cap:
                 return out[:n.value].copy(), origin
             cap = n.value
@@ -968,12 +1020,7 @@ class SdmMap:
     def frontier_cells(self):
         """-> (cell, cluster, unknown_faces): the frontier cells in ascending map-index cell word (uint32), per cell the
         index of its cluster in the table (FRONTIER_NO_CLUSTER: below min_cells) and its number of unknown faces (uint8)"""
-        n = C.c_int64(0)
-        _check(self.L, self.L.sdm_get_frontier_cells(self.h, None, None, None, 0, C.byref(n)), "sdm_get_frontier_cells")
-        k = n.value
-        cell, cluster, faces = np.empty(k, np.uint32), np.empty(k, np.uint32), np.empty(k, np.uint8)
-        _check(self.L, self.L.sdm_get_frontier_cells(self.h, _ptr(cell), _ptr(cluster), _ptr(faces), k, C.byref(n)), "sdm_get_frontier_cells")
-        return cell, cluster, faces
+        return tuple(self._window("sdm_get_frontier_cells", [(np.uint32, ()), (np.uint32, ()), (np.uint8, ())], first=None)[0])
 
     # ---- view scoring (sdm.h).  Like the batched queries: host mode takes numpy and waits, on_device=True takes device
     # pointers, enqueues on the map's stream and returns at once.
@@ -984,21 +1031,20 @@ class SdmMap:
         (n_views VIEW_GAIN), rays_out (n_views * n_rays SEGMENT_HIT, or None) and ray_unknown_out (int32, or None) are
         device pointers, n_views and n_rays their lengths."""
         if on_device:
-            _check(self.L, self.L.sdm_query_views(self.h, _ptr(int(views)), int(n_views), _ptr(int(dirs)), int(n_rays), _ptr(int(out)),
-                                                  _ptr(int(rays_out)) if rays_out else None,
-                                                  _ptr(int(ray_unknown_out)) if ray_unknown_out else None, QUERY_ON_DEVICE), "sdm_query_views")
+            self._call("sdm_query_views", _ptr(int(views)), int(n_views), _ptr(int(dirs)), int(n_rays), _ptr(int(out)), _dev(rays_out),
+                       _dev(ray_unknown_out), QUERY_ON_DEVICE)
             return None
         v = np.ascontiguousarray(views, dtype=VIEW).reshape(-1)
         d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
         gain = np.empty(len(v), VIEW_GAIN)
         rays = np.empty((len(v), len(d)), SEGMENT_HIT) if with_rays else None
         unk = np.empty((len(v), len(d)), np.int32) if with_rays else None
-        _check(self.L, self.L.sdm_query_views(self.h, _ptr(v), len(v), _ptr(d), len(d), _ptr(gain), _ptr(rays), _ptr(unk), 0), "sdm_query_views")
+        self._call("sdm_query_views", _ptr(v), len(v), _ptr(d), len(d), _ptr(gain), _ptr(rays), _ptr(unk), 0)
         return (gain, rays, unk) if with_rays else gain
 
     def set_view_batch(self, max_views_in_flight):
         """Test hook: query_views keeps at most this many views in flight (<= 0: the library's choice) (sdm_debug_view_batch)."""
-        _check(self.L, self.L.sdm_debug_view_batch(self.h, int(max_views_in_flight)), "sdm_debug_view_batch")
+        self._call("sdm_debug_view_batch", int(max_views_in_flight))
 
     # ---- the travel-cost field (sdm.h).  reach_update builds the field from the last frame's results (or, with min_d2 > 0,
     # from the distance field's snapshot) and WAITS until it is complete; reach(), query_reach() and reach_paths() answer
@@ -1006,10 +1052,8 @@ class SdmMap:
     def reach_update(self, starts=None, start_cells=None, min_d2=0, max_cost=0, face_connected=False, through_unknown=False):
         """starts: (n, 3) global positions, or start_cells: n map-index cell words (exactly one of the two)"""
         fl = (REACH_FACE_CONNECTED if face_connected else 0) | (REACH_THROUGH_UNKNOWN if through_unknown else 0)
-        p = None if starts is None else np.ascontiguousarray(starts, dtype=np.float32).reshape(-1, 3)
-        w = None if start_cells is None else np.ascontiguousarray(start_cells, dtype=np.uint32).reshape(-1)
-        n = len(p) if p is not None else len(w) if w is not None else 0
-        _check(self.L, self.L.sdm_reach_update(self.h, _ptr(p), _ptr(w), n, int(min_d2), int(max_cost), fl), "sdm_reach_update")
+        p, w, n = _goals(starts, start_cells, *_WORDS)
+        self._call("sdm_reach_update", _ptr(p), _ptr(w), n, int(min_d2), int(max_cost), fl)
 
     def reach(self):
         """-> (cost, info, origin): cost uint32 shaped [NZ, NY, NX] in map-index order, info a REACH_INFO record, origin the
@@ -1017,44 +1061,23 @@ class SdmMap:
         c = self.cfg
         cost = np.empty((1 << c.z_n, 1 << c.y_n, 1 << c.x_n), np.uint32)
         info, origin = np.zeros(1, REACH_INFO), np.empty(3, np.float32)
-        _check(self.L, self.L.sdm_get_reach(self.h, _ptr(cost), _ptr(info), _ptr(origin)), "sdm_get_reach")
+        self._call("sdm_get_reach", _ptr(cost), _ptr(info), _ptr(origin))
         return cost, info[0], origin
 
     def query_reach(self, xyz=None, cells=None, on_device=False, n=None, out=None):
         """goals as (n, 3) global positions or as n cell words -> REACH_RESULT per goal.  on_device: the one given of xyz /
         cells and out (n REACH_RESULT) are device pointers."""
-        if on_device:
-            _check(self.L, self.L.sdm_query_reach(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
-                                                  _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_reach")
-            return None
-        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
-        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.uint32).reshape(-1)
-        n = len(p) if p is not None else len(w) if w is not None else 0
-        res = np.empty(n, REACH_RESULT)
-        _check(self.L, self.L.sdm_query_reach(self.h, _ptr(p), _ptr(w), n, _ptr(res), 0), "sdm_query_reach")
-        return res
+        return self._goal_query("sdm_query_reach", xyz, cells, _WORDS, REACH_RESULT, on_device, n, out)
 
     def reach_paths(self, xyz=None, cells=None, max_len=0, on_device=False, n=None, cells_out=None, len_out=None, fill=REACH_NO_COST):
         """-> (cells_out, len_out): row g holds the first min(len, max_len) cell words of goal g's path, goal first, and
         `fill` behind them; len_out the true lengths (int32, 0: no path).  on_device: the pointers are device pointers
         (cells_out n * max_len uint32, len_out n int32) and nothing is returned."""
-        if on_device:
-            _check(self.L, self.L.sdm_reach_paths(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
-                                                  int(max_len), _ptr(int(cells_out)) if cells_out else None, _ptr(int(len_out)),
-                                                  QUERY_ON_DEVICE), "sdm_reach_paths")
-            return None
-        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
-        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.uint32).reshape(-1)
-        n = len(p) if p is not None else len(w) if w is not None else 0
-        rows, lens = np.full((n, int(max_len)), fill, np.uint32), np.zeros(n, np.int32)
-        _check(self.L, self.L.sdm_reach_paths(self.h, _ptr(p), _ptr(w), n, int(max_len), _ptr(rows), _ptr(lens), 0), "sdm_reach_paths")
-        return rows, lens
+        return self._goal_paths("sdm_reach_paths", xyz, cells, _WORDS, max_len, fill, on_device, n, cells_out, len_out)
 
     def reach_tiles(self):
         """Diagnostic: the tiles the last reach_update relaxed, summed over its rounds (sdm_debug_reach_tiles)."""
-        n = C.c_int64(0)
-        _check(self.L, self.L.sdm_debug_reach_tiles(self.h, C.byref(n)), "sdm_debug_reach_tiles")
-        return n.value
+        return self._out("sdm_debug_reach_tiles", C.c_int64)
 
     # ---- the forecast (sdm.h).  forecast_update enqueues a build on the map's stream from the last frame's results and the
     # motions given; forecast(), forecast_cells() and the two queries answer for that frame until the next build.
@@ -1062,7 +1085,7 @@ class SdmMap:
         """motions: MOTION records (or None: none), horizons: ascending times in seconds"""
         mo = np.zeros(0, MOTION) if motions is None else np.ascontiguousarray(motions, dtype=MOTION).reshape(-1)
         t = np.ascontiguousarray(horizons, dtype=np.float32).reshape(-1)
-        _check(self.L, self.L.sdm_forecast_update(self.h, _ptr(mo), len(mo), _ptr(t), len(t), FORECAST_SWEPT if swept else 0), "sdm_forecast_update")
+        self._call("sdm_forecast_update", _ptr(mo), len(mo), _ptr(t), len(t), FORECAST_SWEPT if swept else 0)
 
     def forecast(self):
         """-> (mask, first, info, origin): uint32 arrays shaped [NZ, NY, NX] in map-index order, a FORECAST_INFO record,
@@ -1071,42 +1094,25 @@ class SdmMap:
         shape = (1 << c.z_n, 1 << c.y_n, 1 << c.x_n)
         mask, first = np.empty(shape, np.uint32), np.empty(shape, np.uint32)
         info, origin = np.zeros(1, FORECAST_INFO), np.empty(3, np.float32)
-        _check(self.L, self.L.sdm_get_forecast(self.h, _ptr(mask), _ptr(first), _ptr(info), _ptr(origin)), "sdm_get_forecast")
+        self._call("sdm_get_forecast", _ptr(mask), _ptr(first), _ptr(info), _ptr(origin))
         return mask, first, info[0], origin
 
     def forecast_cells(self, cap=None):
         """-> (cell, mask, first): the cells with any horizon bit in ascending map-index cell word and their field words;
         cap: at most so many of them (-> also the true count, as a fourth value)"""
-        n = C.c_int64(0)
-        _check(self.L, self.L.sdm_get_forecast_cells(self.h, None, None, None, 0, C.byref(n)), "sdm_get_forecast_cells")
-        k = n.value if cap is None else min(int(cap), n.value)
-        cell, mask, first = np.empty(k, np.uint32), np.empty(k, np.uint32), np.empty(k, np.uint32)
-        _check(self.L, self.L.sdm_get_forecast_cells(self.h, _ptr(cell), _ptr(mask), _ptr(first), k, C.byref(n)), "sdm_get_forecast_cells")
-        return (cell, mask, first) if cap is None else (cell, mask, first, n.value)
+        cols, _, n = self._window("sdm_get_forecast_cells", [(np.uint32, ())] * 3, first=None, cap=cap)
+        return tuple(cols) if cap is None else (*cols, n)
 
     def query_forecast(self, xyzt, on_device=False, n=None, out=None):
         """xyzt: (n, 4) global positions and times -> FORECAST_RESULT per point.  on_device: xyzt and out (n FORECAST_RESULT)
         are device pointers."""
-        if on_device:
-            _check(self.L, self.L.sdm_query_forecast(self.h, _ptr(int(xyzt)), int(n), _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_forecast")
-            return None
-        p = np.ascontiguousarray(xyzt, dtype=np.float32).reshape(-1, 4)
-        res = np.empty(len(p), FORECAST_RESULT)
-        _check(self.L, self.L.sdm_query_forecast(self.h, _ptr(p), len(p), _ptr(res), 0), "sdm_query_forecast")
-        return res
+        return self._query("sdm_query_forecast", xyzt, np.float32, (-1, 4), FORECAST_RESULT, 0, on_device, n, out)
 
     def query_forecast_segments(self, seg, unknown_blocks=False, vacated_blocks=False, on_device=False, n=None, out=None):
         """seg: (n, 8) rows ax ay az ta bx by bz tb -> FORECAST_HIT per segment.  on_device: seg and out (n FORECAST_HIT)
         are device pointers."""
         fl = (QUERY_UNKNOWN_BLOCKS if unknown_blocks else 0) | (FORECAST_VACATED_BLOCKS if vacated_blocks else 0)
-        if on_device:
-            _check(self.L, self.L.sdm_query_forecast_segments(self.h, _ptr(int(seg)), int(n), _ptr(int(out)), fl | QUERY_ON_DEVICE),
-                   "sdm_query_forecast_segments")
-            return None
-        sg = np.ascontiguousarray(seg, dtype=np.float32).reshape(-1, 8)
-        res = np.empty(len(sg), FORECAST_HIT)
-        _check(self.L, self.L.sdm_query_forecast_segments(self.h, _ptr(sg), len(sg), _ptr(res), fl), "sdm_query_forecast_segments")
-        return res
+        return self._query("sdm_query_forecast_segments", seg, np.float32, (-1, 8), FORECAST_HIT, fl, on_device, n, out)
 
     # ---- the ground layer (sdm.h).  ground_update enqueues a build on the map's stream from the last frame's results;
     # ground(), query_ground() and query_footprints() answer for that frame until the next build.
@@ -1119,40 +1125,27 @@ class SdmMap:
         o["support_labels"] = label_mask(support_labels)
         o["flags"] = ((GROUND_UNKNOWN_PASSABLE if unknown_passable else 0) | (GROUND_IGNORE_MOVABLE if ignore_movable else 0) |
                       (GROUND_NONE_IS_LETHAL if none_is_lethal else 0))
-        _check(self.L, self.L.sdm_ground_update(self.h, _ptr(o)), "sdm_ground_update")
+        self._call("sdm_ground_update", _ptr(o))
 
     def ground(self):
         """-> (cells, d2, info, origin): GROUND_CELL and uint32 arrays shaped [N_v, N_u] (column word = i_u + j_v * N_u), a
         GROUND_INFO record, origin the global position of the min corner of cell (0, 0, 0) of the snapshot (float32[3])"""
         info, origin = np.zeros(1, GROUND_INFO), np.empty(3, np.float32)
-        _check(self.L, self.L.sdm_get_ground(self.h, None, None, _ptr(info), _ptr(origin)), "sdm_get_ground")
+        self._call("sdm_get_ground", None, None, _ptr(info), _ptr(origin))
         shape = (int(info["n_v"][0]), int(info["n_u"][0]))
         cells, d2 = np.empty(shape, GROUND_CELL), np.empty(shape, np.uint32)
-        _check(self.L, self.L.sdm_get_ground(self.h, _ptr(cells), _ptr(d2), None, None), "sdm_get_ground")
+        self._call("sdm_get_ground", _ptr(cells), _ptr(d2), None, None)
         return cells, d2, info[0], origin
 
     def query_ground(self, xyz, on_device=False, n=None, out=None):
         """xyz: (n, 3) global positions -> GROUND_RESULT per point.  on_device: xyz and out (n GROUND_RESULT) are device
         pointers, as for query_points."""
-        if on_device:
-            _check(self.L, self.L.sdm_query_ground(self.h, _ptr(int(xyz)), int(n), _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_ground")
-            return None
-        p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
-        res = np.empty(len(p), GROUND_RESULT)
-        _check(self.L, self.L.sdm_query_ground(self.h, _ptr(p), len(p), _ptr(res), 0), "sdm_query_ground")
-        return res
+        return self._query("sdm_query_ground", xyz, np.float32, (-1, 3), GROUND_RESULT, 0, on_device, n, out)
 
     def query_footprints(self, footprints, on_device=False, n=None, out=None):
         """footprints: FOOTPRINT records -> FOOTPRINT_RESULT per footprint.  on_device: footprints and out (n
         FOOTPRINT_RESULT) are device pointers."""
-        if on_device:
-            _check(self.L, self.L.sdm_query_footprints(self.h, _ptr(int(footprints)), int(n), _ptr(int(out)), QUERY_ON_DEVICE),
-                   "sdm_query_footprints")
-            return None
-        fp = np.ascontiguousarray(footprints, dtype=FOOTPRINT).reshape(-1)
-        res = np.empty(len(fp), FOOTPRINT_RESULT)
-        _check(self.L, self.L.sdm_query_footprints(self.h, _ptr(fp), len(fp), _ptr(res), 0), "sdm_query_footprints")
-        return res
+        return self._query("sdm_query_footprints", footprints, FOOTPRINT, (-1,), FOOTPRINT_RESULT, 0, on_device, n, out)
 
     # ---- the surface mesh (sdm.h).  mesh_update enqueues a build on the map's stream from the last frame's results;
     # mesh() and mesh_device() answer for that frame until the next build.
@@ -1166,13 +1159,13 @@ class SdmMap:
         o["flags"] = ((MESH_STATIC_ONLY if static_only else 0) | (MESH_MOVABLE_ONLY if movable_only else 0) |
                       (MESH_OBSERVED_ONLY if observed_only else 0) | (MESH_SKIP_UNKNOWN_FACES if skip_unknown_faces else 0) |
                       (MESH_SKIP_BORDER_FACES if skip_border_faces else 0))
-        _check(self.L, self.L.sdm_mesh_update(self.h, _ptr(o)), "sdm_mesh_update")
+        self._call("sdm_mesh_update", _ptr(o))
 
     def mesh_info(self):
         """-> (info, origin): a MESH_INFO record (true counts, also of a build over capacity) and the global position of the
         min corner of cell (0, 0, 0) of the snapshot (float32[3])"""
         info, origin = np.zeros(1, MESH_INFO), np.empty(3, np.float32)
-        _check(self.L, self.L.sdm_get_mesh_info(self.h, _ptr(info), _ptr(origin)), "sdm_get_mesh_info")
+        self._call("sdm_get_mesh_info", _ptr(info), _ptr(origin))
         return info[0], origin
 
     def mesh(self):
@@ -1183,15 +1176,15 @@ class SdmMap:
         faces, quads = np.empty(n, MESH_FACE), np.empty((n, 4), np.uint32)
         corners, xyz = np.empty(k, MESH_VERTEX), np.empty((k, 3), np.float32)
         got = C.c_int64(0)
-        _check(self.L, self.L.sdm_get_mesh_faces(self.h, _ptr(faces), _ptr(quads), n, C.byref(got)), "sdm_get_mesh_faces")
-        _check(self.L, self.L.sdm_get_mesh_vertices(self.h, _ptr(corners), _ptr(xyz), k, C.byref(got)), "sdm_get_mesh_vertices")
+        self._call("sdm_get_mesh_faces", _ptr(faces), _ptr(quads), n, C.byref(got))
+        self._call("sdm_get_mesh_vertices", _ptr(corners), _ptr(xyz), k, C.byref(got))
         return dict(faces=faces, quads=quads, corners=corners, xyz=xyz, info=info, origin=origin)
 
     def mesh_device(self):
         """-> (faces, quads, corners): device addresses of the last build's lists (MESH_FACE, 4 uint32 per face, MESH_VERTEX),
         valid until the next mesh_update, to be read in stream order on the map's stream"""
         p = [C.c_void_p() for _ in range(3)]
-        _check(self.L, self.L.sdm_mesh_device(self.h, *(C.byref(x) for x in p)), "sdm_mesh_device")
+        self._call("sdm_mesh_device", *(C.byref(x) for x in p))
         return tuple(x.value for x in p)
 
     # ---- the world archive (sdm.h).  world_update enqueues the merge of the last frame's results into the archive on the
@@ -1200,26 +1193,26 @@ class SdmMap:
         o = np.zeros(1, WORLD_OPTIONS)
         o["flags"] = (WORLD_STATIC_ONLY if static_only else 0) | (WORLD_OBSERVED_ONLY if observed_only else 0)
         o["max_bricks"] = int(max_bricks)
-        _check(self.L, self.L.sdm_world_update(self.h, _ptr(o)), "sdm_world_update")
+        self._call("sdm_world_update", _ptr(o))
 
     def world_clear(self):
-        _check(self.L, self.L.sdm_world_clear(self.h), "sdm_world_clear")
+        self._call("sdm_world_clear")
 
     def world_info(self):
         """-> a WORLD_INFO record; zeros (bmax -1) before any update and after world_clear"""
         info = np.zeros(1, WORLD_INFO)
-        _check(self.L, self.L.sdm_get_world_info(self.h, _ptr(info)), "sdm_get_world_info")
+        self._call("sdm_get_world_info", _ptr(info))
         return info[0]
 
     def world_bricks(self, with_cells=True, first=0, cap=None):
         """-> (bricks WORLD_BRICK[n], cells uint32[n, 512] or None) in brick order: ascending in (bz, by, bx)"""
         got = C.c_int64()
         if cap is None:
-            _check(self.L, self.L.sdm_get_world_bricks(self.h, None, None, 0, 0, C.byref(got)), "sdm_get_world_bricks")
+            self._call("sdm_get_world_bricks", None, None, 0, 0, C.byref(got))
             cap = max(got.value - int(first), 0)
         bricks = np.empty(cap, WORLD_BRICK)
         cells = np.empty((cap, 512), np.uint32) if with_cells else None
-        _check(self.L, self.L.sdm_get_world_bricks(self.h, _ptr(bricks), _ptr(cells), int(first), cap, C.byref(got)), "sdm_get_world_bricks")
+        self._call("sdm_get_world_bricks", _ptr(bricks), _ptr(cells), int(first), cap, C.byref(got))
         n = max(min(got.value - int(first), cap), 0)
         return bricks[:n], (cells[:n] if with_cells else None)
 
@@ -1227,32 +1220,26 @@ class SdmMap:
         """-> (points POINT[min(n, cap)], n): every archived cell with occ >= 1, ascending in (brick order, cell word)"""
         got = C.c_int64()
         if cap is None:
-            _check(self.L, self.L.sdm_get_world_occupied(self.h, None, 0, C.byref(got), 0), "sdm_get_world_occupied")
+            self._call("sdm_get_world_occupied", None, 0, C.byref(got), 0)
             cap = got.value
         out = np.empty(cap, POINT)
-        _check(self.L, self.L.sdm_get_world_occupied(self.h, _ptr(out), cap, C.byref(got), 0), "sdm_get_world_occupied")
+        self._call("sdm_get_world_occupied", _ptr(out), cap, C.byref(got), 0)
         return out[:min(got.value, cap)], got.value
 
     def query_world(self, xyz, on_device=False, n=None, out=None):
         """xyz: (n, 3) global positions -> WORLD_CELL per point.  on_device: xyz and out (n WORLD_CELL) are device pointers,
         as for query_points."""
-        if on_device:
-            _check(self.L, self.L.sdm_query_world_points(self.h, _ptr(int(xyz)), int(n), _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_world_points")
-            return None
-        p = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
-        res = np.empty(len(p), WORLD_CELL)
-        _check(self.L, self.L.sdm_query_world_points(self.h, _ptr(p), len(p), _ptr(res), 0), "sdm_query_world_points")
-        return res
+        return self._query("sdm_query_world_points", xyz, np.float32, (-1, 3), WORLD_CELL, 0, on_device, n, out)
 
     def world_region(self, cell_min, size, on_device=False, out=None):
         """-> uint32 [size z, size y, size x]: the words of the box of world cells from cell_min (x, y, z) on; on_device: out is
         a device pointer to size x * y * z words, filled in stream order"""
         lo, sz = np.ascontiguousarray(cell_min, np.int32).reshape(3), np.ascontiguousarray(size, np.int32).reshape(3)
         if on_device:
-            _check(self.L, self.L.sdm_get_world_region(self.h, _ptr(lo), _ptr(sz), _ptr(int(out)), QUERY_ON_DEVICE), "sdm_get_world_region")
+            self._call("sdm_get_world_region", _ptr(lo), _ptr(sz), _ptr(int(out)), QUERY_ON_DEVICE)
             return None
         words = np.empty((max(int(sz[2]), 0), max(int(sz[1]), 0), max(int(sz[0]), 0)), np.uint32)
-        _check(self.L, self.L.sdm_get_world_region(self.h, _ptr(lo), _ptr(sz), _ptr(words), 0), "sdm_get_world_region")
+        self._call("sdm_get_world_region", _ptr(lo), _ptr(sz), _ptr(words), 0)
         return words
 
     def world_import(self, bricks, cells, offset=(0, 0, 0), fill=False, static_only=False, observed_only=False, max_bricks=0, on_device=False,
@@ -1266,13 +1253,13 @@ class SdmMap:
         o["cell_offset"][0] = np.asarray(offset, np.int64).reshape(3)
         o["max_bricks"] = int(max_bricks)
         if on_device:
-            _check(self.L, self.L.sdm_world_import(self.h, _ptr(o), _ptr(int(bricks)), _ptr(int(cells)), int(n)), "sdm_world_import")
+            self._call("sdm_world_import", _ptr(o), _ptr(int(bricks)), _ptr(int(cells)), int(n))
             return
         b = np.ascontiguousarray(bricks, WORLD_BRICK).reshape(-1)
         c = np.ascontiguousarray(cells, np.uint32).reshape(-1, 512)
         if len(b) != len(c):
             raise ValueError("world_import: %d headers and %d bricks of cells" % (len(b), len(c)))
-        _check(self.L, self.L.sdm_world_import(self.h, _ptr(o), _ptr(b), _ptr(c), len(b) if n is None else int(n)), "sdm_world_import")
+        self._call("sdm_world_import", _ptr(o), _ptr(b), _ptr(c), len(b) if n is None else int(n))
 
     def world_match(self, bricks, cells, offset=(0, 0, 0), radius=(2, 2, 1), weights=WORLD_MATCH_WEIGHTS, static_only=False,
                     observed_only=False, on_device=False, n=None, scores=True, result=None):
@@ -1291,9 +1278,8 @@ class SdmMap:
         for name, w in zip(("w_oo", "w_same", "w_of", "w_fo", "w_ff"), weights):
             o[name] = int(w)
         if on_device:
-            _check(self.L, self.L.sdm_world_match(self.h, _ptr(o), _ptr(int(bricks)), _ptr(int(cells)), int(n),
-                                                  None if scores is None or isinstance(scores, bool) else _ptr(int(scores)), _ptr(int(result))),
-                   "sdm_world_match")
+            self._call("sdm_world_match", _ptr(o), _ptr(int(bricks)), _ptr(int(cells)), int(n),
+                       None if scores is None or isinstance(scores, bool) else _ptr(int(scores)), _ptr(int(result)))
             return None
         b = np.ascontiguousarray(bricks, WORLD_BRICK).reshape(-1)
         c = np.ascontiguousarray(cells, np.uint32).reshape(-1, 512)
@@ -1302,8 +1288,7 @@ class SdmMap:
         r = [int(v) for v in o["radius"][0]]
         res = np.zeros(1, WORLD_MATCH_RESULT)
         sc = np.zeros(max((2 * r[0] + 1) * (2 * r[1] + 1) * (2 * r[2] + 1), 0), WORLD_MATCH_SCORE) if scores else None
-        _check(self.L, self.L.sdm_world_match(self.h, _ptr(o), _ptr(b), _ptr(c), len(b) if n is None else int(n), _ptr(sc), _ptr(res)),
-               "sdm_world_match")
+        self._call("sdm_world_match", _ptr(o), _ptr(b), _ptr(c), len(b) if n is None else int(n), _ptr(sc), _ptr(res))
         return res[0], sc
 
     def world_align(self, bricks, cells, offset=(0, 0, 0), search=(8, 8, 2), **kw):
@@ -1356,9 +1341,7 @@ class SdmMap:
         o["bmin"][0] = np.asarray((-32768,) * 3 if bmin is None else bmin, np.int64).reshape(3)
         o["bmax"][0] = np.asarray((32767,) * 3 if bmax is None else bmax, np.int64).reshape(3)
         o["min_last_stamp"] = int(min_last_stamp)
-        got = C.c_int64()
-        _check(self.L, self.L.sdm_world_retain(self.h, _ptr(o), C.byref(got)), "sdm_world_retain")
-        return got.value
+        return self._out("sdm_world_retain", C.c_int64, _ptr(o))
 
     # ---- world reach (sdm.h).  world_reach_update builds the travel-cost field over the archive's bricks and WAITS until it
     # is complete; world_reach(), query_world_reach() and world_reach_paths() answer for that build - a snapshot that later
@@ -1373,59 +1356,31 @@ class SdmMap:
         o["inflate"], o["max_cost"] = int(inflate), int(max_cost)
         if box is not None:
             o["bmin"], o["bmax"] = box[0], box[1]
-        p = None if starts is None else np.ascontiguousarray(starts, dtype=np.float32).reshape(-1, 3)
-        w = None if start_cells is None else np.ascontiguousarray(start_cells, dtype=np.int32).reshape(-1, 3)
-        n = len(p) if p is not None else len(w) if w is not None else 0
-        _check(self.L, self.L.sdm_world_reach_update(self.h, _ptr(o), _ptr(p), _ptr(w), n), "sdm_world_reach_update")
+        p, w, n = _goals(starts, start_cells, *_WORLD_CELLS)
+        self._call("sdm_world_reach_update", _ptr(o), _ptr(p), _ptr(w), n)
 
     def world_reach(self, with_cost=True, first=0, cap=None):
         """-> (coords int16 [n, 3] (bx, by, bz), cost uint32 [n, 512] or None, info a WORLD_REACH_INFO record): the bricks of
         the field in brick order, rows first .. first + cap - 1"""
-        got = C.c_int64(0)
-        info = np.zeros(1, WORLD_REACH_INFO)
-        _check(self.L, self.L.sdm_get_world_reach(self.h, None, None, 0, 0, C.byref(got), _ptr(info)), "sdm_get_world_reach")
-        take = max(min(got.value - int(first), got.value if cap is None else int(cap)), 0)
-        coords = np.empty((take, 3), np.int16)
-        cost = np.empty((take, 512), np.uint32) if with_cost else None
-        _check(self.L, self.L.sdm_get_world_reach(self.h, _ptr(coords), _ptr(cost), int(first), take, C.byref(got), None), "sdm_get_world_reach")
-        return coords, cost, info[0]
+        cols = [(np.int16, (3,)), (np.uint32, (512,)) if with_cost else None]
+        (coords, cost), info, _ = self._window("sdm_get_world_reach", cols, first, cap, WORLD_REACH_INFO)
+        return coords, cost, info
 
     def query_world_reach(self, xyz=None, cells=None, on_device=False, n=None, out=None):
         """goals as (n, 3) global positions or as (n, 3) world cells -> WORLD_REACH_RESULT per goal.  on_device: the one
         given of xyz / cells and out (n WORLD_REACH_RESULT) are device pointers."""
-        if on_device:
-            _check(self.L, self.L.sdm_query_world_reach(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
-                                                        _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_world_reach")
-            return None
-        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
-        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
-        n = len(p) if p is not None else len(w) if w is not None else 0
-        res = np.empty(n, WORLD_REACH_RESULT)
-        _check(self.L, self.L.sdm_query_world_reach(self.h, _ptr(p), _ptr(w), n, _ptr(res), 0), "sdm_query_world_reach")
-        return res
+        return self._goal_query("sdm_query_world_reach", xyz, cells, _WORLD_CELLS, WORLD_REACH_RESULT, on_device, n, out)
 
     def world_reach_paths(self, xyz=None, cells=None, max_len=0, on_device=False, n=None, cells_out=None, len_out=None,
                           fill=WORLD_REACH_NO_CELL):
         """-> (cells_out int32 [n, max_len, 3], len_out): row g holds the first min(len, max_len) world cells of goal g's
         path, goal first, and `fill` behind them; len_out the true lengths (int32, 0: no path).  on_device: the pointers are
         device pointers (cells_out n * max_len * 3 int32, len_out n int32) and nothing is returned."""
-        if on_device:
-            _check(self.L, self.L.sdm_world_reach_paths(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
-                                                        int(max_len), _ptr(int(cells_out)) if cells_out else None, _ptr(int(len_out)),
-                                                        QUERY_ON_DEVICE), "sdm_world_reach_paths")
-            return None
-        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
-        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
-        n = len(p) if p is not None else len(w) if w is not None else 0
-        rows, lens = np.full((n, int(max_len), 3), fill, np.int32), np.zeros(n, np.int32)
-        _check(self.L, self.L.sdm_world_reach_paths(self.h, _ptr(p), _ptr(w), n, int(max_len), _ptr(rows), _ptr(lens), 0), "sdm_world_reach_paths")
-        return rows, lens
+        return self._goal_paths("sdm_world_reach_paths", xyz, cells, _WORLD_CELLS, max_len, fill, on_device, n, cells_out, len_out)
 
     def world_reach_bricks_relaxed(self):
         """Diagnostic: the bricks the last world_reach_update relaxed, summed over its rounds (sdm_debug_world_reach_bricks)."""
-        n = C.c_int64(0)
-        _check(self.L, self.L.sdm_debug_world_reach_bricks(self.h, C.byref(n)), "sdm_debug_world_reach_bricks")
-        return n.value
+        return self._out("sdm_debug_world_reach_bricks", C.c_int64)
 
     # ---- world frontiers (sdm.h).  world_frontiers_update builds the frontier cells of the archive's bricks and their
     # clusters and WAITS until they are complete; world_frontiers() and world_frontier_cells() answer for that build - a
@@ -1439,27 +1394,21 @@ class SdmMap:
         o["min_cells"], o["max_cells"] = int(min_cells), int(max_cells)
         if box is not None:
             o["bmin"], o["bmax"] = box[0], box[1]
-        _check(self.L, self.L.sdm_world_frontiers_update(self.h, _ptr(o)), "sdm_world_frontiers_update")
+        self._call("sdm_world_frontiers_update", _ptr(o))
 
     def world_frontiers(self):
         """-> (clusters, info): WORLD_FRONTIER_CLUSTER entries in ascending first_index, a WORLD_FRONTIERS_INFO record"""
         got = C.c_int32(0)
         info = np.zeros(1, WORLD_FRONTIERS_INFO)
-        _check(self.L, self.L.sdm_get_world_frontier_clusters(self.h, None, 0, C.byref(got), _ptr(info)), "sdm_get_world_frontier_clusters")
+        self._call("sdm_get_world_frontier_clusters", None, 0, C.byref(got), _ptr(info))
         out = np.empty(got.value, WORLD_FRONTIER_CLUSTER)
-        _check(self.L, self.L.sdm_get_world_frontier_clusters(self.h, _ptr(out), got.value, C.byref(got), None), "sdm_get_world_frontier_clusters")
+        self._call("sdm_get_world_frontier_clusters", _ptr(out), got.value, C.byref(got), None)
         return out, info[0]
 
     def world_frontier_cells(self, first=0, cap=None):
         """-> (cells int32 [n, 3] world cells, cluster uint32, unknown_faces uint8): rows first .. first + cap - 1 of the cell
         list, ascending in (brick order, cell word); cluster indexes the table (WORLD_FRONTIER_NO_CLUSTER: below min_cells)"""
-        got = C.c_int64(0)
-        _check(self.L, self.L.sdm_get_world_frontier_cells(self.h, None, None, None, 0, 0, C.byref(got)), "sdm_get_world_frontier_cells")
-        take = max(min(got.value - int(first), got.value if cap is None else int(cap)), 0)
-        cells, cluster, faces = np.empty((take, 3), np.int32), np.empty(take, np.uint32), np.empty(take, np.uint8)
-        _check(self.L, self.L.sdm_get_world_frontier_cells(self.h, _ptr(cells), _ptr(cluster), _ptr(faces), int(first), take, C.byref(got)),
-               "sdm_get_world_frontier_cells")
-        return cells, cluster, faces
+        return tuple(self._window("sdm_get_world_frontier_cells", [(np.int32, (3,)), (np.uint32, ()), (np.uint8, ())], first, cap)[0])
 
     # ---- world objects (sdm.h).  world_objects_update builds the connected same-key components of the archive's occupied
     # cells and WAITS until they are complete; world_objects(), world_object_cells(), world_object_labels() and
@@ -1477,32 +1426,26 @@ class SdmMap:
         o["labels"] = label_mask(labels)
         if box is not None:
             o["bmin"], o["bmax"] = box[0], box[1]
-        _check(self.L, self.L.sdm_world_objects_update(self.h, _ptr(o)), "sdm_world_objects_update")
+        self._call("sdm_world_objects_update", _ptr(o))
 
     def world_objects(self):
         """-> (table, info): WORLD_OBJECT entries in ascending first_index, a WORLD_OBJECTS_INFO record"""
         got = C.c_int32(0)
         info = np.zeros(1, WORLD_OBJECTS_INFO)
-        _check(self.L, self.L.sdm_get_world_objects(self.h, None, 0, C.byref(got), _ptr(info)), "sdm_get_world_objects")
+        self._call("sdm_get_world_objects", None, 0, C.byref(got), _ptr(info))
         out = np.empty(got.value, WORLD_OBJECT)
-        _check(self.L, self.L.sdm_get_world_objects(self.h, _ptr(out), got.value, C.byref(got), None), "sdm_get_world_objects")
+        self._call("sdm_get_world_objects", _ptr(out), got.value, C.byref(got), None)
         return out, info[0]
 
     def world_object_cells(self, first=0, cap=None):
         """-> (cells int32 [n, 3] world cells, object uint32, words uint32): rows first .. first + cap - 1 of the cell list,
         ascending in (brick order, cell word); object indexes the table (WORLD_OBJECT_UNLISTED: below min_cells)"""
-        got = C.c_int64(0)
-        _check(self.L, self.L.sdm_get_world_object_cells(self.h, None, None, None, 0, 0, C.byref(got)), "sdm_get_world_object_cells")
-        take = max(min(got.value - int(first), got.value if cap is None else int(cap)), 0)
-        cells, obj, words = np.empty((take, 3), np.int32), np.empty(take, np.uint32), np.empty(take, np.uint32)
-        _check(self.L, self.L.sdm_get_world_object_cells(self.h, _ptr(cells), _ptr(obj), _ptr(words), int(first), take, C.byref(got)),
-               "sdm_get_world_object_cells")
-        return cells, obj, words
+        return tuple(self._window("sdm_get_world_object_cells", [(np.int32, (3,)), (np.uint32, ()), (np.uint32, ())], first, cap)[0])
 
     def world_object_labels(self):
         """-> (cells uint64 [256], objects uint32 [256]): per label the counted cells and the objects in all"""
         cells, objects = np.zeros(256, np.uint64), np.zeros(256, np.uint32)
-        _check(self.L, self.L.sdm_get_world_object_labels(self.h, _ptr(cells), _ptr(objects)), "sdm_get_world_object_labels")
+        self._call("sdm_get_world_object_labels", _ptr(cells), _ptr(objects))
         return cells, objects
 
     def world_object_members(self, i):
@@ -1514,16 +1457,7 @@ class SdmMap:
     def query_world_objects(self, xyz=None, cells=None, on_device=False, n=None, out=None):
         """(n, 3) global positions or (n, 3) world cells -> WORLD_OBJECT_RESULT per entry.  on_device: the one given of
         xyz / cells and out (n WORLD_OBJECT_RESULT) are device pointers."""
-        if on_device:
-            _check(self.L, self.L.sdm_query_world_objects(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
-                                                          _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_world_objects")
-            return None
-        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
-        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
-        n = len(p) if p is not None else len(w) if w is not None else 0
-        res = np.empty(n, WORLD_OBJECT_RESULT)
-        _check(self.L, self.L.sdm_query_world_objects(self.h, _ptr(p), _ptr(w), n, _ptr(res), 0), "sdm_query_world_objects")
-        return res
+        return self._goal_query("sdm_query_world_objects", xyz, cells, _WORLD_CELLS, WORLD_OBJECT_RESULT, on_device, n, out)
 
     # ---- world distance field (sdm.h).  world_esdf_update builds the truncated distance field over the archive's bricks
     # (it waits once, for the field's brick count); world_esdf() and query_world_distance() answer for that build - a
@@ -1537,34 +1471,20 @@ class SdmMap:
         o["radius"] = int(radius)
         if box is not None:
             o["bmin"], o["bmax"] = box[0], box[1]
-        _check(self.L, self.L.sdm_world_esdf_update(self.h, _ptr(o)), "sdm_world_esdf_update")
+        self._call("sdm_world_esdf_update", _ptr(o))
 
     def world_esdf(self, first=0, cap=None):
         """-> (coords int16 [n, 3] (bx, by, bz), d2 uint16 [n, 512] (WORLD_ESDF_NONE: beyond the radius), offset int8
         [n, 512, 3] (dx, dy, dz) to the nearest obstacle, info a WORLD_ESDF_INFO record): the bricks of the field in brick
         order, rows first .. first + cap - 1"""
-        got = C.c_int64(0)
-        info = np.zeros(1, WORLD_ESDF_INFO)
-        _check(self.L, self.L.sdm_get_world_esdf(self.h, None, None, None, 0, 0, C.byref(got), _ptr(info)), "sdm_get_world_esdf")
-        take = max(min(got.value - int(first), got.value if cap is None else int(cap)), 0)
-        coords, d2, offset = np.empty((take, 3), np.int16), np.empty((take, 512), np.uint16), np.empty((take, 512, 3), np.int8)
-        _check(self.L, self.L.sdm_get_world_esdf(self.h, _ptr(coords), _ptr(d2), _ptr(offset), int(first), take, C.byref(got), None),
-               "sdm_get_world_esdf")
-        return coords, d2, offset, info[0]
+        cols = [(np.int16, (3,)), (np.uint16, (512,)), (np.int8, (512, 3))]
+        (coords, d2, offset), info, _ = self._window("sdm_get_world_esdf", cols, first, cap, WORLD_ESDF_INFO)
+        return coords, d2, offset, info
 
     def query_world_distance(self, xyz=None, cells=None, on_device=False, n=None, out=None):
         """(n, 3) global positions or (n, 3) world cells -> WORLD_DISTANCE_RESULT per entry.  on_device: the one given of
         xyz / cells and out (n WORLD_DISTANCE_RESULT) are device pointers."""
-        if on_device:
-            _check(self.L, self.L.sdm_query_world_distance(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
-                                                           _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_world_distance")
-            return None
-        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
-        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
-        n = len(p) if p is not None else len(w) if w is not None else 0
-        res = np.empty(n, WORLD_DISTANCE_RESULT)
-        _check(self.L, self.L.sdm_query_world_distance(self.h, _ptr(p), _ptr(w), n, _ptr(res), 0), "sdm_query_world_distance")
-        return res
+        return self._goal_query("sdm_query_world_distance", xyz, cells, _WORLD_CELLS, WORLD_DISTANCE_RESULT, on_device, n, out)
 
     # ---- world ground layer (sdm.h).  world_ground_update builds the height map, the costmap and the truncated distance
     # to the nearest lethal column over the archive's bricks (it waits once, for the tile count); world_ground(),
@@ -1583,46 +1503,25 @@ class SdmMap:
                       (WORLD_GROUND_BOX if box is not None else 0))
         if box is not None:
             o["tmin"], o["tmax"] = box[0], box[1]
-        _check(self.L, self.L.sdm_world_ground_update(self.h, _ptr(o)), "sdm_world_ground_update")
+        self._call("sdm_world_ground_update", _ptr(o))
 
     def world_ground(self, first=0, cap=None):
         """-> (coords int16 [n, 2] (bu, bv), cells GROUND_CELL [n, 64], d2 uint16 [n, 64] (WORLD_GROUND_NONE: beyond the
         radius), info a WORLD_GROUND_INFO record): the tiles in (bv, bu) order, rows first .. first + cap - 1; a column's
         word is cu | cv << 3; level and top are relative to h_lo"""
-        got = C.c_int64(0)
-        info = np.zeros(1, WORLD_GROUND_INFO)
-        _check(self.L, self.L.sdm_get_world_ground(self.h, None, None, None, 0, 0, C.byref(got), _ptr(info)), "sdm_get_world_ground")
-        take = max(min(got.value - int(first), got.value if cap is None else int(cap)), 0)
-        coords, cells, d2 = np.empty((take, 2), np.int16), np.empty((take, 64), GROUND_CELL), np.empty((take, 64), np.uint16)
-        _check(self.L, self.L.sdm_get_world_ground(self.h, _ptr(coords), _ptr(cells), _ptr(d2), int(first), take, C.byref(got), None),
-               "sdm_get_world_ground")
-        return coords, cells, d2, info[0]
+        cols = [(np.int16, (2,)), (GROUND_CELL, (64,)), (np.uint16, (64,))]
+        (coords, cells, d2), info, _ = self._window("sdm_get_world_ground", cols, first, cap, WORLD_GROUND_INFO)
+        return coords, cells, d2, info
 
     def query_world_ground(self, xyz=None, cells=None, on_device=False, n=None, out=None):
         """(n, 3) global positions or (n, 3) world cells -> WORLD_GROUND_RESULT per entry.  on_device: the one given of
         xyz / cells and out (n WORLD_GROUND_RESULT) are device pointers."""
-        if on_device:
-            _check(self.L, self.L.sdm_query_world_ground(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
-                                                         _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_world_ground")
-            return None
-        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
-        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
-        n = len(p) if p is not None else len(w) if w is not None else 0
-        res = np.empty(n, WORLD_GROUND_RESULT)
-        _check(self.L, self.L.sdm_query_world_ground(self.h, _ptr(p), _ptr(w), n, _ptr(res), 0), "sdm_query_world_ground")
-        return res
+        return self._goal_query("sdm_query_world_ground", xyz, cells, _WORLD_CELLS, WORLD_GROUND_RESULT, on_device, n, out)
 
     def query_world_footprints(self, footprints, on_device=False, n=None, out=None):
         """footprints: FOOTPRINT records (centre in world metres along u and v) -> WORLD_FOOTPRINT_RESULT per footprint.
         on_device: footprints and out (n WORLD_FOOTPRINT_RESULT) are device pointers."""
-        if on_device:
-            _check(self.L, self.L.sdm_query_world_footprints(self.h, _ptr(int(footprints)), int(n), _ptr(int(out)), QUERY_ON_DEVICE),
-                   "sdm_query_world_footprints")
-            return None
-        fp = np.ascontiguousarray(footprints, dtype=FOOTPRINT).reshape(-1)
-        res = np.empty(len(fp), WORLD_FOOTPRINT_RESULT)
-        _check(self.L, self.L.sdm_query_world_footprints(self.h, _ptr(fp), len(fp), _ptr(res), 0), "sdm_query_world_footprints")
-        return res
+        return self._query("sdm_query_world_footprints", footprints, FOOTPRINT, (-1,), WORLD_FOOTPRINT_RESULT, 0, on_device, n, out)
 
     # ---- world ground reach (sdm.h).  world_ground_reach_update builds the 2-D travel-cost field over the last
     # world_ground_update's costmap and WAITS until it is complete; world_ground_reach(), query_world_ground_reach() and
@@ -1638,37 +1537,20 @@ class SdmMap:
         o["min_d2"], o["soft_d2"], o["penalty"], o["max_climb"], o["max_cost"] = int(min_d2), int(soft_d2), int(penalty), int(max_climb), int(max_cost)
         if box is not None:
             o["tmin"], o["tmax"] = box[0], box[1]
-        p = None if starts is None else np.ascontiguousarray(starts, dtype=np.float32).reshape(-1, 3)
-        w = None if start_cells is None else np.ascontiguousarray(start_cells, dtype=np.int32).reshape(-1, 3)
-        n = len(p) if p is not None else len(w) if w is not None else 0
-        _check(self.L, self.L.sdm_world_ground_reach_update(self.h, _ptr(o), _ptr(p), _ptr(w), n), "sdm_world_ground_reach_update")
+        p, w, n = _goals(starts, start_cells, *_WORLD_CELLS)
+        self._call("sdm_world_ground_reach_update", _ptr(o), _ptr(p), _ptr(w), n)
 
     def world_ground_reach(self, with_cost=True, first=0, cap=None):
         """-> (coords int16 [n, 2] (bu, bv), cost uint32 [n, 64] or None, info a WORLD_GROUND_REACH_INFO record): the tiles
         of the field in (bv, bu) order, rows first .. first + cap - 1; a column's word is cu | cv << 3"""
-        got = C.c_int64(0)
-        info = np.zeros(1, WORLD_GROUND_REACH_INFO)
-        _check(self.L, self.L.sdm_get_world_ground_reach(self.h, None, None, 0, 0, C.byref(got), _ptr(info)), "sdm_get_world_ground_reach")
-        take = max(min(got.value - int(first), got.value if cap is None else int(cap)), 0)
-        coords = np.empty((take, 2), np.int16)
-        cost = np.empty((take, 64), np.uint32) if with_cost else None
-        _check(self.L, self.L.sdm_get_world_ground_reach(self.h, _ptr(coords), _ptr(cost), int(first), take, C.byref(got), None),
-               "sdm_get_world_ground_reach")
-        return coords, cost, info[0]
+        cols = [(np.int16, (2,)), (np.uint32, (64,)) if with_cost else None]
+        (coords, cost), info, _ = self._window("sdm_get_world_ground_reach", cols, first, cap, WORLD_GROUND_REACH_INFO)
+        return coords, cost, info
 
     def query_world_ground_reach(self, xyz=None, cells=None, on_device=False, n=None, out=None):
         """goals as (n, 3) global positions or as (n, 3) world cells -> WORLD_GROUND_REACH_RESULT per goal.  on_device: the
         one given of xyz / cells and out (n WORLD_GROUND_REACH_RESULT) are device pointers."""
-        if on_device:
-            _check(self.L, self.L.sdm_query_world_ground_reach(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
-                                                               _ptr(int(out)), QUERY_ON_DEVICE), "sdm_query_world_ground_reach")
-            return None
-        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
-        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
-        n = len(p) if p is not None else len(w) if w is not None else 0
-        res = np.empty(n, WORLD_GROUND_REACH_RESULT)
-        _check(self.L, self.L.sdm_query_world_ground_reach(self.h, _ptr(p), _ptr(w), n, _ptr(res), 0), "sdm_query_world_ground_reach")
-        return res
+        return self._goal_query("sdm_query_world_ground_reach", xyz, cells, _WORLD_CELLS, WORLD_GROUND_REACH_RESULT, on_device, n, out)
 
     def world_ground_reach_paths(self, xyz=None, cells=None, max_len=0, on_device=False, n=None, cells_out=None, len_out=None,
                                  fill=WORLD_REACH_NO_CELL):
@@ -1676,24 +1558,11 @@ class SdmMap:
         path, goal first - the cells the robot's base stands in -, and `fill` behind them; len_out the true lengths (int32,
         0: no path).  on_device: the pointers are device pointers (cells_out n * max_len * 3 int32, len_out n int32) and
         nothing is returned."""
-        if on_device:
-            _check(self.L, self.L.sdm_world_ground_reach_paths(self.h, _ptr(int(xyz)) if xyz else None, _ptr(int(cells)) if cells else None, int(n),
-                                                               int(max_len), _ptr(int(cells_out)) if cells_out else None, _ptr(int(len_out)),
-                                                               QUERY_ON_DEVICE), "sdm_world_ground_reach_paths")
-            return None
-        p = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
-        w = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
-        n = len(p) if p is not None else len(w) if w is not None else 0
-        rows, lens = np.full((n, int(max_len), 3), fill, np.int32), np.zeros(n, np.int32)
-        _check(self.L, self.L.sdm_world_ground_reach_paths(self.h, _ptr(p), _ptr(w), n, int(max_len), _ptr(rows), _ptr(lens), 0),
-               "sdm_world_ground_reach_paths")
-        return rows, lens
+        return self._goal_paths("sdm_world_ground_reach_paths", xyz, cells, _WORLD_CELLS, max_len, fill, on_device, n, cells_out, len_out)
 
     def world_ground_reach_tiles_relaxed(self):
         """Diagnostic: the tiles the last world_ground_reach_update relaxed, summed over its rounds."""
-        n = C.c_int64(0)
-        _check(self.L, self.L.sdm_debug_world_ground_reach_tiles(self.h, C.byref(n)), "sdm_debug_world_ground_reach_tiles")
-        return n.value
+        return self._out("sdm_debug_world_ground_reach_tiles", C.c_int64)
 
     # ---- world rays (sdm.h).  Segments and views through the archive, read live in stream order: host mode takes numpy
     # and waits, on_device=True takes device pointers (outputs 8-byte aligned), enqueues on the map's stream and returns.
@@ -1701,15 +1570,7 @@ class SdmMap:
         """a, b: (n, 3) end points -> WORLD_SEGMENT_HIT per segment.  on_device: a is a device pointer to n rows of
         (ax ay az bx by bz) floats, b is None, out a device pointer to n WORLD_SEGMENT_HIT."""
         fl = (QUERY_UNKNOWN_BLOCKS if unknown_blocks else 0) | (WORLD_RAYS_IGNORE_MOVABLE if ignore_movable else 0)
-        if on_device:
-            assert b is None
-            _check(self.L, self.L.sdm_query_world_segments(self.h, _ptr(int(a)), int(n), _ptr(int(out)), fl | QUERY_ON_DEVICE),
-                   "sdm_query_world_segments")
-            return None
-        ab = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float32).reshape(-1, 3), np.asarray(b, np.float32).reshape(-1, 3)], axis=1))
-        res = np.empty(len(ab), WORLD_SEGMENT_HIT)
-        _check(self.L, self.L.sdm_query_world_segments(self.h, _ptr(ab), len(ab), _ptr(res), fl), "sdm_query_world_segments")
-        return res
+        return self._query("sdm_query_world_segments", _rows6(a, b, on_device), np.float32, (-1, 6), WORLD_SEGMENT_HIT, fl, on_device, n, out)
 
     def query_world_views(self, views, dirs, reach_cells, with_rays=False, ignore_movable=False, on_device=False, n_views=None, n_rays=None,
                           out=None, rays_out=None):
@@ -1719,22 +1580,20 @@ class SdmMap:
         WORLD_SEGMENT_HIT, or None) are device pointers, n_views and n_rays their lengths."""
         fl = WORLD_RAYS_IGNORE_MOVABLE if ignore_movable else 0
         if on_device:
-            _check(self.L, self.L.sdm_query_world_views(self.h, _ptr(int(views)), int(n_views), _ptr(int(dirs)), int(n_rays), int(reach_cells),
-                                                        _ptr(int(out)), _ptr(int(rays_out)) if rays_out else None, fl | QUERY_ON_DEVICE),
-                   "sdm_query_world_views")
+            self._call("sdm_query_world_views", _ptr(int(views)), int(n_views), _ptr(int(dirs)), int(n_rays), int(reach_cells), _ptr(int(out)),
+                       _dev(rays_out), fl | QUERY_ON_DEVICE)
             return None
         v = np.ascontiguousarray(views, dtype=VIEW).reshape(-1)
         d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
         gain = np.empty(len(v), VIEW_GAIN)
         rays = np.empty((len(v), len(d)), WORLD_SEGMENT_HIT) if with_rays else None
-        _check(self.L, self.L.sdm_query_world_views(self.h, _ptr(v), len(v), _ptr(d), len(d), int(reach_cells), _ptr(gain), _ptr(rays), fl),
-               "sdm_query_world_views")
+        self._call("sdm_query_world_views", _ptr(v), len(v), _ptr(d), len(d), int(reach_cells), _ptr(gain), _ptr(rays), fl)
         return (gain, rays) if with_rays else gain
 
     def set_world_view_batch(self, max_views_in_flight):
         """Test hook: query_world_views keeps at most this many views in flight (<= 0: the library's choice)
         (sdm_debug_world_view_batch)."""
-        _check(self.L, self.L.sdm_debug_world_view_batch(self.h, int(max_views_in_flight)), "sdm_debug_world_view_batch")
+        self._call("sdm_debug_world_view_batch", int(max_views_in_flight))
 
     # ---- the world mesh (sdm.h).  world_mesh_update builds the faces and welded vertices of the archive's surface and WAITS
     # for the counts that size its lists; world_mesh() and world_mesh_device() answer for that build - a snapshot - until the
@@ -1752,12 +1611,12 @@ class SdmMap:
                       (WORLD_MESH_SKIP_ABSENT_FACES if skip_absent_faces else 0) | (WORLD_MESH_BOX if box is not None else 0))
         if box is not None:
             o["bmin"], o["bmax"] = np.asarray(box[0], np.int32), np.asarray(box[1], np.int32)
-        _check(self.L, self.L.sdm_world_mesh_update(self.h, _ptr(o)), "sdm_world_mesh_update")
+        self._call("sdm_world_mesh_update", _ptr(o))
 
     def world_mesh_info(self):
         """-> a WORLD_MESH_INFO record (true counts, also of a build over a cap)"""
         info = np.zeros(1, WORLD_MESH_INFO)
-        _check(self.L, self.L.sdm_get_world_mesh_info(self.h, _ptr(info)), "sdm_get_world_mesh_info")
+        self._call("sdm_get_world_mesh_info", _ptr(info))
         return info[0]
 
     def world_mesh(self):
@@ -1769,16 +1628,15 @@ class SdmMap:
         coords, faces, quads = np.empty((b, 3), np.int16), np.empty(n, WORLD_MESH_FACE), np.empty((n, 4), np.uint32)
         corners, xyz = np.empty((k, 3), np.int32), np.empty((k, 3), np.float32)
         got = C.c_int64(0)
-        _check(self.L, self.L.sdm_get_world_mesh_faces(self.h, _ptr(coords), _ptr(faces), _ptr(quads), 0, n, C.byref(got)),
-               "sdm_get_world_mesh_faces")
-        _check(self.L, self.L.sdm_get_world_mesh_vertices(self.h, _ptr(corners), _ptr(xyz), 0, k, C.byref(got)), "sdm_get_world_mesh_vertices")
+        self._call("sdm_get_world_mesh_faces", _ptr(coords), _ptr(faces), _ptr(quads), 0, n, C.byref(got))
+        self._call("sdm_get_world_mesh_vertices", _ptr(corners), _ptr(xyz), 0, k, C.byref(got))
         return dict(coords=coords, faces=faces, quads=quads, corners=corners, xyz=xyz, info=info)
 
     def world_mesh_device(self):
         """-> (faces, quads, corners): device addresses of the last build's lists (WORLD_MESH_FACE, 4 uint32 per face, 3 int32
         per vertex), valid until the next world_mesh_update, to be read in stream order on the map's stream"""
         p = [C.c_void_p() for _ in range(3)]
-        _check(self.L, self.L.sdm_world_mesh_device(self.h, *(C.byref(x) for x in p)), "sdm_world_mesh_device")
+        self._call("sdm_world_mesh_device", *(C.byref(x) for x in p))
         return tuple(x.value for x in p)
 
     def save_world_ply(self, path, **update_kwargs):
@@ -1823,7 +1681,7 @@ class SdmMap:
         C.memmove(c.perm, pm.ctypes.data, 256)
         c.background_label, c.colour_by_label = int(background_label), 1 if colour_by_label else 0
         c.jet_axis, c.evaluation_format = int(jet_axis), 1 if evaluation_format else 0
-        _check(self.L, self.L.sdm_set_colours(self.h, C.byref(c)), "sdm_set_colours")
+        self._call("sdm_set_colours", C.byref(c))
 
     def occupied_rgb(self, cap=None, zero_center=False, free=False):
         """getOccupancyResult's cloud coloured and packed on the device: POINT_XYZRGB records."""
@@ -1835,15 +1693,13 @@ class SdmMap:
         return out[:min(n.value, cap)], n.value
 
     def object_particle_count(self, track):
-        n = C.c_int64()
-        _check(self.L, self.L.sdm_object_particle_count(self.h, track, C.byref(n)), "sdm_object_particle_count")
-        return n.value
+        return self._out("sdm_object_particle_count", C.c_int64, track)
 
     def tracks_with_particles(self):
         """Track ids that own at least one slot, ascending (the non-empty keys of the reference's indices_map)."""
         out = np.zeros(65536, np.int32)
         n = C.c_int32(0)
-        _check(self.L, self.L.sdm_tracks_with_particles(self.h, _ptr(out), out.size, C.byref(n)), "sdm_tracks_with_particles")
+        self._call("sdm_tracks_with_particles", _ptr(out), out.size, C.byref(n))
         return out[:n.value].copy()
 
     def stats_unchecked(self):
@@ -1862,14 +1718,14 @@ class SdmMap:
         return d
 
     def set_profiling(self, on=True):
-        _check(self.L, self.L.sdm_set_profiling(self.h, 1 if on else 0), "sdm_set_profiling")
+        self._call("sdm_set_profiling", 1 if on else 0)
 
     def force_generic_flood(self, on=True):
-        _check(self.L, self.L.sdm_debug_force_generic_flood(self.h, 1 if on else 0), "sdm_debug_force_generic_flood")
+        self._call("sdm_debug_force_generic_flood", 1 if on else 0)
 
     def ring_state(self):
         r = RingState()
-        _check(self.L, self.L.sdm_get_ring_state(self.h, C.byref(r)), "sdm_get_ring_state")
+        self._call("sdm_get_ring_state", C.byref(r))
         return {"global_time_stamp": r.global_time_stamp, "moved_steps": list(r.moved_steps),
                 "eq_steps": list(r.eq_steps), "map_center": list(r.map_center), "last_pos": list(r.last_pos),
                 "birth_cursor": r.birth_cursor, "move_cursor": r.move_cursor}
@@ -1884,97 +1740,90 @@ class SdmMap:
             r.last_pos[i] = d["last_pos"][i]
         r.birth_cursor = d["birth_cursor"]
         r.move_cursor = d["move_cursor"]
-        _check(self.L, self.L.sdm_set_ring_state(self.h, C.byref(r)), "sdm_set_ring_state")
+        self._call("sdm_set_ring_state", C.byref(r))
 
     def stamps(self):
         c = self.cfg
         sx = np.empty(1 << c.x_n, np.uint32)
         sy = np.empty(1 << c.y_n, np.uint32)
         sz = np.empty(1 << c.z_n, np.uint32)
-        _check(self.L, self.L.sdm_get_stamps(self.h, _ptr(sx), _ptr(sy), _ptr(sz)), "sdm_get_stamps")
+        self._call("sdm_get_stamps", _ptr(sx), _ptr(sy), _ptr(sz))
         return sx, sy, sz
 
     def set_stamps(self, sx, sy, sz):
         sx, sy, sz = (np.ascontiguousarray(a, dtype=np.uint32) for a in (sx, sy, sz))
-        _check(self.L, self.L.sdm_set_stamps(self.h, _ptr(sx), _ptr(sy), _ptr(sz)), "sdm_set_stamps")
+        self._call("sdm_set_stamps", _ptr(sx), _ptr(sy), _ptr(sz))
 
     def dump_state(self):
         n = self.v_count * self.S
         st = {k: np.empty(n, dt) for k, dt in STATE_FIELDS}
-        _check(self.L, self.L.sdm_dump_state(self.h, *[_ptr(st[k]) for k, _ in STATE_FIELDS]), "sdm_dump_state")
+        self._call("sdm_dump_state", *[_ptr(st[k]) for k, _ in STATE_FIELDS])
         return st
 
     def load_state(self, st):
         arrs = [np.ascontiguousarray(st[k], dtype=dt) for k, dt in STATE_FIELDS]
-        _check(self.L, self.L.sdm_load_state(self.h, *[_ptr(a) for a in arrs]), "sdm_load_state")
+        self._call("sdm_load_state", *[_ptr(a) for a in arrs])
 
     def ck_kappa(self):
         out = np.empty(self.W * self.H, np.float32)
-        _check(self.L, self.L.sdm_get_ck_kappa(self.h, _ptr(out)), "sdm_get_ck_kappa")
+        self._call("sdm_get_ck_kappa", _ptr(out))
         return out.reshape(self.H, self.W)
 
     def bin_counts(self):
         out = np.empty(self.W * self.H, np.uint32)
-        _check(self.L, self.L.sdm_get_bin_counts(self.h, _ptr(out)), "sdm_get_bin_counts")
+        self._call("sdm_get_bin_counts", _ptr(out))
         return out.reshape(self.H, self.W)
 
     def bins(self):
         n = C.c_int64()
-        _check(self.L, self.L.sdm_get_bins(self.h, None, 0, C.byref(n)), "sdm_get_bins")
+        self._call("sdm_get_bins", None, 0, C.byref(n))
         out = np.empty(max(n.value, 1), np.uint32)
-        _check(self.L, self.L.sdm_get_bins(self.h, _ptr(out), n.value, C.byref(n)), "sdm_get_bins")
+        self._call("sdm_get_bins", _ptr(out), n.value, C.byref(n))
         return out[:n.value]
 
     def extrinsic(self):
         out = np.empty(16, np.float32)
-        _check(self.L, self.L.sdm_get_extrinsic(self.h, _ptr(out)), "sdm_get_extrinsic")
+        self._call("sdm_get_extrinsic", _ptr(out))
         return out.reshape(4, 4)
 
     def fill_dense_ex(self, mode):
-        _check(self.L, self.L.sdm_debug_fill_dense_ex(self.h, mode), "sdm_debug_fill_dense_ex")
+        self._call("sdm_debug_fill_dense_ex", mode)
 
     def hinted_groups(self):
-        n = C.c_int64()
-        _check(self.L, self.L.sdm_debug_hinted_groups(self.h, C.byref(n)), "sdm_debug_hinted_groups")
-        return n.value
+        return self._out("sdm_debug_hinted_groups", C.c_int64)
 
     def force_sweep_lists(self, mode):
         """Test hook: 1 / 0 = the non-incremental sweeps always / never hand their sparse voxels to per-tile lists, -1 = the
         library picks per sweep (sdm_debug_sweep_lists)."""
-        _check(self.L, self.L.sdm_debug_sweep_lists(self.h, int(mode)), "sdm_debug_sweep_lists")
+        self._call("sdm_debug_sweep_lists", int(mode))
 
     def sweep_mode(self):
         """Test hook: bit 0 - the next non-incremental sweep uses per-tile lists; bit 1 - it is one launch (every group of
         512 voxels was dense in the last one) (sdm_debug_sweep_mode)."""
-        v = C.c_int32(0)
-        _check(self.L, self.L.sdm_debug_sweep_mode(self.h, C.byref(v)), "sdm_debug_sweep_mode")
-        return v.value
+        return self._out("sdm_debug_sweep_mode", C.c_int32)
 
     def set_alias_cap(self, cap):
         """Test hook: the table of older owner-set memberships reports its overflow at `cap` entries (before the first frame)."""
-        _check(self.L, self.L.sdm_debug_alias_cap(self.h, int(cap)), "sdm_debug_alias_cap")
+        self._call("sdm_debug_alias_cap", int(cap))
 
     def fill_dense(self):
-        _check(self.L, self.L.sdm_debug_fill_dense(self.h), "sdm_debug_fill_dense")
+        self._call("sdm_debug_fill_dense")
 
     def time_occupancy_sweep(self, iters=20):
-        ms = C.c_float()
-        _check(self.L, self.L.sdm_time_occupancy_sweep(self.h, iters, C.byref(ms)), "sdm_time_occupancy_sweep")
-        return ms.value
+        return self._out("sdm_time_occupancy_sweep", C.c_float, iters)
 
 
 def forecast_stamps(voxel_size, motions, horizons, swept=False, cap=None):
     """The stamps a forecast build makes of these motions and horizons (sdm_forecast_stamps: host code, no map, no device)
     -> FORECAST_STAMP records (with cap: at most so many, and the true count as a second value)"""
-    L = load_library()
     mo = np.zeros(0, MOTION) if motions is None else np.ascontiguousarray(motions, dtype=MOTION).reshape(-1)
     t = np.ascontiguousarray(horizons, dtype=np.float32).reshape(-1)
     fl, n = FORECAST_SWEPT if swept else 0, C.c_int64(0)
     if cap is None:
-        _check(L, L.sdm_forecast_stamps(float(voxel_size), _ptr(mo), len(mo), _ptr(t), len(t), fl, None, 0, C.byref(n)), "sdm_forecast_stamps")
+        _call("sdm_forecast_stamps", float(voxel_size), _ptr(mo), len(mo), _ptr(t), len(t), fl, None, 0, C.byref(n))
     k = n.value if cap is None else int(cap)
     out = np.zeros(k, FORECAST_STAMP)
-    _check(L, L.sdm_forecast_stamps(float(voxel_size), _ptr(mo), len(mo), _ptr(t), len(t), fl, _ptr(out), k, C.byref(n)), "sdm_forecast_stamps")
+    _call("sdm_forecast_stamps", float(voxel_size), _ptr(mo), len(mo), _ptr(t), len(t), fl, _ptr(out), k, C.byref(n))
     return out if cap is None else (out[:min(k, n.value)], n.value)
 
 
@@ -1994,26 +1843,23 @@ def pinhole_rays(cfg, stride=1):
 
 def comm_unique_id():
     """128-byte RCCL id drawn on this process (rank 0 broadcasts it to the other ranks)."""
-    L = load_library()
     buf = np.zeros(128, np.uint8)
-    _check(L, L.sdm_comm_unique_id(_ptr(buf)), "sdm_comm_unique_id")
+    _call("sdm_comm_unique_id", _ptr(buf))
     return buf.tobytes()
 
 
 def test_scan(a):
-    L = load_library()
     a = np.ascontiguousarray(a, dtype=np.uint32)
     out = np.empty_like(a)
-    _check(L, L.sdm_test_scan(_ptr(a), _ptr(out), a.size), "sdm_test_scan")
+    _call("sdm_test_scan", _ptr(a), _ptr(out), a.size)
     return out
 
 
 def test_sort_pairs(keys, vals, nbits):
-    L = load_library()
     keys = np.ascontiguousarray(keys, dtype=np.uint32)
     vals = np.ascontiguousarray(vals, dtype=np.uint32)
     ko, vo = np.empty_like(keys), np.empty_like(vals)
-    _check(L, L.sdm_test_sort_pairs(_ptr(keys), _ptr(vals), _ptr(ko), _ptr(vo), keys.size, nbits), "sdm_test_sort_pairs")
+    _call("sdm_test_sort_pairs", _ptr(keys), _ptr(vals), _ptr(ko), _ptr(vo), keys.size, nbits)
     return ko, vo
 
 
@@ -2022,9 +1868,8 @@ TEST_IN_PLACE, TEST_COUNT_ON_DEVICE, TEST_GUARD_WORDS = 1, 2, 64  # sdm.h, SDM_T
 
 def test_scratch_elems(sort, n):
     """words of scratch the scan (sort = False) or the sort (True) asks for at n elements (sdm_test_scratch_elems)"""
-    L = load_library()
     v = C.c_int64(0)
-    _check(L, L.sdm_test_scratch_elems(int(bool(sort)), int(n), C.byref(v)), "sdm_test_scratch_elems")
+    _call("sdm_test_scratch_elems", int(bool(sort)), int(n), C.byref(v))
     return v.value
 
 
@@ -2043,14 +1888,12 @@ def test_scan_seq(capacity, a, out, count=None, in_place=False, count_on_device=
     """sdm_test_scan_seq: scans of the slices of `a` (capacity[i] words each) back to back on one scratch.  `out` is what the
     output buffer holds before the calls.  Returns (the output buffer after them, guard words intact, the scratch as the last
     call left it or None)."""
-    L = load_library()
     capacity, count, (a, out) = _seq_args(capacity, count, [a, out])
     out = out.copy()
     flags = (TEST_IN_PLACE if in_place else 0) | (TEST_COUNT_ON_DEVICE if count_on_device else 0)
     scratch = np.empty(test_scratch_elems(False, capacity.max()), np.uint32) if want_scratch else None
     ok = C.c_int32(0)
-    _check(L, L.sdm_test_scan_seq(capacity.size, _ptr(capacity), _ptr(count), flags, _ptr(a), _ptr(out), C.byref(ok), _ptr(scratch)),
-           "sdm_test_scan_seq")
+    _call("sdm_test_scan_seq", capacity.size, _ptr(capacity), _ptr(count), flags, _ptr(a), _ptr(out), C.byref(ok), _ptr(scratch))
     return out, bool(ok.value), scratch
 
 
@@ -2058,14 +1901,12 @@ def test_sort_pairs_seq(capacity, nbits, keys, vals, keys_out, vals_out, count=N
     """sdm_test_sort_pairs_seq: sorts of the slices of (keys, vals) back to back on one scratch; keys_out / vals_out are what
     the second pair of buffers holds before the calls.  Returns (keys, vals of the pair each call named, the value each call
     returned, guard words intact, the scratch as the last call left it or None)."""
-    L = load_library()
     capacity, count, (keys, vals, keys_out, vals_out) = _seq_args(capacity, count, [keys, vals, keys_out, vals_out])
     nbits = np.ascontiguousarray(np.broadcast_to(np.asarray(nbits, np.int32), capacity.shape))
     keys_out, vals_out = keys_out.copy(), vals_out.copy()
     which = np.zeros(capacity.size, np.int32)
     scratch = np.empty(test_scratch_elems(True, capacity.max()), np.uint32) if want_scratch else None
     ok = C.c_int32(0)
-    _check(L, L.sdm_test_sort_pairs_seq(capacity.size, _ptr(capacity), _ptr(count), _ptr(nbits),
-                                        TEST_COUNT_ON_DEVICE if count_on_device else 0, _ptr(keys), _ptr(vals), _ptr(keys_out),
-                                        _ptr(vals_out), _ptr(which), C.byref(ok), _ptr(scratch)), "sdm_test_sort_pairs_seq")
+    _call("sdm_test_sort_pairs_seq", capacity.size, _ptr(capacity), _ptr(count), _ptr(nbits), TEST_COUNT_ON_DEVICE if count_on_device else 0,
+          _ptr(keys), _ptr(vals), _ptr(keys_out), _ptr(vals_out), _ptr(which), C.byref(ok), _ptr(scratch))
     return keys_out, vals_out, which, bool(ok.value), scratch

@@ -5,18 +5,13 @@ import subprocess
 
 import pytest
 
-from semantic_dsp_map_amd import binding
+from tests.adapter_build import ROOT, build_adapter
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "tests", "cpp", "adapter_smoke")
 
 
 def build_exe():
-    csrc = os.path.dirname(binding.LIB_PATH)
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "tests", "mock_includes"), "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "adapter_smoke.cpp"), "-o", EXE, "-L", csrc, "-lsdm_hip",
-           "-Wl,-rpath," + csrc, "-Wl,-rpath,/opt/rocm/lib"]
-    subprocess.check_call(cmd)
+    build_adapter("adapter_smoke", EXE)
 
 
 def test_adapter_header_compiles_and_links():
@@ -32,23 +27,10 @@ def test_adapter_header_compiles_and_links():
 ])
 def test_adapter_honours_the_setting_macros(defs, setting, boost, tmp_path):
     """`#define SETTING n` / BOOST_MODE select the adapter's preset like they select the reference's constants."""
-    csrc = os.path.dirname(binding.LIB_PATH)
-    exe = str(tmp_path / "adapter_setting")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall"] + defs +
-                          ["-I", os.path.join(ROOT, "tests", "mock_includes"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "adapter_setting.cpp"), "-o", exe, "-L", csrc, "-lsdm_hip",
-                           "-Wl,-rpath," + csrc, "-Wl,-rpath,/opt/rocm/lib"])
+    exe = build_adapter("adapter_setting", tmp_path / "adapter_setting", defs)
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "preset ok" in out.stdout, out.stdout + out.stderr
     assert "setting %d boost %d:" % (setting, boost) in out.stdout, out.stdout
-
-
-def build_setting_exe(defs, exe):
-    csrc = os.path.dirname(binding.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall"] + defs +
-                          ["-I", os.path.join(ROOT, "tests", "mock_includes"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "adapter_setting.cpp"), "-o", exe, "-L", csrc, "-lsdm_hip",
-                           "-Wl,-rpath," + csrc, "-Wl,-rpath,/opt/rocm/lib"])
 
 
 @pytest.mark.gpu
@@ -56,8 +38,7 @@ def build_setting_exe(defs, exe):
 def test_adapter_runs_the_shipped_grids(defs, tmp_path):
     """The default-constructed class at every grid the reference ships (nothing defined = SETTING 3 + BOOST_MODE, its ZED2
     configuration with 1280 x 720 inputs reduced on the device) takes a wall scene through update()."""
-    exe = str(tmp_path / "adapter_setting")
-    build_setting_exe(defs, exe)
+    exe = build_adapter("adapter_setting", tmp_path / "adapter_setting", defs)
     out = subprocess.run([exe, "run"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "occupied voxels after 4 frames" in out.stdout, out.stdout + out.stderr
 

@@ -1,23 +1,15 @@
 """SemanticDSPMap::frontiers (include/semantic_dsp_map.h): tests/cpp/adapter_frontiers.cpp compiled against the stand-in
 Eigen/OpenCV/PCL headers and linked with libsdm_hip.so; constructed here, driven through a wall scene with one movable
 object on the GPU and compared there with the C ABI called directly."""
-import os
 import subprocess
 
 import pytest
 
-from semantic_dsp_map_amd import binding
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.adapter_build import build_adapter
 
 
 def build_exe(tmp_path):
-    csrc = os.path.dirname(binding.LIB_PATH)
-    exe = str(tmp_path / "adapter_frontiers")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "tests", "mock_includes"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "adapter_frontiers.cpp"), "-o", exe, "-L", csrc, "-lsdm_hip",
-                           "-Wl,-rpath," + csrc, "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
+    return build_adapter("adapter_frontiers", tmp_path / "adapter_frontiers")
 
 
 def test_adapter_frontiers_compiles_and_links(tmp_path):

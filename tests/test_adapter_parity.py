@@ -15,6 +15,7 @@ import pytest
 
 from semantic_dsp_map_amd import binding
 from tests import adapter_clip, adapter_model
+from tests.adapter_build import build_adapter
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "adapter_clips.npz")
@@ -48,10 +49,7 @@ def test_fixture_is_what_the_oracle_model_emits(name):
 
 
 def build_exe(exe):
-    csrc = os.path.dirname(binding.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "tests", "mock_includes"), "-I",
-                           os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "adapter_parity.cpp"), "-o", exe, "-L", csrc,
-                           "-lsdm_hip", "-Wl,-rpath," + csrc, "-Wl,-rpath,/opt/rocm/lib"])
+    build_adapter("adapter_parity", exe)
 
 
 def test_parity_driver_builds(tmp_path):

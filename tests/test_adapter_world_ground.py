@@ -3,23 +3,15 @@ tests/cpp/adapter_world_ground.cpp compiled against the stand-in Eigen/OpenCV/PC
 constructed here, and on the GPU the ground layer of the archive of a wall scene, the wall taken as the ground - the answers
 against the C ABI called directly, one cell of height per cell walked away from the wall, a footprint of nine columns, the
 snapshot under a worldRetain."""
-import os
 import subprocess
 
 import pytest
 
-from semantic_dsp_map_amd import binding
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.adapter_build import build_adapter
 
 
 def build_exe(tmp_path):
-    csrc = os.path.dirname(binding.LIB_PATH)
-    exe = str(tmp_path / "adapter_world_ground")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "tests", "mock_includes"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "adapter_world_ground.cpp"), "-o", exe, "-L", csrc, "-lsdm_hip",
-                           "-Wl,-rpath," + csrc, "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
+    return build_adapter("adapter_world_ground", tmp_path / "adapter_world_ground")
 
 
 def test_adapter_world_ground_compiles_and_links(tmp_path):

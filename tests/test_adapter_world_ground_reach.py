@@ -3,23 +3,15 @@ tests/cpp/adapter_world_ground_reach.cpp compiled against the stand-in Eigen/Ope
 libsdm_hip.so; constructed here, and on the GPU the field over the ground layer of a wall scene's archive, the wall taken as
 the ground - the answers against the C ABI called directly, the cost's closed form on the flat wall and paths as long as it
 says, every path cell on ground, the snapshot under a worldRetain that empties the archive."""
-import os
 import subprocess
 
 import pytest
 
-from semantic_dsp_map_amd import binding
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.adapter_build import build_adapter
 
 
 def build_exe(tmp_path):
-    csrc = os.path.dirname(binding.LIB_PATH)
-    exe = str(tmp_path / "adapter_world_ground_reach")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "tests", "mock_includes"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "adapter_world_ground_reach.cpp"), "-o", exe, "-L", csrc, "-lsdm_hip",
-                           "-Wl,-rpath," + csrc, "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
+    return build_adapter("adapter_world_ground_reach", tmp_path / "adapter_world_ground_reach")
 
 
 def test_adapter_world_ground_reach_compiles_and_links(tmp_path):

@@ -2,23 +2,15 @@
 compiled against the stand-in Eigen/OpenCV/PCL headers and linked with libsdm_hip.so; constructed here, and on the GPU one
 map's archive of a wall scene is handed to a second map - at offset 0, with FILL, moved by an offset - and trimmed, the
 trim compared with the C ABI called directly."""
-import os
 import subprocess
 
 import pytest
 
-from semantic_dsp_map_amd import binding
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.adapter_build import build_adapter
 
 
 def build_exe(tmp_path):
-    csrc = os.path.dirname(binding.LIB_PATH)
-    exe = str(tmp_path / "adapter_world_io")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "tests", "mock_includes"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "adapter_world_io.cpp"), "-o", exe, "-L", csrc, "-lsdm_hip",
-                           "-Wl,-rpath," + csrc, "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
+    return build_adapter("adapter_world_io", tmp_path / "adapter_world_io")
 
 
 def test_adapter_world_io_compiles_and_links(tmp_path):

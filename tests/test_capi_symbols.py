@@ -7,14 +7,7 @@ import re
 import pytest
 
 from semantic_dsp_map_amd import binding
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared_functions(header="sdm.h"):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(sdm_[a-z0-9_]+)\s*\(", text)))
+from tests.abi_checks import ROOT, declared_functions
 
 
 def test_library_loads_and_exports_every_declared_symbol():

@@ -3,15 +3,13 @@ sdm_get_forecast_cells / sdm_query_forecast / sdm_query_forecast_segments): the 
 the layouts and constants agree with the header, the calls that need a map are refused without one, and the stamp routine
 - host code that needs no device - gives the stamps of tests/forecast_ref.py and refuses what the header says it refuses."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 from semantic_dsp_map_amd import binding
 from tests import forecast_ref as fc
-from tests.test_capi_symbols import ROOT, declared_functions
+from tests.abi_checks import assert_bound, assert_layout, define
 
 NAMES = ("sdm_forecast_stamps", "sdm_forecast_update", "sdm_get_forecast", "sdm_get_forecast_cells", "sdm_query_forecast",
          "sdm_query_forecast_segments")
@@ -20,29 +18,22 @@ SIZE = 0.1
 
 
 def test_symbols_are_declared_exported_and_bound():
-    names = declared_functions()
-    lib = C.CDLL(binding.LIB_PATH)
-    L = binding.load_library()
-    for n in NAMES:
-        assert n in names and hasattr(lib, n) and getattr(L, n).argtypes is not None, n
-    assert [len(getattr(L, n).argtypes) for n in NAMES] == [9, 6, 5, 6, 5, 5]
+    assert_bound(dict(zip(NAMES, [9, 6, 5, 6, 5, 5])))
     for f in ("forecast_update", "forecast", "forecast_cells", "query_forecast", "query_forecast_segments"):
         assert callable(getattr(binding.SdmMap, f)), f
     assert callable(binding.forecast_stamps)
 
 
 def test_layouts_and_constants_agree_with_the_header():
-    text = open(os.path.join(ROOT, "include", "sdm.h")).read()
-    value = lambda name: int(re.search(r"#define\s+%s\s+(\w+)" % name, text).group(1).rstrip("u"), 0)  # noqa: E731
-    assert value("SDM_FORECAST_SWEPT") == binding.FORECAST_SWEPT == fc.SWEPT == 1
-    assert value("SDM_FORECAST_VACATED_BLOCKS") == binding.FORECAST_VACATED_BLOCKS == 4
+    assert define("SDM_FORECAST_SWEPT") == binding.FORECAST_SWEPT == fc.SWEPT == 1
+    assert define("SDM_FORECAST_VACATED_BLOCKS") == binding.FORECAST_VACATED_BLOCKS == 4
     assert binding.FORECAST_VACATED_BLOCKS & (binding.QUERY_ON_DEVICE | binding.QUERY_UNKNOWN_BLOCKS) == 0
-    assert value("SDM_FORECAST_MAX_HORIZONS") == binding.FORECAST_MAX_HORIZONS == fc.MAX_HORIZONS == 16
-    assert value("SDM_FORECAST_MAX_STAMPS") == binding.FORECAST_MAX_STAMPS == fc.MAX_STAMPS == 65536
-    sizes = [d.itemsize for d in (binding.MOTION, binding.FORECAST_STAMP, binding.FORECAST_INFO, binding.FORECAST_RESULT, binding.FORECAST_HIT)]
-    assert sizes == [16, 12, 40, 8, 16]
-    for name, size in zip(("sdm_motion", "sdm_forecast_stamp", "sdm_forecast_info", "sdm_forecast_result", "sdm_forecast_hit"), sizes):
-        assert re.search(r"typedef struct \{\s*/\* %d bytes \*/[^}]*\} %s;" % (size, name), text), name
+    assert define("SDM_FORECAST_MAX_HORIZONS") == binding.FORECAST_MAX_HORIZONS == fc.MAX_HORIZONS == 16
+    assert define("SDM_FORECAST_MAX_STAMPS") == binding.FORECAST_MAX_STAMPS == fc.MAX_STAMPS == 65536
+    dtypes = dict(sdm_motion=(binding.MOTION, 16), sdm_forecast_stamp=(binding.FORECAST_STAMP, 12), sdm_forecast_info=(binding.FORECAST_INFO, 40),
+                  sdm_forecast_result=(binding.FORECAST_RESULT, 8), sdm_forecast_hit=(binding.FORECAST_HIT, 16))
+    for name, (dt, size) in dtypes.items():
+        assert_layout(dt, name, size)
     assert binding.MOTION == fc.MOTION and binding.FORECAST_STAMP == fc.STAMP
     assert binding.FORECAST_INFO.names == ("n_motions", "n_horizons", "n_stamps", "flags", "n_sources", "n_marked", "n_marks_in", "n_marks_out")
     assert binding.FORECAST_INFO.fields["n_marks_in"][1] == 24

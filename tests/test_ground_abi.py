@@ -2,39 +2,18 @@
 sdm_query_footprints): the symbols are declared, exported and bound, the structs have the sizes and fields the header
 gives them, the constants agree with the header, and the calls that need no device are refused as the header says."""
 import ctypes as C
-import os
-import re
 
 from semantic_dsp_map_amd import binding
-from tests.test_capi_symbols import ROOT, declared_functions
+from tests.abi_checks import HEADER, assert_bound, assert_layout, define
 
 NAMES = ("sdm_ground_update", "sdm_get_ground", "sdm_query_ground", "sdm_query_footprints")
-HEADER = open(os.path.join(ROOT, "include", "sdm.h")).read()
 
 
 def test_symbols_are_declared_exported_and_bound():
-    names = declared_functions()
-    lib = C.CDLL(binding.LIB_PATH)
-    L = binding.load_library()
-    for n in NAMES:
-        assert n in names and hasattr(lib, n) and getattr(L, n).argtypes is not None, n
-    assert [len(getattr(L, n).argtypes) for n in NAMES] == [2, 5, 5, 5]
+    assert_bound(dict(zip(NAMES, [2, 5, 5, 5])))
     for f in ("ground_update", "ground", "query_ground", "query_footprints"):
         assert callable(getattr(binding.SdmMap, f)), f
     assert callable(binding.ground_band) and callable(binding.label_mask)
-
-
-def _struct_fields(name):
-    """the field names of `typedef struct { ... } name;` in declaration order"""
-    body = re.search(r"typedef struct \{([^}]*)\}\s*%s;" % name, HEADER).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            first, *rest = decl.split(",")
-            fields += [re.sub(r"\[\d+\]", "", first.split()[-1])] + [re.sub(r"\[\d+\]", "", r.strip()) for r in rest]
-    return tuple(fields)
 
 
 def test_struct_sizes_and_fields():
@@ -42,24 +21,14 @@ def test_struct_sizes_and_fields():
     dtypes = dict(sdm_ground_options=binding.GROUND_OPTIONS, sdm_ground_cell=binding.GROUND_CELL, sdm_ground_info=binding.GROUND_INFO,
                   sdm_ground_result=binding.GROUND_RESULT, sdm_footprint=binding.FOOTPRINT, sdm_footprint_result=binding.FOOTPRINT_RESULT)
     for name, size in sizes.items():
-        assert dtypes[name].itemsize == size, name
-        assert dtypes[name].names == _struct_fields(name), name
-        assert re.search(r"typedef struct \{\s*/\* %d bytes" % size, HEADER[:HEADER.index("} %s;" % name)][-1500:]), name
-    # every field naturally aligned, no hidden padding: the offsets are the running sum of the sizes
-    for dt in dtypes.values():
-        at = 0
-        for f in dt.names:
-            assert dt.fields[f][1] == at, (dt, f)
-            at += dt.fields[f][0].itemsize
-        assert at == dt.itemsize
+        assert_layout(dtypes[name], name, size)
     assert binding.GROUND_RESULT.fields["cell"][0] == binding.GROUND_CELL and binding.GROUND_INFO.fields["options"][0] == binding.GROUND_OPTIONS
 
 
 def test_constants_agree_with_the_header():
-    value = lambda name: int(re.search(r"#define\s+%s\s+(\w+)" % name, HEADER).group(1).rstrip("u"), 0)  # noqa: E731
-    assert value("SDM_GROUND_UNKNOWN_PASSABLE") == binding.GROUND_UNKNOWN_PASSABLE == 1
-    assert value("SDM_GROUND_IGNORE_MOVABLE") == binding.GROUND_IGNORE_MOVABLE == 2
-    assert value("SDM_GROUND_NONE_IS_LETHAL") == binding.GROUND_NONE_IS_LETHAL == 4
+    assert define("SDM_GROUND_UNKNOWN_PASSABLE") == binding.GROUND_UNKNOWN_PASSABLE == 1
+    assert define("SDM_GROUND_IGNORE_MOVABLE") == binding.GROUND_IGNORE_MOVABLE == 2
+    assert define("SDM_GROUND_NONE_IS_LETHAL") == binding.GROUND_NONE_IS_LETHAL == 4
     assert binding.GROUND_NO_LEVEL == 0xFFFF and binding.GROUND_MAX_FOOTPRINT_CELLS == 64
     assert "half_len + half_wid > 64 * voxel_size" in HEADER
 

@@ -2,26 +2,17 @@
 sdm_get_mesh_vertices / sdm_mesh_device): the symbols are declared, exported and bound, the structs have the sizes and
 fields the header gives them, the constants agree with the header, and every call is refused without a map."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 
 from semantic_dsp_map_amd import binding
-from tests.test_capi_symbols import ROOT, declared_functions
-from tests.test_ground_abi import _struct_fields
+from tests.abi_checks import assert_bound, assert_layout, define
 
 NAMES = ("sdm_mesh_update", "sdm_get_mesh_info", "sdm_get_mesh_faces", "sdm_get_mesh_vertices", "sdm_mesh_device")
-HEADER = open(os.path.join(ROOT, "include", "sdm.h")).read()
 
 
 def test_symbols_are_declared_exported_and_bound():
-    names = declared_functions()
-    lib = C.CDLL(binding.LIB_PATH)
-    L = binding.load_library()
-    for n in NAMES:
-        assert n in names and hasattr(lib, n) and getattr(L, n).argtypes is not None, n
-    assert [len(getattr(L, n).argtypes) for n in NAMES] == [2, 3, 5, 5, 4]
+    assert_bound(dict(zip(NAMES, [2, 3, 5, 5, 4])))
     for f in ("mesh_update", "mesh", "mesh_info", "mesh_device"):
         assert callable(getattr(binding.SdmMap, f)), f
     assert callable(binding.mesh_triangles) and callable(binding.write_ply)
@@ -32,31 +23,20 @@ def test_struct_sizes_and_fields():
     dtypes = dict(sdm_mesh_options=binding.MESH_OPTIONS, sdm_mesh_face=binding.MESH_FACE, sdm_mesh_vertex=binding.MESH_VERTEX,
                   sdm_mesh_info=binding.MESH_INFO)
     for name, size in sizes.items():
-        assert dtypes[name].itemsize == size, name
-        assert dtypes[name].names == _struct_fields(name), name
-        assert re.search(r"typedef struct \{\s*/\* %d bytes" % size, HEADER[:HEADER.index("} %s;" % name)][-1500:]), name
-    # every field naturally aligned, no hidden padding: the offsets are the running sum of the sizes
-    for dt in dtypes.values():
-        at = 0
-        for f in dt.names:
-            assert dt.fields[f][1] == at, (dt, f)
-            assert at % dt.fields[f][0].base.alignment == 0 or dt.fields[f][0].names, (dt, f)
-            at += dt.fields[f][0].itemsize
-        assert at == dt.itemsize
+        assert_layout(dtypes[name], name, size)
     assert binding.MESH_INFO.fields["options"][0] == binding.MESH_OPTIONS and binding.MESH_INFO.fields["options"][1] % 8 == 0
     assert binding.MESH_OPTIONS.fields["max_faces"][1] % 8 == 0
 
 
 def test_constants_agree_with_the_header():
-    value = lambda name: int(re.search(r"#define\s+%s\s+(\w+)" % name, HEADER).group(1).rstrip("u"), 0)  # noqa: E731
-    assert value("SDM_MESH_STATIC_ONLY") == binding.MESH_STATIC_ONLY == 0x01
-    assert value("SDM_MESH_MOVABLE_ONLY") == binding.MESH_MOVABLE_ONLY == 0x02
-    assert value("SDM_MESH_OBSERVED_ONLY") == binding.MESH_OBSERVED_ONLY == 0x04
-    assert value("SDM_MESH_SKIP_UNKNOWN_FACES") == binding.MESH_SKIP_UNKNOWN_FACES == 0x08
-    assert value("SDM_MESH_SKIP_BORDER_FACES") == binding.MESH_SKIP_BORDER_FACES == 0x10
-    assert value("SDM_MESH_BYTES_PER_FACE") == binding.MESH_FACE.itemsize + 16 == 28
-    assert value("SDM_MESH_BYTES_PER_VERTEX") == binding.MESH_VERTEX.itemsize == 8
-    assert value("SDM_MESH_BYTES_PER_WORD") == 3 * 8 + 4 and value("SDM_MESH_BYTES_PER_CORNER_WORD") == 8 + 4
+    assert define("SDM_MESH_STATIC_ONLY") == binding.MESH_STATIC_ONLY == 0x01
+    assert define("SDM_MESH_MOVABLE_ONLY") == binding.MESH_MOVABLE_ONLY == 0x02
+    assert define("SDM_MESH_OBSERVED_ONLY") == binding.MESH_OBSERVED_ONLY == 0x04
+    assert define("SDM_MESH_SKIP_UNKNOWN_FACES") == binding.MESH_SKIP_UNKNOWN_FACES == 0x08
+    assert define("SDM_MESH_SKIP_BORDER_FACES") == binding.MESH_SKIP_BORDER_FACES == 0x10
+    assert define("SDM_MESH_BYTES_PER_FACE") == binding.MESH_FACE.itemsize + 16 == 28
+    assert define("SDM_MESH_BYTES_PER_VERTEX") == binding.MESH_VERTEX.itemsize == 8
+    assert define("SDM_MESH_BYTES_PER_WORD") == 3 * 8 + 4 and define("SDM_MESH_BYTES_PER_CORNER_WORD") == 8 + 4
 
 
 def test_calls_without_a_map_are_refused():

@@ -2,32 +2,23 @@
 sdm_reach_paths): the symbols are declared, exported and bound, the constants agree with the header, and the calls
 that need no device are refused as the header says."""
 import ctypes as C
-import os
-import re
 
 from semantic_dsp_map_amd import binding
-from tests.test_capi_symbols import ROOT, declared_functions
+from tests.abi_checks import assert_bound, define
 
 NAMES = ("sdm_reach_update", "sdm_get_reach", "sdm_query_reach", "sdm_reach_paths", "sdm_debug_reach_tiles")
 
 
 def test_symbols_are_declared_exported_and_bound():
-    names = declared_functions()
-    lib = C.CDLL(binding.LIB_PATH)
-    L = binding.load_library()
-    for n in NAMES:
-        assert n in names and hasattr(lib, n) and getattr(L, n).argtypes is not None, n
-    assert [len(getattr(L, n).argtypes) for n in NAMES] == [7, 4, 6, 8, 2]
+    assert_bound(dict(zip(NAMES, [7, 4, 6, 8, 2])))
     for f in ("reach_update", "reach", "query_reach", "reach_paths"):
         assert callable(getattr(binding.SdmMap, f)), f
 
 
 def test_constants_agree_with_the_header():
-    text = open(os.path.join(ROOT, "include", "sdm.h")).read()
-    value = lambda name: int(re.search(r"#define\s+%s\s+(\w+)" % name, text).group(1).rstrip("u"), 0)  # noqa: E731
-    assert value("SDM_REACH_FACE_CONNECTED") == binding.REACH_FACE_CONNECTED == 1
-    assert value("SDM_REACH_THROUGH_UNKNOWN") == binding.REACH_THROUGH_UNKNOWN == 2
-    assert value("SDM_REACH_COST_PER_CELL") == binding.REACH_COST_PER_CELL == 10
+    assert define("SDM_REACH_FACE_CONNECTED") == binding.REACH_FACE_CONNECTED == 1
+    assert define("SDM_REACH_THROUGH_UNKNOWN") == binding.REACH_THROUGH_UNKNOWN == 2
+    assert define("SDM_REACH_COST_PER_CELL") == binding.REACH_COST_PER_CELL == 10
     assert binding.REACH_INFO.names == ("n_starts_used", "n_traversable", "n_reached", "max_cost_reached", "rounds", "flags", "min_d2", "max_cost")
 
 

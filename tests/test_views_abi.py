@@ -1,15 +1,15 @@
 """CPU-side checks of the view-scoring boundary (include/sdm.h: sdm_query_views): the record layouts ctypes and numpy
 see, the exported and bound symbols, and the ray table of a pinhole camera."""
-import ctypes as C
 
 import numpy as np
 
 from semantic_dsp_map_amd import binding, synth
-from tests.test_capi_symbols import declared_functions
+from tests.abi_checks import assert_bound, assert_layout
 
 
 def test_layouts():
-    assert binding.VIEW.itemsize == 32 and binding.VIEW_GAIN.itemsize == 40
+    assert_layout(binding.VIEW, "sdm_view", 32)
+    assert_layout(binding.VIEW_GAIN, "sdm_view_gain", 40)
     assert [binding.VIEW.fields[k][1] for k in ("pos", "q", "range")] == [0, 12, 28]
     off = {k: binding.VIEW_GAIN.fields[k][1] for k in binding.VIEW_GAIN.names}
     assert off == dict(n_unknown=0, n_free=4, n_occupied=8, rays_hit=12, rays_in_map=16, pad=20, ray_cells=24, ray_unknown=32)
@@ -17,13 +17,7 @@ def test_layouts():
 
 
 def test_symbols_are_declared_exported_and_bound():
-    names = declared_functions()
-    assert "sdm_query_views" in names and "sdm_debug_view_batch" in names
-    lib = C.CDLL(binding.LIB_PATH)
-    L = binding.load_library()
-    for n in ("sdm_query_views", "sdm_debug_view_batch"):
-        assert hasattr(lib, n) and getattr(L, n).argtypes is not None
-    assert len(L.sdm_query_views.argtypes) == 9 and len(L.sdm_debug_view_batch.argtypes) == 2
+    assert_bound(dict(sdm_query_views=9, sdm_debug_view_batch=2))
     assert callable(binding.SdmMap.query_views) and callable(binding.SdmMap.set_view_batch)
 
 

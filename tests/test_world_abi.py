@@ -3,27 +3,18 @@ sdm_get_world_bricks / sdm_get_world_occupied / sdm_query_world_points / sdm_get
 exported and bound, the structs have the sizes and fields the header gives them, the constants agree with the header, and
 every call is refused without a map."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 
 from semantic_dsp_map_amd import binding
-from tests.test_capi_symbols import ROOT, declared_functions
-from tests.test_ground_abi import _struct_fields
+from tests.abi_checks import assert_bound, assert_layout, define
 
 NAMES = ("sdm_world_update", "sdm_world_clear", "sdm_get_world_info", "sdm_get_world_bricks", "sdm_get_world_occupied",
          "sdm_query_world_points", "sdm_get_world_region")
-HEADER = open(os.path.join(ROOT, "include", "sdm.h")).read()
 
 
 def test_symbols_are_declared_exported_and_bound():
-    names = declared_functions()
-    lib = C.CDLL(binding.LIB_PATH)
-    L = binding.load_library()
-    for n in NAMES:
-        assert n in names and hasattr(lib, n) and getattr(L, n).argtypes is not None, n
-    assert [len(getattr(L, n).argtypes) for n in NAMES] == [2, 1, 2, 6, 5, 5, 5]
+    assert_bound(dict(zip(NAMES, [2, 1, 2, 6, 5, 5, 5])))
     for f in ("world_update", "world_info", "world_bricks", "world_occupied", "query_world", "world_region", "world_clear"):
         assert callable(getattr(binding.SdmMap, f)), f
 
@@ -33,26 +24,15 @@ def test_struct_sizes_and_fields():
     dtypes = dict(sdm_world_options=binding.WORLD_OPTIONS, sdm_world_brick=binding.WORLD_BRICK, sdm_world_cell=binding.WORLD_CELL,
                   sdm_world_info=binding.WORLD_INFO)
     for name, size in sizes.items():
-        assert dtypes[name].itemsize == size, name
-        assert dtypes[name].names == _struct_fields(name), name
-        assert re.search(r"typedef struct \{\s*/\* %d bytes" % size, HEADER[:HEADER.index("} %s;" % name)][-1500:]), name
-    # every field naturally aligned, no hidden padding: the offsets are the running sum of the sizes
-    for dt in dtypes.values():
-        at = 0
-        for f in dt.names:
-            assert dt.fields[f][1] == at, (dt, f)
-            assert at % dt.fields[f][0].base.alignment == 0, (dt, f)
-            at += dt.fields[f][0].itemsize
-        assert at == dt.itemsize
+        assert_layout(dtypes[name], name, size)
     assert binding.WORLD_OPTIONS.fields["max_bricks"][1] == 8 and binding.WORLD_INFO.fields["dropped_total"][1] == 24
 
 
 def test_constants_agree_with_the_header():
-    value = lambda name: int(re.search(r"#define\s+%s\s+(\w+)" % name, HEADER).group(1).rstrip("u"), 0)  # noqa: E731
-    assert value("SDM_WORLD_STATIC_ONLY") == binding.WORLD_STATIC_ONLY == 0x01
-    assert value("SDM_WORLD_OBSERVED_ONLY") == binding.WORLD_OBSERVED_ONLY == 0x02
+    assert define("SDM_WORLD_STATIC_ONLY") == binding.WORLD_STATIC_ONLY == 0x01
+    assert define("SDM_WORLD_OBSERVED_ONLY") == binding.WORLD_OBSERVED_ONLY == 0x02
     # per brick of capacity: the words, the header, two hash slots (key and pool slot), four sort words and a count
-    assert value("SDM_WORLD_BYTES_PER_BRICK") == 512 * 4 + binding.WORLD_BRICK.itemsize + 2 * (8 + 4) + 4 * 4 + 4
+    assert define("SDM_WORLD_BYTES_PER_BRICK") == 512 * 4 + binding.WORLD_BRICK.itemsize + 2 * (8 + 4) + 4 * 4 + 4
     assert binding.WORLD_UNKNOWN_WORD == 0xFF000000
 
 

@@ -4,26 +4,17 @@ sizes, fields and offsets the header gives them, the flag bits are distinct and 
 per archived brick and per field brick are the stated sums, and every call is refused without a map."""
 import ctypes as C
 import inspect
-import os
-import re
 
 import numpy as np
 
 from semantic_dsp_map_amd import binding
-from tests.test_capi_symbols import ROOT, declared_functions
-from tests.test_ground_abi import _struct_fields
+from tests.abi_checks import assert_bound, assert_layout, define
 
 NAMES = ("sdm_world_esdf_update", "sdm_get_world_esdf", "sdm_query_world_distance")
-HEADER = open(os.path.join(ROOT, "include", "sdm.h")).read()
 
 
 def test_symbols_are_declared_exported_and_bound():
-    names = declared_functions()
-    lib = C.CDLL(binding.LIB_PATH)
-    L = binding.load_library()
-    for n in NAMES:
-        assert n in names and hasattr(lib, n) and getattr(L, n).argtypes is not None, n
-    assert [len(getattr(L, n).argtypes) for n in NAMES] == [2, 8, 6]
+    L = assert_bound(dict(zip(NAMES, [2, 8, 6])))
     assert L.sdm_get_world_esdf.argtypes[4:7] == [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
     assert L.sdm_query_world_distance.argtypes[3] == C.c_int64 and L.sdm_query_world_distance.argtypes[5] == C.c_uint32
     want = dict(world_esdf_update=["radius", "unknown_is_obstacle", "static_only", "box"], world_esdf=["first", "cap"],
@@ -40,16 +31,7 @@ def test_struct_sizes_fields_and_offsets():
     dtypes = dict(sdm_world_esdf_options=binding.WORLD_ESDF_OPTIONS, sdm_world_esdf_info=binding.WORLD_ESDF_INFO,
                   sdm_world_distance_result=binding.WORLD_DISTANCE_RESULT)
     for name, dt in dtypes.items():
-        assert dt.itemsize == 32, name
-        assert dt.names == _struct_fields(name), name
-        assert re.search(r"typedef struct \{\s*/\* 32 bytes", HEADER[:HEADER.index("} %s;" % name)][-1200:]), name
-    for dt in dtypes.values():   # every field naturally aligned, no hidden padding: the offsets are the running sum of the sizes
-        at = 0
-        for f in dt.names:
-            assert dt.fields[f][1] == at, (dt, f)
-            assert at % dt.fields[f][0].base.alignment == 0, (dt, f)
-            at += dt.fields[f][0].itemsize
-        assert at == dt.itemsize
+        assert_layout(dt, name, 32)
     offsets = lambda dt: {f: dt.fields[f][1] for f in dt.names}  # noqa: E731
     assert offsets(binding.WORLD_ESDF_OPTIONS) == dict(flags=0, radius=4, bmin=8, bmax=20)
     assert offsets(binding.WORLD_ESDF_INFO) == dict(n_bricks=0, flags=4, radius=8, stamp=12, n_obstacle_cells=16, n_near_cells=24)
@@ -60,16 +42,15 @@ def test_struct_sizes_fields_and_offsets():
 
 
 def test_flag_bits_constants_and_the_stated_bytes():
-    value = lambda name: int(re.search(r"#define\s+%s\s+(\w+)" % name, HEADER).group(1).rstrip("u"), 0)  # noqa: E731
-    bits = [value("SDM_WORLD_ESDF_UNKNOWN_IS_OBSTACLE"), value("SDM_WORLD_ESDF_STATIC_ONLY"), value("SDM_WORLD_ESDF_BOX")]
+    bits = [define("SDM_WORLD_ESDF_UNKNOWN_IS_OBSTACLE"), define("SDM_WORLD_ESDF_STATIC_ONLY"), define("SDM_WORLD_ESDF_BOX")]
     assert bits == [binding.WORLD_ESDF_UNKNOWN_IS_OBSTACLE, binding.WORLD_ESDF_STATIC_ONLY, binding.WORLD_ESDF_BOX] == [1, 2, 4]
-    assert value("SDM_WORLD_ESDF_MAX_RADIUS") == binding.WORLD_ESDF_MAX_RADIUS == 16
-    assert value("SDM_WORLD_ESDF_NONE") == binding.WORLD_ESDF_NONE == 0xFFFF and value("SDM_WORLD_ESDF_FAR") == binding.WORLD_ESDF_FAR == 0xFFFFFFFE
+    assert define("SDM_WORLD_ESDF_MAX_RADIUS") == binding.WORLD_ESDF_MAX_RADIUS == 16
+    assert define("SDM_WORLD_ESDF_NONE") == binding.WORLD_ESDF_NONE == 0xFFFF and define("SDM_WORLD_ESDF_FAR") == binding.WORLD_ESDF_FAR == 0xFFFFFFFE
     # per archived brick: the box flag, the rank, eight 64-bit obstacle words
-    assert value("SDM_WORLD_ESDF_BYTES_PER_ARCHIVED_BRICK") == 4 + 4 + 8 * 8
+    assert define("SDM_WORLD_ESDF_BYTES_PER_ARCHIVED_BRICK") == 4 + 4 + 8 * 8
     # per brick of the field: 512 packed words (10 bits of d2, 3 x 6 bits of offset), the coordinates (two words), two hash
     # slots of a 64-bit key and a 32-bit rank
-    assert value("SDM_WORLD_ESDF_BYTES_PER_BRICK") == 512 * 4 + 2 * 4 + 2 * (8 + 4)
+    assert define("SDM_WORLD_ESDF_BYTES_PER_BRICK") == 512 * 4 + 2 * 4 + 2 * (8 + 4)
     assert 16 * 16 < (1 << 10) - 1 and 2 * 16 + 1 <= 1 << 6     # what the packed word has to hold
 
 

@@ -5,26 +5,17 @@ agree with the header, the header's bytes per brick and per cell are the binding
 without a map."""
 import ctypes as C
 import inspect
-import os
-import re
 
 import numpy as np
 
 from semantic_dsp_map_amd import binding
-from tests.test_capi_symbols import ROOT, declared_functions
-from tests.test_ground_abi import _struct_fields
+from tests.abi_checks import assert_bound, assert_layout, define
 
 NAMES = ("sdm_world_frontiers_update", "sdm_get_world_frontier_clusters", "sdm_get_world_frontier_cells")
-HEADER = open(os.path.join(ROOT, "include", "sdm.h")).read()
 
 
 def test_symbols_are_declared_exported_and_bound():
-    names = declared_functions()
-    lib = C.CDLL(binding.LIB_PATH)
-    L = binding.load_library()
-    for n in NAMES:
-        assert n in names and hasattr(lib, n) and getattr(L, n).argtypes is not None, n
-    assert [len(getattr(L, n).argtypes) for n in NAMES] == [2, 5, 7]
+    L = assert_bound(dict(zip(NAMES, [2, 5, 7])))
     assert L.sdm_get_world_frontier_clusters.argtypes[2:4] == [C.c_int32, C.POINTER(C.c_int32)]
     assert L.sdm_get_world_frontier_cells.argtypes[4:7] == [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
     want = dict(world_frontiers_update=["face_connected", "box", "inside_bricks", "min_cells", "max_cells"], world_frontiers=[],
@@ -40,16 +31,7 @@ def test_struct_sizes_fields_and_offsets():
                   sdm_world_frontiers_info=binding.WORLD_FRONTIERS_INFO)
     sizes = dict(sdm_world_frontiers_options=40, sdm_world_frontier_cluster=120, sdm_world_frontiers_info=48)
     for name, size in sizes.items():
-        assert dtypes[name].itemsize == size, name
-        assert dtypes[name].names == _struct_fields(name), name
-        assert re.search(r"typedef struct \{\s*/\* %d bytes" % size, HEADER[:HEADER.index("} %s;" % name)][-1500:]), name
-    for dt in dtypes.values():   # every field naturally aligned, no hidden padding: the offsets are the running sum of the sizes
-        at = 0
-        for f in dt.names:
-            assert dt.fields[f][1] == at, (dt, f)
-            assert at % dt.fields[f][0].base.alignment == 0, (dt, f)
-            at += dt.fields[f][0].itemsize
-        assert at == dt.itemsize
+        assert_layout(dtypes[name], name, size)
     offsets = lambda dt: {f: dt.fields[f][1] for f in dt.names}  # noqa: E731
     assert offsets(binding.WORLD_FRONTIERS_OPTIONS) == dict(flags=0, min_cells=4, max_cells=8, bmin=16, bmax=28)
     assert offsets(binding.WORLD_FRONTIER_CLUSTER) == dict(first_index=0, n_cells=4, n_unknown_faces=8, pad0=12, first_cell=16, cell_min=28,
@@ -63,14 +45,13 @@ def test_struct_sizes_fields_and_offsets():
 
 
 def test_flag_bits_and_the_stated_bytes():
-    value = lambda name: int(re.search(r"#define\s+%s\s+(\w+)" % name, HEADER).group(1).rstrip("u"), 0)  # noqa: E731
-    bits = [value("SDM_WORLD_FRONTIERS_FACE_CONNECTED"), value("SDM_WORLD_FRONTIERS_BOX"), value("SDM_WORLD_FRONTIERS_INSIDE_BRICKS")]
+    bits = [define("SDM_WORLD_FRONTIERS_FACE_CONNECTED"), define("SDM_WORLD_FRONTIERS_BOX"), define("SDM_WORLD_FRONTIERS_INSIDE_BRICKS")]
     assert bits == [binding.WORLD_FRONTIERS_FACE_CONNECTED, binding.WORLD_FRONTIERS_BOX, binding.WORLD_FRONTIERS_INSIDE_BRICKS] == [1, 2, 4]
     assert binding.WORLD_FRONTIER_NO_CLUSTER == 0xFFFFFFFF
     # per cell: accumulator (56), table entry, world cell, parent / root / scan words, unknown_faces
-    assert value("SDM_WORLD_FRONTIERS_BYTES_PER_CELL") == 56 + binding.WORLD_FRONTIER_CLUSTER.itemsize + 12 + 3 * 4 + 1
-    assert value("SDM_WORLD_FRONTIERS_BYTES_PER_BRICK") == 8 + 4 + 27 * 4 + 6 * 4 + 8 * 8 + 8 * 4
-    assert value("SDM_WORLD_FRONTIERS_BYTES_PER_ARCHIVED_BRICK") == 4 + 4 + 2 * 64
+    assert define("SDM_WORLD_FRONTIERS_BYTES_PER_CELL") == 56 + binding.WORLD_FRONTIER_CLUSTER.itemsize + 12 + 3 * 4 + 1
+    assert define("SDM_WORLD_FRONTIERS_BYTES_PER_BRICK") == 8 + 4 + 27 * 4 + 6 * 4 + 8 * 8 + 8 * 4
+    assert define("SDM_WORLD_FRONTIERS_BYTES_PER_ARCHIVED_BRICK") == 4 + 4 + 2 * 64
 
 
 def test_calls_without_a_map_are_refused():

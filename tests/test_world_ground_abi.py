@@ -5,28 +5,19 @@ header, the header's bytes per archived brick and per tile are the stated sums, 
 without a map."""
 import ctypes as C
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
 
 from semantic_dsp_map_amd import binding
-from tests.test_capi_symbols import ROOT, declared_functions
-from tests.test_ground_abi import _struct_fields
+from tests.abi_checks import assert_bound, assert_layout, define
 
 NAMES = ("sdm_world_ground_update", "sdm_get_world_ground", "sdm_query_world_ground", "sdm_query_world_footprints")
-HEADER = open(os.path.join(ROOT, "include", "sdm.h")).read()
 SIZES = dict(sdm_world_ground_options=80, sdm_world_ground_info=136, sdm_world_ground_result=40, sdm_world_footprint_result=40)
 
 
 def test_symbols_are_declared_exported_and_bound():
-    names = declared_functions()
-    lib = C.CDLL(binding.LIB_PATH)
-    L = binding.load_library()
-    for n in NAMES:
-        assert n in names and hasattr(lib, n) and getattr(L, n).argtypes is not None, n
-    assert [len(getattr(L, n).argtypes) for n in NAMES] == [2, 8, 6, 5]
+    L = assert_bound(dict(zip(NAMES, [2, 8, 6, 5])))
     assert L.sdm_get_world_ground.argtypes[4:7] == [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
     assert L.sdm_query_world_ground.argtypes[3] == C.c_int64 and L.sdm_query_world_ground.argtypes[5] == C.c_uint32
     assert L.sdm_query_world_footprints.argtypes[2] == C.c_int64 and L.sdm_query_world_footprints.argtypes[4] == C.c_uint32
@@ -44,17 +35,7 @@ def test_struct_sizes_fields_and_offsets():
     dtypes = dict(sdm_world_ground_options=binding.WORLD_GROUND_OPTIONS, sdm_world_ground_info=binding.WORLD_GROUND_INFO,
                   sdm_world_ground_result=binding.WORLD_GROUND_RESULT, sdm_world_footprint_result=binding.WORLD_FOOTPRINT_RESULT)
     for name, dt in dtypes.items():
-        assert dt.itemsize == SIZES[name], name
-        assert dt.names == _struct_fields(name), name
-        assert re.search(r"typedef struct \{\s*/\* %d bytes" % SIZES[name], HEADER[:HEADER.index("} %s;" % name)][-1500:]), name
-    for name, dt in dtypes.items():   # no hidden padding: the offsets are the running sum of the sizes; naturally aligned fields
-        at = 0
-        for f in dt.names:
-            assert dt.fields[f][1] == at, (name, f)
-            base = dt.fields[f][0].base
-            assert at % (2 if base == binding.GROUND_CELL else base.alignment if base.names is None else 4) == 0, (name, f)
-            at += dt.fields[f][0].itemsize
-        assert at == dt.itemsize
+        assert_layout(dt, name, SIZES[name])
     offsets = lambda dt: {f: dt.fields[f][1] for f in dt.names}  # noqa: E731
     assert offsets(binding.WORLD_GROUND_OPTIONS) == dict(flags=0, up_axis=4, up_sign=8, h_lo=12, h_hi=16, clearance=20, max_step=24, radius=28,
                                                         tmin=32, tmax=40, support_labels=48)
@@ -70,20 +51,19 @@ def test_struct_sizes_fields_and_offsets():
 
 
 def test_flag_bits_constants_and_the_stated_bytes():
-    value = lambda name: int(re.search(r"#define\s+%s\s+(\w+)" % name, HEADER).group(1).rstrip("u"), 0)  # noqa: E731
-    bits = [value("SDM_WORLD_GROUND_" + n) for n in ("UNKNOWN_PASSABLE", "IGNORE_MOVABLE", "NONE_IS_LETHAL", "ABSENT_IS_LETHAL", "BOX")]
+    bits = [define("SDM_WORLD_GROUND_" + n) for n in ("UNKNOWN_PASSABLE", "IGNORE_MOVABLE", "NONE_IS_LETHAL", "ABSENT_IS_LETHAL", "BOX")]
     assert bits == [binding.WORLD_GROUND_UNKNOWN_PASSABLE, binding.WORLD_GROUND_IGNORE_MOVABLE, binding.WORLD_GROUND_NONE_IS_LETHAL,
                     binding.WORLD_GROUND_ABSENT_IS_LETHAL, binding.WORLD_GROUND_BOX] == [1, 2, 4, 8, 16]
     # the three cell flags are the block's
     assert bits[:3] == [binding.GROUND_UNKNOWN_PASSABLE, binding.GROUND_IGNORE_MOVABLE, binding.GROUND_NONE_IS_LETHAL]
-    assert value("SDM_WORLD_GROUND_MAX_RADIUS") == binding.WORLD_GROUND_MAX_RADIUS == 16
-    assert value("SDM_WORLD_GROUND_MAX_SPAN") == binding.WORLD_GROUND_MAX_SPAN == 4096
-    assert value("SDM_WORLD_GROUND_NONE") == binding.WORLD_GROUND_NONE == 0xFFFF and value("SDM_WORLD_GROUND_FAR") == binding.WORLD_GROUND_FAR == 0xFFFFFFFE
+    assert define("SDM_WORLD_GROUND_MAX_RADIUS") == binding.WORLD_GROUND_MAX_RADIUS == 16
+    assert define("SDM_WORLD_GROUND_MAX_SPAN") == binding.WORLD_GROUND_MAX_SPAN == 4096
+    assert define("SDM_WORLD_GROUND_NONE") == binding.WORLD_GROUND_NONE == 0xFFFF and define("SDM_WORLD_GROUND_FAR") == binding.WORLD_GROUND_FAR == 0xFFFFFFFE
     assert 16 * 16 < binding.WORLD_GROUND_NONE and 4095 + 255 < 0xFFFF       # what d2 and a relative height have to hold
     # per archived brick: the claim flag, the rank, two slots of a 64-bit key and a 32-bit rank
-    assert value("SDM_WORLD_GROUND_BYTES_PER_ARCHIVED_BRICK") == 4 + 4 + 2 * (8 + 4)
+    assert define("SDM_WORLD_GROUND_BYTES_PER_ARCHIVED_BRICK") == 4 + 4 + 2 * (8 + 4)
     # per tile: 64 cells of 8 bytes, 64 distances of 2, the lethal word, the key, the sort's two keys and two values
-    assert value("SDM_WORLD_GROUND_BYTES_PER_TILE") == 64 * 8 + 64 * 2 + 8 + 4 + 4 * 4
+    assert define("SDM_WORLD_GROUND_BYTES_PER_TILE") == 64 * 8 + 64 * 2 + 8 + 4 + 4 * 4
 
 
 def test_the_band_helper():

@@ -5,28 +5,19 @@ flag bits are distinct and agree with the header, the header's bytes per tile ar
 refused without a map."""
 import ctypes as C
 import inspect
-import os
-import re
 
 import numpy as np
 
 from semantic_dsp_map_amd import binding
-from tests.test_capi_symbols import ROOT, declared_functions
-from tests.test_ground_abi import _struct_fields
+from tests.abi_checks import assert_bound, assert_layout, define
 
 NAMES = ("sdm_world_ground_reach_update", "sdm_get_world_ground_reach", "sdm_query_world_ground_reach", "sdm_world_ground_reach_paths",
          "sdm_debug_world_ground_reach_tiles")
-HEADER = open(os.path.join(ROOT, "include", "sdm.h")).read()
 SIZES = dict(sdm_world_ground_reach_options=48, sdm_world_ground_reach_info=80, sdm_world_ground_reach_result=24)
 
 
 def test_symbols_are_declared_exported_and_bound():
-    names = declared_functions()
-    lib = C.CDLL(binding.LIB_PATH)
-    L = binding.load_library()
-    for n in NAMES:
-        assert n in names and hasattr(lib, n) and getattr(L, n).argtypes is not None, n
-    assert [len(getattr(L, n).argtypes) for n in NAMES] == [5, 7, 6, 8, 2]
+    L = assert_bound(dict(zip(NAMES, [5, 7, 6, 8, 2])))
     assert L.sdm_world_ground_reach_update.argtypes[4] == C.c_int64
     assert L.sdm_get_world_ground_reach.argtypes[3:6] == [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
     assert L.sdm_query_world_ground_reach.argtypes[3] == C.c_int64 and L.sdm_query_world_ground_reach.argtypes[5] == C.c_uint32
@@ -48,17 +39,7 @@ def test_struct_sizes_fields_and_offsets():
     dtypes = dict(sdm_world_ground_reach_options=binding.WORLD_GROUND_REACH_OPTIONS, sdm_world_ground_reach_info=binding.WORLD_GROUND_REACH_INFO,
                   sdm_world_ground_reach_result=binding.WORLD_GROUND_REACH_RESULT)
     for name, dt in dtypes.items():
-        assert dt.itemsize == SIZES[name], name
-        assert dt.names == _struct_fields(name), name
-        assert re.search(r"typedef struct \{\s*/\* %d bytes" % SIZES[name], HEADER[:HEADER.index("} %s;" % name)][-1500:]), name
-    for name, dt in dtypes.items():   # no hidden padding: the offsets are the running sum of the sizes; naturally aligned fields
-        at = 0
-        for f in dt.names:
-            assert dt.fields[f][1] == at, (name, f)
-            base = dt.fields[f][0].base
-            assert at % (base.alignment if base.names is None else 4) == 0, (name, f)
-            at += dt.fields[f][0].itemsize
-        assert at == dt.itemsize
+        assert_layout(dt, name, SIZES[name])
     offsets = lambda dt: {f: dt.fields[f][1] for f in dt.names}  # noqa: E731
     assert offsets(binding.WORLD_GROUND_REACH_OPTIONS) == dict(flags=0, min_d2=4, soft_d2=8, penalty=12, max_climb=16, max_cost=20, tmin=24, tmax=32,
                                                               pad=40)
@@ -74,13 +55,12 @@ def test_struct_sizes_fields_and_offsets():
 
 
 def test_flag_bits_and_the_stated_bytes():
-    value = lambda name: int(re.search(r"#define\s+%s\s+(\w+)" % name, HEADER).group(1).rstrip("u"), 0)  # noqa: E731
-    bits = [value("SDM_WORLD_GROUND_REACH_" + n) for n in ("FACE_CONNECTED", "BOX")]
+    bits = [define("SDM_WORLD_GROUND_REACH_" + n) for n in ("FACE_CONNECTED", "BOX")]
     assert bits == [binding.WORLD_GROUND_REACH_FACE_CONNECTED, binding.WORLD_GROUND_REACH_BOX] == [1, 2]
     # per tile: 64 costs, the traversable and the penalty word, 64 levels, eight neighbour ranks, the key, two slots of a 64-bit
     # key and a 32-bit rank, the list word
     per_tile = 64 * 4 + 8 + 8 + 64 * 2 + 8 * 4 + 4 + 2 * (8 + 4) + 4
-    assert value("SDM_WORLD_GROUND_REACH_BYTES_PER_TILE") == binding.WORLD_GROUND_REACH_BYTES_PER_TILE == per_tile == 464
+    assert define("SDM_WORLD_GROUND_REACH_BYTES_PER_TILE") == binding.WORLD_GROUND_REACH_BYTES_PER_TILE == per_tile == 464
     # what a cost and a threshold have to hold: the largest penalised move below 2^17; R^2 + 1 of the largest radius
     assert 14 + 65535 < 1 << 17 and binding.WORLD_GROUND_MAX_RADIUS ** 2 + 1 < binding.WORLD_GROUND_NONE
 

@@ -2,26 +2,17 @@
 sdm_world_retain): the symbols are declared, exported and bound, the option structs have the sizes, fields and offsets the
 header gives them, the constants agree with the header and with each other, and both calls are refused without a map."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 
 from semantic_dsp_map_amd import binding
-from tests.test_capi_symbols import ROOT, declared_functions
-from tests.test_ground_abi import _struct_fields
+from tests.abi_checks import assert_bound, assert_layout, define
 
 NAMES = ("sdm_world_import", "sdm_world_retain")
-HEADER = open(os.path.join(ROOT, "include", "sdm.h")).read()
 
 
 def test_symbols_are_declared_exported_and_bound():
-    names = declared_functions()
-    lib = C.CDLL(binding.LIB_PATH)
-    L = binding.load_library()
-    for n in NAMES:
-        assert n in names and hasattr(lib, n) and getattr(L, n).argtypes is not None, n
-    assert [len(getattr(L, n).argtypes) for n in NAMES] == [5, 3]
+    L = assert_bound(dict(zip(NAMES, [5, 3])))
     assert L.sdm_world_import.argtypes[4] is C.c_int64 and L.sdm_world_retain.argtypes[2] is C.POINTER(C.c_int64)
     for f in ("world_import", "world_retain", "save_world", "load_world"):
         assert callable(getattr(binding.SdmMap, f)), f
@@ -31,17 +22,7 @@ def test_struct_sizes_fields_and_offsets():
     sizes = dict(sdm_world_import_options=24, sdm_world_retain_options=32)
     dtypes = dict(sdm_world_import_options=binding.WORLD_IMPORT_OPTIONS, sdm_world_retain_options=binding.WORLD_RETAIN_OPTIONS)
     for name, size in sizes.items():
-        assert dtypes[name].itemsize == size, name
-        assert dtypes[name].names == _struct_fields(name), name
-        assert re.search(r"typedef struct \{\s*/\* %d bytes" % size, HEADER[:HEADER.index("} %s;" % name)][-1500:]), name
-    # every field naturally aligned, no hidden padding: the offsets are the running sum of the sizes
-    for dt in dtypes.values():
-        at = 0
-        for f in dt.names:
-            assert dt.fields[f][1] == at, (dt, f)
-            assert at % dt.fields[f][0].base.alignment == 0, (dt, f)
-            at += dt.fields[f][0].itemsize
-        assert at == dt.itemsize
+        assert_layout(dtypes[name], name, size)
     offsets = lambda dt: {f: dt.fields[f][1] for f in dt.names}  # noqa: E731
     assert offsets(binding.WORLD_IMPORT_OPTIONS) == dict(flags=0, cell_offset=4, max_bricks=16)
     assert offsets(binding.WORLD_RETAIN_OPTIONS) == dict(bmin=0, bmax=12, min_last_stamp=24, flags=28)
@@ -51,10 +32,9 @@ def test_struct_sizes_fields_and_offsets():
 
 
 def test_constants_agree_with_the_header():
-    value = lambda name: int(re.search(r"#define\s+%s\s+(\w+)" % name, HEADER).group(1).rstrip("u"), 0)  # noqa: E731
-    assert value("SDM_WORLD_IMPORT_FILL") == binding.WORLD_IMPORT_FILL == 0x10
-    assert value("SDM_WORLD_IMPORT_ON_DEVICE") == binding.WORLD_IMPORT_ON_DEVICE
-    bits = [value("SDM_WORLD_STATIC_ONLY"), value("SDM_WORLD_OBSERVED_ONLY"), value("SDM_WORLD_IMPORT_FILL"), value("SDM_WORLD_IMPORT_ON_DEVICE")]
+    assert define("SDM_WORLD_IMPORT_FILL") == binding.WORLD_IMPORT_FILL == 0x10
+    assert define("SDM_WORLD_IMPORT_ON_DEVICE") == binding.WORLD_IMPORT_ON_DEVICE
+    bits = [define("SDM_WORLD_STATIC_ONLY"), define("SDM_WORLD_OBSERVED_ONLY"), define("SDM_WORLD_IMPORT_FILL"), define("SDM_WORLD_IMPORT_ON_DEVICE")]
     assert all(b and not b & (b - 1) for b in bits) and len(set(bits)) == 4     # four distinct bits share the import's flags word
 
 

@@ -2,24 +2,19 @@
 bound with its signature, the three structs have the sizes, fields and offsets the header gives them, the constants agree
 with the header and with the import's, and the call is refused without a map."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 
 from semantic_dsp_map_amd import binding
-from tests.test_capi_symbols import ROOT, declared_functions
-from tests.test_ground_abi import _struct_fields
+from tests.abi_checks import HEADER, assert_bound, assert_layout, define
 
-HEADER = open(os.path.join(ROOT, "include", "sdm.h")).read()
 DTYPES = dict(sdm_world_match_options=binding.WORLD_MATCH_OPTIONS, sdm_world_match_score=binding.WORLD_MATCH_SCORE,
               sdm_world_match_result=binding.WORLD_MATCH_RESULT)
 
 
 def test_the_symbol_is_declared_exported_and_bound():
-    lib = C.CDLL(binding.LIB_PATH)
-    L = binding.load_library()
-    assert "sdm_world_match" in declared_functions() and hasattr(lib, "sdm_world_match")
+    L = assert_bound(dict(sdm_world_match=7))
     vp = C.c_void_p
     assert L.sdm_world_match.argtypes == [vp, vp, vp, vp, C.c_int64, vp, vp]
     decl = re.search(r"sdm_status sdm_world_match\(([^;]*)\);", HEADER).group(1)
@@ -35,16 +30,7 @@ def test_the_symbol_is_declared_exported_and_bound():
 def test_struct_sizes_fields_and_offsets():
     sizes = dict(sdm_world_match_options=56, sdm_world_match_score=32, sdm_world_match_result=56)
     for name, size in sizes.items():
-        assert DTYPES[name].itemsize == size, name
-        assert DTYPES[name].names == _struct_fields(name), name
-        assert re.search(r"typedef struct \{\s*/\* %d bytes" % size, HEADER[:HEADER.index("} %s;" % name)][-1500:]), name
-    for dt in DTYPES.values():                             # every field naturally aligned, no hidden padding
-        at = 0
-        for f in dt.names:
-            assert dt.fields[f][1] == at, (dt, f)
-            assert at % dt.fields[f][0].base.alignment == 0, (dt, f)
-            at += dt.fields[f][0].itemsize
-        assert at == dt.itemsize
+        assert_layout(DTYPES[name], name, size)
     offsets = lambda dt: {f: dt.fields[f][1] for f in dt.names}  # noqa: E731
     assert offsets(binding.WORLD_MATCH_OPTIONS) == dict(flags=0, cell_offset=4, radius=16, w_oo=28, w_same=32, w_of=36, w_fo=40, w_ff=44, pad=48)
     assert offsets(binding.WORLD_MATCH_SCORE) == dict(offset=0, n_oo=12, n_of=16, n_fo=20, n_ff=24, n_same=28)
@@ -57,10 +43,9 @@ def test_struct_sizes_fields_and_offsets():
 
 
 def test_constants_agree_with_the_header():
-    value = lambda name: int(re.search(r"#define\s+%s\s+(\w+)" % name, HEADER).group(1).rstrip("u"), 0)  # noqa: E731
-    assert value("SDM_WORLD_MATCH_ON_DEVICE") == binding.WORLD_MATCH_ON_DEVICE == value("SDM_WORLD_IMPORT_ON_DEVICE") == 0x20
-    assert value("SDM_WORLD_MATCH_MAX_RADIUS") == binding.WORLD_MATCH_MAX_RADIUS == 8
-    bits = [value("SDM_WORLD_STATIC_ONLY"), value("SDM_WORLD_OBSERVED_ONLY"), value("SDM_WORLD_MATCH_ON_DEVICE")]
+    assert define("SDM_WORLD_MATCH_ON_DEVICE") == binding.WORLD_MATCH_ON_DEVICE == define("SDM_WORLD_IMPORT_ON_DEVICE") == 0x20
+    assert define("SDM_WORLD_MATCH_MAX_RADIUS") == binding.WORLD_MATCH_MAX_RADIUS == 8
+    bits = [define("SDM_WORLD_STATIC_ONLY"), define("SDM_WORLD_OBSERVED_ONLY"), define("SDM_WORLD_MATCH_ON_DEVICE")]
     assert all(b and not b & (b - 1) for b in bits) and len(set(bits)) == 3
     assert tuple(binding.WORLD_MATCH_WEIGHTS) == (4, 1, -2, -2, 0)
 

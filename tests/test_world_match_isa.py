@@ -4,7 +4,7 @@ metadata only.  (tests/test_isa_hygiene.py scans the object for FLAT memory inst
 import os
 import re
 
-from tests.test_capi_symbols import ROOT
+from tests.abi_checks import ROOT
 from tests.test_isa_hygiene import device_elf, hip_units, kernels_meta
 from tests.test_reach_isa import sgpr_spills
 from tests.test_world_frontiers_isa import lds_bytes

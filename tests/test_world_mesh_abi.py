@@ -4,26 +4,17 @@ bound with their signatures, the three structs have the sizes, fields and offset
 distinct and agree with the header, the header's bytes are the stated sums, and every call is refused without a map."""
 import ctypes as C
 import inspect
-import os
-import re
 
 import numpy as np
 
 from semantic_dsp_map_amd import binding
-from tests.test_capi_symbols import ROOT, declared_functions
-from tests.test_ground_abi import _struct_fields
+from tests.abi_checks import assert_bound, assert_layout, define
 
 NAMES = ("sdm_world_mesh_update", "sdm_get_world_mesh_info", "sdm_get_world_mesh_faces", "sdm_get_world_mesh_vertices", "sdm_world_mesh_device")
-HEADER = open(os.path.join(ROOT, "include", "sdm.h")).read()
 
 
 def test_symbols_are_declared_exported_and_bound():
-    names = declared_functions()
-    lib = C.CDLL(binding.LIB_PATH)
-    L = binding.load_library()
-    for n in NAMES:
-        assert n in names and hasattr(lib, n) and getattr(L, n).argtypes is not None, n
-    assert [len(getattr(L, n).argtypes) for n in NAMES] == [2, 2, 7, 6, 4]
+    L = assert_bound(dict(zip(NAMES, [2, 2, 7, 6, 4])))
     assert L.sdm_get_world_mesh_faces.argtypes[4:7] == [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
     assert L.sdm_get_world_mesh_vertices.argtypes[3:6] == [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
     assert L.sdm_world_mesh_device.argtypes[1:] == [C.POINTER(C.c_void_p)] * 3
@@ -40,16 +31,7 @@ def test_struct_sizes_fields_and_offsets():
     dtypes = dict(sdm_world_mesh_options=(binding.WORLD_MESH_OPTIONS, 80), sdm_world_mesh_face=(binding.WORLD_MESH_FACE, 12),
                   sdm_world_mesh_info=(binding.WORLD_MESH_INFO, 200))
     for name, (dt, size) in dtypes.items():
-        assert dt.itemsize == size, name
-        assert dt.names == _struct_fields(name), name
-        assert re.search(r"typedef struct \{\s*/\* %d bytes" % size, HEADER[:HEADER.index("} %s;" % name)][-1200:]), name
-    for dt, _ in dtypes.values():   # every field naturally aligned, no hidden padding: the offsets are the running sum of the sizes
-        at = 0
-        for f in dt.names:
-            assert dt.fields[f][1] == at, (dt, f)
-            assert at % dt.fields[f][0].base.alignment == 0, (dt, f)
-            at += dt.fields[f][0].itemsize
-        assert at == dt.itemsize
+        assert_layout(dt, name, size)
     offsets = lambda dt: {f: dt.fields[f][1] for f in dt.names}  # noqa: E731
     assert offsets(binding.WORLD_MESH_OPTIONS) == dict(flags=0, track=4, labels=8, bmin=40, bmax=52, max_faces=64, max_vertices=72)
     assert offsets(binding.WORLD_MESH_FACE) == dict(brick=0, cell=4, dir=6, kind=7, track=8, label=10, occ=11)
@@ -62,14 +44,13 @@ def test_struct_sizes_fields_and_offsets():
 
 
 def test_flag_bits_constants_and_the_stated_bytes():
-    value = lambda name: int(re.search(r"#define\s+%s\s+(\w+)" % name, HEADER).group(1).rstrip("u"), 0)  # noqa: E731
     flags = ("STATIC_ONLY", "MOVABLE_ONLY", "OBSERVED_ONLY", "SKIP_UNKNOWN_FACES", "SKIP_ABSENT_FACES", "BOX")
-    assert [value("SDM_WORLD_MESH_" + f) for f in flags] == [getattr(binding, "WORLD_MESH_" + f) for f in flags] == [1, 2, 4, 8, 16, 32]
+    assert [define("SDM_WORLD_MESH_" + f) for f in flags] == [getattr(binding, "WORLD_MESH_" + f) for f in flags] == [1, 2, 4, 8, 16, 32]
     # the solid rule's bits are the block mesh's
     assert [binding.WORLD_MESH_STATIC_ONLY, binding.WORLD_MESH_MOVABLE_ONLY, binding.WORLD_MESH_OBSERVED_ONLY, binding.WORLD_MESH_SKIP_UNKNOWN_FACES] == \
         [binding.MESH_STATIC_ONLY, binding.MESH_MOVABLE_ONLY, binding.MESH_OBSERVED_ONLY, binding.MESH_SKIP_UNKNOWN_FACES]
     for name in ("ARCHIVED_BRICK", "BRICK", "VERTEX_SLOT", "VERTEX_BRICK", "FACE", "VERTEX"):
-        assert value("SDM_WORLD_MESH_BYTES_PER_" + name) == getattr(binding, "WORLD_MESH_BYTES_PER_" + name), name
+        assert define("SDM_WORLD_MESH_BYTES_PER_" + name) == getattr(binding, "WORLD_MESH_BYTES_PER_" + name), name
     assert binding.WORLD_MESH_BYTES_PER_ARCHIVED_BRICK == 4 + 4 + 3 * 8 * 8          # box flag, rank, three masks of eight words
     assert binding.WORLD_MESH_BYTES_PER_BRICK == 8 + 4 + 6 * 4 + 2 * 8 * 4 + 8 * 4   # coordinates, slot, neighbours, owners twice, prefix
     assert binding.WORLD_MESH_BYTES_PER_VERTEX_SLOT == 8 + 4 + 4 + 512 // 8          # key, rank, place in the list, 512 corner bits

@@ -5,27 +5,18 @@ are distinct and agree with the header, the header's bytes per brick, cell and o
 call is refused without a map."""
 import ctypes as C
 import inspect
-import os
-import re
 
 import numpy as np
 
 from semantic_dsp_map_amd import binding
-from tests.test_capi_symbols import ROOT, declared_functions
-from tests.test_ground_abi import _struct_fields
+from tests.abi_checks import assert_bound, assert_layout, define
 
 NAMES = ("sdm_world_objects_update", "sdm_get_world_objects", "sdm_get_world_object_cells", "sdm_get_world_object_labels",
          "sdm_query_world_objects")
-HEADER = open(os.path.join(ROOT, "include", "sdm.h")).read()
 
 
 def test_symbols_are_declared_exported_and_bound():
-    names = declared_functions()
-    lib = C.CDLL(binding.LIB_PATH)
-    L = binding.load_library()
-    for n in NAMES:
-        assert n in names and hasattr(lib, n) and getattr(L, n).argtypes is not None, n
-    assert [len(getattr(L, n).argtypes) for n in NAMES] == [2, 5, 7, 3, 6]
+    L = assert_bound(dict(zip(NAMES, [2, 5, 7, 3, 6])))
     assert L.sdm_get_world_objects.argtypes[2:4] == [C.c_int32, C.POINTER(C.c_int32)]
     assert L.sdm_get_world_object_cells.argtypes[4:7] == [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
     assert L.sdm_query_world_objects.argtypes[3] == C.c_int64 and L.sdm_query_world_objects.argtypes[5] == C.c_uint32
@@ -45,16 +36,7 @@ def test_struct_sizes_fields_and_offsets():
                   sdm_world_objects_info=binding.WORLD_OBJECTS_INFO, sdm_world_object_result=binding.WORLD_OBJECT_RESULT)
     sizes = dict(sdm_world_objects_options=72, sdm_world_object=168, sdm_world_objects_info=40, sdm_world_object_result=24)
     for name, size in sizes.items():
-        assert dtypes[name].itemsize == size, name
-        assert dtypes[name].names == _struct_fields(name), name
-        assert re.search(r"typedef struct \{\s*/\* %d bytes" % size, HEADER[:HEADER.index("} %s;" % name)][-1800:]), name
-    for dt in dtypes.values():   # every field naturally aligned, no hidden padding: the offsets are the running sum of the sizes
-        at = 0
-        for f in dt.names:
-            assert dt.fields[f][1] == at, (dt, f)
-            assert at % dt.fields[f][0].base.alignment == 0, (dt, f)
-            at += dt.fields[f][0].itemsize
-        assert at == dt.itemsize
+        assert_layout(dtypes[name], name, size)
     offsets = lambda dt: {f: dt.fields[f][1] for f in dt.names}  # noqa: E731
     assert offsets(binding.WORLD_OBJECTS_OPTIONS) == dict(flags=0, min_cells=4, max_cells=8, labels=16, bmin=48, bmax=60)
     assert offsets(binding.WORLD_OBJECT) == dict(first_index=0, n_cells=4, n_guessed=8, track=12, label=14, mixed_tracks=15, first_cell=16,
@@ -72,20 +54,19 @@ def test_struct_sizes_fields_and_offsets():
 
 
 def test_flag_bits_and_the_stated_bytes():
-    value = lambda name: int(re.search(r"#define\s+%s\s+(\w+)" % name, HEADER).group(1).rstrip("u"), 0)  # noqa: E731
     names = ("FACE_CONNECTED", "BOX", "BY_TRACK", "STATIC_ONLY", "MOVABLE_ONLY", "OBSERVED_ONLY")
-    bits = [value("SDM_WORLD_OBJECTS_" + n) for n in names]
+    bits = [define("SDM_WORLD_OBJECTS_" + n) for n in names]
     assert bits == [getattr(binding, "WORLD_OBJECTS_" + n) for n in names] == [1, 2, 4, 8, 16, 32]
-    assert value("SDM_WORLD_OBJECT_UNLISTED") == binding.WORLD_OBJECT_UNLISTED == 0xFFFFFFFE
-    assert value("SDM_WORLD_OBJECT_NONE") == binding.WORLD_OBJECT_NONE == 0xFFFFFFFF
+    assert define("SDM_WORLD_OBJECT_UNLISTED") == binding.WORLD_OBJECT_UNLISTED == 0xFFFFFFFE
+    assert define("SDM_WORLD_OBJECT_NONE") == binding.WORLD_OBJECT_NONE == 0xFFFFFFFF
     # per archived brick: flag, rank; per brick: coordinates, pool slot, 27 neighbours, counted words, prefix, two hash slots
-    assert value("SDM_WORLD_OBJECTS_BYTES_PER_ARCHIVED_BRICK") == binding.WORLD_OBJECTS_BYTES_PER_ARCHIVED_BRICK == 4 + 4
-    assert value("SDM_WORLD_OBJECTS_BYTES_PER_BRICK") == binding.WORLD_OBJECTS_BYTES_PER_BRICK == 8 + 4 + 27 * 4 + 8 * 8 + 8 * 4 + 2 * (8 + 4)
+    assert define("SDM_WORLD_OBJECTS_BYTES_PER_ARCHIVED_BRICK") == binding.WORLD_OBJECTS_BYTES_PER_ARCHIVED_BRICK == 4 + 4
+    assert define("SDM_WORLD_OBJECTS_BYTES_PER_BRICK") == binding.WORLD_OBJECTS_BYTES_PER_BRICK == 8 + 4 + 27 * 4 + 8 * 8 + 8 * 4 + 2 * (8 + 4)
     # per cell: world cell, word, object, root, scan - within the 32 bytes the layer was given
-    assert value("SDM_WORLD_OBJECTS_BYTES_PER_CELL") == binding.WORLD_OBJECTS_BYTES_PER_CELL == 12 + 4 + 3 * 4 <= 32
+    assert define("SDM_WORLD_OBJECTS_BYTES_PER_CELL") == binding.WORLD_OBJECTS_BYTES_PER_CELL == 12 + 4 + 3 * 4 <= 32
     # per object: the table entry, the accumulator (3 sums, 6 products, 2 counts, 6 box codes, the OR and a pad), first cell, scan
     acc = 3 * 8 + 6 * 8 + 2 * 4 + 6 * 4 + 4 + 4
-    assert value("SDM_WORLD_OBJECTS_BYTES_PER_OBJECT") == binding.WORLD_OBJECTS_BYTES_PER_OBJECT == binding.WORLD_OBJECT.itemsize + acc + 4 + 4
+    assert define("SDM_WORLD_OBJECTS_BYTES_PER_OBJECT") == binding.WORLD_OBJECTS_BYTES_PER_OBJECT == binding.WORLD_OBJECT.itemsize + acc + 4 + 4
     assert binding.label_mask(binding.ALL_LABELS).tolist() == [0xFFFFFFFF] * 8
 
 

@@ -4,26 +4,17 @@ the size, fields and offsets the header gives it, the new flag bit clashes with 
 with, the constants agree with the header, and every call is refused without a map."""
 import ctypes as C
 import inspect
-import os
-import re
 
 import numpy as np
 
 from semantic_dsp_map_amd import binding
-from tests.test_capi_symbols import ROOT, declared_functions
-from tests.test_ground_abi import _struct_fields
+from tests.abi_checks import assert_bound, assert_layout, define
 
 NAMES = ("sdm_query_world_segments", "sdm_query_world_views", "sdm_debug_world_view_batch")
-HEADER = open(os.path.join(ROOT, "include", "sdm.h")).read()
 
 
 def test_symbols_are_declared_exported_and_bound():
-    names = declared_functions()
-    lib = C.CDLL(binding.LIB_PATH)
-    L = binding.load_library()
-    for n in NAMES:
-        assert n in names and hasattr(lib, n) and getattr(L, n).argtypes is not None, n
-    assert [len(getattr(L, n).argtypes) for n in NAMES] == [5, 9, 2]
+    L = assert_bound(dict(zip(NAMES, [5, 9, 2])))
     assert L.sdm_query_world_segments.argtypes[2] == C.c_int64 and L.sdm_query_world_segments.argtypes[4] == C.c_uint32
     assert L.sdm_query_world_views.argtypes[2] == C.c_int64 and L.sdm_query_world_views.argtypes[4:6] == [C.c_int32, C.c_int32]
     assert L.sdm_query_world_views.argtypes[8] == C.c_uint32 and L.sdm_debug_world_view_batch.argtypes[1] == C.c_int32
@@ -38,13 +29,7 @@ def test_symbols_are_declared_exported_and_bound():
 
 def test_struct_size_fields_and_offsets():
     dt = binding.WORLD_SEGMENT_HIT
-    assert dt.itemsize == 32 and dt.names == _struct_fields("sdm_world_segment_hit")
-    assert re.search(r"typedef struct \{\s*/\* 32 bytes", HEADER[:HEADER.index("} sdm_world_segment_hit;")][-900:])
-    at = 0
-    for f in dt.names:   # every field naturally aligned, no hidden padding: the offsets are the running sum of the sizes
-        assert dt.fields[f][1] == at and at % dt.fields[f][0].base.alignment == 0, f
-        at += dt.fields[f][0].itemsize
-    assert at == 32
+    assert_layout(dt, "sdm_world_segment_hit", 32)
     assert {f: dt.fields[f][1] for f in dt.names} == dict(t=0, cells=4, cell=8, track=20, label=22, occ=23, unknown=24, stamp=28)
     assert dt.fields["t"][0] == np.dtype("<f4") and dt.fields["cell"][0].base == np.dtype("<i4") and dt.fields["cell"][0].shape == (3,)
     assert dt.fields["occ"][0] == np.dtype("i1") and dt.fields["unknown"][0] == np.dtype("<i4") and dt.fields["stamp"][0] == np.dtype("<u4")
@@ -53,14 +38,13 @@ def test_struct_size_fields_and_offsets():
 
 
 def test_flag_bits_and_constants():
-    value = lambda name: int(re.search(r"#define\s+%s\s+(\w+)" % name, HEADER).group(1).rstrip("u"), 0)  # noqa: E731
-    ignore = value("SDM_WORLD_RAYS_IGNORE_MOVABLE")
+    ignore = define("SDM_WORLD_RAYS_IGNORE_MOVABLE")
     assert ignore == binding.WORLD_RAYS_IGNORE_MOVABLE == 0x10
-    others = [value("SDM_QUERY_ON_DEVICE"), value("SDM_QUERY_UNKNOWN_BLOCKS")]
+    others = [define("SDM_QUERY_ON_DEVICE"), define("SDM_QUERY_UNKNOWN_BLOCKS")]
     assert others == [binding.QUERY_ON_DEVICE, binding.QUERY_UNKNOWN_BLOCKS] == [1, 2]
     assert all(ignore & o == 0 for o in others) and bin(ignore).count("1") == 1
-    assert value("SDM_WORLD_SEGMENT_MAX_CELLS") == binding.WORLD_SEGMENT_MAX_CELLS == 8192
-    assert value("SDM_WORLD_VIEW_MAX_REACH") == binding.WORLD_VIEW_MAX_REACH == 255
+    assert define("SDM_WORLD_SEGMENT_MAX_CELLS") == binding.WORLD_SEGMENT_MAX_CELLS == 8192
+    assert define("SDM_WORLD_VIEW_MAX_REACH") == binding.WORLD_VIEW_MAX_REACH == 255
     # the mask of the largest window: 511^3 bits, at least three of them in a pool of 64 MiB, its bit index within 32 bits
     S = 2 * binding.WORLD_VIEW_MAX_REACH + 1
     assert (64 << 20) // (-(-S ** 3 // 32) * 4) == 4 and S ** 3 < 1 << 32

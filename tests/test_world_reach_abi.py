@@ -4,26 +4,17 @@ three structs have the sizes, fields and offsets the header gives them, the flag
 header, and every call is refused without a map."""
 import ctypes as C
 import inspect
-import os
-import re
 
 import numpy as np
 
 from semantic_dsp_map_amd import binding
-from tests.test_capi_symbols import ROOT, declared_functions
-from tests.test_ground_abi import _struct_fields
+from tests.abi_checks import assert_bound, assert_layout, define
 
 NAMES = ("sdm_world_reach_update", "sdm_get_world_reach", "sdm_query_world_reach", "sdm_world_reach_paths")
-HEADER = open(os.path.join(ROOT, "include", "sdm.h")).read()
 
 
 def test_symbols_are_declared_exported_and_bound():
-    names = declared_functions()
-    lib = C.CDLL(binding.LIB_PATH)
-    L = binding.load_library()
-    for n in NAMES:
-        assert n in names and hasattr(lib, n) and getattr(L, n).argtypes is not None, n
-    assert [len(getattr(L, n).argtypes) for n in NAMES] == [5, 7, 6, 8]
+    L = assert_bound(dict(zip(NAMES, [5, 7, 6, 8])))
     assert L.sdm_world_reach_update.argtypes[4] is C.c_int64
     assert L.sdm_get_world_reach.argtypes[3:6] == [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]
     assert L.sdm_query_world_reach.argtypes[3] is C.c_int64 and L.sdm_query_world_reach.argtypes[5] is C.c_uint32
@@ -40,16 +31,7 @@ def test_struct_sizes_fields_and_offsets():
                   sdm_world_reach_result=binding.WORLD_REACH_RESULT)
     sizes = dict(sdm_world_reach_options=40, sdm_world_reach_info=40, sdm_world_reach_result=24)
     for name, size in sizes.items():
-        assert dtypes[name].itemsize == size, name
-        assert dtypes[name].names == _struct_fields(name), name
-        assert re.search(r"typedef struct \{\s*/\* %d bytes" % size, HEADER[:HEADER.index("} %s;" % name)][-1500:]), name
-    for dt in dtypes.values():   # every field naturally aligned, no hidden padding: the offsets are the running sum of the sizes
-        at = 0
-        for f in dt.names:
-            assert dt.fields[f][1] == at, (dt, f)
-            assert at % dt.fields[f][0].base.alignment == 0, (dt, f)
-            at += dt.fields[f][0].itemsize
-        assert at == dt.itemsize
+        assert_layout(dtypes[name], name, size)
     offsets = lambda dt: {f: dt.fields[f][1] for f in dt.names}  # noqa: E731
     assert offsets(binding.WORLD_REACH_OPTIONS) == dict(flags=0, inflate=4, max_cost=8, pad=12, bmin=16, bmax=28)
     assert offsets(binding.WORLD_REACH_INFO) == dict(n_bricks=0, n_starts_used=4, n_traversable=8, n_reached=12, max_cost_reached=16, rounds=20,
@@ -59,9 +41,8 @@ def test_struct_sizes_fields_and_offsets():
 
 
 def test_flag_bits_are_distinct_and_agree_with_the_header():
-    value = lambda name: int(re.search(r"#define\s+%s\s+(\w+)" % name, HEADER).group(1).rstrip("u"), 0)  # noqa: E731
-    bits = [value("SDM_WORLD_REACH_FACE_CONNECTED"), value("SDM_WORLD_REACH_THROUGH_UNKNOWN"), value("SDM_WORLD_REACH_IGNORE_MOVABLE"),
-            value("SDM_WORLD_REACH_BOX")]
+    bits = [define("SDM_WORLD_REACH_FACE_CONNECTED"), define("SDM_WORLD_REACH_THROUGH_UNKNOWN"), define("SDM_WORLD_REACH_IGNORE_MOVABLE"),
+            define("SDM_WORLD_REACH_BOX")]
     assert bits == [binding.WORLD_REACH_FACE_CONNECTED, binding.WORLD_REACH_THROUGH_UNKNOWN, binding.WORLD_REACH_IGNORE_MOVABLE,
                     binding.WORLD_REACH_BOX] == [1, 2, 4, 8]
     assert all(b and not b & (b - 1) for b in bits) and len(set(bits)) == 4
