@@ -1369,6 +1369,150 @@ sdm_status sdm_get_world_object_labels(sdm_map *m, uint64_t cells[256], uint32_t
 sdm_status sdm_query_world_objects(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n,
                                    sdm_world_object_result *out, uint32_t flags);
 
+/* ---- world changes: is the place the block has come back to still as the archive remembers it? ----
+ * sdm_world_changes_update compares, on the map's stream, what the block sees with what the archive remembers, cell by
+ * cell, lists the cells that changed, joins them into regions and makes a table of those.  The intended use is one call
+ * between a frame and its archiving: sdm_update -> sdm_world_changes_update -> sdm_world_update (which then overwrites the
+ * difference this call has found).  Like sdm_world_objects_update IT WAITS, three times: for the bricks of the field, for
+ * the listed cells and for the regions, and sizes its buffers from them.  Cells are world cells (int32 per axis, brick =
+ * cell >> 3).
+ * What is compared: the block side is the result array of the last frame enqueued before the call; the archive side is the
+ * archive as the last sdm_world_update, sdm_world_import or sdm_world_retain left it, read live in stream order.  The two
+ * sides meet at the same world cell, g = moved_steps + i - (N >> 1) per axis: sdm_world_update's own geometry.
+ * Field candidates: the bricks the block overlaps, at most ceil(N / 8) + 1 per axis, in brick order - ascending in
+ * (bz, by, bx) -, the candidates of sdm_world_update.  Cells of such a brick that lie outside the block read unknown on the
+ * block side.
+ * Class of a side: a word is OCCUPIED (occ >= 1) or FREE (occ == 0) iff it would write under the archive's own rule with
+ * this layer's flags in place of the archive's: occ >= 0; with SDM_WORLD_CHANGES_STATIC_ONLY no movable track on an occupied
+ * cell (1 <= track <= max_movable_track); with SDM_WORLD_CHANGES_OBSERVED_ONLY no occ == 2.  Everything else is UNKNOWN.
+ * Both sides go through the same rule.  The archive side is also UNKNOWN where the archive has no brick, where the brick is
+ * beyond the int16 range, and - with SDM_WORLD_CHANGES_OLDER - where the brick's last_stamp > max_last_stamp (a plain
+ * unsigned compare, like sdm_world_retain's min_last_stamp).
+ * Class of a cell, block / archive:  O / F  SDM_WORLD_CHANGE_APPEARED (1);  F / O  SDM_WORLD_CHANGE_VANISHED (2);  O / O with
+ * different label bytes  SDM_WORLD_CHANGE_RELABELLED (3);  O / O with equal label bytes counts as n_same_occupied;  F / F
+ * n_same_free;  O / U  n_new_occupied;  F / U  n_new_free;  U / O and U / F  n_remembered;  U / U nothing.  The three
+ * change classes count as n_appeared, n_vanished, n_relabelled.  Three more close the sums: n_known_now and n_known_before,
+ * the cells of either side that are not UNKNOWN (n_known_now = the three changes + the two same + the two new;
+ * n_known_before = the three changes + the two same + n_remembered), and n_outside, the cells of the candidates that lie
+ * outside the block.  Every counter is a true count over all candidates, before any mask.
+ * Listed cell: a changed cell whose class has its bit set in `classes` (bit 1, 2 or 3) and one of whose occupied sides'
+ * labels l is admitted by `labels` (bit l & 31 of labels[l >> 5], the rule of the world objects): the block's label for
+ * APPEARED, the archive's for VANISHED, either for RELABELLED.  All-zero masks list nothing, which is no error.
+ * Field: the candidates with at least one listed cell, ranked in brick order.
+ * Cell list: the listed cells, ascending in (brick rank, cell word cx | cy << 3 | cz << 6); per cell the world cell, the
+ * block's word `now`, the archive's word `before`, the class and the region index.
+ * Region: a connected component of listed cells with EQUAL KEYS, in world cells across brick borders, 26-connected, or
+ * 6-connected with SDM_WORLD_CHANGES_FACE_CONNECTED.  The key is the class; with SDM_WORLD_CHANGES_BY_LABEL it is
+ * class | label_now << 8 | label_before << 16, a side's label being 0 when that side is not occupied.  As with the world
+ * objects two cells of one key that touch only at an edge or a corner are joined under 26-connectivity whatever lies
+ * between them, and a cell of another key carries nothing across.  A region's identity is the list index of its first
+ * cell; the table ascends in first_index.  min_cells <= 1 lists every region; a larger value leaves smaller regions out of
+ * the table, their cells stay in the list with region SDM_WORLD_CHANGE_UNLISTED: the debounce for the flicker at occupancy
+ * borders.
+ * Table entry: cls, label_now and label_before are the first cell's (a side's label 0 when it is not occupied); mixed is 1
+ * if not every cell has that label pair (always 0 with BY_LABEL).  cell_sum: signed sums of the world cells.  Float fields,
+ * one IEEE operation at a time, no contraction: box_min = (float)cell_min * voxel_size, box_max = (float)(cell_max + 1) *
+ * voxel_size, centroid = (float)(((double)cell_sum / (double)n_cells + 0.5) * (double)voxel_size).  Everything accumulated
+ * is an integer sum, minimum, maximum or OR and a region's identity is its smallest cell index: two builds give the same
+ * bytes.
+ * The build is a SNAPSHOT: it owns the field's coordinates, a hash table of its own from brick to rank, the listed words
+ * with their prefix, the lists and the table, and answers the same bytes after any later frame, sdm_world_update,
+ * sdm_world_import, sdm_world_retain or sdm_world_clear, until the next sdm_world_changes_update.  Nothing of the map or of
+ * the archive is modified.
+ * max_cells > 0 caps the cell-proportional buffers: with more listed cells than that the build writes no list and returns
+ * SDM_ERR_CAPACITY; sdm_get_world_changes then still fills info (the eleven counters, n_candidates, n_bricks and n_cells
+ * are the true counts, the region counts are 0), sdm_get_world_change_cells still sets *n_out to the true count, and they,
+ * sdm_get_world_change_labels and sdm_query_world_changes return SDM_ERR_CAPACITY until a build with room.  max_cells == 0:
+ * no cap.
+ * sdm_get_world_changes: the first min(n, cap) table entries, *n_out = n, the regions listed; info may be NULL.
+ * sdm_get_world_change_cells: rows first .. first + cap - 1 of the cell list - cell_xyz three int32 a cell, now and before
+ * the two words, cls the class (one byte), region the index into the table (SDM_WORLD_CHANGE_UNLISTED: below min_cells);
+ * every array may be NULL; *n_out = the cells in all.  sdm_get_world_change_labels: listed cells per label - an appeared or
+ * relabelled cell under the block's label, a vanished cell under the archive's; each array may be NULL.
+ * sdm_query_world_changes answers for the last build, for points (three floats each; world cell = floorf(p * recip) per
+ * axis) or world cells (three int32 each) under the protocol of sdm_query_world_objects: exactly one of the two pointers is
+ * non-NULL, also with n == 0; `cell` is (0, 0, 0) for a point that is non-finite or beyond the brick range, a cell given is
+ * echoed as given.  region: the table index, SDM_WORLD_CHANGE_UNLISTED for a listed cell of a region below min_cells,
+ * SDM_WORLD_CHANGE_NONE where the cell is no listed cell; index: its place in the cell list or SDM_WORLD_CHANGE_NONE; cls:
+ * its class, SDM_WORLD_CHANGE_NONE if it has none.  SDM_QUERY_ON_DEVICE as for the other queries.
+ * Memory, allocated at the first build, grown by a build that needs more, freed by sdm_destroy:
+ *   SDM_WORLD_CHANGES_BYTES_PER_CANDIDATE x (the map's largest candidate count + 1, in steps of 256)
+ * + SDM_WORLD_CHANGES_BYTES_PER_BRICK x (bricks of the field, in steps of 256) + 12, which counts two hash slots a brick: the
+ *   table has the power of two at or above twice that stepped count, so up to 12 more bytes for each of up to two more slots a brick
+ * + SDM_WORLD_CHANGES_BYTES_PER_CELL x (listed cells, in steps of 4096) + 4
+ * + SDM_WORLD_CHANGES_BYTES_PER_REGION x (regions in all, in steps of 1024) + 4
+ * + 23576 (the counters in 64 spread copies, the per-label counters and their landing area).
+ * Errors: SDM_ERR_INVALID_ARGUMENT for a NULL map, options or output (n_out, out), unknown flag or class bits, non-zero
+ * pads, negative max_cells, counts, cap or first, a NULL out with cap > 0, none or both of xyz and cells, a Z-slab shard
+ * (shard_count > 1), a build before the archive has had an update or import, and a getter or the query before any build.
+ * An archive that holds no brick the block overlaps is no error: everything known then counts as new. */
+#define SDM_WORLD_CHANGES_FACE_CONNECTED 0x01u  /* regions under 6- instead of 26-connectivity */
+#define SDM_WORLD_CHANGES_BY_LABEL       0x02u  /* the key is class and label pair, not the class alone */
+#define SDM_WORLD_CHANGES_STATIC_ONLY    0x04u  /* an occupied cell on a movable track reads unknown, on either side */
+#define SDM_WORLD_CHANGES_OBSERVED_ONLY  0x08u  /* occ == 2 reads unknown, on either side */
+#define SDM_WORLD_CHANGES_OLDER          0x10u  /* a brick with last_stamp > max_last_stamp reads unknown */
+#define SDM_WORLD_CHANGE_APPEARED   1u          /* occupied now, free before */
+#define SDM_WORLD_CHANGE_VANISHED   2u          /* free now, occupied before */
+#define SDM_WORLD_CHANGE_RELABELLED 3u          /* occupied on both sides, the label bytes differ */
+#define SDM_WORLD_CHANGE_UNLISTED 0xfffffffeu   /* a listed cell of a region below min_cells */
+#define SDM_WORLD_CHANGE_NONE     0xffffffffu   /* no listed cell */
+#define SDM_WORLD_CHANGES_BYTES_PER_CANDIDATE 204  /* flag, rank, pool slot, listed words and two class planes */
+#define SDM_WORLD_CHANGES_BYTES_PER_BRICK 368   /* coordinates, pool slot, 27 neighbours, listed words, prefix, two class planes, two hash slots */
+#define SDM_WORLD_CHANGES_BYTES_PER_CELL  37    /* world cell, now, before, key, class, region, root, scan */
+#define SDM_WORLD_CHANGES_BYTES_PER_REGION 176  /* table entry 112, accumulator 56, first cell's index, scan */
+typedef struct {            /* 64 bytes, every field naturally aligned */
+  uint32_t flags;
+  int32_t  min_cells;       /* <= 1: every region is listed */
+  int64_t  max_cells;       /* 0: no cap */
+  uint32_t labels[8];       /* bit l & 31 of word l >> 5 admits label l */
+  uint32_t classes;         /* bit c admits class c: 0x2 appeared, 0x4 vanished, 0x8 relabelled */
+  uint32_t max_last_stamp;  /* read only with SDM_WORLD_CHANGES_OLDER */
+  uint32_t pad[2];          /* 0 */
+} sdm_world_changes_options;
+typedef struct {            /* 112 bytes, every field naturally aligned */
+  uint32_t first_index;     /* of the region's first cell in the cell list: its identity */
+  uint32_t n_cells;
+  uint8_t  cls;             /* of the first cell, and of every other */
+  uint8_t  label_now;       /* of the first cell; 0 where the block side is not occupied */
+  uint8_t  label_before;    /* of the first cell; 0 where the archive side is not occupied */
+  uint8_t  mixed;           /* 1: not every cell carries that label pair */
+  int32_t  first_cell[3];   /* world cell of the first cell */
+  int32_t  cell_min[3], cell_max[3]; /* inclusive */
+  int64_t  cell_sum[3];     /* signed */
+  float    box_min[3], box_max[3], centroid[3];
+  uint32_t pad;             /* 0 */
+} sdm_world_change_region;
+typedef struct {            /* 128 bytes, every field naturally aligned */
+  uint64_t n_appeared, n_vanished, n_relabelled;  /* the three change classes, before any mask */
+  uint64_t n_same_occupied, n_same_free;          /* O / O with equal labels, F / F */
+  uint64_t n_new_occupied, n_new_free;            /* O / U, F / U */
+  uint64_t n_remembered;                          /* U / O and U / F */
+  uint64_t n_known_now, n_known_before;           /* cells of the block side / of the archive side that are not UNKNOWN */
+  uint64_t n_outside;                             /* cells of the candidates that lie outside the block */
+  uint32_t n_candidates;    /* bricks the block overlaps */
+  uint32_t n_bricks;        /* bricks of the field */
+  int64_t  n_cells;         /* listed cells */
+  uint32_t n_regions;       /* regions listed: the table's length */
+  uint32_t n_regions_total; /* regions in all, those below min_cells included */
+  uint32_t flags;
+  int32_t  min_cells;       /* as given */
+  uint32_t frame_stamp;     /* the frame's global_time_stamp */
+  uint32_t stamp;           /* the archive's stamp at the build: sdm_world_info.stamp */
+} sdm_world_changes_info;
+typedef struct {            /* 24 bytes */
+  int32_t  cell[3];         /* the world cell asked about */
+  uint32_t region;          /* table index, SDM_WORLD_CHANGE_UNLISTED or SDM_WORLD_CHANGE_NONE */
+  uint32_t index;           /* place in the cell list; SDM_WORLD_CHANGE_NONE if none */
+  uint32_t cls;             /* the class; SDM_WORLD_CHANGE_NONE if none */
+} sdm_world_change_result;
+sdm_status sdm_world_changes_update(sdm_map *m, const sdm_world_changes_options *o);
+sdm_status sdm_get_world_changes(sdm_map *m, sdm_world_change_region *regions, int32_t cap, int32_t *n_out, sdm_world_changes_info *info);
+sdm_status sdm_get_world_change_cells(sdm_map *m, int32_t *cell_xyz, uint32_t *now, uint32_t *before, uint8_t *cls, uint32_t *region,
+                                      int64_t first, int64_t cap, int64_t *n_out);
+sdm_status sdm_get_world_change_labels(sdm_map *m, uint64_t appeared[256], uint64_t vanished[256], uint64_t relabelled[256]);
+sdm_status sdm_query_world_changes(sdm_map *m, const float *xyz, const int32_t *cells, int64_t n,
+                                   sdm_world_change_result *out, uint32_t flags);
+
 /* ---- world reach: how far is it, through everything the map remembers, to a place the block has left? ----
  * sdm_world_reach_update builds, on the map's stream, the travel-cost field of sdm_reach_update over the bricks of the
  * world archive instead of the map block, from a set of start cells.  Like sdm_reach_update IT WAITS: the host decides

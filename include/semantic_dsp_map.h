@@ -916,6 +916,29 @@ class SemanticDSPMap {
   size_t queryWorldObjects(const std::vector<Eigen::Vector3d> &points, std::vector<sdm_world_object_result> &out) {
     return batched(sdm_query_world_objects, "sdm_query_world_objects", flat_points(points), 3, out, nullptr);
   }
+  /// Is the place the block has come back to still as the map remembers it (sdm.h, "world changes")?  Compares the last
+  /// frame's results with the archive cell by cell and returns the table of the regions of changed cells - appeared,
+  /// vanished, relabelled - that the options admit, ascending in first_index.  Call it between a frame and its
+  /// worldUpdate(), which overwrites what this call finds.  The build is a snapshot: queryWorldChanges() answers for it
+  /// until the next worldChanges().  The call waits for the build.  info (may be null): the counters and the build's counts.
+  /// Returns false before the first worldUpdate() or worldImport() or when a call fails.
+  bool worldChanges(const sdm_world_changes_options &options, std::vector<sdm_world_change_region> &regions, sdm_world_changes_info *info = nullptr) {
+    regions.clear();
+    if (!map_) return false;
+    if (!check(sdm_world_changes_update(map_, &options), "sdm_world_changes_update")) return false;
+    int32_t n = 0;
+    if (!check(sdm_get_world_changes(map_, nullptr, 0, &n, info), "sdm_get_world_changes")) return false;
+    regions.resize((size_t)n);
+    if (n && !check(sdm_get_world_changes(map_, regions.data(), n, &n, nullptr), "sdm_get_world_changes")) regions.clear();
+    return (int32_t)regions.size() == n;
+  }
+  /// Per position (global frame) of the last worldChanges(): its world cell, the index of the region it belongs to in that
+  /// call's table - SDM_WORLD_CHANGE_UNLISTED for a cell of a region below min_cells, SDM_WORLD_CHANGE_NONE where nothing
+  /// changed -, its place in the cell list and its class.  Waits.  Returns the number of points answered; 0 (and an empty
+  /// vector) before the first worldChanges() or when the call fails.
+  size_t queryWorldChanges(const std::vector<Eigen::Vector3d> &points, std::vector<sdm_world_change_result> &out) {
+    return batched(sdm_query_world_changes, "sdm_query_world_changes", flat_points(points), 3, out, nullptr);
+  }
   /// How close is a remembered place to an obstacle (sdm.h, "world distance field")?  Builds the truncated Euclidean
   /// distance field over the bricks of the world archive: exact up to max_metres - radius = ceil(max_metres / voxel_size)
   /// cells, at least 1 and at most SDM_WORLD_ESDF_MAX_RADIUS - and "far" beyond.  unknown_is_obstacle: never-observed

@@ -264,6 +264,36 @@ WORLD_OBJECTS_BYTES_PER_CELL = 28
 WORLD_OBJECTS_BYTES_PER_OBJECT = 288
 ALL_LABELS = tuple(range(256))
 
+# world changes (sdm.h: sdm_world_changes_update / sdm_get_world_changes / sdm_get_world_change_cells /
+# sdm_get_world_change_labels / sdm_query_world_changes); the client is the class WorldChanges below
+WORLD_CHANGES_COUNTERS = ("n_appeared", "n_vanished", "n_relabelled", "n_same_occupied", "n_same_free", "n_new_occupied", "n_new_free",
+                          "n_remembered", "n_known_now", "n_known_before", "n_outside")
+WORLD_CHANGES_OPTIONS = np.dtype([("flags", "<u4"), ("min_cells", "<i4"), ("max_cells", "<i8"), ("labels", "<u4", (8,)), ("classes", "<u4"),
+                                  ("max_last_stamp", "<u4"), ("pad", "<u4", (2,))])
+WORLD_CHANGE_REGION = np.dtype([("first_index", "<u4"), ("n_cells", "<u4"), ("cls", "u1"), ("label_now", "u1"), ("label_before", "u1"),
+                                ("mixed", "u1"), ("first_cell", "<i4", (3,)), ("cell_min", "<i4", (3,)), ("cell_max", "<i4", (3,)),
+                                ("cell_sum", "<i8", (3,)), ("box_min", "<f4", (3,)), ("box_max", "<f4", (3,)), ("centroid", "<f4", (3,)),
+                                ("pad", "<u4")])
+WORLD_CHANGES_INFO = np.dtype([(name, "<u8") for name in WORLD_CHANGES_COUNTERS] +
+                              [("n_candidates", "<u4"), ("n_bricks", "<u4"), ("n_cells", "<i8"), ("n_regions", "<u4"), ("n_regions_total", "<u4"),
+                               ("flags", "<u4"), ("min_cells", "<i4"), ("frame_stamp", "<u4"), ("stamp", "<u4")])
+WORLD_CHANGE_RESULT = np.dtype([("cell", "<i4", (3,)), ("region", "<u4"), ("index", "<u4"), ("cls", "<u4")])
+assert WORLD_CHANGES_OPTIONS.itemsize == 64 and WORLD_CHANGE_REGION.itemsize == 112 and WORLD_CHANGES_INFO.itemsize == 128
+assert WORLD_CHANGE_RESULT.itemsize == 24
+WORLD_CHANGES_FACE_CONNECTED = 0x01
+WORLD_CHANGES_BY_LABEL = 0x02
+WORLD_CHANGES_STATIC_ONLY = 0x04
+WORLD_CHANGES_OBSERVED_ONLY = 0x08
+WORLD_CHANGES_OLDER = 0x10
+WORLD_CHANGE_APPEARED, WORLD_CHANGE_VANISHED, WORLD_CHANGE_RELABELLED = 1, 2, 3
+ALL_CHANGE_CLASSES = (WORLD_CHANGE_APPEARED, WORLD_CHANGE_VANISHED, WORLD_CHANGE_RELABELLED)
+WORLD_CHANGE_UNLISTED = 0xFFFFFFFE   # a listed cell of a region below min_cells
+WORLD_CHANGE_NONE = 0xFFFFFFFF       # no listed cell
+WORLD_CHANGES_BYTES_PER_CANDIDATE = 204
+WORLD_CHANGES_BYTES_PER_BRICK = 368
+WORLD_CHANGES_BYTES_PER_CELL = 37
+WORLD_CHANGES_BYTES_PER_REGION = 176
+
 STATE_FIELDS = [("px", np.float32), ("py", np.float32), ("pz", np.float32), ("w", np.float32),
                 ("ts", np.uint16), ("track", np.uint16), ("label", np.uint8), ("status", np.uint8),
                 ("forget", np.uint8), ("owner", np.uint16)]
@@ -513,6 +543,11 @@ def load_library():
         "sdm_get_world_object_cells": [vp, vp, vp, vp, i64, i64, C.POINTER(i64)],
         "sdm_get_world_object_labels": [vp, vp, vp],
         "sdm_query_world_objects": [vp, vp, vp, i64, vp, u32],
+        "sdm_world_changes_update": [vp, vp],
+        "sdm_get_world_changes": [vp, vp, i32, C.POINTER(i32), vp],
+        "sdm_get_world_change_cells": [vp, vp, vp, vp, vp, vp, i64, i64, C.POINTER(i64)],
+        "sdm_get_world_change_labels": [vp, vp, vp, vp],
+        "sdm_query_world_changes": [vp, vp, vp, i64, vp, u32],
         "sdm_world_esdf_update": [vp, vp],
         "sdm_get_world_esdf": [vp, vp, vp, vp, i64, i64, C.POINTER(i64), vp],
         "sdm_query_world_distance": [vp, vp, vp, i64, vp, u32],
@@ -1910,3 +1945,55 @@ def test_sort_pairs_seq(capacity, nbits, keys, vals, keys_out, vals_out, count=N
     _call("sdm_test_sort_pairs_seq", capacity.size, _ptr(capacity), _ptr(count), _ptr(nbits), TEST_COUNT_ON_DEVICE if count_on_device else 0,
           _ptr(keys), _ptr(vals), _ptr(keys_out), _ptr(vals_out), _ptr(which), C.byref(ok), _ptr(scratch))
     return keys_out, vals_out, which, bool(ok.value), scratch
+
+
+class WorldChanges:
+    """What the block sees against what the archive remembers (sdm.h, "world changes"): the client of one map's change
+    layer.  update() compares the last frame's results with the archive and WAITS until the build is complete; regions(),
+    cells(), labels() and query() answer for that build - a snapshot that later frames, updates, imports, retains and clears
+    leave alone.  The intended use is one update() between a frame and its world_update()."""
+
+    def __init__(self, map):
+        self.map = map
+
+    def update(self, face_connected=False, by_label=False, static_only=False, observed_only=False, max_last_stamp=None,
+               labels=ALL_LABELS, classes=ALL_CHANGE_CLASSES, min_cells=1, max_cells=0):
+        """labels: the label ids that admit a changed cell (default: all); classes: the change classes listed (default: all
+        three); max_last_stamp: only bricks last archived at or before that stamp are compared; by_label: a region's key is
+        class and label pair"""
+        o = np.zeros(1, WORLD_CHANGES_OPTIONS)
+        o["flags"] = ((WORLD_CHANGES_FACE_CONNECTED if face_connected else 0) | (WORLD_CHANGES_BY_LABEL if by_label else 0) |
+                      (WORLD_CHANGES_STATIC_ONLY if static_only else 0) | (WORLD_CHANGES_OBSERVED_ONLY if observed_only else 0) |
+                      (WORLD_CHANGES_OLDER if max_last_stamp is not None else 0))
+        o["min_cells"], o["max_cells"] = int(min_cells), int(max_cells)
+        o["labels"] = label_mask(labels)
+        o["classes"] = sum(1 << int(c) for c in set(classes))
+        o["max_last_stamp"] = 0 if max_last_stamp is None else int(max_last_stamp)
+        self.map._call("sdm_world_changes_update", _ptr(o))
+
+    def regions(self):
+        """-> (table, info): WORLD_CHANGE_REGION entries in ascending first_index, a WORLD_CHANGES_INFO record"""
+        got = C.c_int32(0)
+        info = np.zeros(1, WORLD_CHANGES_INFO)
+        self.map._call("sdm_get_world_changes", None, 0, C.byref(got), _ptr(info))
+        out = np.empty(got.value, WORLD_CHANGE_REGION)
+        self.map._call("sdm_get_world_changes", _ptr(out), got.value, C.byref(got), None)
+        return out, info[0]
+
+    def cells(self, first=0, cap=None):
+        """-> (cells int32 [n, 3], now uint32 [n], before uint32 [n], cls uint8 [n], region uint32 [n]): rows first ..
+        first + cap - 1 of the cell list, ascending in (brick order, cell word); region indexes the table
+        (WORLD_CHANGE_UNLISTED: below min_cells)"""
+        cols = [(np.int32, (3,)), (np.uint32, ()), (np.uint32, ()), (np.uint8, ()), (np.uint32, ())]
+        return tuple(self.map._window("sdm_get_world_change_cells", cols, first, cap)[0])
+
+    def labels(self):
+        """-> (appeared, vanished, relabelled), uint64 [256] each: the listed cells per label"""
+        out = [np.zeros(256, np.uint64) for _ in range(3)]
+        self.map._call("sdm_get_world_change_labels", *[_ptr(a) for a in out])
+        return tuple(out)
+
+    def query(self, xyz=None, cells=None, on_device=False, n=None, out=None):
+        """(n, 3) global positions or (n, 3) world cells -> WORLD_CHANGE_RESULT per entry.  on_device: the one given of
+        xyz / cells and out (n WORLD_CHANGE_RESULT) are device pointers."""
+        return self.map._goal_query("sdm_query_world_changes", xyz, cells, _WORLD_CELLS, WORLD_CHANGE_RESULT, on_device, n, out)

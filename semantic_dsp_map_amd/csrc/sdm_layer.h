@@ -1,8 +1,8 @@
 // sdm_layer.h — device helpers of the derived map layers (queries.hip, esdf.hip, instances.hip, frontiers.hip, views.hip,
-// reach.hip, forecast.hip, ground.hip, mesh.hip, world.hip, world_io.hip, world_snapshot.hip, world_reach.hip, world_frontiers.hip, world_esdf.hip, world_ground.hip, world_ground_reach.hip, world_rays.hip, world_mesh.hip, world_match.hip, world_objects.hip): how they read a result word, go from a global position to a map-index
+// reach.hip, forecast.hip, ground.hip, mesh.hip, world.hip, world_io.hip, world_snapshot.hip, world_reach.hip, world_frontiers.hip, world_esdf.hip, world_ground.hip, world_ground_reach.hip, world_rays.hip, world_mesh.hip, world_match.hip, world_objects.hip, world_changes.hip): how they read a result word, go from a global position to a map-index
 // coordinate and to a cell, between a cell word and its (x, y, z), and from a map-index cell to its storage index; how a
 // wave loads the results of chunks of 64 cells in map-index order; a neighbour's bit in a 64-cell mask word; the rank of a
-// lane's bit; reductions over the 64 lanes of a wave.  Only those twenty-one units include it (the three that walk segments
+// lane's bit; reductions over the 64 lanes of a wave.  Only those twenty-two units include it (the three that walk segments
 // through the block through sdm_walk.h): the frame pipeline's units see sdm_internal.h alone.
 #pragma once
 #include "sdm_internal.h"

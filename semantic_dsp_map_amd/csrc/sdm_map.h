@@ -316,6 +316,36 @@ struct WorldObjectsLayer : Derived {
   bool over = false;
 };
 
+// world changes (world_changes.hip): a snapshot of where the block and the archive disagree.  Per candidate brick of the
+// block (cap_cand, the map's largest candidate count) the flag "has a listed cell", its rank in the field, the archive's pool
+// slot and the eight listed words with the two bit planes of the class - the build's own; per brick of the field
+// (cap_bricks) its coordinates, the pool slot and the ranks of the 27 bricks round it (the build's own), the listed words,
+// their prefix and the class planes, and the hash table from brick key to rank (hmask + 1 slots in use) - what the query
+// reads.  Per listed cell (cap_cells) the world cell, the block's and the archive's word, the key, the class, parent (the
+// region index in the end), root and the scanned root flags; per region (cap_regions) the accumulator (empty between
+// builds), the index of its first cell, the scanned listing flags and the table.  The build's counters and per-label
+// counters (and their page-locked landing area, whose last word takes a count the build waits for), its arguments, the
+// frame's and the archive's stamp; over: the build found more cells than max_cells and wrote no list.  Every buffer is
+// grown by the build that needs more.
+struct WorldChangesLayer : Derived {
+  uint32_t *flag = nullptr, *rank = nullptr, *cslot = nullptr;
+  unsigned long long *lw_c = nullptr, *p0_c = nullptr, *p1_c = nullptr;
+  uint32_t *coord = nullptr, *slot_of = nullptr, *nbr = nullptr, *pre = nullptr, *vals = nullptr;
+  unsigned long long *cw = nullptr, *c0 = nullptr, *c1 = nullptr, *keys = nullptr;
+  int32_t *xyz = nullptr;
+  uint32_t *now = nullptr, *before = nullptr, *key = nullptr, *parent = nullptr, *root = nullptr, *idx = nullptr;
+  uint8_t *cls = nullptr;
+  unsigned char *acc = nullptr;
+  uint32_t *first = nullptr, *lidx = nullptr;
+  sdm_world_change_region *table = nullptr;
+  unsigned long long *meta = nullptr, *h_meta = nullptr;
+  size_t cap_cand = 0, cap_bricks = 0, cap_cells = 0, cap_regions = 0;
+  uint32_t n = 0, hmask = 0, n_roots = 0, n_candidates = 0, stamp = 0, frame_stamp = 0;
+  int32_t min_cells = 0;
+  int64_t n_cells = 0, max_cells = 0;
+  bool over = false;
+};
+
 struct sdm_map {
   sdm_config cfg{};
   sdm_params prm{};
@@ -487,6 +517,7 @@ struct sdm_map {
   WorldMatchPool wmatch;
   WorldMeshLayer wmesh;
   WorldObjectsLayer wobj;
+  WorldChangesLayer wchg;
   // the scan scratch the layers share (layer_scan_scratch): they all enqueue on `stream` only, so their scans are ordered
   uint32_t *layer_scan = nullptr;
   size_t layer_scan_elems = 0;  // its capacity in uint32

@@ -5,12 +5,13 @@
 // world_ground_reach.hip: the 2-D travel-cost field over that costmap; world_rays.hip: segments and views through the
 // bricks; world_mesh.hip: the faces and welded vertices of the bricks' surface; world_match.hip: foreign bricks scored
 // against the archive under a window of whole-cell offsets; world_objects.hip: the connected same-key components of the
-// bricks' occupied cells): the hash table's key, hash, lookup and
+// bricks' occupied cells; world_changes.hip: the block's results against the archived bricks it overlaps, and the connected
+// regions of what changed): the hash table's key, hash, lookup and
 // insertion, which cells write, the header-word layout, the indices of the counters, an update's geometry, how an entry of
 // a query becomes a world cell, the packing of brick coordinates and tile keys; the inline device code the layers share
 //  - the 3 x 3 x 3 offset tables, a wave's loads of a brick, list indices, the 64-bit layer words and the
-// lateral shifts inside them, the min-linking union-find with the seam body and the two ends of the brick-local labelling
-// over it; the host scaffold of a snapshot build (its buffers' one way to grow included) and of the two route planners, and
+// lateral shifts inside them, the min-linking union-find with the seam body, the two ends of the brick-local labelling
+// over it and the keyed sweep between them (5y); the host scaffold of a snapshot build (its buffers' one way to grow included) and of the two route planners, and
 // the host entry points of world.hip and world_snapshot.hip that the other units call.  No kernel lives here: everything
 // in the unnamed namespace has internal linkage and each unit compiles its own copy, so a kernel here would land in every
 // object.
@@ -279,6 +280,86 @@ __device__ __forceinline__ void store_local_roots(const uint32_t (&v)[8], const 
     const uint32_t at = pre[(size_t)r * 8u + z] + lane_rank(m[z], lane);  // (list_index, on the word the lane holds since the opening)
     const uint32_t root = list_index(words, pre, (size_t)r * 8u + lz, lb);
     if (at < n_cells) parent[at] = root;
+  }
+}
+// ... and what lies between the two, for the layers whose cells join under a key (world_objects.hip: label, or label and
+// track; world_changes.hip: the class, or class and label pair).  A wave per brick, a lane per (cx, cy): k[z] is the key of the
+// lane's cell of layer z, NO_KEY for a cell that is not listed (a key has 24 bits at most), v[z] its label from local_labels.
+constexpr uint32_t NO_KEY = 0xffffffffu;
+// a, or the neighbour's label t if it is smaller and bit `bit` of eq allows it (an equal key: both cells are listed, t is a
+// label); the bit, spread over the word, turns a forbidden t into all ones
+__device__ __forceinline__ uint32_t take_label(uint32_t a, uint32_t t, uint32_t eq, int bit) {
+  return min(a, t | ~(uint32_t)((int)(eq << (31 - bit)) >> 31));
+}
+// The keys never change, so who may join whom is settled ONCE, then labels are swept until a sweep changes nothing (at most
+// 512 sweeps): explicit comparisons against every neighbour, no separable minimum.  No LDS, no global memory.
+template <bool FACE>
+__device__ __forceinline__ void sweep_local_labels(const uint32_t (&k)[8], uint32_t (&v)[8], uint32_t lane) {
+  uint32_t eq[8];
+#pragma unroll
+  for (int z = 0; z < 8; ++z) eq[z] = 0u;
+  const int cx = (int)(lane & 7u), cy = (int)(lane >> 3);
+  // who may join whom: bit nb_bit(dx, dy, dz) of eq[c] - that neighbour of cell c lies in the brick, is listed and
+  // carries c's key.  The lane of a neighbour beyond the brick's border is the lane itself, and its key reads NO_KEY.  The
+  // in-layer directions are a loop that stays a loop (i: dx = i % 3 - 1, dy = i / 3 - 1; for 6-connectivity the four
+  // lateral ones, the column's own z neighbours apart): unrolled, the 208 tests of a sweep, which no sweep changes, would
+  // be hoisted out of the sweeps and held in registers.
+#pragma unroll 1
+  for (int i = 0; i < (FACE ? 4 : 9); ++i) {
+    const int d = FACE ? 2 * i + 1 : i, dx = d % 3 - 1, dy = d / 3 - 1;
+    const bool inside = cx + dx >= 0 && cx + dx <= 7 && cy + dy >= 0 && cy + dy <= 7;
+    const int from = inside ? (int)lane + dx + 8 * dy : (int)lane;
+#pragma unroll
+    for (int z = 0; z < 8; ++z) {
+      const uint32_t got = (uint32_t)__shfl((int)k[z], from, 64), nk = inside ? got : NO_KEY;
+#pragma unroll
+      for (int dz = FACE ? 0 : -1; dz <= (FACE ? 0 : 1); ++dz) {
+        const int c = z - dz;  // the cell whose neighbour at (dx, dy, dz) is this one
+        if (c < 0 || c > 7) continue;
+        eq[c] |= (k[c] != NO_KEY && nk == k[c] ? 1u : 0u) << (d + 9 * (dz + 1));
+      }
+    }
+  }
+#pragma unroll
+  for (int z = 0; z < 8; ++z) {
+    if (FACE && z > 0) eq[z] |= (k[z] != NO_KEY && k[z - 1] == k[z] ? 1u : 0u) << nb_bit(0, 0, -1);
+    if (FACE && z < 7) eq[z] |= (k[z] != NO_KEY && k[z + 1] == k[z] ? 1u : 0u) << nb_bit(0, 0, 1);
+    eq[z] &= ~(1u << nb_bit(0, 0, 0));  // (the cell itself)
+  }
+  for (int sweep = 0; sweep < 512; ++sweep) {  // a label falls by at least one cell of its component a sweep
+    uint32_t a[8];
+#pragma unroll
+    for (int z = 0; z < 8; ++z) a[z] = v[z];
+#pragma unroll 1
+    for (int i = 0; i < (FACE ? 4 : 9); ++i) {
+      const int d = FACE ? 2 * i + 1 : i, dx = d % 3 - 1, dy = d / 3 - 1;
+      const bool inside = cx + dx >= 0 && cx + dx <= 7 && cy + dy >= 0 && cy + dy <= 7;
+      const int from = inside ? (int)lane + dx + 8 * dy : (int)lane;
+#pragma unroll
+      for (int z = 0; z < 8; ++z) {
+        const uint32_t t = (uint32_t)__shfl((int)v[z], from, 64);
+#pragma unroll
+        for (int dz = FACE ? 0 : -1; dz <= (FACE ? 0 : 1); ++dz) {
+          const int c = z - dz;
+          if (c < 0 || c > 7) continue;
+          a[c] = take_label(a[c], t, eq[c], d + 9 * (dz + 1));
+        }
+      }
+    }
+    if (FACE) {
+#pragma unroll
+      for (int z = 0; z < 8; ++z) {
+        if (z > 0) a[z] = take_label(a[z], v[z - 1], eq[z], nb_bit(0, 0, -1));
+        if (z < 7) a[z] = take_label(a[z], v[z + 1], eq[z], nb_bit(0, 0, 1));
+      }
+    }
+    bool changed = false;
+#pragma unroll
+    for (int z = 0; z < 8; ++z) {
+      changed = changed || a[z] != v[z];
+      v[z] = a[z];
+    }
+    if (!__ballot(changed)) break;
   }
 }
 // The seams, a wave per word and a lane per cell: the cell `lane` of layer lz of brick r (of n), if it is listed and lies on

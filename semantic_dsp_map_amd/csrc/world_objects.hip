@@ -45,7 +45,8 @@
 // The build waits three times: for the number of bricks of the field, for the number of cells, for the number of objects.
 // This unit includes no code of a frame unit and defines every kernel it launches but those of world_snapshot.hip; the
 // opening and the end of the local labelling, the seam body, the union-find, the offset tables and the brick loads are
-// sdm_world.h's, shared with world_frontiers.hip; the sweeps are its own (5v says why they differ).
+// sdm_world.h's, shared with world_frontiers.hip; the keyed sweep between the two ends is sdm_world.h's
+// sweep_local_labels, shared with world_changes.hip (5y; 5v says why it differs from the frontiers').
 #include "sdm_world.h"
 
 #pragma clang fp contract(off)
@@ -69,7 +70,6 @@ constexpr int QT = 256;             // the kernels of a thread or a wave per ite
 constexpr uint32_t WO_GRID = 4096;  // the largest grid of the kernels over cells: they stride
 constexpr uint32_t ALL_WO_FLAGS = SDM_WORLD_OBJECTS_FACE_CONNECTED | SDM_WORLD_OBJECTS_BOX | SDM_WORLD_OBJECTS_BY_TRACK |
                                   SDM_WORLD_OBJECTS_STATIC_ONLY | SDM_WORLD_OBJECTS_MOVABLE_ONLY | SDM_WORLD_OBJECTS_OBSERVED_ONLY;
-constexpr uint32_t NO_KEY = 0xffffffffu;   // k_wo_label_local: the key of a cell that is not counted (a key has 24 bits at most)
 // the build's counters, 64 bits each: the guessed cells in G_SPREAD copies (a wave adds to copy rank & 63, the getter sums
 // them), the objects listed, per label the cells, per label the objects (32 bits each, two a word)
 enum { G_GUESSED = 0, G_SPREAD = 64, G_LISTED = G_SPREAD, G_LAB_CELLS, G_LAB_OBJS = G_LAB_CELLS + 256, G_WORDS = G_LAB_OBJS + 128 };
@@ -158,12 +158,6 @@ __global__ __launch_bounds__(QT) void k_wo_compact(const uint32_t *__restrict__ 
 }
 
 // ---- labels, inside a brick --------------------------------------------------------------------------------------------
-// a, or the neighbour's label t if it is smaller and bit `bit` of eq allows it (an equal key: both cells are counted, t is a
-// label); the bit, spread over the word, turns a forbidden t into all ones
-__device__ __forceinline__ uint32_t take_label(uint32_t a, uint32_t t, uint32_t eq, int bit) {
-  return min(a, t | ~(uint32_t)((int)(eq << (31 - bit)) >> 31));
-}
-
 template <bool FACE>
 __global__ __launch_bounds__(QT) void k_wo_label_local(const uint32_t *__restrict__ slot_of, const uint32_t *__restrict__ cells,
                                                        const u64 *__restrict__ cw, const uint32_t *__restrict__ pre, uint32_t n, uint32_t max_bricks,
@@ -172,7 +166,7 @@ __global__ __launch_bounds__(QT) void k_wo_label_local(const uint32_t *__restric
   const uint32_t r = blockIdx.x * (QT / 64) + (threadIdx.x >> 6);
   if (r >= n) return;  // (wave-uniform: nothing below waits for another wave)
   u64 cm[8];
-  uint32_t k[8], v[8], eq[8];
+  uint32_t k[8], v[8];
   if (!local_labels(cw, r, lane, cm, v)) return;
   const uint32_t slot = slot_of[r];
   if (slot >= max_bricks) return;  // (never)
@@ -180,71 +174,8 @@ __global__ __launch_bounds__(QT) void k_wo_label_local(const uint32_t *__restric
 #pragma unroll
   for (int z = 0; z < 8; ++z) {
     k[z] = v[z] != NO_LABEL ? key_of(k[z], by_track) : NO_KEY;  // (a start label: the cell is counted)
-    eq[z] = 0u;
   }
-  const int cx = (int)(lane & 7u), cy = (int)(lane >> 3);
-  // who may join whom: bit nb_bit(dx, dy, dz) of eq[c] - that neighbour of cell c lies in the brick, is counted and
-  // carries c's key.  The lane of a neighbour beyond the brick's border is the lane itself, and its key reads NO_KEY.  The
-  // in-layer directions are a loop that stays a loop (i: dx = i % 3 - 1, dy = i / 3 - 1; for 6-connectivity the four
-  // lateral ones, the column's own z neighbours apart): unrolled, the 208 tests of a sweep, which no sweep changes, would
-  // be hoisted out of the sweeps and held in registers.
-#pragma unroll 1
-  for (int i = 0; i < (FACE ? 4 : 9); ++i) {
-    const int d = FACE ? 2 * i + 1 : i, dx = d % 3 - 1, dy = d / 3 - 1;
-    const bool inside = cx + dx >= 0 && cx + dx <= 7 && cy + dy >= 0 && cy + dy <= 7;
-    const int from = inside ? (int)lane + dx + 8 * dy : (int)lane;
-#pragma unroll
-    for (int z = 0; z < 8; ++z) {
-      const uint32_t got = (uint32_t)__shfl((int)k[z], from, 64), nk = inside ? got : NO_KEY;
-#pragma unroll
-      for (int dz = FACE ? 0 : -1; dz <= (FACE ? 0 : 1); ++dz) {
-        const int c = z - dz;  // the cell whose neighbour at (dx, dy, dz) is this one
-        if (c < 0 || c > 7) continue;
-        eq[c] |= (k[c] != NO_KEY && nk == k[c] ? 1u : 0u) << (d + 9 * (dz + 1));
-      }
-    }
-  }
-#pragma unroll
-  for (int z = 0; z < 8; ++z) {
-    if (FACE && z > 0) eq[z] |= (k[z] != NO_KEY && k[z - 1] == k[z] ? 1u : 0u) << nb_bit(0, 0, -1);
-    if (FACE && z < 7) eq[z] |= (k[z] != NO_KEY && k[z + 1] == k[z] ? 1u : 0u) << nb_bit(0, 0, 1);
-    eq[z] &= ~(1u << nb_bit(0, 0, 0));  // (the cell itself)
-  }
-  for (int sweep = 0; sweep < 512; ++sweep) {  // a label falls by at least one cell of its component a sweep
-    uint32_t a[8];
-#pragma unroll
-    for (int z = 0; z < 8; ++z) a[z] = v[z];
-#pragma unroll 1
-    for (int i = 0; i < (FACE ? 4 : 9); ++i) {
-      const int d = FACE ? 2 * i + 1 : i, dx = d % 3 - 1, dy = d / 3 - 1;
-      const bool inside = cx + dx >= 0 && cx + dx <= 7 && cy + dy >= 0 && cy + dy <= 7;
-      const int from = inside ? (int)lane + dx + 8 * dy : (int)lane;
-#pragma unroll
-      for (int z = 0; z < 8; ++z) {
-        const uint32_t t = (uint32_t)__shfl((int)v[z], from, 64);
-#pragma unroll
-        for (int dz = FACE ? 0 : -1; dz <= (FACE ? 0 : 1); ++dz) {
-          const int c = z - dz;
-          if (c < 0 || c > 7) continue;
-          a[c] = take_label(a[c], t, eq[c], d + 9 * (dz + 1));
-        }
-      }
-    }
-    if (FACE) {
-#pragma unroll
-      for (int z = 0; z < 8; ++z) {
-        if (z > 0) a[z] = take_label(a[z], v[z - 1], eq[z], nb_bit(0, 0, -1));
-        if (z < 7) a[z] = take_label(a[z], v[z + 1], eq[z], nb_bit(0, 0, 1));
-      }
-    }
-    bool changed = false;
-#pragma unroll
-    for (int z = 0; z < 8; ++z) {
-      changed = changed || a[z] != v[z];
-      v[z] = a[z];
-    }
-    if (!__ballot(changed)) break;
-  }
+  sweep_local_labels<FACE>(k, v, lane);
   store_local_roots(v, cm, cw, pre, r, lane, n_cells, parent);
 }
 
